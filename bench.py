@@ -5,13 +5,20 @@ Headline (BASELINE.json `metric`): Mpix/s encode+decode of 8K RGB 4:4:4 q75 fram
 frames resident in HBM when the timed region starts. One STEP = one pass of the hot path over one batch of synthetic input:
 every one of the S pipelines (HIP stream + encoder + decoder + host thread) codes and decodes `frames_per_step_per_pipeline`
 frames -- gpujpeg_encoder_encode (GPU_IMAGE input, stream left in HBM) followed by gpujpeg_decoder_decode of that stream into
-HBM. The batch size is fixed during warm-up so that the K timed steps take at least half a second whatever K is; `value` =
-pixels of all ranks / max-over-ranks time of exactly K steps, `ms_per_step` = that time / K.
+HBM. The batch size is fixed during warm-up so that the K timed steps take at least half a second whatever K is (a whole number
+of turns of the ROTATE frames of every pipeline); `value` = pixels of all ranks / max-over-ranks time of exactly K steps,
+`ms_per_step` = that time / K.
+
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, sizing of the step, W warm-up steps, the K
+timed steps and the result line. `--dump-outputs DIR` then writes what the last timed step computed (the last JPEG stream of every
+pipeline and the decoded frame in each of its output buffers, a fixed sample of each, float32) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.
 
 Multi-GPU: frames are independent, ranks shard them with no data-path collective (weak scaling; RCCL carries the barrier and
 the max-over-ranks of the elapsed time only). N > 1 is launched by torch.distributed.run.
 
-On rank 0 at N = 1 the same JSON line also carries (each a short bounded run; --lean skips them):
+With --full, rank 0 adds to the same JSON line the roofline (at any N) and, at N = 1, the rest of this list (each a short bounded
+run; --lean keeps the roofline only):
   roofline          the dominant kernel of the step: algorithmic bytes per launch (raw in + JPEG out for the encoder direction,
                     JPEG in + raw out for the decoder) / its average hipEvent duration in a SOLO timed region (one pipeline, the GPU
                     otherwise idle, events on the coder's own stream) against 8 TB/s; `by_kernel` has every kernel of the step,
@@ -446,8 +453,8 @@ def kernel_names(spec, enc_ms, token_mode):
 
 
 def measure(lib, spec, device, local_rank, barrier, mode="both", streams=4, steps=20, warmup=3, min_seconds=0.5, host_io=False, keep_coefs=False,
-            want_solo=False):
-    """Run one workload; returns a dict with throughput and timings."""
+            want_solo=False, dump_dir=None):
+    """Run one workload; returns a dict with throughput and timings. dump_dir: write the outputs of the last timed step there (dump_outputs)."""
     L = Lanes(lib, spec, device, streams, host_io=host_io, keep_coefs=keep_coefs)
     L.c_loop = C_LOOP_OK["ok"]
     sync = lambda: torch.cuda.synchronize()
@@ -460,9 +467,13 @@ def measure(lib, spec, device, local_rank, barrier, mode="both", streams=4, step
     t_probe, *_ = L.run(mode, 1, 8, sync, local_rank)
     per_frame = max(t_probe / 8, 1e-6)
     reps = max(1, int(np.ceil(1.15 * min_seconds / (steps * per_frame)))) if min_seconds > 0 else 1
+    # whole turns of the rotation: every step codes each frame of a pipeline equally often, and the last frame of a region is always the same one
+    reps = -(-reps // ROTATE) * ROTATE
     if warmup > 0:  # W untimed steps of exactly the shape of the timed ones (same threads, same frames per step)
         L.run(mode, warmup, reps, sync, local_rank)
     elapsed, enc_wall, dec_wall, _ = L.run(mode, steps, reps, barrier, local_rank)
+    if dump_dir:
+        dump_outputs(L, mode, dump_dir)
     kms = np.zeros(9)
     if want_solo:  # per-kernel durations with all pipelines running: their own short region, with the events on
         L.set_stats(True)
@@ -472,6 +483,44 @@ def measure(lib, spec, device, local_rank, barrier, mode="both", streams=4, step
     L.close()
     return {"elapsed": elapsed, "reps": reps, "streams": S, "enc_wall": enc_wall, "dec_wall": dec_wall, "kernel_ms": kms, "solo_ms": solo,
             "jpeg_bytes": jsize, "frames": S * steps * reps}
+
+
+def stream_tensor(jp, js, device):
+    """the JPEG stream an encoder left in device memory (enc_out_val_device), copied into a uint8 tensor on that device"""
+    jt = torch.empty(js, dtype=torch.uint8, device=device)
+    rc = C.cdll.LoadLibrary("libamdhip64.so").hipMemcpy(C.c_void_p(jt.data_ptr()), C.cast(jp, C.c_void_p), C.c_size_t(js), 3)
+    assert rc == 0, f"hipMemcpy of the stream failed ({rc})"
+    torch.cuda.synchronize()
+    return jt
+
+
+DUMP_BYTES = 48 << 20  # what --dump-outputs writes at most, whatever the frame size and the number of pipelines
+
+
+def dump_outputs(L, mode, dirname):
+    """--dump-outputs: what the last timed step handed its callers, per pipeline i: `jpeg_<i>`, the last encoded stream (its bytes), and
+    `decoded_<i>_<k>`, the decoded frame in rotation slot k (its samples), as float32; `jpeg_bytes` holds the size of every pipeline's last stream
+    (float64). An array larger than its share of DUMP_BYTES is replaced by a fixed sample: its elements at seeded positions, in order. The inputs
+    are seeded and every step codes whole turns of the rotation (measure), so the same arguments give the same files on every run."""
+    arrays = {}
+    for i, ln in enumerate(L.lanes):
+        jp, js = ln["last"]
+        if mode != "decode":
+            arrays[f"jpeg_{i}"] = np.ctypeslib.as_array(jp, shape=(js,)) if L.host_io else stream_tensor(jp, js, L.device)
+        if mode != "encode":
+            for k, out in enumerate(ln["outs"]):
+                arrays[f"decoded_{i}_{k}"] = out
+    cap = max(1, DUMP_BYTES // 4 // len(arrays))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        flat = a.reshape(-1)
+        n = flat.shape[0]
+        if n > cap:
+            idx = np.sort(np.random.default_rng(12345).integers(0, n, cap))
+            flat = flat[torch.from_numpy(idx).to(flat.device)] if torch.is_tensor(flat) else flat[idx]
+        host = flat.cpu().numpy() if torch.is_tensor(flat) else flat
+        np.save(os.path.join(dirname, name + ".npy"), host.astype(np.float32))
+    np.save(os.path.join(dirname, "jpeg_bytes.npy"), np.array([ln["last"][1] for ln in L.lanes], np.float64))
 
 
 def cpu_baseline(spec, frame_host, frames=2):
@@ -554,7 +603,8 @@ def cpu_baseline_all_cores(spec, frame_host, max_procs=64):
     lib = os.path.join(ROOT, "oracle", "_ref", "libgpujpeg_refcpu_native.so")
     if not os.path.exists(lib):
         return None
-    procs = max(1, min(max_procs, (os.cpu_count() or 1)))
+    # (the CPUs this process may run on, and no more than a job-wide thread limit where one is set: a shared host hands a job part of its cores)
+    procs = max(1, min(max_procs, len(os.sched_getaffinity(0)), int(os.environ.get("OMP_NUM_THREADS") or max_procs)))
     with tempfile.NamedTemporaryFile(suffix=".npy", dir="/dev/shm" if os.path.isdir("/dev/shm") else None, delete=False) as f:
         np.save(f, frame_host)
         path = f.name
@@ -803,7 +853,7 @@ def main():
     ap.add_argument("--mode", default="both", choices=["both", "encode", "decode"],
                     help="what a timed step does: encode then decode (the headline metric), or only one direction")
     ap.add_argument("--min-seconds", type=float, default=0.5, help="lower bound of the timed region: the frames per pipeline and step are chosen for it")
-    ap.add_argument("--lean", action="store_true", help="headline + roofline only (no other workloads, no full-API run, no CPU baselines)")
+    ap.add_argument("--lean", action="store_true", help="with --full: headline + roofline only (no other workloads, no full-API run, no CPU baselines)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-workloads", action="store_true")
     ap.add_argument("--internal-rgb", action="store_true", help="code RGB without colour transform (tuning aid; not the headline config)")
@@ -813,19 +863,26 @@ def main():
     ap.add_argument("--host-io", action="store_true", help="the timed region with pinned host buffers in and out (what `full_api` reports; tuning aid, not the headline)")
     ap.add_argument("--tune", action="append", default=[], metavar="NAME[=VALUE]", help="developer setting for every coder of this run (gpujpeg_amd_tuning; INTEGRATION.md), repeatable")
     ap.add_argument("--verify", action="store_true", help="check the results of the last frame(s) against the oracle (slow)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline as well: roofline and per-kernel times, each direction alone, "
+                    "host buffers, the other workloads, batches, CPU baselines (see the module docstring); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (streams and decoded frames, float32 samples) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.batch:
+        ap.error("--dump-outputs covers the headline path, not --batch")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` as ONE process (the driver's command shape): become the launcher of N ranks, one per GPU,
-        # under torch.distributed.run on this node; the ranks re-enter main() with RANK / LOCAL_RANK / WORLD_SIZE set.
+        # `python bench.py --gpus N` as ONE process (the driver's command shape): start the launcher of N ranks, one per GPU,
+        # under torch.distributed.run on this node as a child and wait for it; the ranks enter main() with RANK / LOCAL_RANK / WORLD_SIZE set.
         import socket
+        import subprocess
         s = socket.socket()
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
         s.close()
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -869,7 +926,8 @@ def main():
 
     spec = Spec(lib, args.workload, args.pattern, args.quality, device, 12345 + rank, internal_rgb=args.internal_rgb)
     head = measure(lib, spec, device, dev_index, barrier, mode=args.mode, streams=args.streams, steps=args.steps, warmup=args.warmup,
-                   min_seconds=args.min_seconds, keep_coefs=args.keep_coefs, want_solo=True, host_io=args.host_io)
+                   min_seconds=args.min_seconds, keep_coefs=args.keep_coefs, want_solo=args.full, host_io=args.host_io,
+                   dump_dir=args.dump_outputs if rank == 0 else None)
     # whole-job figures: max over ranks of the elapsed time, SUM over ranks of the frames each rank really coded (every rank sizes its
     # own batch from its own probe, so the counts differ by a few per cent)
     from gpujpeg_amd.sharding import barrier_and_max, gather_counts
@@ -880,58 +938,6 @@ def main():
 
     if rank == 0:
         S, reps, jsize = head["streams"], head["reps"], head["jpeg_bytes"]
-        nblocks = ((width + 7) // 8) * ((height + 7) // 8) * (2 if spec.is422 else 3)
-        token_mode = nblocks >= (900000 if spec.is422 else 300000) and jsize <= (12 if spec.is422 else 16) * nblocks and not args.keep_coefs and not _TUNE["no_tokens"]
-        names = kernel_names(spec, head["solo_ms"], token_mode)
-        alg = spec.raw_bytes + jsize  # encoder: raw in + JPEG out; decoder: JPEG in + raw out (the same sum)
-        solo, cont = head["solo_ms"], head["kernel_ms"]
-        standard = spec.quality == (90 if spec.is422 else 75) and args.pattern == "natural" and not args.internal_rgb
-        traffic = load_traffic("kernels", args.workload) if standard else {}
-
-        def roof(name, ms):
-            ach = alg / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-            return {"kernel": name, "ms": round(float(ms), 4), "achieved": round(ach, 2), "frac": round(ach / HBM_PEAK_GBS, 5), "algorithmic_bytes": int(alg)}
-
-        def stage(name, ms):
-            #  a kernel that is ONE STAGE of its direction -- entropy decoder, IDCT, k_gather, the marker scan -- does not move the
-            # direction's algorithmic bytes: it is reported with the bytes it touched (PMC passes under profiles/, when taken on these sources)
-            # against the peak and with its vector-issue fraction, not with an HBM `frac` of bytes it never sees
-            if owns_direction(name):
-                return dict(roof(name, ms), owns_direction_bytes=True, traffic=traffic.get(name), **issue(name, ms))
-            t = traffic.get(name)
-            touched = None if not t or ms <= 0 else round(t / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-            return dict({"kernel": name, "ms": round(float(ms), 4), "owns_direction_bytes": False, "bytes_touched": t, "bytes_touched_frac_of_peak": touched}, **issue(name, ms))
-
-        live = [i for i in range(9) if solo[i] > 0.006]  # (event slots of kernels this configuration does not launch hold only the gap between two events)
-        dom = max(live, key=lambda i: solo[i])
-        # what an event pair measures with NOTHING between the two records (the slots of kernels this configuration does not launch): the part of every
-        # `ms` below that is the event records themselves -- rocprofv3's kernel durations (profiles/) correspond to ms - event_gap_ms
-        idle_slots = [float(solo[i]) for i in range(9) if 0.0005 < solo[i] <= 0.006]
-        event_gap = round(sum(idle_slots) / len(idle_slots), 4) if idle_slots else None
-        valu = load_traffic("valu_insts", args.workload) if traffic else {}
-
-        cyc, share4 = load_isa_mix()
-
-        def issue(name, ms):
-            n = valu.get(name)
-            if not n or ms <= 0:
-                return {}
-            s4 = share4.get(name, 1.0)  # (a kernel without a counted mix: the slow class for all, the conservative floor)
-            per = lambda c: n * c / SIMDS / CLOCK_HZ * 1e3  # noqa: E731
-            weighted = per((1.0 - s4) * cyc["valu2"] + s4 * cyc["valu4"])
-            return {"valu_insts": n, "valu_share_4cycle_class": s4, "valu_issue_floor_ms": round(weighted, 4),
-                    "valu_issue_floor_ms_if_all_2cycle": round(per(cyc["valu2"]), 4), "valu_issue_floor_ms_if_all_4cycle": round(per(cyc["valu4"]), 4),
-                    "valu_issue_frac": round(weighted / ms, 3)}
-
-        by_kernel = [stage(names[i], solo[i]) for i in live]
-        r = roof(names[dom], solo[dom])
-        enc_total, dec_total = float(sum(solo[i] for i in live if i < 5)), float(sum(solo[i] for i in live if i >= 5))  # (slots of kernels that were not launched hold the gap between two events)
-        n_enc, n_dec = sum(1 for i in live if i < 5), sum(1 for i in live if i >= 5)
-        gap = event_gap or 0.0  # (an event pair brackets the kernel AND one event record: rocprofv3's kernel durations are the net values)
-        enc_net, dec_net = max(enc_total - n_enc * gap, 0.0), max(dec_total - n_dec * gap, 0.0)
-
-        def dir_frac(nbytes, ms):
-            return round(nbytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if ms > 0 else None
         result = {
             "metric": ("Mpix/s encode+decode (8K RGB q75)" if args.workload == "8k" else f"Mpix/s encode+decode ({args.workload})") if args.mode == "both"
                       else f"Mpix/s {args.mode} only ({args.workload})",
@@ -945,54 +951,107 @@ def main():
                        "untimed_before": f"16 frames per pipeline (sizing of the step), then {args.warmup} warm-up steps of the timed shape; the interpreter's "
                                          "objects are frozen out of the garbage collector first (gc.freeze: round 3's 'stream halt' was a generation-2 collection)",
                        "jpeg_bytes": int(jsize), "parallelism": f"frame-sharded x{world}, no collective",
-                       "timed_with": "perf_stats = 0 (no per-kernel events in the timed region; `roofline.contended` comes from its own short region); "
+                       "timed_with": "perf_stats = 0 (no per-kernel events in the timed region; with --full `roofline.contended` comes from its own short region); "
                                      + ("frame loop of every launch thread in C (tools/bench_loop.c, public API only)" if c_loop(C_LOOP_OK["ok"]) else "frame loop in Python"),
                        "cpu_affinity_rank0": args.affinity},
             # API calls of pipeline 0 alone (one call at a time per pipeline; the aggregate of all pipelines is `value`)
             "encode_mpix_s_pipeline0": round(spec.pixels * args.steps * reps / head["enc_wall"] / 1e6, 2) if args.mode != "decode" else None,
             "decode_mpix_s_pipeline0": round(spec.pixels * args.steps * reps / head["dec_wall"] / 1e6, 2) if args.mode != "encode" else None,
-            "roofline": {"bound": "hbm", "kernel": r["kernel"], "achieved": r["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": r["frac"],
-                         "frac_basis": ("the dominant kernel's own bytes: a fused encoder moves its direction's algorithmic bytes (raw in + JPEG out) alone"
-                                        if owns_direction(names[dom]) else
-                                        "FLATTERING for this kernel: `frac` divides the whole decode direction's algorithmic bytes (JPEG in + raw out) by the duration "
-                                        "of ONE of its stage kernels, which never writes a pixel; the figures the driver's clock and the profiles support are "
-                                        "frac_path, frac_encode_direction, frac_decode_direction and frac_hbm_read_encode below"),
-                         #  the four fractions a reader can recompute: whole path from the driver-timed region, each direction from the
-                         # sum of its kernels' solo durations (hipEvents net of the event record, = rocprofv3's kernel durations under profiles/),
-                         # and north_star's own definition: raw input bytes of the encoder / encoder direction time / peak, target 0.70
-                         "frac_path": round(2 * alg * frames_all / elapsed / 1e9 / HBM_PEAK_GBS, 5) if args.mode == "both" else None,
-                         "frac_path_basis": "(encode + decode algorithmic bytes per frame) / (ms_per_step / frames_per_step_per_gpu) / peak: every kernel, launch gap and "
-                                            "host call of the timed region included, four pipelines sharing the device",
-                         "frac_encode_direction": dir_frac(alg, enc_net), "frac_decode_direction": dir_frac(alg, dec_net),
-                         "frac_hbm_read_encode": dir_frac(spec.raw_bytes, enc_net), "target": 0.70,
-                         "frac_hbm_read_encode_basis": "BASELINE.json north_star: raw input bytes of the encoder (HBM read) / sum of the encoder kernels' solo durations / "
-                                                       "8 TB/s; the target is 0.70. These kernels are bound by vector-instruction issue (valu_issue_frac), not by HBM: DESIGN 4",
-                         "direction_ms_net_of_event_gap": {"encode": round(enc_net, 4), "decode": round(dec_net, 4), "encode_kernels": n_enc, "decode_kernels": n_dec},
-                         "traffic": traffic.get(names[dom]), "ms": r["ms"], "algorithmic_bytes_per_launch": int(alg), **issue(names[dom], solo[dom]),
-                         "valu_note": "valu_issue_frac: SQ_INSTS_VALU per launch (profiles/r6_traffic.json) x the cycles of the kernel's instruction class mix "
-                                      "(2.4 / 4.3 cycles per wave64 instruction, profiles/r6_isa_mix.json) / 1024 SIMDs / 2.4 GHz / duration -- the roofline that "
-                                      "actually bounds these kernels; the all-2-cycle and all-4-cycle floors bracket it",
-                         "timing": "average hipEvent duration over 10 solo launches inside this run (one pipeline, GPU otherwise idle, events on the "
-                                   "coder's stream); profiles/r6_* hold the rocprofv3 --kernel-trace --stats summary of the same configuration",
-                         "dominant": ("the launch with the longest solo duration of an encoded and decoded frame. Since the encoder's last tiles are split "
-                                      "(round 5: k_encode_rgb444 84 -> 75 us alone) that is the token decoder on most runs, a stage of the decode direction: "
-                                      "`achieved` prices the direction's algorithmic bytes per frame (SURVEY 8(d)) against its duration, `traffic` is what it "
-                                      "touches itself; by_kernel / by_direction carry the others"),
-                         "event_gap_ms": event_gap,
-                         "ms_net_of_event_gap": None if event_gap is None else round(r["ms"] - event_gap, 4),
-                         "frac_net_of_event_gap": None if event_gap is None else round(alg / ((r["ms"] - event_gap) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                         "event_gap_note": "hipEvent duration of an event pair with no launch between the records, from the library's event slots of kernels this "
-                                           "configuration does not launch; `ms` and `frac` above are the raw event durations (kernel + one event record), the "
-                                           "rocprofv3 durations under profiles/ agree with the net values",
-                         "by_kernel": by_kernel,
-                         "solo_vs_filled": None,  # (filled in by extras(): the same kernel's per-frame cost when the device is full)
-                         "by_direction": {"encode": dict(roof("all encoder kernels", enc_total)), "decode": dict(roof("all decoder kernels", dec_total))},
-                         "contended": dict(roof(names[dom], cont[dom]), concurrent_pipelines=S,
-                                           kernel_ms={names[i]: round(float(cont[i]), 4) for i in live})},
         }
+        if args.full:
+            nblocks = ((width + 7) // 8) * ((height + 7) // 8) * (2 if spec.is422 else 3)
+            token_mode = nblocks >= (900000 if spec.is422 else 300000) and jsize <= (12 if spec.is422 else 16) * nblocks and not args.keep_coefs and not _TUNE["no_tokens"]
+            names = kernel_names(spec, head["solo_ms"], token_mode)
+            alg = spec.raw_bytes + jsize  # encoder: raw in + JPEG out; decoder: JPEG in + raw out (the same sum)
+            solo, cont = head["solo_ms"], head["kernel_ms"]
+            standard = spec.quality == (90 if spec.is422 else 75) and args.pattern == "natural" and not args.internal_rgb
+            traffic = load_traffic("kernels", args.workload) if standard else {}
+
+            def roof(name, ms):
+                ach = alg / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+                return {"kernel": name, "ms": round(float(ms), 4), "achieved": round(ach, 2), "frac": round(ach / HBM_PEAK_GBS, 5), "algorithmic_bytes": int(alg)}
+
+            def stage(name, ms):
+                #  a kernel that is ONE STAGE of its direction -- entropy decoder, IDCT, k_gather, the marker scan -- does not move the
+                # direction's algorithmic bytes: it is reported with the bytes it touched (PMC passes under profiles/, when taken on these sources)
+                # against the peak and with its vector-issue fraction, not with an HBM `frac` of bytes it never sees
+                if owns_direction(name):
+                    return dict(roof(name, ms), owns_direction_bytes=True, traffic=traffic.get(name), **issue(name, ms))
+                t = traffic.get(name)
+                touched = None if not t or ms <= 0 else round(t / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                return dict({"kernel": name, "ms": round(float(ms), 4), "owns_direction_bytes": False, "bytes_touched": t, "bytes_touched_frac_of_peak": touched}, **issue(name, ms))
+
+            live = [i for i in range(9) if solo[i] > 0.006]  # (event slots of kernels this configuration does not launch hold only the gap between two events)
+            dom = max(live, key=lambda i: solo[i])
+            # what an event pair measures with NOTHING between the two records (the slots of kernels this configuration does not launch): the part of every
+            # `ms` below that is the event records themselves -- rocprofv3's kernel durations (profiles/) correspond to ms - event_gap_ms
+            idle_slots = [float(solo[i]) for i in range(9) if 0.0005 < solo[i] <= 0.006]
+            event_gap = round(sum(idle_slots) / len(idle_slots), 4) if idle_slots else None
+            valu = load_traffic("valu_insts", args.workload) if traffic else {}
+
+            cyc, share4 = load_isa_mix()
+
+            def issue(name, ms):
+                n = valu.get(name)
+                if not n or ms <= 0:
+                    return {}
+                s4 = share4.get(name, 1.0)  # (a kernel without a counted mix: the slow class for all, the conservative floor)
+                per = lambda c: n * c / SIMDS / CLOCK_HZ * 1e3  # noqa: E731
+                weighted = per((1.0 - s4) * cyc["valu2"] + s4 * cyc["valu4"])
+                return {"valu_insts": n, "valu_share_4cycle_class": s4, "valu_issue_floor_ms": round(weighted, 4),
+                        "valu_issue_floor_ms_if_all_2cycle": round(per(cyc["valu2"]), 4), "valu_issue_floor_ms_if_all_4cycle": round(per(cyc["valu4"]), 4),
+                        "valu_issue_frac": round(weighted / ms, 3)}
+
+            by_kernel = [stage(names[i], solo[i]) for i in live]
+            r = roof(names[dom], solo[dom])
+            enc_total, dec_total = float(sum(solo[i] for i in live if i < 5)), float(sum(solo[i] for i in live if i >= 5))  # (slots of kernels that were not launched hold the gap between two events)
+            n_enc, n_dec = sum(1 for i in live if i < 5), sum(1 for i in live if i >= 5)
+            gap = event_gap or 0.0  # (an event pair brackets the kernel AND one event record: rocprofv3's kernel durations are the net values)
+            enc_net, dec_net = max(enc_total - n_enc * gap, 0.0), max(dec_total - n_dec * gap, 0.0)
+
+            def dir_frac(nbytes, ms):
+                return round(nbytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if ms > 0 else None
+            result["roofline"] = {"bound": "hbm", "kernel": r["kernel"], "achieved": r["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": r["frac"],
+                                  "frac_basis": ("the dominant kernel's own bytes: a fused encoder moves its direction's algorithmic bytes (raw in + JPEG out) alone"
+                                                 if owns_direction(names[dom]) else
+                                                 "FLATTERING for this kernel: `frac` divides the whole decode direction's algorithmic bytes (JPEG in + raw out) by the duration "
+                                                 "of ONE of its stage kernels, which never writes a pixel; the figures the driver's clock and the profiles support are "
+                                                 "frac_path, frac_encode_direction, frac_decode_direction and frac_hbm_read_encode below"),
+                                  #  the four fractions a reader can recompute: whole path from the driver-timed region, each direction from the
+                                  # sum of its kernels' solo durations (hipEvents net of the event record, = rocprofv3's kernel durations under profiles/),
+                                  # and north_star's own definition: raw input bytes of the encoder / encoder direction time / peak, target 0.70
+                                  "frac_path": round(2 * alg * frames_all / elapsed / 1e9 / HBM_PEAK_GBS, 5) if args.mode == "both" else None,
+                                  "frac_path_basis": "(encode + decode algorithmic bytes per frame) / (ms_per_step / frames_per_step_per_gpu) / peak: every kernel, launch gap and "
+                                                     "host call of the timed region included, four pipelines sharing the device",
+                                  "frac_encode_direction": dir_frac(alg, enc_net), "frac_decode_direction": dir_frac(alg, dec_net),
+                                  "frac_hbm_read_encode": dir_frac(spec.raw_bytes, enc_net), "target": 0.70,
+                                  "frac_hbm_read_encode_basis": "BASELINE.json north_star: raw input bytes of the encoder (HBM read) / sum of the encoder kernels' solo durations / "
+                                                                "8 TB/s; the target is 0.70. These kernels are bound by vector-instruction issue (valu_issue_frac), not by HBM: DESIGN 4",
+                                  "direction_ms_net_of_event_gap": {"encode": round(enc_net, 4), "decode": round(dec_net, 4), "encode_kernels": n_enc, "decode_kernels": n_dec},
+                                  "traffic": traffic.get(names[dom]), "ms": r["ms"], "algorithmic_bytes_per_launch": int(alg), **issue(names[dom], solo[dom]),
+                                  "valu_note": "valu_issue_frac: SQ_INSTS_VALU per launch (profiles/r6_traffic.json) x the cycles of the kernel's instruction class mix "
+                                               "(2.4 / 4.3 cycles per wave64 instruction, profiles/r6_isa_mix.json) / 1024 SIMDs / 2.4 GHz / duration -- the roofline that "
+                                               "actually bounds these kernels; the all-2-cycle and all-4-cycle floors bracket it",
+                                  "timing": "average hipEvent duration over 10 solo launches inside this run (one pipeline, GPU otherwise idle, events on the "
+                                            "coder's stream); profiles/r6_* hold the rocprofv3 --kernel-trace --stats summary of the same configuration",
+                                  "dominant": ("the launch with the longest solo duration of an encoded and decoded frame. Since the encoder's last tiles are split "
+                                               "(round 5: k_encode_rgb444 84 -> 75 us alone) that is the token decoder on most runs, a stage of the decode direction: "
+                                               "`achieved` prices the direction's algorithmic bytes per frame (SURVEY 8(d)) against its duration, `traffic` is what it "
+                                               "touches itself; by_kernel / by_direction carry the others"),
+                                  "event_gap_ms": event_gap,
+                                  "ms_net_of_event_gap": None if event_gap is None else round(r["ms"] - event_gap, 4),
+                                  "frac_net_of_event_gap": None if event_gap is None else round(alg / ((r["ms"] - event_gap) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                  "event_gap_note": "hipEvent duration of an event pair with no launch between the records, from the library's event slots of kernels this "
+                                                    "configuration does not launch; `ms` and `frac` above are the raw event durations (kernel + one event record), the "
+                                                    "rocprofv3 durations under profiles/ agree with the net values",
+                                  "by_kernel": by_kernel,
+                                  "solo_vs_filled": None,  # (filled in by extras(): the same kernel's per-frame cost when the device is full)
+                                  "by_direction": {"encode": dict(roof("all encoder kernels", enc_total)), "decode": dict(roof("all decoder kernels", dec_total))},
+                                  "contended": dict(roof(names[dom], cont[dom]), concurrent_pipelines=S,
+                                                    kernel_ms={names[i]: round(float(cont[i]), 4) for i in live})}
         if args.verify:
             result.update(verify_headline(lib, spec, device, args))
-        if world == 1 and not args.lean:
+        if world == 1 and args.full and not args.lean:
             extras(result, args, lib, spec, device, dev_index, barrier)
         print(json.dumps(result), flush=True)
     if world > 1:
@@ -1012,9 +1071,7 @@ def verify_headline(lib, spec, device, args):
     img = (O.make_image(spec.width, spec.height, pixel_format=3, color_space=3, quality=spec.quality, interleaved=1) if spec.is422
            else O.make_image(spec.width, spec.height, quality=spec.quality, color_space_internal=1 if args.internal_rgb else 3))
     want = O.encode(img, host)
-    jt = torch.empty(js, dtype=torch.uint8, device=device)
-    C.cdll.LoadLibrary("libamdhip64.so").hipMemcpy(C.c_void_p(jt.data_ptr()), C.cast(jp, C.c_void_p), C.c_size_t(js), 3)
-    torch.cuda.synchronize()
+    jt = stream_tensor(jp, js, device)
     r = {"verified_bit_exact_encode": bool(np.array_equal(jt.cpu().numpy(), want)),
          "verified_bit_exact_decode": bool(np.array_equal(ln["out"].cpu().numpy().reshape(-1), (O.decode(want, 3, 3) if spec.is422 else O.decode(want))[0]))}
     L.close()

@@ -68,7 +68,7 @@ def test_batch_calls_at_full_size_bit_exact(gpu_lib, workload, frames):
 
 def test_two_ranks_headline_line(gpu_lib):
     """the weak-scaling headline path at N = 2: one JSON line, whole-job throughput over both ranks, per-rank frames of their own seed"""
-    d = _torchrun(2, ["--gpus", "2", "--workload", "hd", "--steps", "3", "--warmup", "1", "--min-seconds", "0.1", "--lean", "--verify"])
+    d = _torchrun(2, ["--gpus", "2", "--workload", "hd", "--steps", "3", "--warmup", "1", "--min-seconds", "0.1", "--full", "--lean", "--verify"])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["verified_bit_exact_encode"] is True and d["verified_bit_exact_decode"] is True
     assert d["roofline"]["frac"] > 0

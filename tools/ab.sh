@@ -9,7 +9,7 @@ shift
 for rep in 0 1; do
   for lib in "$@"; do
     f=gpurun_out/${TAG}_${lib%.so}_$rep.json
-    timeout 600 python bench.py --lean --verify $ARGS --lib gpujpeg_amd/lib/$lib > $f 2> gpurun_out/${TAG}_${lib%.so}_$rep.err || tail -3 gpurun_out/${TAG}_${lib%.so}_$rep.err
+    timeout 600 python bench.py --full --lean --verify $ARGS --lib gpujpeg_amd/lib/$lib > $f 2> ${f%.json}.err || tail -3 ${f%.json}.err
     echo "== $lib rep $rep"
     python tools/bench_brief.py $f
     python -c "import json,sys; d=json.loads(open('$f').read().strip().splitlines()[-1]); print('verified', d.get('verified_bit_exact_encode'), d.get('verified_bit_exact_decode'))"

@@ -9,7 +9,7 @@ OUT=$PWD/gpurun_out
 W=${WORKLOAD:-8k}
 TAG=${TAG:-r6_$W}
 rm -rf $OUT/prof_stats $OUT/prof_fetch $OUT/prof_write $OUT/prof_sq
-ARGS="--workload $W --streams ${STREAMS:-1} --lean ${BENCH_ARGS}"
+ARGS="--workload $W --streams ${STREAMS:-1} --full --lean ${BENCH_ARGS}"
 if [ -n "$BATCH" ]; then ARGS="--workload 4k --batch $BATCH --streams ${STREAMS:-4} ${BENCH_ARGS}"; fi
 TRACE_ARGS="$ARGS" # (the counter passes of a batch run another shape: the header of the summary names both commands, each with its own arguments)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -- python bench.py --steps ${STEPS:-20} --warmup 3 $ARGS > $OUT/prof_stats.log 2>&1

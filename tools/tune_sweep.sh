@@ -11,7 +11,7 @@ for set in "$@"; do
   T=""
   if [ "$set" != "-" ]; then for s in ${set//,/ }; do T="$T --tune $s"; done; fi
   f=gpurun_out/${TAG}_$n.json
-  timeout 600 python bench.py --lean $ARGS $T > $f 2> gpurun_out/${TAG}_$n.err || tail -3 gpurun_out/${TAG}_$n.err
+  timeout 600 python bench.py --full --lean $ARGS $T > $f 2> ${f%.json}.err || tail -3 ${f%.json}.err
   echo "== $set"
   python tools/bench_brief.py $f | head -3
   n=$((n+1))
