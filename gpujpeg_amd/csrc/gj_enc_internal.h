@@ -7,7 +7,8 @@
 //                        lane-per-block coder they share (gj_code_tile)
 //   gj_enc_assemble.hip  tile streams / segment streams -> the file: k_gather (behind the fused encoders); k_scan_segments + k_assemble (behind
 //                        k_huffman), k_segment_info (APP13 index)
-//   gj_enc_planes.hip    the paths through coefficient planes: k_preprocess / k_copy_planes_in, k_dct, k_fused_rgb444, k_fused_uyvy422, k_huffman
+//   gj_enc_planes.hip    the paths through coefficient planes: k_preprocess / k_copy_planes_in, k_dct, k_fused_rgb444, k_fused_uyvy422, k_huffman,
+//                        k_huffman_count (symbol statistics of per-frame optimal tables)
 // The reference runs preprocess -> (DCT per component) -> codeword kernel -> serialisation kernel -> compaction
 // kernel and stitches segments on the host (src/gpujpeg_encoder.c:485-629); the arithmetic restates
 // src/gpujpeg_preprocessor.cu, src/gpujpeg_colorspace.h, src/gpujpeg_dct_gpu.cu and src/gpujpeg_huffman_gpu_encoder.cu.
@@ -164,6 +165,7 @@ __global__ void k_copy_planes_in(const gj_geom g, const uint8_t* __restrict__ ra
 __global__ void k_dct(const gj_geom g, const uint8_t* __restrict__ planes, int16_t* __restrict__ coefs, const float* __restrict__ q_luma, const float* __restrict__ q_chroma);
 __global__ void k_huffman(const gj_geom g, const int16_t* __restrict__ coefs, const uint32_t* __restrict__ lut, uint8_t* __restrict__ temp, uint32_t* __restrict__ seg_bytes,
                           uint32_t* __restrict__ seg_ff);
+__global__ void k_huffman_count(const gj_geom g, const int16_t* __restrict__ coefs, uint32_t* __restrict__ freq);
 __global__ void k_gather(const GjTail T0);
 __global__ void k_scan_segments(const gj_enc_job J, unsigned long long* __restrict__ partial, const uint32_t epoch);
 __global__ void k_assemble(const gj_enc_job J);

@@ -511,6 +511,97 @@ __global__ __launch_bounds__(256) void k_huffman(const gj_geom g, const int16_t*
     }
 }
 
+// ================================================================================================
+// Symbol statistics for per-frame optimal tables (enc_opt_huffman=optimal): one LANE per 8x8 block, every block on its own.
+// freq[type][DC, AC][256] receives the counts of exactly the symbols k_huffman emits (gj_code_block): the DC category of dc - pred,
+// a ZRL per 16 zeros in front of a non-zero coefficient, (run << 4) | size per non-zero coefficient, EOB unless coefficient 63 is
+// non-zero. The predecessor's DC is read straight from the planes (block k - dist of the same segment, as k_huffman step 2), so no
+// block waits for another whatever the restart interval. Counts go to a 4 KiB LDS histogram and leave once per workgroup, one
+// atomic per non-zero bin (integer sums: the result does not depend on the order). freq must be zero on entry.
+// ================================================================================================
+__global__ __launch_bounds__(256) void k_huffman_count(const gj_geom g, const int16_t* __restrict__ coefs, uint32_t* __restrict__ freq)
+{
+    __shared__ uint32_t s_hist[1024];
+    for (int t = threadIdx.x; t < 1024; t += 256) s_hist[t] = 0;
+    __syncthreads();
+    const unsigned B = (unsigned)g.seg_blocks;
+    const unsigned total = (unsigned)g.segment_count * B; // (segment s, block k) -> s * B + k; k beyond a short segment is idle
+    for (unsigned base = blockIdx.x * 256u; base < total; base += gridDim.x * 256u) {
+        const unsigned n = base + threadIdx.x;
+        const unsigned s = n / B, k = n - s * B;
+        GjSeg sg;
+        sg.nblocks = 0;
+        if (n < total) sg = gj_segment(g, (int)s);
+        const bool active = (int)k < sg.nblocks;
+        int type = 0;
+        bool eob = false;
+        if (active) {
+            int comp, mcu_pos;
+            const uint64_t off = gj_segment_block(g, sg, (int)k, &comp, &mcu_pos);
+            const int dist = g.interleaved ? g.mcu_prev[mcu_pos] : 1;
+            int pred = 0;
+            if ((int)k - dist >= 0) {
+                int pc, pp;
+                pred = coefs[gj_segment_block(g, sg, (int)k - dist, &pc, &pp)];
+            }
+            const uint4* src = reinterpret_cast<const uint4*>(coefs + off);
+            uint32_t w[32];
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                const uint4 v = src[r];
+                w[r * 4 + 0] = v.x; w[r * 4 + 1] = v.y; w[r * 4 + 2] = v.z; w[r * 4 + 3] = v.w;
+            }
+            type = g.comp[comp].type;
+            uint32_t* h = s_hist + type * 512;
+            int nbits;
+            uint32_t bits;
+            gj_value_bits((int)(int16_t)(w[0] & 0xFFFF) - pred, nbits, bits);
+            atomicAdd(&h[nbits], 1u);
+            // size category of every AC coefficient in zig-zag order, a nibble each (cat[q >> 3] holds positions 8 (q >> 3) ..),
+            // and the mask of the non-zero ones: the walk below visits only those
+            uint32_t cat[8];
+            uint64_t mask = 0;
+#pragma unroll
+            for (int q = 0; q < 64; q++) {
+                if ((q & 7) == 0) cat[q >> 3] = 0;
+                if (q == 0) continue;
+                const int na = GJ_ZZ[q];
+                const int v = (na & 1) ? ((int)w[na >> 1] >> 16) : (int)(int16_t)(w[na >> 1] & 0xFFFF);
+                const int a = v < 0 ? -v : v;
+                const uint32_t c = a ? 32u - (uint32_t)__builtin_clz((unsigned)a) : 0u;
+                cat[q >> 3] |= c << (4 * (q & 7));
+                mask |= (uint64_t)(a != 0) << q;
+            }
+            int prev = 0;
+            while (mask) {
+                const int p = __builtin_ctzll(mask);
+                mask &= mask - 1;
+                int run = p - prev - 1;
+                prev = p;
+                if (run >= 16) {
+                    atomicAdd(&h[256 + 0xF0], (uint32_t)(run >> 4));
+                    run &= 15;
+                }
+                uint32_t cw = cat[0]; // (a select chain: no dynamically indexed register array)
+#pragma unroll
+                for (int j = 1; j < 8; j++)
+                    if ((p >> 3) == j) cw = cat[j];
+                atomicAdd(&h[256 + ((run << 4) | (int)((cw >> (4 * (p & 7))) & 15u))], 1u);
+            }
+            eob = prev != 63;
+        }
+        // EOB, the bin nearly every block adds to: one add per wave and table type
+        const uint64_t e0 = __ballot(eob && type == 0), e1 = __ballot(eob && type == 1);
+        if ((threadIdx.x & 63) == 0) {
+            if (e0) atomicAdd(&s_hist[256], (uint32_t)__popcll(e0));
+            if (e1) atomicAdd(&s_hist[512 + 256], (uint32_t)__popcll(e1));
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < 1024; t += 256)
+        if (s_hist[t]) atomicAdd(&freq[t], s_hist[t]);
+}
+
 
 // fused kernel for this configuration, or nullptr when the generic path has to be used
 gj_fused_kernel_t gj_fused_kernel(const gj_geom& g)

@@ -4,6 +4,7 @@
 // Pipeline (all in one stream, the bitstream is assembled on the device):
 //   k_encode_rgb444 / k_encode_uyvy422 / k_encode_blocks -> k_gather            pixels -> tile streams -> file (the default)
 //   k_fused_* or k_preprocess + k_dct -> k_huffman -> k_scan_segments + k_assemble   through coefficient planes
+//   optimal tables: the same, cut in two calls behind the planes: ... -> k_huffman_count | host builds the tables | k_huffman -> ...
 #include "gj_enc_internal.h"
 
 // k_gather's arguments (and the encoder kernels': they use the tile list and the group totals) for a launch that leaves
@@ -74,6 +75,7 @@ static bool gj_is_uyvy_layout(const gj_enc_job* job)
 static int gj_tile_kernel(const gj_enc_job* job)
 {
     const gj_geom& g = job->g;
+    if (job->stage != GJ_ENC_STAGE_ALL) return 0; // (the two calls of a frame with optimal tables meet at the coefficient planes)
     const bool segs_ok = g.restart_interval > 0 && g.seg_blocks <= 256 && g.seg_blocks >= 256 / GJ_ENC_MAX_SPT;
     gj_encode_kernel_t whole = (job->use_fused && !job->keep_coefs) ? gj_encode_kernel(g) : nullptr;
     if (whole && job->tune.enc_by_blocks > 0 && gj_blocks_kernel_mode(g) == 0) whole = nullptr; // (k_encode_blocks instead)
@@ -100,9 +102,11 @@ extern "C" int gj_hip_encode(const gj_enc_job* job, gj_stream_t stream, gj_event
     if (g.blocks_per_mcu > GJ_MAX_MCU_BLOCKS) return -1;
     const unsigned frames = job->batch.count > 1 ? job->batch.count : 1u;
     if (frames > 1 && (!gj_hip_encode_batchable(job) || frames > 65535u)) return -1;
+    if (job->stage != GJ_ENC_STAGE_ALL && (frames > 1 || (job->stage == GJ_ENC_STAGE_COUNT && !job->d_huff_freq))) return -1;
     gj_hip_note_reset();
-    if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[0], st));
-    if (job->channel_remap) { // the reference permutes the channels of the raw image in place first (src/gpujpeg_preprocessor.cu:570-575)
+    const bool code_only = job->stage == GJ_ENC_STAGE_CODE; // the planes are there already (GJ_ENC_STAGE_COUNT of this frame)
+    if (ev && !code_only) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[0], st));
+    if (job->channel_remap && !code_only) { // the reference permutes the channels of the raw image in place first (src/gpujpeg_preprocessor.cu:570-575)
         const unsigned n = (unsigned)g.width * (unsigned)g.height;
         hipLaunchKernelGGL(k_channel_remap, dim3((n + 255) / 256), dim3(256), 0, st, g, const_cast<uint8_t*>(job->d_raw), job->channel_remap & 0xFFFFu);
     }
@@ -160,7 +164,8 @@ extern "C" int gj_hip_encode(const gj_enc_job* job, gj_stream_t stream, gj_event
                            job->d_seg_bytes, job->d_seg_ff, T);
     } else {
     tiles = false;
-    if (uyvy) { // packed 4:2:2 without colour transform: pixels -> coefficients, one thread per MCU
+    if (code_only) {
+    } else if (uyvy) { // packed 4:2:2 without colour transform: pixels -> coefficients, one thread per MCU
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[1], st));
         const unsigned nm = (unsigned)(g.comp[1].blocks_x * g.comp[1].blocks_y);
         hipLaunchKernelGGL(gj_fused_uyvy422_kernel(), dim3((nm + 255) / 256), dim3(256), 0, st, g, job->d_raw, job->d_coefs, job->d_fwd_q[0], job->d_fwd_q[1]);
@@ -180,6 +185,16 @@ extern "C" int gj_hip_encode(const gj_enc_job* job, gj_stream_t stream, gj_event
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[1], st));
         hipLaunchKernelGGL(k_dct, dim3(((unsigned)g.block_count + 255) / 256), dim3(256), 0, st, g, job->d_planes, job->d_coefs,
                            job->d_fwd_q[0], job->d_fwd_q[1]);
+    }
+    if (job->stage == GJ_ENC_STAGE_COUNT) { // symbol counts of the frame; the host builds its tables from them and comes back with GJ_ENC_STAGE_CODE
+        if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[6], st));
+        GJ_HIP_CHECK(hipMemsetAsync(job->d_huff_freq, 0, 1024 * sizeof(uint32_t), st));
+        // (grid-stride over the blocks: four workgroups per CU keep enough loads in flight, and the flush is one atomic per used bin and workgroup)
+        const unsigned total = (unsigned)g.segment_count * (unsigned)g.seg_blocks;
+        const unsigned fill = (unsigned)gj_hip_cu_count() * 4u, wgs = (total + 255) / 256 < fill ? (total + 255) / 256 : fill;
+        hipLaunchKernelGGL(k_huffman_count, dim3(wgs), dim3(256), 0, st, g, job->d_coefs, job->d_huff_freq);
+        if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[7], st));
+        return (hipGetLastError() == hipSuccess && !gj_hip_noted()) ? 0 : -1;
     }
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
     const int B = g.seg_blocks;

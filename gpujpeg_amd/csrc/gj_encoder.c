@@ -60,6 +60,10 @@ struct gpujpeg_encoder {
     uint8_t* b_gather; size_t b_gather_cap;              /* frames given as separate buffers (encode_batch_ptrs), gathered back to back */
     int b_last_batched, b_last_single; /* frames of the last batch call coded by batched launches / frame by frame */
     int b_chunk;                       /* gpujpeg_amd_encoder_set_batch_chunk: frames per launch at most, 0 = the default */
+    /* enc_opt_huffman=optimal: every frame gets tables built from its own symbol counts (allocated on first use) */
+    int huff_optimal;
+    uint32_t* d_huff_freq; uint32_t* h_huff_freq; /* [2 types][DC, AC][256] counts of the frame (k_huffman_count); pinned copy */
+    uint32_t* d_opt_lut; uint32_t* h_opt_lut;     /* the frame's coder tables (d_huff_lut's layout; never d_huff_lut itself); pinned staging */
 };
 
 /* ------------------------------------------------------------------ input helpers (gpujpeg_encoder.h:77-110) */
@@ -95,17 +99,7 @@ struct gpujpeg_encoder* gpujpeg_encoder_create(cudaStream_t stream)
     e->h_header = gj_hip_host_alloc(GJ_MAIN_HEADER_CAP);
     if (!e->d_fwd_q[0] || !e->d_fwd_q[1] || !e->d_huff_lut || !e->d_result || !e->h_result || !e->h_header) goto fail;
     uint32_t lut[GJ_CODER_LUT_OFFSET + GJ_CODER_LUT_WORDS];
-    gj_huffman_encoder_lut(lut);
-    /* the same tables as the fused encoders' coder reads them (gj_encode.hip: GjCoderLds::lut): per table type 256 AC entries indexed by
-     * (run << 4) | ((16 - nbits) & 15), then 16 DC entries indexed by nbits; entry = (code length + nbits) << 26 | code << nbits */
-    for (int t = 0; t < GJ_CODER_LUT_WORDS; t++) {
-        const int type = t >= 272, idx = t - type * 272, ac = idx < 256;
-        const int sym = ac ? idx : idx - 256, nbits = ac ? (sym & 15) : sym;
-        const uint32_t old = lut[(type * 2 + ac) * 256 + sym];
-        /* (the AC entries sit at (run << 4) | ((16 - nbits) & 15): the walk indexes them with 32 - nbits as v_ffbh_i32 delivers it; EOB and ZRL, nbits = 0, stay where they were) */
-        const int at = ac ? type * 272 + ((sym & 0xF0) | ((16 - nbits) & 15)) : t;
-        lut[GJ_CODER_LUT_OFFSET + at] = (((old & 0xFFu) + (uint32_t)nbits) << 26) | ((old >> 8) << nbits);
-    }
+    gj_huffman_encoder_lut(NULL, lut); /* Annex K.3, in k_huffman's layout and in the fused encoders' coder layout */
     if (gj_hip_memcpy_h2d(e->d_huff_lut, lut, sizeof lut, e->coder.stream) != 0 || gj_hip_stream_sync(e->coder.stream) != 0) goto fail;
     return e;
 fail:
@@ -124,6 +118,7 @@ int gpujpeg_encoder_destroy(struct gpujpeg_encoder* e)
     gj_hip_free(e->coder.d_raw_own); gj_hip_free(e->coder.d_planes); gj_hip_free(e->coder.d_coefs);
     gj_hip_host_free(e->h_result); gj_hip_host_free(e->h_header); free(e->hdr_sent);
     gj_hip_free(e->b_gather);
+    gj_hip_free(e->d_huff_freq); gj_hip_free(e->d_opt_lut); gj_hip_host_free(e->h_huff_freq); gj_hip_host_free(e->h_opt_lut);
     gj_hip_free(e->b_temp); gj_hip_free(e->b_seg); gj_hip_free(e->b_tail); gj_hip_free(e->b_jpeg); gj_hip_free(e->b_result); gj_hip_free(e->b_raw);
     gj_hip_host_free(e->bh_result); free(e->b_hdr_sent);
     if (e->b_out_pinned) gj_hip_host_free(e->b_out); else free(e->b_out);
@@ -226,6 +221,64 @@ static int ensure_out_buffer(struct gpujpeg_encoder* e, size_t need)
     return e->out_buf ? 0 : -1;
 }
 
+/* The main header of a call (host bytes, placed at the start of the device stream); huff = NULL: Annex K.3. Returns its size, 0 on error.
+ * (the kernels write behind it, so it is uploaded again only when it changes -- parameters, the frame's own tables, or the wall clock of an
+ * Exif header -- or the stream buffer was reallocated) */
+static size_t place_main_header(struct gpujpeg_encoder* e, const struct gpujpeg_parameters* p, const struct gj_huff_spec* huff)
+{
+    struct gj_coder* c = &e->coder;
+    const size_t hdr = gj_write_main_header(e->h_header, GJ_MAIN_HEADER_CAP, &c->geom, p, e->header_type, (const uint8_t(*)[64])e->qraw, &e->metadata,
+                                            e->exif_tags, huff);
+    if (hdr > GJ_MAIN_HEADER_CAP) {
+        GJ_ERROR("The main header (%zu B: Exif tags, metadata) does not fit its %d B staging buffer.\n", hdr, GJ_MAIN_HEADER_CAP);
+        return 0;
+    }
+    if (!e->hdr_sent) e->hdr_sent = malloc(GJ_MAIN_HEADER_CAP);
+    if (!e->hdr_sent) return 0;
+    if (e->hdr_sent_to != e->d_jpeg || e->hdr_sent_len != hdr || memcmp(e->hdr_sent, e->h_header, hdr) != 0) {
+        if (gj_hip_memcpy_h2d(e->d_jpeg, e->h_header, hdr, c->stream) != 0) return 0;
+        /* (h_header is rewritten by the next call. With the frame's own tables the header changes from frame to frame, and the call waits
+         * for its stream before it returns anyway: no wait of its own then) */
+        if (!huff && gj_hip_stream_sync(c->stream) != 0) return 0;
+        memcpy(e->hdr_sent, e->h_header, hdr);
+        e->hdr_sent_len = hdr;
+        e->hdr_sent_to = e->d_jpeg;
+    }
+    return hdr;
+}
+
+/* enc_opt_huffman=optimal: the tables of the frame from its symbol counts (freq[type][DC, AC][256]), for the table types that occur */
+static int build_optimal_tables(const gj_geom* g, const uint32_t* freq, struct gj_huff_spec* spec)
+{
+    memset(spec, 0, sizeof *spec);
+    for (int type = 0; type < 2; type++) {
+        bool used = false;
+        for (int c = 0; c < g->comp_count; c++) used = used || g->comp[c].type == type;
+        if (!used) continue;
+        int longest[2];
+        for (int ac = 0; ac < 2; ac++) {
+            if (gj_huffman_optimal(freq + (type * 2 + ac) * 256, spec->bits[type][ac], spec->vals[type][ac]) < 0) return -1;
+            longest[ac] = 16;
+            while (longest[ac] > 0 && spec->bits[type][ac][longest[ac]] == 0) longest[ac]--;
+        }
+        /* Worst-case block: DC code <= 12 bits (at most 12 categories + the reserved code point) + 11 magnitude bits, then 63 x (AC code
+         * <= 16 bits + 10 magnitude bits) = 1661 bits: within the coder's room per block (GJ_TEMP_BYTES_PER_BLOCK = 1664 bits, a segment's
+         * padding included) and within the 26 bits of code + magnitude its table entries pack */
+        assert(longest[0] <= 12 && longest[1] <= 16);
+        assert(longest[0] + 11 + 63 * (longest[1] + 10) <= GJ_TEMP_BYTES_PER_BLOCK * 8);
+    }
+    return 0;
+}
+
+static int ensure_optimal_buffers(struct gpujpeg_encoder* e)
+{
+    if (!e->d_huff_freq) e->d_huff_freq = gj_hip_malloc(1024 * sizeof(uint32_t));
+    if (!e->h_huff_freq) e->h_huff_freq = gj_hip_host_alloc(1024 * sizeof(uint32_t));
+    if (!e->d_opt_lut) e->d_opt_lut = gj_hip_malloc((GJ_CODER_LUT_OFFSET + GJ_CODER_LUT_WORDS) * sizeof(uint32_t));
+    if (!e->h_opt_lut) e->h_opt_lut = gj_hip_host_alloc((GJ_CODER_LUT_OFFSET + GJ_CODER_LUT_WORDS) * sizeof(uint32_t));
+    return (e->d_huff_freq && e->h_huff_freq && e->d_opt_lut && e->h_opt_lut) ? 0 : -1;
+}
+
 /* ------------------------------------------------------------------ encode (src/gpujpeg_encoder.c:352-644) */
 int gpujpeg_encoder_encode(struct gpujpeg_encoder* e, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi,
                            const struct gpujpeg_encoder_input* input, uint8_t** image_compressed, size_t* image_compressed_size)
@@ -276,22 +329,10 @@ int gpujpeg_encoder_encode(struct gpujpeg_encoder* e, const struct gpujpeg_param
         return -1;
     }
 
-    /* main header: host bytes, placed at the start of the device stream */
-    const size_t hdr = gj_write_main_header(e->h_header, GJ_MAIN_HEADER_CAP, g, &p, e->header_type, (const uint8_t(*)[64])e->qraw, &e->metadata, e->exif_tags);
-    if (hdr > GJ_MAIN_HEADER_CAP) {
-        GJ_ERROR("The main header (%zu B: Exif tags, metadata) does not fit its %d B staging buffer.\n", hdr, GJ_MAIN_HEADER_CAP);
-        return -1;
-    }
-    /* (the kernels write behind it, so it is uploaded again only when it changes -- parameters, or the wall clock of an Exif header -- or
-     * the stream buffer was reallocated) */
-    if (!e->hdr_sent) e->hdr_sent = malloc(GJ_MAIN_HEADER_CAP);
-    if (!e->hdr_sent) return -1;
-    if (e->hdr_sent_to != e->d_jpeg || e->hdr_sent_len != hdr || memcmp(e->hdr_sent, e->h_header, hdr) != 0) {
-        if (gj_hip_memcpy_h2d(e->d_jpeg, e->h_header, hdr, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) return -1; /* (h_header is rewritten by the next call) */
-        memcpy(e->hdr_sent, e->h_header, hdr);
-        e->hdr_sent_len = hdr;
-        e->hdr_sent_to = e->d_jpeg;
-    }
+    /* main header (with optimal tables: once the frame's tables are known) */
+    const bool optimal = e->huff_optimal != 0;
+    size_t hdr = 0;
+    if (!optimal && (hdr = place_main_header(e, &p, NULL)) == 0) return -1;
 
     gj_enc_job job;
     memset(&job, 0, sizeof job);
@@ -339,10 +380,35 @@ int gpujpeg_encoder_encode(struct gpujpeg_encoder* e, const struct gpujpeg_param
     /* the sets of group totals alternate only between calls that end in k_gather, which clears the idle one: a call that takes the
      * coefficient planes (flip, kept coefficients, fused path off) leaves both as they are (it used to flip, and the next
      * tile-path call added its sizes to an older frame's totals) */
-    if (gj_hip_encode_tiles(&job)) e->tail_set ^= 1;
-    GJ_HT(c, 0);
+    if (optimal) {
+        /* 1. pixels -> coefficient planes + the frame's symbol counts; 2. the counts to the host (the one wait this mode adds); 3. the
+         * tables; 4. header and tables up (the tables into a buffer of their own: d_huff_lut keeps Annex K.3 for every other call);
+         * 5. the planes -> entropy-coded segments -> the file with those tables */
+        if (ensure_optimal_buffers(e) != 0) return -1;
+        job.stage = GJ_ENC_STAGE_COUNT;
+        job.d_huff_freq = e->d_huff_freq;
+        GJ_HT(c, 0);
+        if (gj_hip_encode(&job, c->stream, stats ? c->timers.ev : NULL) != 0 ||
+            gj_hip_memcpy_d2h(e->h_huff_freq, e->d_huff_freq, 1024 * sizeof(uint32_t), c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) {
+            GJ_ERROR("Encoder kernels failed: %s\n", gj_hip_last_error());
+            c->configured = false;
+            return -1;
+        }
+        struct gj_huff_spec spec;
+        if (build_optimal_tables(g, e->h_huff_freq, &spec) != 0) return -1;
+        gj_huffman_encoder_lut(&spec, e->h_opt_lut);
+        if (gj_hip_memcpy_h2d(e->d_opt_lut, e->h_opt_lut, (GJ_CODER_LUT_OFFSET + GJ_CODER_LUT_WORDS) * sizeof(uint32_t), c->stream) != 0) return -1;
+        if ((hdr = place_main_header(e, &p, &spec)) == 0) return -1;
+        job.main_hdr_size = (uint32_t)hdr;
+        job.stage = GJ_ENC_STAGE_CODE;
+        job.d_huff_lut = e->d_opt_lut;
+    } else {
+        if (gj_hip_encode_tiles(&job)) e->tail_set ^= 1;
+        GJ_HT(c, 0);
+    }
     if (gj_hip_encode(&job, c->stream, stats ? c->timers.ev : NULL) != 0) {
         GJ_ERROR("Encoder kernels failed: %s\n", gj_hip_last_error());
+        if (optimal) gj_hip_stream_sync(c->stream); /* (copies from the pinned staging may still be in flight) */
         c->configured = false; /* (the next call sets the device-side state up again) */
         return -1;
     }
@@ -375,11 +441,15 @@ int gpujpeg_encoder_encode(struct gpujpeg_encoder* e, const struct gpujpeg_param
 
     if (stats) {
         struct gpujpeg_duration_stats* s = &c->stats;
-        s->duration_preprocessor = gj_hip_event_elapsed_ms(c->timers.ev[0], c->timers.ev[1]);
-        s->duration_dct_quantization = gj_hip_event_elapsed_ms(c->timers.ev[1], c->timers.ev[2]);
-        s->duration_huffman_coder = gj_hip_event_elapsed_ms(c->timers.ev[2], c->timers.ev[5]);
+        /* (optimal tables: the DCT ends at event 6, k_huffman_count runs from 6 to 7, the second call starts at 2; duration_in_gpu includes the
+         * host's round trip in between) */
+        for (int k = 0; k < 5; k++) c->kernel_ms[k] = gj_hip_event_elapsed_ms(c->timers.ev[k], c->timers.ev[optimal && k == 1 ? 6 : k + 1]);
+        c->kernel_ms[5] = optimal ? gj_hip_event_elapsed_ms(c->timers.ev[6], c->timers.ev[7]) : 0.0f;
+        c->kernel_ms[6] = c->kernel_ms[7] = 0.0f;
+        s->duration_preprocessor = c->kernel_ms[0];
+        s->duration_dct_quantization = c->kernel_ms[1];
+        s->duration_huffman_coder = gj_hip_event_elapsed_ms(c->timers.ev[2], c->timers.ev[5]) + c->kernel_ms[5];
         s->duration_in_gpu = gj_hip_event_elapsed_ms(c->timers.ev[0], c->timers.ev[5]);
-        for (int k = 0; k < GJ_ENC_EVENTS - 1; k++) c->kernel_ms[k] = gj_hip_event_elapsed_ms(c->timers.ev[k], c->timers.ev[k + 1]);
         if (d_raw == c->d_raw_own) s->duration_memory_to = gj_hip_event_elapsed_ms(c->timers.copy_in[0], c->timers.copy_in[1]);
         if (e->out_location != GJ_OUT_DEVICE) s->duration_memory_from = gj_hip_event_elapsed_ms(c->timers.copy_out[0], c->timers.copy_out[1]);
         c->timers.valid = true;
@@ -466,8 +536,8 @@ int gpujpeg_amd_encoder_encode_batch(struct gpujpeg_encoder* e, const struct gpu
     job.use_fused = e->use_fused && !e->flipped;
     job.keep_coefs = e->keep_coefs;
 
-    if (!gj_hip_encode_batchable(&job)) {
-        /* another configuration than the fully fused kernel's: frame by frame, every stream copied to its slot */
+    if (e->huff_optimal || !gj_hip_encode_batchable(&job)) {
+        /* another configuration than the fully fused kernel's, or tables per frame: frame by frame, every stream copied to its slot */
         for (int f = 0; f < count; f++) {
             struct gpujpeg_encoder_input in;
             if (frames_on_device) gpujpeg_encoder_input_set_gpu_image(&in, (uint8_t*)(uintptr_t)(frames + (size_t)f * frame_stride));
@@ -490,7 +560,7 @@ int gpujpeg_amd_encoder_encode_batch(struct gpujpeg_encoder* e, const struct gpu
         e->b_last_batched = count;
         e->b_last_single = 0;
         /* main header: the same bytes at the start of every slot, uploaded when they change (as gpujpeg_encoder_encode does for its one buffer) */
-        const size_t hdr = gj_write_main_header(e->h_header, GJ_MAIN_HEADER_CAP, g, &p, e->header_type, (const uint8_t(*)[64])e->qraw, &e->metadata, e->exif_tags);
+        const size_t hdr = gj_write_main_header(e->h_header, GJ_MAIN_HEADER_CAP, g, &p, e->header_type, (const uint8_t(*)[64])e->qraw, &e->metadata, e->exif_tags, NULL);
         if (hdr > GJ_MAIN_HEADER_CAP) {
             GJ_ERROR("The main header (%zu B: Exif tags, metadata) does not fit its %d B staging buffer.\n", hdr, GJ_MAIN_HEADER_CAP);
             return -1;
@@ -749,6 +819,15 @@ int gpujpeg_encoder_set_option(struct gpujpeg_encoder* e, const char* opt, const
         e->header_type = GPUJPEG_HEADER_EXIF;
         return gj_exif_add_tag(&e->exif_tags, val) == 0 ? GPUJPEG_NOERR : GPUJPEG_ERROR;
     }
+    if (strcmp(opt, GPUJPEG_AMD_ENC_OPT_HUFFMAN) == 0) { /* MI355X extension: per-frame optimal tables (include/gpujpeg_amd_ext.h) */
+        if (strcmp(val, GPUJPEG_AMD_ENC_HUFFMAN_VAL_STANDARD) == 0) e->huff_optimal = 0;
+        else if (strcmp(val, GPUJPEG_AMD_ENC_HUFFMAN_VAL_OPTIMAL) == 0) e->huff_optimal = 1;
+        else {
+            GJ_ERROR("Unknown Huffman table mode: %s\n", val);
+            return GPUJPEG_ERROR;
+        }
+        return GPUJPEG_NOERR;
+    }
     GJ_ERROR("Invalid encoder option: %s!\n", opt);
     return GPUJPEG_ERROR;
 }
@@ -765,6 +844,8 @@ void gpujpeg_encoder_print_options(void)
            "\t\t'210' for GBR; special placeholders 'F' and 'Z' to set a channel to all-ones or all-zeros\n");
     printf("\t" GPUJPEG_ENC_OPT_EXIF_TAG "=<key>=<value>|help - custom EXIF tag (use help for syntax)\n");
     printf("\t" GPUJPEG_ENC_OPT_METADATA "=<key>=<value>|help - set image metadata\n");
+    printf("\t" GPUJPEG_AMD_ENC_OPT_HUFFMAN "=[" GPUJPEG_AMD_ENC_HUFFMAN_VAL_STANDARD "|" GPUJPEG_AMD_ENC_HUFFMAN_VAL_OPTIMAL
+           "] - Huffman tables: the typical ones of T.81 Annex K.3, or built per frame from its own symbol counts (smaller files)\n");
 }
 
 /* ------------------------------------------------------------------ MI355X extensions (include/gpujpeg_amd_ext.h) */
@@ -799,7 +880,7 @@ void gpujpeg_amd_encoder_set_fused(struct gpujpeg_encoder* e, int enabled) { e->
 void gpujpeg_amd_encoder_keep_coefficients(struct gpujpeg_encoder* e, int enabled) { e->keep_coefs = enabled != 0; }
 
 /* durations of the kernels of the last encode: [0] preprocess (generic path), [1] DCT+quant (fused: incl. preprocess),
- * [2] k_huffman, [3] k_scan_segments, [4] k_assemble; needs perf_stats or verbose >= 1 */
+ * [2] k_huffman, [3] k_scan_segments, [4] k_assemble, [5] k_huffman_count (optimal tables); needs perf_stats or verbose >= 1 */
 int gpujpeg_amd_encoder_get_kernel_times(struct gpujpeg_encoder* e, float ms[8])
 {
     if (!e->coder.timers.valid) return -1;
@@ -853,7 +934,7 @@ size_t gpujpeg_amd_host_headers_exif(const struct gpujpeg_parameters* param, con
     gj_quant_table_raw(0, p.quality, qraw[0]);
     gj_quant_table_raw(1, p.quality, qraw[1]);
     uint8_t hdr[GJ_MAIN_HEADER_CAP];
-    const size_t n = gj_write_main_header(hdr, sizeof hdr, &g, &p, (enum gpujpeg_header_type)header_type, (const uint8_t(*)[64])qraw, &md, tags);
+    const size_t n = gj_write_main_header(hdr, sizeof hdr, &g, &p, (enum gpujpeg_header_type)header_type, (const uint8_t(*)[64])qraw, &md, tags, NULL);
     gj_exif_tags_destroy(tags);
     struct gj_scan_headers sh;
     memset(&sh, 0, sizeof sh);

@@ -47,7 +47,15 @@ void gj_quant_table_raw(int type, int quality, uint8_t raw_zigzag[64]);         
 void gj_quant_table_forward(const uint8_t raw_zigzag[64], float fwd[64]);                    /* src/gpujpeg_table.c:103-123 */
 void gj_quant_table_inverse(const uint8_t raw_zigzag[64], uint16_t inv[64]);                 /* src/gpujpeg_table.c:154-160 */
 void gj_huffman_std_spec(int type, int is_ac, const uint8_t** bits17, const uint8_t** vals, int* count); /* :190-254 */
-void gj_huffman_encoder_lut(uint32_t lut[4 * 256]);                                          /* src/gpujpeg_huffman_gpu_encoder.cu:958-969 */
+/* Huffman tables of an encoded frame, [table type][DC, AC]: BITS[1..16] and HUFFVAL (enc_opt_huffman=optimal; NULL where a function takes
+ * one = the typical tables of Annex K.3) */
+struct gj_huff_spec {
+    uint8_t bits[2][2][17];
+    uint8_t vals[2][2][256];
+};
+void gj_huffman_spec_table(const struct gj_huff_spec* spec, int type, int is_ac, const uint8_t** bits17, const uint8_t** vals, int* count);
+void gj_huffman_encoder_lut(const struct gj_huff_spec* spec, uint32_t lut[GJ_CODER_LUT_OFFSET + GJ_CODER_LUT_WORDS]); /* src/gpujpeg_huffman_gpu_encoder.cu:958-969 */
+int gj_huffman_optimal(const uint32_t freq[256], uint8_t bits17[17], uint8_t vals[256]); /* ITU T.81 K.2 + the decoder-fit rule; returns the length limit used */
 int gj_huffman_decoder_table(const uint8_t bits17[17], const uint8_t* vals, uint16_t out[GJ_DEC_TAB_WORDS]); /* src/gpujpeg_table.c:384-449 */
 int gj_huffman_decoder_table2(const uint8_t bits17[17], const uint8_t* vals, int is_ac, uint16_t out[GJ_DEC2_WORDS]);
 
@@ -110,7 +118,8 @@ struct gj_exif_tags; /* user Exif tags (enc_exif_tag), gj_writer.c */
 int gj_exif_add_tag(struct gj_exif_tags** tags, const char* cfg); /* 0 = added, -1 = error or "help" */
 void gj_exif_tags_destroy(struct gj_exif_tags* tags);
 size_t gj_write_main_header(uint8_t* out, size_t out_cap, const gj_geom* g, const struct gpujpeg_parameters* param, enum gpujpeg_header_type header_type,
-                            const uint8_t qraw[2][64], const struct gpujpeg_image_metadata* metadata, const struct gj_exif_tags* exif_tags);
+                            const uint8_t qraw[2][64], const struct gpujpeg_image_metadata* metadata, const struct gj_exif_tags* exif_tags,
+                            const struct gj_huff_spec* huff /* NULL: Annex K.3 */);
 int gj_write_scan_headers(struct gj_scan_headers* sh, const gj_geom* g, const struct gpujpeg_parameters* param);
 
 /* ---- raster file formats behind gpujpeg_image_load_from_file / save_to_file (gj_image_io.c, gj_image_png.c) ---- */

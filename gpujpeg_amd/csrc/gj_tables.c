@@ -82,16 +82,31 @@ void gj_huffman_std_spec(int type, int is_ac, const uint8_t** bits, const uint8_
     }
 }
 
-/* symbol -> (code << 8) | size, canonical assignment of ITU T.81 Annex C (figures C.1-C.3).
- * Table order for the kernels: luminance DC, luminance AC, chrominance DC, chrominance AC. */
-void gj_huffman_encoder_lut(uint32_t lut[4 * 256])
+void gj_huffman_spec_table(const struct gj_huff_spec* spec, int type, int is_ac, const uint8_t** bits, const uint8_t** vals, int* count)
 {
-    memset(lut, 0, 4 * 256 * sizeof(uint32_t));
+    if (!spec) {
+        gj_huffman_std_spec(type, is_ac, bits, vals, count);
+        return;
+    }
+    *bits = spec->bits[type][is_ac];
+    *vals = spec->vals[type][is_ac];
+    int n = 0;
+    for (int len = 1; len <= 16; len++) n += spec->bits[type][is_ac][len];
+    *count = n;
+}
+
+/* symbol -> (code << 8) | size, canonical assignment of ITU T.81 Annex C (figures C.1-C.3), for the tables of `spec` (NULL: Annex K.3),
+ * in both layouts of gj_enc_job::d_huff_lut: [4][256] for k_huffman (luminance DC, luminance AC, chrominance DC, chrominance AC), then at
+ * GJ_CODER_LUT_OFFSET the tables as the fused encoders' coder reads them (gj_encode.hip: GjCoderLds::lut): per table type 256 AC entries
+ * indexed by (run << 4) | ((16 - nbits) & 15), then 16 DC entries indexed by nbits; entry = (code length + nbits) << 26 | code << nbits */
+void gj_huffman_encoder_lut(const struct gj_huff_spec* spec, uint32_t lut[GJ_CODER_LUT_OFFSET + GJ_CODER_LUT_WORDS])
+{
+    memset(lut, 0, (GJ_CODER_LUT_OFFSET + GJ_CODER_LUT_WORDS) * sizeof(uint32_t));
     for (int type = 0; type < 2; type++) {
         for (int is_ac = 0; is_ac < 2; is_ac++) {
             const uint8_t *bits, *vals;
             int count;
-            gj_huffman_std_spec(type, is_ac, &bits, &vals, &count);
+            gj_huffman_spec_table(spec, type, is_ac, &bits, &vals, &count);
             uint32_t* t = lut + (type * 2 + is_ac) * 256;
             unsigned code = 0;
             int p = 0;
@@ -101,6 +116,89 @@ void gj_huffman_encoder_lut(uint32_t lut[4 * 256])
             }
         }
     }
+    for (int t = 0; t < GJ_CODER_LUT_WORDS; t++) {
+        const int type = t >= 272, idx = t - type * 272, ac = idx < 256;
+        const int sym = ac ? idx : idx - 256, nbits = ac ? (sym & 15) : sym;
+        const uint32_t old = lut[(type * 2 + ac) * 256 + sym];
+        /* (the AC entries sit at (run << 4) | ((16 - nbits) & 15): the walk indexes them with 32 - nbits as v_ffbh_i32 delivers it; EOB and ZRL, nbits = 0, stay where they were) */
+        const int at = ac ? type * 272 + ((sym & 0xF0) | ((16 - nbits) & 15)) : t;
+        lut[GJ_CODER_LUT_OFFSET + at] = (((old & 0xFFu) + (uint32_t)nbits) << 26) | ((old >> 8) << nbits);
+    }
+}
+
+/* Optimal table of one class from a frame's symbol counts (ITU T.81 Annex K.2):
+ *  1. code sizes by Figure K.1, with the reserved symbol 256 at count 1 so that no code is all ones. Of two equal counts the one of the
+ *     LARGER symbol value is taken first (the search keeps the last of the smallest counts), the rule of libjpeg's table generator;
+ *  2. BITS of those sizes, limited to L bits by Figure K.3, the reserved code removed again;
+ *  3. HUFFVAL by Figure K.4: symbols ordered by their UNADJUSTED code size, then by value;
+ *  4. L is the largest of 16 .. 10 whose table the decoder's two-level layout takes (gj_huffman_decoder_table2: at most GJ_DEC2_SUBTABLES
+ *     second-level tables), so that the library never writes a stream that turns off its own token and batch decoders.
+ * Returns L, or -1 when no symbol has a count. */
+int gj_huffman_optimal(const uint32_t freq_in[256], uint8_t bits[17], uint8_t vals[256])
+{
+    uint64_t freq[257];
+    int codesize[257], others[257], live[257], sym[257], n = 0;
+    for (int i = 0; i < 256; i++) {
+        freq[i] = freq_in[i];
+        if (freq_in[i]) sym[n++] = i; /* (the symbols that occur, by value: the K.4 order below walks them) */
+    }
+    const int nsym = n;
+    if (nsym == 0) return -1;
+    freq[256] = 1;
+    sym[n++] = 256;
+    for (int i = 0; i < 257; i++) {
+        codesize[i] = 0;
+        others[i] = -1;
+    }
+    memcpy(live, sym, (size_t)n * sizeof(int));
+    while (n > 1) { /* Figure K.1 over the live nodes: c1 = the smallest count, c2 = the next; equal counts: the larger symbol value first */
+        int a = -1, b = -1; /* positions in live[] of c1, c2 */
+        for (int k = 0; k < n; k++) {
+            const int i = live[k];
+            if (a < 0 || freq[i] < freq[live[a]] || (freq[i] == freq[live[a]] && i > live[a])) { b = a; a = k; }
+            else if (b < 0 || freq[i] < freq[live[b]] || (freq[i] == freq[live[b]] && i > live[b])) b = k;
+        }
+        int c1 = live[a], c2 = live[b];
+        freq[c1] += freq[c2];
+        freq[c2] = 0;
+        live[b] = live[--n];
+        codesize[c1]++;
+        while (others[c1] >= 0) { c1 = others[c1]; codesize[c1]++; }
+        others[c1] = c2;
+        codesize[c2]++;
+        while (others[c2] >= 0) { c2 = others[c2]; codesize[c2]++; }
+    }
+    int sizes[258] = {0}, longest = 0; /* Figure K.2 (a code size is at most 256: 257 symbols) */
+    for (int k = 0; k <= nsym; k++) {
+        sizes[codesize[sym[k]]]++;
+        if (codesize[sym[k]] > longest) longest = codesize[sym[k]];
+    }
+    int p = 0; /* Figure K.4 */
+    for (int size = 1; size <= longest; size++)
+        for (int k = 0; k < nsym; k++)
+            if (codesize[sym[k]] == size) vals[p++] = (uint8_t)sym[k];
+    uint16_t tab[GJ_DEC2_WORDS];
+    for (int L = 16; L >= 10; L--) {
+        int b[258];
+        memcpy(b, sizes, sizeof b);
+        for (int i = longest; i > L; i--) /* Figure K.3 */
+            while (b[i] > 0) {
+                int j = i - 2;
+                while (b[j] == 0) j--;
+                b[i] -= 2;
+                b[i - 1]++;
+                b[j + 1] += 2;
+                b[j]--;
+            }
+        int i = L;
+        while (b[i] == 0) i--;
+        b[i]--; /* the reserved code */
+        bits[0] = 0;
+        for (int len = 1; len <= 16; len++) bits[len] = (uint8_t)(len <= L ? b[len] : 0);
+        /* (the fit depends on BITS only; the class changes what the entries hold, not where they are) */
+        if (gj_huffman_decoder_table2(bits, vals, 1, tab) == 0) return L;
+    }
+    return -1; /* (not reached: codes of at most 10 bits need no second-level table) */
 }
 
 /* decode table for one DHT table: see GJ_DEC_TAB_WORDS (gj_hip.h) for the layout */
@@ -184,6 +282,11 @@ int gj_huffman_decoder_table2(const uint8_t bits[17], const uint8_t* vals, int i
 #include <stdlib.h>
 
 #include "gpujpeg_amd_ext.h"
+
+int gpujpeg_amd_host_huffman_optimal(const uint32_t freq[256], uint8_t bits[17], uint8_t vals[256])
+{
+    return gj_huffman_optimal(freq, bits, vals);
+}
 
 int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], const uint8_t* vals, int is_ac)
 {

@@ -372,7 +372,8 @@ static void exif_app1(struct bw* w, const gj_geom* g, const struct gpujpeg_image
 }
 
 size_t gj_write_main_header(uint8_t* out, size_t out_cap, const gj_geom* g, const struct gpujpeg_parameters* param, enum gpujpeg_header_type header_type,
-                            const uint8_t qraw[2][64], const struct gpujpeg_image_metadata* md, const struct gj_exif_tags* exif_tags)
+                            const uint8_t qraw[2][64], const struct gpujpeg_image_metadata* md, const struct gj_exif_tags* exif_tags,
+                            const struct gj_huff_spec* huff)
 {
     struct bw w = {out, 0, out_cap}; /* (returns the size the header needs: larger than out_cap = it does not fit, and was cut) */
     marker(&w, 0xD8);
@@ -416,14 +417,14 @@ size_t gj_write_main_header(uint8_t* out, size_t out_cap, const gj_geom* g, cons
         b1(&w, g->comp[c].type == GJ_LUMA ? 0 : 1);
     }
     seen = 0;
-    for (int c = 0; c < g->comp_count; c++) { /* DHT: DC then AC table of each type that occurs */
+    for (int c = 0; c < g->comp_count; c++) { /* DHT: DC then AC table of each type that occurs (Annex K.3, or the frame's own tables) */
         const int t = g->comp[c].type;
         if (seen & (1u << t)) continue;
         seen |= 1u << t;
         for (int ac = 0; ac < 2; ac++) {
             const uint8_t *bits, *vals;
             int count;
-            gj_huffman_std_spec(t, ac, &bits, &vals, &count);
+            gj_huffman_spec_table(huff, t, ac, &bits, &vals, &count);
             marker(&w, 0xC4);
             b2(&w, count + 2 + 1 + 16);
             b1(&w, (ac ? 16 : 0) + t);

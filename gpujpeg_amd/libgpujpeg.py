@@ -25,6 +25,9 @@ ENCODER_INPUT_IMAGE, ENCODER_INPUT_OPENGL_TEXTURE, ENCODER_INPUT_GPU_IMAGE = 0, 
 (DECODER_OUTPUT_INTERNAL_BUFFER, DECODER_OUTPUT_CUSTOM_BUFFER, DECODER_OUTPUT_OPENGL_TEXTURE,
  DECODER_OUTPUT_CUDA_BUFFER, DECODER_OUTPUT_CUSTOM_CUDA_BUFFER) = range(5)
 RESTART_AUTO, RESTART_NONE = -1, 0
+# encoder option of the MI355X build (gpujpeg_amd_ext.h: GPUJPEG_AMD_ENC_OPT_HUFFMAN): Annex K.3 tables, or tables built per frame
+ENC_OPT_HUFFMAN = "enc_opt_huffman"
+ENC_HUFFMAN_STANDARD, ENC_HUFFMAN_OPTIMAL = "standard", "optimal"
 
 
 def MK_SUBSAMPLING(*f):
@@ -290,11 +293,12 @@ class Encoder:
         """Leave the quantised coefficients of the following encode calls in HBM (for coefficients())."""
         self.lib.L.gpujpeg_amd_encoder_keep_coefficients(self.h, int(enabled))
 
-    def kernel_times(self):
+    def kernel_times(self, count=5):
+        """durations of the last perf_stats call's kernels; count=6 adds [5] k_huffman_count (optimal tables)"""
         ms = (C.c_float * 8)()
         if self.lib.L.gpujpeg_amd_encoder_get_kernel_times(self.h, ms) != 0:
             return None
-        return list(ms)[:5]
+        return list(ms)[:count]
 
     def coefficients(self, count):
         a = np.empty(count, np.int16)

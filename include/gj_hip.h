@@ -215,15 +215,22 @@ typedef struct gj_enc_job {
     int flipped;                   /* enc_opt_flipped: flip the component planes vertically after the colour stage (generic path) */
     uint32_t channel_remap;        /* enc_opt_channel_remap: packed mapping, 0 = none; applied to d_raw IN PLACE before anything else */
     gj_batch batch;                /* count > 1: a batch of frames (fully fused 4:4:4 kernel only; d_result / h_result hold two words per frame) */
+    /* Per-frame optimal Huffman tables (enc_opt_huffman=optimal) split a frame's encode in two calls, both through the coefficient planes:
+     * GJ_ENC_STAGE_COUNT   pixels -> planes, then k_huffman_count adds the frame's symbol counts to d_huff_freq (zeroed first on the stream);
+     * GJ_ENC_STAGE_CODE    planes -> k_huffman (with the tables d_huff_lut points to) -> k_scan_segments -> k_assemble (+ k_segment_info).
+     * GJ_ENC_STAGE_ALL (0) is the one-call encode of every other frame. */
+    int stage;
+    uint32_t* d_huff_freq;         /* GJ_ENC_STAGE_COUNT: [2 table types][DC, AC][256] symbol counts */
 } gj_enc_job;
+enum { GJ_ENC_STAGE_ALL = 0, GJ_ENC_STAGE_COUNT = 1, GJ_ENC_STAGE_CODE = 2 };
 /* 1 when gj_hip_encode takes a batch (gj_enc_job::batch.count > 1) of this job's configuration */
 GJ_HIP_API int gj_hip_encode_batchable(const gj_enc_job* job);
 /* 1 when gj_hip_encode codes this job through tile streams + k_gather (the launch that uses and clears gj_enc_job::tail_set's group totals) */
 GJ_HIP_API int gj_hip_encode_tiles(const gj_enc_job* job);
 
-/* events (may be NULL): 0 start, 1 after preprocess, 2 after DCT/quant, 3 after k_huffman, 4 after k_scan_segments,
- * 5 after k_assemble (+ segment info) */
-#define GJ_ENC_EVENTS 6
+/* events (may be NULL): 0 start, 1 after preprocess, 2 after DCT/quant (GJ_ENC_STAGE_CODE: its start), 3 after k_huffman, 4 after k_scan_segments,
+ * 5 after k_assemble (+ segment info); GJ_ENC_STAGE_COUNT: 6 after DCT/quant, 7 after k_huffman_count (and nothing from 2 on) */
+#define GJ_ENC_EVENTS 8
 GJ_HIP_API int gj_hip_encode(const gj_enc_job* job, gj_stream_t stream, gj_event_t ev[GJ_ENC_EVENTS]);
 
 

@@ -69,10 +69,22 @@ GPUJPEG_API int gpujpeg_amd_host_geometry(const struct gpujpeg_parameters* param
  * gpujpeg_decoder_decode does and reports 0 = accepted, -1 = rejected (over-subscribed or more than 256 symbols). Lets the CPU
  * test-suite feed hostile tables to the builders without a GPU. */
 GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], const uint8_t* vals, int is_ac);
+/* Encoder option (gpujpeg_encoder_set_option): Huffman tables of the written streams.
+ *   "standard" (default)  the typical tables of ITU T.81 Annex K.3 -- byte for byte the reference's streams;
+ *   "optimal"             per frame, tables built from the frame's own symbol counts (counted on the GPU, k_huffman_count): smaller files
+ *                         with the same coefficients. One more host wait per frame (the 4 KiB histogram), and the frame goes through the
+ *                         coefficient planes; batch calls code such frames one by one. Outside reference parity by construction. */
+#define GPUJPEG_AMD_ENC_OPT_HUFFMAN "enc_opt_huffman"
+#define GPUJPEG_AMD_ENC_HUFFMAN_VAL_STANDARD "standard"
+#define GPUJPEG_AMD_ENC_HUFFMAN_VAL_OPTIMAL "optimal"
+/* Host-only: the table enc_opt_huffman=optimal builds for one class from symbol counts freq[256] (ITU T.81 Annex K.2: Figures K.1, K.3, K.4;
+ * reserved code point, ties to the larger symbol value), code lengths limited to the largest L of 16 .. 10 whose table the library's
+ * two-level decode tables take. Writes BITS (bits[1..16]) and HUFFVAL; returns L, or -1 when no count is non-zero. */
+GPUJPEG_API int gpujpeg_amd_host_huffman_optimal(const uint32_t freq[256], uint8_t bits[17], uint8_t vals[256]);
 
 /* per-kernel durations (ms, hipEvents on the coder's stream) of the last call made with perf_stats != 0:
  * encoder: [0] preprocess, [1] DCT+quant (fused path: preprocess included), [2] k_huffman or k_encode_*, [3] k_gather (behind k_huffman:
- *          k_scan_segments), [4] k_assemble (behind k_huffman only)
+ *          k_scan_segments), [4] k_assemble (behind k_huffman only), [5] k_huffman_count (enc_opt_huffman=optimal; 0 otherwise)
  * decoder: [0] entropy decoder, [1] IDCT (fused path: postprocess included), [2] postprocess, [3] marker scan (k_markers; 0 when the host walked the stream) */
 GPUJPEG_API int gpujpeg_amd_encoder_get_kernel_times(struct gpujpeg_encoder* encoder, float ms[8]);
 GPUJPEG_API int gpujpeg_amd_decoder_get_kernel_times(struct gpujpeg_decoder* decoder, float ms[8]);
