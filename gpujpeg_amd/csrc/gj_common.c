@@ -511,6 +511,32 @@ int gj_ensure_device_buffer(void** p, size_t* cap, size_t need)
     return 0;
 }
 
+/* the same for pinned host memory; a buffer that has to grow is replaced by one of grow_to >= need bytes (the caller's headroom: reallocating
+ * pinned memory takes milliseconds) */
+int gj_ensure_pinned_buffer(void** p, size_t* cap, size_t need, size_t grow_to)
+{
+    if (need <= *cap) return 0;
+    gj_hip_host_free(*p);
+    *p = gj_hip_host_alloc(grow_to);
+    *cap = *p ? grow_to : 0;
+    return *p ? 0 : -1;
+}
+
+/* dec_opt_channel_remap / enc_opt_channel_remap (packed, 0 = none) against the pixel format of the call */
+int gj_channel_remap_check(unsigned remap, enum gpujpeg_pixel_format pf)
+{
+    if (!remap) return 0;
+    if ((int)(remap >> 24) != gpujpeg_pixel_format_get_comp_count(pf)) {
+        GJ_ERROR("Wrong channel remapping given, given %u channels but pixel format has %d!\n", remap >> 24, gpujpeg_pixel_format_get_comp_count(pf));
+        return -1;
+    }
+    if (pf != GPUJPEG_U8 && pf != GPUJPEG_444_U8_P012 && pf != GPUJPEG_4444_U8_P0123 && pf != GPUJPEG_444_U8_P0P1P2) {
+        GJ_ERROR("Channel remapping is implemented for pixel formats whose pixels do not share samples (u8, 444-u8-p012, 4444-u8-p0123, 444-u8-p0p1p2).\n");
+        return -1;
+    }
+    return 0;
+}
+
 int gj_timers_create(struct gj_timers* t)
 {
     memset(t, 0, sizeof *t);

@@ -188,12 +188,8 @@ static int decoder_configure(struct gpujpeg_decoder* d, const struct gpujpeg_par
     if (gj_ensure_device_buffer((void**)&c->d_coefs, &c->d_coefs_cap, g->data_size * sizeof(int16_t)) != 0) return -1;
     if (gj_ensure_device_buffer((void**)&c->d_planes, &c->d_planes_cap, g->data_size) != 0) return -1;
     if (gj_ensure_device_buffer((void**)&d->d_seg, &d->d_seg_cap, ((size_t)g->segment_count * 3 + 4) * sizeof(uint32_t)) != 0) return -1;
-    if ((size_t)g->segment_count * 3 * sizeof(uint32_t) > d->h_seg_cap) {
-        gj_hip_host_free(d->h_seg);
-        d->h_seg_cap = (size_t)g->segment_count * 3 * sizeof(uint32_t);
-        d->h_seg = gj_hip_host_alloc(d->h_seg_cap);
-        if (!d->h_seg) { d->h_seg_cap = 0; return -1; }
-    }
+    const size_t seg_bytes = (size_t)g->segment_count * 3 * sizeof(uint32_t);
+    if (gj_ensure_pinned_buffer((void**)&d->h_seg, &d->h_seg_cap, seg_bytes, seg_bytes) != 0) return -1;
     c->configured = true;
     return 0;
 }
@@ -243,409 +239,470 @@ static int accept_device_scan(const gj_scan_summary* su, struct gj_reader_result
 
 /* the longest restart segment of the device's table: the maximum of the per-chunk values the marker scan left (valid once the stream has been
  * waited for) */
-static void summary_take_maxlen(struct gpujpeg_decoder* d)
+static void summary_take_maxlen(gj_scan_summary* su, const uint32_t* parts, uint32_t n)
 {
     uint32_t m = 0;
-    for (uint32_t i = 0; i < d->maxlen_parts; i++)
-        if (d->h_maxlen[i] > m) m = d->h_maxlen[i];
-    d->h_summary->max_seg_len = m;
+    for (uint32_t i = 0; i < n; i++)
+        if (parts[i] > m) m = parts[i];
+    su->max_seg_len = m;
 }
 
-/* careful: this call must not use the entropy decoders that take whole restart segments into LDS (a previous attempt on this stream met a
- * segment that does not fit), and it does not launch on the header cache */
-static int decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t image_size, struct gpujpeg_decoder_output* output, bool careful)
+/* entropy-coded bytes per scan: what the entropy decoder's batch sizes are cut to (luminance segments are 2-3 x the chrominance ones) */
+static void summary_scan_bytes(const gj_scan_summary* su, uint32_t bytes[GJ_MAX_COMP])
+{
+    for (int sc = 0; sc < GJ_MAX_COMP; sc++) bytes[sc] = sc < (int)su->scan_count ? su->scan_end[sc] - su->scan_start[sc] : 0;
+}
+
+/* The acceptance rule of a launch on the cached header (single frames and batches): now that the summary of the stream is on the host, was
+ * the stream what the launch assumed? Same header, nothing the fast kernels could not stage, the usual scan structure with the cached
+ * header's table selectors, and every segment present (a stream with missing segments needs the planes cleared first). */
+static bool spec_summary_ok(const struct gpujpeg_decoder* d, const gj_scan_summary* su, const gj_geom* g)
+{
+    const struct gj_reader_result* r = &d->hdr_cache_r;
+    struct gj_reader_result chk = *r;
+    if (su->header_differs != 0 || su->seq_overflow != 0 || accept_device_scan(su, &chk, g) != 0 || (int)su->segment_count != g->segment_count) return false;
+    for (int i = 0; i < g->comp_count; i++)
+        if (chk.huff_map[i][0] != r->huff_map[i][0] || chk.huff_map[i][1] != r->huff_map[i][1]) return false;
+    return true;
+}
+
+/* what the kernels are to know about the last accepted frame of this header (speculative launches and batches plan with it) */
+static void remember_summary(struct gpujpeg_decoder* d, const gj_scan_summary* su)
+{
+    summary_scan_bytes(su, d->last_scan_bytes);
+    d->last_max_seg_len = su->max_seg_len;
+}
+
+static void geom_take_tables(gj_geom* g, const struct gj_reader_result* r)
+{
+    for (int i = 0; i < g->comp_count; i++) {
+        g->comp[i].q_table = r->quant_map[i];
+        g->comp[i].dc_table = r->huff_map[i][0];
+        g->comp[i].ac_table = r->huff_map[i][1];
+    }
+}
+
+/* everything of a job that comes from the decoder's state and options (geometry with its table selectors included: set those first) */
+static void dec_job_base(const struct gpujpeg_decoder* d, bool tab2_ok, gj_dec_job* job)
+{
+    const struct gj_coder* c = &d->coder;
+    memset(job, 0, sizeof *job);
+    job->g = c->geom;
+    job->d_huff_tab = d->d_huff_tab;
+    job->d_qtab = d->d_qtab;
+    job->d_qtabf = (const float*)(const void*)(d->d_huff_tab + GJ_TABS_QF_OFFSET);
+    job->d_huff_tab2 = tab2_ok ? d->d_qtab + 4 * 64 : NULL;
+    job->d_coefs = c->d_coefs;
+    job->d_planes = c->d_planes;
+    job->use_fused = d->use_fused && !d->flipped;
+    job->flipped = d->flipped;
+    job->channel_remap = d->channel_remap;
+    job->tune = d->tune;
+}
+
+/* One call = up to three attempts (decoder_decode). What the stages of an attempt share: */
+struct dec_call {
+    uint8_t* image; size_t image_size;       /* the stream as the caller gave it */
+    struct gpujpeg_decoder_output* output;
+    bool jpeg_on_device;                     /* device-resident stream (MI355X extension) */
+    bool stats; double t_read0;
+    bool careful;        /* this attempt must not use the entropy decoders that take whole restart segments into LDS (a previous attempt on this
+                            stream met a segment that does not fit), and it does not launch on the header cache */
+    bool spec;           /* launched on the cached header, validated afterwards */
+    bool device_scan;    /* the device finds the segments (decided by dec_headers; dec_segment_table may hand over to the host walk) */
+    bool host_io;        /* copies from or into the caller's host memory have been queued on the coder's stream */
+    const uint8_t* himage; /* host view of (at least the headers of) the stream */
+    uint8_t* host_copy;    /* the whole of a device-resident stream for the host walk; freed by decoder_decode */
+    const uint8_t* d_jpeg;
+    uint8_t* d_raw;
+    int seg_count;
+    const uint32_t* d_seg_count;
+    gj_scan_deferred scan_deferred;
+    bool tab2_ok;
+    struct gj_reader_result r;
+};
+/* what an attempt and its stages return: 0, a negative error code of the call, or DEC_AGAIN (dec_after only: another attempt, with k->careful as
+ * this one left it). dec_device_scan alone uses 1 for something else: "not a stream for the device scan". */
+enum { DEC_DONE = 0, DEC_FAILED = -1, DEC_AGAIN = 1 };
+
+/* the one place that brings the whole of a device-resident stream to the host, and the full parse of the host walk; 0 or the error code of the call */
+static int dec_host_view(struct gpujpeg_decoder* d, struct dec_call* k)
 {
     struct gj_coder* c = &d->coder;
-    GJ_HT_START(c);
-    const bool stats = c->param.perf_stats != 0 || c->param.verbose >= GPUJPEG_LL_STATUS;
-    c->start_time = stats ? gpujpeg_get_time() : 0;
-    memset(&c->stats, 0, sizeof c->stats);
-    const double t_read0 = stats ? gpujpeg_get_time() : 0;
-    uint8_t* host_copy = NULL;
-    int rc = -1;
+    if (k->jpeg_on_device && !k->host_copy) {
+        k->host_copy = malloc(k->image_size);
+        if (!k->host_copy || gj_hip_memcpy_d2h(k->host_copy, k->image, k->image_size, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) return -1;
+    }
+    k->himage = k->jpeg_on_device ? k->host_copy : k->image;
+    const int rc = gj_reader_parse(k->himage, k->image_size, c->param.verbose, d->ff_cs_itu601_is_709, d->req_pixel_format, d->req_color_space,
+                                   d->req_alignment, &k->r, false);
+    if (rc != 0) GJ_ERROR("Decoder failed when decoding image data!\n");
+    return rc > 0 ? -1 : rc; /* (the reader's own error code is what the call returns; a positive one would read as DEC_AGAIN) */
+}
 
-    /* ---- 1. headers. A device-resident stream (MI355X extension) is parsed from a 64 KiB window. ---- */
-    const bool jpeg_on_device = gj_hip_is_device_ptr(image) != 0;
-    const uint8_t* himage = image; /* host view of (at least the headers of) the stream */
-    size_t hsize = image_size;
-    struct gj_reader_result r;
-    bool device_scan = !d->host_scan;
+/* ---- 1. headers. A device-resident stream (MI355X extension) is parsed from a 64 KiB window. Decides who finds the segments. ---- */
+static int dec_headers(struct gpujpeg_decoder* d, struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    const bool may_scan = !d->host_scan;
+    k->himage = k->image;
     /* speculative path: same header as last time (compared on the device for a device-resident stream) */
-    bool spec = device_scan && d->hdr_cache_valid && image_size > d->hdr_cache_len && !d->tune.dec_no_spec && !careful;
-    if (spec && !jpeg_on_device) spec = memcmp(image, d->hdr_cache, d->hdr_cache_len) == 0;
-    if (spec) {
-        r = d->hdr_cache_r;
-        rc = 0;
-    } else {
-    if (jpeg_on_device) {
-        hsize = image_size < GJ_HDR_WINDOW ? image_size : GJ_HDR_WINDOW;
-        if (gj_hip_memcpy_d2h(d->h_hdr, image, hsize, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) return -1;
-        himage = d->h_hdr;
+    k->spec = may_scan && d->hdr_cache_valid && k->image_size > d->hdr_cache_len && !d->tune.dec_no_spec && !k->careful;
+    if (k->spec && !k->jpeg_on_device) k->spec = memcmp(k->image, d->hdr_cache, d->hdr_cache_len) == 0;
+    if (k->spec) {
+        k->r = d->hdr_cache_r;
+        k->device_scan = true;
+        return 0;
     }
-    rc = device_scan ? gj_reader_parse(himage, hsize, hsize < image_size ? GPUJPEG_LL_QUIET - 1 : c->param.verbose, d->ff_cs_itu601_is_709,
-                                       d->req_pixel_format, d->req_color_space, d->req_alignment, &r, true)
-                     : -1;
-    if (rc != 0 || r.seg_info_count[0] > 0) device_scan = false; /* odd header, or an APP13 index that makes scanning unnecessary */
-    if (!device_scan) {
-        if (jpeg_on_device) { /* the host walk needs the whole stream */
-            host_copy = malloc(image_size);
-            if (!host_copy || gj_hip_memcpy_d2h(host_copy, image, image_size, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) goto out;
-            himage = host_copy;
-            hsize = image_size;
-        }
-        rc = gj_reader_parse(himage, image_size, c->param.verbose, d->ff_cs_itu601_is_709, d->req_pixel_format, d->req_color_space,
-                             d->req_alignment, &r, false);
-        if (rc != 0) {
-            GJ_ERROR("Decoder failed when decoding image data!\n");
-            goto out;
-        }
+    size_t hsize = k->image_size;
+    if (k->jpeg_on_device) {
+        hsize = k->image_size < GJ_HDR_WINDOW ? k->image_size : GJ_HDR_WINDOW;
+        if (gj_hip_memcpy_d2h(d->h_hdr, k->image, hsize, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) return -1;
+        k->himage = d->h_hdr;
     }
-    }
-    rc = -1;
-    for (int i = 0; i < GPUJPEG_METADATA_COUNT; i++) d->metadata.vals[i] = r.metadata.vals[i];
-    if (decoder_configure(d, &r.param, &r.param_image) != 0) goto out;
-    c->init_end_time = stats ? gpujpeg_get_time() : 0;
-    gj_geom* g = &c->geom;
+    /* an odd header, or an APP13 index that makes scanning unnecessary: the host walk */
+    k->device_scan = may_scan &&
+                     gj_reader_parse(k->himage, hsize, hsize < k->image_size ? GPUJPEG_LL_QUIET - 1 : c->param.verbose, d->ff_cs_itu601_is_709,
+                                     d->req_pixel_format, d->req_color_space, d->req_alignment, &k->r, true) == 0 &&
+                     k->r.seg_info_count[0] == 0;
+    return k->device_scan ? 0 : dec_host_view(d, k);
+}
 
-    /* ---- 2. stream to HBM ---- */
-    if (stats || !jpeg_on_device) gj_hip_event_record(c->timers.copy_in[0], c->stream); /* (without perf_stats too: see gj_internal.h, copy markers) */
-    const uint8_t* d_jpeg;
-    if (jpeg_on_device) {
-        d_jpeg = image;
-    } else {
-        if (gj_ensure_device_buffer((void**)&d->d_jpeg, &d->d_jpeg_cap, image_size + 64) != 0) goto out;
-        if (gj_hip_memcpy_h2d(d->d_jpeg, image, image_size, c->stream) != 0) goto out; /* (on the coder's own stream, not in the upload lane behind other coders' images) */
-        d_jpeg = d->d_jpeg;
+/* ---- 2. stream to HBM ---- */
+static int dec_upload(struct gpujpeg_decoder* d, struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    if (k->stats || !k->jpeg_on_device) gj_hip_event_record(c->timers.copy_in[0], c->stream); /* (without perf_stats too: see gj_internal.h, copy markers) */
+    if (k->jpeg_on_device) {
+        k->d_jpeg = k->image;
+        return 0;
     }
+    if (gj_ensure_device_buffer((void**)&d->d_jpeg, &d->d_jpeg_cap, k->image_size + 64) != 0) return -1;
+    k->host_io = true;
+    k->d_jpeg = d->d_jpeg;
+    return gj_hip_memcpy_h2d(d->d_jpeg, k->image, k->image_size, c->stream); /* (on the coder's own stream, not in the upload lane behind other coders' images) */
+}
 
-    /* ---- 3. segment table ---- */
-    int seg_count = 0;
-    const uint32_t* d_seg_count = NULL;
-    gj_scan_summary* sum_cur = d->d_summary;
-    gj_scan_deferred scan_deferred;
-    memset(&scan_deferred, 0, sizeof scan_deferred);
+/* the marker scan on the device: the plain one is waited for and judged here (-> 1 when the stream is not for it), a speculative one leaves its
+ * second launch to gj_hip_decode and is judged once everything has run */
+static int dec_device_scan(struct gpujpeg_decoder* d, struct dec_call* k, size_t S)
+{
+    struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    const size_t begin = k->r.scan_begin[0];
+    const size_t words = gj_hip_find_segments_scratch_words(begin, k->image_size, (uint32_t)g->segment_count);
+    if (gj_ensure_device_buffer((void**)&d->d_scan_scratch, &d->d_scan_scratch_cap, words * sizeof(uint32_t)) != 0) return -1;
+    /* (a speculative launch on a device-resident stream has its header compared with the cached one by the scan's first kernel) */
+    const bool cmp = k->spec && k->jpeg_on_device;
+    const uint8_t* d_hdr = cmp ? d->d_hdr_cache : NULL;
+    const uint32_t hdr_len = cmp ? (uint32_t)d->hdr_cache_len : 0u;
+    /* the kernels write what the host validates straight into pinned host memory */
+    /* (a word per scanning workgroup, or -- when the table launch is folded into the token decoder -- per batch of that kernel: at most a few thousand) */
+    size_t max_chunks = gj_hip_find_segments_max_chunks(begin, k->image_size);
+    if (max_chunks < 4096) max_chunks = 4096;
+    int frc = gj_ensure_pinned_buffer((void**)&d->h_maxlen, &d->h_maxlen_cap, max_chunks * sizeof(uint32_t), max_chunks * sizeof(uint32_t) * 2);
+    const uint32_t maxlen_cap = (uint32_t)(d->h_maxlen_cap / sizeof(uint32_t));
+    d->h_summary->rst_irregular = 0;
+    d->h_summary->seq_overflow = 0;
+    d->h_summary->header_differs = 0;
+    GJ_HT(c, 0);
+    if (k->stats) gj_hip_event_record(c->timers.ev[4], c->stream); /* (the marker scan is GPU time of this call: events 4 and 5 bracket it) */
+    /* speculative launches leave the scan's second launch to gj_hip_decode: the token decoder does without it (gj_scan_deferred) */
+    if (frc == 0 && k->spec)
+        frc = gj_hip_find_segments_deferred(g, k->d_jpeg, begin, k->image_size, d->d_seg, d->d_seg + S, d->d_seg + 2 * S, (uint32_t)g->segment_count,
+                                            d->d_scan_scratch, d->d_summary, d_hdr, hdr_len, d->h_summary, d->h_maxlen, maxlen_cap, &d->maxlen_parts,
+                                            c->stream, &d->tune, &k->scan_deferred);
+    else if (frc == 0)
+        frc = gj_hip_find_segments(g, k->d_jpeg, begin, k->image_size, d->d_seg, d->d_seg + S, d->d_seg + 2 * S, (uint32_t)g->segment_count,
+                                   d->d_scan_scratch, d->d_summary, d_hdr, hdr_len, d->h_summary, d->h_maxlen, maxlen_cap, &d->maxlen_parts, c->stream,
+                                   &d->tune);
+    if (k->stats) gj_hip_event_record(c->timers.ev[5], c->stream);
+    d->scan_timed = k->stats;
+    if (frc != 0 || (!k->spec && gj_hip_stream_sync(c->stream) != 0)) {
+        GJ_ERROR("Marker scan failed: %s\n", gj_hip_last_error());
+        return -1;
+    }
+    if (k->spec) { /* the kernels take the segment count from the device; the summary is checked once everything has run */
+        k->seg_count = g->segment_count;
+        k->d_seg_count = &d->d_summary->segment_count;
+        return 0;
+    }
+    summary_take_maxlen(d->h_summary, d->h_maxlen, d->maxlen_parts);
+    if (accept_device_scan(d->h_summary, &k->r, g) != 0) return 1;
+    k->seg_count = (int)d->h_summary->segment_count;
+    return 0;
+}
+
+/* the reference's way: the host walks the stream and the table is uploaded */
+static int dec_host_scan(struct gpujpeg_decoder* d, struct dec_call* k, size_t S)
+{
+    struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    if (gj_reader_split_scans(k->himage, &k->r, g, &d->segs, c->param.verbose) != 0) return -1;
+    if (d->segs.count > g->segment_count) {
+        GJ_ERROR("Decoder can't decode image that has segment count %d (maximum segment count for specified parameters is %d)!\n", d->segs.count, g->segment_count);
+        return -1;
+    }
+    k->seg_count = d->segs.count;
+    const size_t ns = (size_t)k->seg_count;
+    if (gj_ensure_pinned_buffer((void**)&d->h_seg, &d->h_seg_cap, ns * 3 * sizeof(uint32_t), ns * 3 * sizeof(uint32_t)) != 0) return -1;
+    memcpy(d->h_seg, d->segs.pos, ns * sizeof(uint32_t));
+    memcpy(d->h_seg + ns, d->segs.len, ns * sizeof(uint32_t));
+    memcpy(d->h_seg + 2 * ns, d->segs.index, ns * sizeof(uint32_t));
+    if (gj_hip_memcpy_h2d(d->d_seg, d->h_seg, ns * sizeof(uint32_t), c->stream) != 0 ||
+        gj_hip_memcpy_h2d(d->d_seg + S, d->h_seg + ns, ns * sizeof(uint32_t), c->stream) != 0 ||
+        gj_hip_memcpy_h2d(d->d_seg + 2 * S, d->h_seg + 2 * ns, ns * sizeof(uint32_t), c->stream) != 0)
+        return -1;
+    return 0;
+}
+
+/* ---- 3. segment table ---- */
+static int dec_segment_table(struct gpujpeg_decoder* d, struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    k->seg_count = 0;
+    k->d_seg_count = NULL;
+    memset(&k->scan_deferred, 0, sizeof k->scan_deferred);
     const size_t S = (size_t)g->segment_count + GJ_MAX_COMP;
-    if (gj_ensure_device_buffer((void**)&d->d_seg, &d->d_seg_cap, (S * 4 + 8) * sizeof(uint32_t)) != 0) goto out;
-    if (device_scan) {
-        const size_t words = gj_hip_find_segments_scratch_words(r.scan_begin[0], image_size, (uint32_t)g->segment_count);
-        if (gj_ensure_device_buffer((void**)&d->d_scan_scratch, &d->d_scan_scratch_cap, words * sizeof(uint32_t)) != 0) goto out;
-        /* (a speculative launch on a device-resident stream has its header compared with the cached one by the scan's first kernel) */
-        const bool cmp = spec && jpeg_on_device;
-        /* the kernels write what the host validates straight into pinned host memory */
-        /* (a word per scanning workgroup, or -- when the table launch is folded into the token decoder -- per batch of that kernel: at most a few thousand) */
-        size_t max_chunks = gj_hip_find_segments_max_chunks(r.scan_begin[0], image_size);
-        if (max_chunks < 4096) max_chunks = 4096;
-        int frc = 0;
-        if (max_chunks * sizeof(uint32_t) > d->h_maxlen_cap) {
-            gj_hip_host_free(d->h_maxlen);
-            d->h_maxlen_cap = max_chunks * sizeof(uint32_t) * 2;
-            d->h_maxlen = gj_hip_host_alloc(d->h_maxlen_cap);
-            if (!d->h_maxlen) { d->h_maxlen_cap = 0; frc = -1; }
-        }
-        d->h_summary->rst_irregular = 0;
-        d->h_summary->seq_overflow = 0;
-        d->h_summary->header_differs = 0;
-        GJ_HT(c, 0);
-        if (stats) gj_hip_event_record(c->timers.ev[4], c->stream); /* (the marker scan is GPU time of this call: events 4 and 5 bracket it) */
-        /* speculative launches leave the scan's second launch to gj_hip_decode: the token decoder does without it (gj_scan_deferred) */
-        if (frc == 0 && spec)
-            frc = gj_hip_find_segments_deferred(g, d_jpeg, r.scan_begin[0], image_size, d->d_seg, d->d_seg + S, d->d_seg + 2 * S, (uint32_t)g->segment_count,
-                                                d->d_scan_scratch, sum_cur, cmp ? d->d_hdr_cache : NULL, cmp ? (uint32_t)d->hdr_cache_len : 0u, d->h_summary,
-                                                d->h_maxlen, (uint32_t)(d->h_maxlen_cap / sizeof(uint32_t)), &d->maxlen_parts, c->stream, &d->tune, &scan_deferred);
-        else if (frc == 0)
-            frc = gj_hip_find_segments(g, d_jpeg, r.scan_begin[0], image_size, d->d_seg, d->d_seg + S, d->d_seg + 2 * S, (uint32_t)g->segment_count,
-                                       d->d_scan_scratch, sum_cur, cmp ? d->d_hdr_cache : NULL, cmp ? (uint32_t)d->hdr_cache_len : 0u, d->h_summary,
-                                       d->h_maxlen, (uint32_t)(d->h_maxlen_cap / sizeof(uint32_t)), &d->maxlen_parts, c->stream, &d->tune);
-        if (stats) gj_hip_event_record(c->timers.ev[5], c->stream);
-        d->scan_timed = stats;
-        if (frc != 0 || (!spec && gj_hip_stream_sync(c->stream) != 0)) {
-            GJ_ERROR("Marker scan failed: %s\n", gj_hip_last_error());
-            goto out;
-        }
-        if (!spec) summary_take_maxlen(d);
-        if (spec) { /* the kernels take the segment count from the device; the summary is checked once everything has run */
-            seg_count = g->segment_count;
-            d_seg_count = &sum_cur->segment_count;
-        } else if (accept_device_scan(d->h_summary, &r, g) == 0) {
-            seg_count = (int)d->h_summary->segment_count;
-            d_seg_count = NULL;
-        } else {
+    if (gj_ensure_device_buffer((void**)&d->d_seg, &d->d_seg_cap, (S * 4 + 8) * sizeof(uint32_t)) != 0) return -1;
+    if (k->device_scan) {
+        const int src = dec_device_scan(d, k, S);
+        if (src < 0) return -1;
+        if (src > 0) {
             /* unusual stream (markers between scans, damaged data...): the host walk decides */
             GJ_DEBUG(c->param.verbose, "device marker scan not applicable (status %u), walking the stream on the host\n", d->h_summary->status);
-            device_scan = false;
-            if (jpeg_on_device && !host_copy) {
-                host_copy = malloc(image_size);
-                if (!host_copy || gj_hip_memcpy_d2h(host_copy, image, image_size, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) goto out;
-                himage = host_copy;
-            } else if (!jpeg_on_device) {
-                himage = image;
-            }
-            rc = gj_reader_parse(himage, image_size, c->param.verbose, d->ff_cs_itu601_is_709, d->req_pixel_format, d->req_color_space,
-                                 d->req_alignment, &r, false);
-            if (rc != 0) {
-                GJ_ERROR("Decoder failed when decoding image data!\n");
-                goto out;
-            }
-            rc = -1;
+            k->device_scan = false;
+            const int vrc = dec_host_view(d, k);
+            if (vrc != 0) return vrc;
         }
     }
-    if (!device_scan) {
-        if (gj_reader_split_scans(himage, &r, g, &d->segs, c->param.verbose) != 0) goto out;
-        if (d->segs.count > g->segment_count) {
-            GJ_ERROR("Decoder can't decode image that has segment count %d (maximum segment count for specified parameters is %d)!\n", d->segs.count, g->segment_count);
-            goto out;
-        }
-        seg_count = d->segs.count;
-        const size_t ns = (size_t)seg_count;
-        if (ns * 3 * sizeof(uint32_t) > d->h_seg_cap) {
-            gj_hip_host_free(d->h_seg);
-            d->h_seg_cap = ns * 3 * sizeof(uint32_t);
-            d->h_seg = gj_hip_host_alloc(d->h_seg_cap);
-            if (!d->h_seg) { d->h_seg_cap = 0; goto out; }
-        }
-        memcpy(d->h_seg, d->segs.pos, ns * sizeof(uint32_t));
-        memcpy(d->h_seg + ns, d->segs.len, ns * sizeof(uint32_t));
-        memcpy(d->h_seg + 2 * ns, d->segs.index, ns * sizeof(uint32_t));
-        if (gj_hip_memcpy_h2d(d->d_seg, d->h_seg, ns * sizeof(uint32_t), c->stream) != 0 ||
-            gj_hip_memcpy_h2d(d->d_seg + S, d->h_seg + ns, ns * sizeof(uint32_t), c->stream) != 0 ||
-            gj_hip_memcpy_h2d(d->d_seg + 2 * S, d->h_seg + 2 * ns, ns * sizeof(uint32_t), c->stream) != 0)
-            goto out;
-    }
-    if (seg_count != g->segment_count && c->param.verbose >= 0) GJ_WARN("%d segments read, expected %d. Broken JPEG?\n", seg_count, g->segment_count);
-    c->stats.duration_stream = stats ? (gpujpeg_get_time() - t_read0) * 1000.0 : 0;
+    if (!k->device_scan && dec_host_scan(d, k, S) != 0) return -1;
+    if (k->seg_count != g->segment_count && c->param.verbose >= 0) GJ_WARN("%d segments read, expected %d. Broken JPEG?\n", k->seg_count, g->segment_count);
+    c->stats.duration_stream = k->stats ? (gpujpeg_get_time() - k->t_read0) * 1000.0 : 0;
+    return 0;
+}
 
-    /* ---- 4. tables: decode tables for every DHT slot present, natural-order quantisation tables ---- */
-    for (int i = 0; i < g->comp_count; i++) {
-        g->comp[i].q_table = r.quant_map[i];
-        g->comp[i].dc_table = r.huff_map[i][0];
-        g->comp[i].ac_table = r.huff_map[i][1];
-    }
-    bool tab2_ok = d->tab2_ok;
-    if (!spec) {
+/* ---- 4. tables: decode tables for every DHT slot present, natural-order quantisation tables (on the device already for the cached header) ---- */
+static int dec_tables(struct gpujpeg_decoder* d, struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    gj_geom* g = &c->geom;
+    const struct gj_reader_result* r = &k->r;
+    geom_take_tables(g, r);
+    k->tab2_ok = d->tab2_ok;
+    if (k->spec) return 0;
     memset(d->h_tabs, 0, GJ_TABS_WORDS * sizeof(uint16_t));
     for (int th = 0; th < 4; th++)
         for (int tc = 0; tc < 2; tc++)
-            if (r.h_present[th][tc] && gj_huffman_decoder_table(r.hbits[th][tc], r.hvals[th][tc], d->h_tabs + (th * 2 + tc) * GJ_DEC_TAB_WORDS) != 0) {
+            if (r->h_present[th][tc] && gj_huffman_decoder_table(r->hbits[th][tc], r->hvals[th][tc], d->h_tabs + (th * 2 + tc) * GJ_DEC_TAB_WORDS) != 0) {
                 GJ_ERROR("Invalid Huffman table %d/%d!\n", th, tc);
-                goto out;
+                return -1;
             }
     for (int t = 0; t < 4; t++)
-        if (r.q_present[t]) {
+        if (r->q_present[t]) {
             uint16_t* qi = d->h_tabs + 8 * GJ_DEC_TAB_WORDS + t * 64;
             float* qf = (float*)(void*)(d->h_tabs + GJ_TABS_QF_OFFSET) + t * 64;
-            gj_quant_table_inverse(r.qraw[t], qi);
+            gj_quant_table_inverse(r->qraw[t], qi);
             for (int i = 0; i < 64; i++) qf[i] = (float)qi[i];
         }
     /* two-level tables of the sub-sequence decoder: slots 0 and 1 only, every table has to fit the layout */
-    tab2_ok = true;
+    k->tab2_ok = true;
     for (int i = 0; i < g->comp_count; i++)
-        if (g->comp[i].dc_table > 1 || g->comp[i].ac_table > 1) tab2_ok = false;
-    for (int th = 0; th < 2 && tab2_ok; th++)
+        if (g->comp[i].dc_table > 1 || g->comp[i].ac_table > 1) k->tab2_ok = false;
+    for (int th = 0; th < 2 && k->tab2_ok; th++)
         for (int tc = 0; tc < 2; tc++)
-            if (r.h_present[th][tc] && gj_huffman_decoder_table2(r.hbits[th][tc], r.hvals[th][tc], tc,
-                                                                  d->h_tabs + 8 * GJ_DEC_TAB_WORDS + 4 * 64 + (th * 2 + tc) * GJ_DEC2_WORDS) != 0)
-                tab2_ok = false;
+            if (r->h_present[th][tc] && gj_huffman_decoder_table2(r->hbits[th][tc], r->hvals[th][tc], tc,
+                                                                   d->h_tabs + 8 * GJ_DEC_TAB_WORDS + 4 * 64 + (th * 2 + tc) * GJ_DEC2_WORDS) != 0)
+                k->tab2_ok = false;
     for (int i = 0; i < g->comp_count; i++) {
-        if (g->comp[i].q_table > 3 || g->comp[i].dc_table > 3 || g->comp[i].ac_table > 3 || !r.q_present[g->comp[i].q_table] ||
-            !r.h_present[g->comp[i].dc_table][0] || !r.h_present[g->comp[i].ac_table][1]) {
+        if (g->comp[i].q_table > 3 || g->comp[i].dc_table > 3 || g->comp[i].ac_table > 3 || !r->q_present[g->comp[i].q_table] ||
+            !r->h_present[g->comp[i].dc_table][0] || !r->h_present[g->comp[i].ac_table][1]) {
             GJ_ERROR("Component %d refers to a table that was not defined!\n", i);
-            goto out;
+            return -1;
         }
     }
     if (gj_hip_memcpy_h2d(d->d_huff_tab, d->h_tabs, GJ_TABS_WORDS * sizeof(uint16_t), c->stream) != 0) {
         GJ_ERROR("Decoder copy compressed data failed: %s\n", gj_hip_last_error());
-        goto out;
+        return -1;
     }
-    d->tab2_ok = tab2_ok;
-    }
-    if (stats) gj_hip_event_record(c->timers.copy_in[1], c->stream);
+    d->tab2_ok = k->tab2_ok;
+    return 0;
+}
 
-    /* ---- 5. destination (:336-375) ---- */
-    uint8_t* d_raw;
-    if (output->type == GPUJPEG_DECODER_OUTPUT_CUSTOM_CUDA_BUFFER) {
-        d_raw = output->data;
-    } else if (output->type == GPUJPEG_DECODER_OUTPUT_OPENGL_TEXTURE) {
+/* ---- 5. destination (:336-375) ---- */
+static int dec_destination(struct gpujpeg_decoder* d, struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    if (k->output->type == GPUJPEG_DECODER_OUTPUT_CUSTOM_CUDA_BUFFER) {
+        k->d_raw = k->output->data;
+    } else if (k->output->type == GPUJPEG_DECODER_OUTPUT_OPENGL_TEXTURE) {
         GJ_ERROR("OpenGL texture output is not supported by the MI355X build.\n");
-        goto out;
+        return -1;
     } else {
-        if (gj_ensure_device_buffer((void**)&c->d_raw_own, &c->d_raw_cap, g->raw_size) != 0) goto out;
-        d_raw = c->d_raw_own;
+        if (gj_ensure_device_buffer((void**)&c->d_raw_own, &c->d_raw_cap, c->geom.raw_size) != 0) return -1;
+        k->d_raw = c->d_raw_own;
     }
+    return 0;
+}
 
+/* ---- 6. the kernels ---- */
+static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    const size_t S = (size_t)g->segment_count + GJ_MAX_COMP;
     gj_dec_job job;
-    memset(&job, 0, sizeof job);
-    job.g = *g;
-    job.d_jpeg = d_jpeg;
-    job.jpeg_size = image_size;
+    dec_job_base(d, k->tab2_ok, &job);
+    job.d_jpeg = k->d_jpeg;
+    job.jpeg_size = k->image_size;
     job.d_seg_pos = d->d_seg;
     job.d_seg_len = d->d_seg + S;
     job.d_seg_index = d->d_seg + 2 * S;
-    job.seg_count = seg_count;
-    job.d_seg_count = d_seg_count;
-    job.scan = scan_deferred;
+    job.seg_count = k->seg_count;
+    job.d_seg_count = k->d_seg_count;
+    job.scan = k->scan_deferred;
     d->last_folded = 0;
     job.scan.folded = &d->last_folded;
-    if (spec) d->n_spec++;
-    job.d_huff_tab = d->d_huff_tab;
-    job.d_qtab = d->d_qtab;
-    job.d_qtabf = (const float*)(const void*)(d->d_huff_tab + GJ_TABS_QF_OFFSET);
-    job.d_huff_tab2 = tab2_ok ? d->d_qtab + 4 * 64 : NULL;
-    job.d_coefs = c->d_coefs;
-    job.d_planes = c->d_planes;
-    job.d_raw = d_raw;
-    job.use_fused = d->use_fused && !d->flipped;
-    job.flipped = d->flipped;
-    job.channel_remap = d->channel_remap;
-    if (d->channel_remap) {
-        const enum gpujpeg_pixel_format pf = c->param_image.pixel_format;
-        if ((int)(d->channel_remap >> 24) != gpujpeg_pixel_format_get_comp_count(pf)) {
-            GJ_ERROR("Wrong channel remapping given, given %u channels but pixel format has %d!\n", d->channel_remap >> 24, gpujpeg_pixel_format_get_comp_count(pf));
-            goto out;
-        }
-        if (pf != GPUJPEG_U8 && pf != GPUJPEG_444_U8_P012 && pf != GPUJPEG_4444_U8_P0123 && pf != GPUJPEG_444_U8_P0P1P2) {
-            GJ_ERROR("Channel remapping is implemented for pixel formats whose pixels do not share samples (u8, 444-u8-p012, 4444-u8-p0123, 444-u8-p0p1p2).\n");
-            goto out;
-        }
-    }
+    if (k->spec) d->n_spec++;
+    job.d_raw = k->d_raw;
+    if (gj_channel_remap_check(d->channel_remap, c->param_image.pixel_format) != 0) return -1;
     /* the sub-sequence entropy decoder zero-fills every block it decodes; a full clear is needed only when segments are missing
      * from the table (their blocks would keep the previous frame's coefficients) -- unknown before the end in the speculative path,
      * which is validated and repeated then */
-    job.clear_coefs = !spec && seg_count != g->segment_count;
+    job.clear_coefs = !k->spec && k->seg_count != g->segment_count;
     job.zero_coefs = 0;
     /* token mode buffers (gj_hip.h): one record per block, 4 tokens per stream byte at most */
-    if (!d->keep_coefs && job.use_fused && tab2_ok && image_size < ((size_t)1 << 29) && gj_hip_decode_wants_tokens(&job.g, image_size, &d->tune)) {
-        const size_t tok_need = (image_size * 4 + 64) * sizeof(uint16_t);
+    if (!d->keep_coefs && job.use_fused && k->tab2_ok && k->image_size < ((size_t)1 << 29) && gj_hip_decode_wants_tokens(&job.g, k->image_size, &d->tune)) {
+        const size_t tok_need = (k->image_size * 4 + 64) * sizeof(uint16_t);
         if (tok_need > d->d_tok_cap) { /* (grown with headroom: frames of a sequence vary in size) */
-            if (gj_ensure_device_buffer((void**)&d->d_tok, &d->d_tok_cap, tok_need + tok_need / 4) != 0) goto out;
+            if (gj_ensure_device_buffer((void**)&d->d_tok, &d->d_tok_cap, tok_need + tok_need / 4) != 0) return -1;
         }
         if ((size_t)g->block_count * 8 + 64 > d->d_blkrec_cap) {
-            if (gj_ensure_device_buffer((void**)&d->d_blkrec, &d->d_blkrec_cap, (size_t)g->block_count * 8 + 64) != 0) goto out;
+            if (gj_ensure_device_buffer((void**)&d->d_blkrec, &d->d_blkrec_cap, (size_t)g->block_count * 8 + 64) != 0) return -1;
             gj_hip_memset(d->d_blkrec, 0, d->d_blkrec_cap, c->stream);
         }
         job.tokens = 1;
         job.d_tok = d->d_tok;
-        job.tok_cap = (uint32_t)(image_size * 4);
+        job.tok_cap = (uint32_t)(k->image_size * 4);
         job.d_blkrec = d->d_blkrec;
     }
-    job.tune = d->tune;
-    job.tune.dec_careful = careful || d->need_planes;
-    /* bytes per scan: what the entropy decoder's batch sizes are cut to (luminance segments are 2-3 x the chrominance ones) */
+    job.tune.dec_careful = k->careful || d->need_planes;
     /* the word the entropy decoders raise when they meet a segment they cannot stage: in the host's (pinned, device-visible) summary */
     d->h_summary->seq_overflow = 0;
     job.d_overflow = &d->h_summary->seq_overflow;
-    if (spec) {
+    if (k->spec) {
         memcpy(job.scan_bytes, d->last_scan_bytes, sizeof job.scan_bytes);
         job.max_seg_len = d->last_max_seg_len;
+    } else if (k->device_scan) {
+        job.max_seg_len = d->h_summary->max_seg_len;
+        summary_scan_bytes(d->h_summary, job.scan_bytes);
     } else {
-        if (device_scan) {
-            job.max_seg_len = d->h_summary->max_seg_len;
-        } else {
-            job.max_seg_len = 0;
-            for (int i = 0; i < d->segs.count; i++)
-                if (d->segs.len[i] > job.max_seg_len) job.max_seg_len = d->segs.len[i];
+        job.max_seg_len = 0;
+        for (int i = 0; i < d->segs.count; i++)
+            if (d->segs.len[i] > job.max_seg_len) job.max_seg_len = d->segs.len[i];
+        for (int sc = 0; sc < k->r.scan_count && sc < GJ_MAX_COMP; sc++) { /* (the others stay 0) */
+            const size_t from = k->r.scan_begin[sc], to = k->r.scan_end[sc];
+            if (to > from) job.scan_bytes[sc] = (uint32_t)(to - from);
         }
-        for (int sc = 0; sc < GJ_MAX_COMP; sc++) {
-            if (device_scan) job.scan_bytes[sc] = sc < (int)d->h_summary->scan_count ? d->h_summary->scan_end[sc] - d->h_summary->scan_start[sc] : 0;
-            else job.scan_bytes[sc] = sc < r.scan_count && r.scan_end[sc] > r.scan_begin[sc] ? (uint32_t)(r.scan_end[sc] - r.scan_begin[sc]) : 0;
-        }
-        if (seg_count != g->segment_count) memset(job.scan_bytes, 0, sizeof job.scan_bytes); /* (table and geometry out of step: one batch size) */
     }
-    if (gj_hip_decode(&job, c->stream, stats ? c->timers.ev : NULL) != 0) {
+    if (!k->spec && k->seg_count != g->segment_count) memset(job.scan_bytes, 0, sizeof job.scan_bytes); /* (table and geometry out of step: one batch size) */
+    if (gj_hip_decode(&job, c->stream, k->stats ? c->timers.ev : NULL) != 0) {
         GJ_ERROR("Decoder kernels failed: %s\n", gj_hip_last_error());
-        goto out;
+        return -1;
     }
     /* (the lane-per-segment entropy decoder may have met a segment it cannot stage: known once everything has run) */
+    return 0;
+}
 
+/* ---- 7. pixels to where the caller wants them ---- */
+static int dec_download(struct gpujpeg_decoder* d, struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    struct gpujpeg_decoder_output* output = k->output;
     output->data_size = g->raw_size;
     output->param_image = c->param_image;
     if (output->param_image.color_space == GPUJPEG_NONE) output->param_image.color_space = c->param.color_space_internal;
-    if (output->type == GPUJPEG_DECODER_OUTPUT_INTERNAL_BUFFER || output->type == GPUJPEG_DECODER_OUTPUT_CUSTOM_BUFFER) {
-        uint8_t* dst;
-        if (output->type == GPUJPEG_DECODER_OUTPUT_INTERNAL_BUFFER) {
-            if (g->raw_size > d->h_raw_cap) {
-                gj_hip_host_free(d->h_raw);
-                d->h_raw = gj_hip_host_alloc(g->raw_size);
-                d->h_raw_cap = d->h_raw ? g->raw_size : 0;
-                if (!d->h_raw) goto out;
-            }
-            dst = d->h_raw;
-            output->data = d->h_raw;
-        } else {
-            assert(output->data != NULL);
-            dst = output->data;
-        }
-        gj_hip_event_record(c->timers.copy_out[0], c->stream);
-        if (gj_hip_download(dst, d_raw, g->raw_size, c->stream, stats ? NULL : c->timers.lane_out) != 0) goto out; /* (the process's download lane) */
-        if (stats) gj_hip_event_record(c->timers.copy_out[1], c->stream);
+    if (output->type != GPUJPEG_DECODER_OUTPUT_INTERNAL_BUFFER && output->type != GPUJPEG_DECODER_OUTPUT_CUSTOM_BUFFER) {
+        output->data = k->d_raw;
+        return 0;
+    }
+    if (output->type == GPUJPEG_DECODER_OUTPUT_INTERNAL_BUFFER) {
+        if (gj_ensure_pinned_buffer((void**)&d->h_raw, &d->h_raw_cap, g->raw_size, g->raw_size) != 0) return -1;
+        output->data = d->h_raw;
     } else {
-        output->data = d_raw;
+        assert(output->data != NULL);
     }
-    if (d->last_folded) d->n_folded++;
-    GJ_HT(c, 1);
-    if (gj_hip_stream_sync(c->stream) != 0) {
-        GJ_ERROR("Decoder failed: %s\n", gj_hip_last_error());
-        goto out;
-    }
-    GJ_HT(c, 2);
+    gj_hip_event_record(c->timers.copy_out[0], c->stream);
+    k->host_io = true;
+    if (gj_hip_download(output->data, k->d_raw, g->raw_size, c->stream, k->stats ? NULL : c->timers.lane_out) != 0) return -1; /* (the process's download lane) */
+    if (k->stats) gj_hip_event_record(c->timers.copy_out[1], c->stream);
+    return 0;
+}
 
-    if (!spec && d->h_summary->seq_overflow && !careful) { /* (a kernel forced on a stream with segments it cannot stage; or, after a host
-                                                               walk, a table whose longest segment the host did not foresee) */
+/* ---- 8. everything has run: was a launch on the cached header justified? Which header do the next calls launch on? ---- */
+static int dec_after(struct gpujpeg_decoder* d, struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    const gj_scan_summary* su = d->h_summary;
+    if (!k->spec && su->seq_overflow && !k->careful) { /* (a kernel forced on a stream with segments it cannot stage; or, after a host
+                                                           walk, a table whose longest segment the host did not foresee) */
         GJ_DEBUG(c->param.verbose, "a restart segment did not fit the entropy decoder's LDS stage: decoding again through the coefficient planes\n");
-        free(host_copy);
         d->need_planes = true; /* (and so for the frames that follow with this header) */
-        return decoder_decode(d, image, image_size, output, true);
+        k->careful = true;
+        return DEC_AGAIN;
     }
-    if (spec) { /* now the summary of this stream is on the host: was it what we assumed? */
-        summary_take_maxlen(d);
-        struct gj_reader_result chk = r;
-        bool ok = d->h_summary->header_differs == 0 && d->h_summary->seq_overflow == 0 && accept_device_scan(d->h_summary, &chk, g) == 0 &&
-                  (int)d->h_summary->segment_count == g->segment_count; /* (a stream with missing segments needs the planes cleared first) */
-        for (int i = 0; ok && i < g->comp_count; i++)
-            if (chk.huff_map[i][0] != r.huff_map[i][0] || chk.huff_map[i][1] != r.huff_map[i][1]) ok = false;
-        if (!ok) { /* different header or unusual scan structure: decode again the careful way */
+    if (k->spec) { /* now the summary of this stream is on the host: was it what we assumed? */
+        summary_take_maxlen(d->h_summary, d->h_maxlen, d->maxlen_parts);
+        if (!spec_summary_ok(d, su, g)) { /* different header or unusual scan structure: decode again the careful way */
             d->n_again++;
             if (d->last_folded) d->n_folded--; /* (counted at the launch: only accepted launches count as folded) */
-            const bool overflow_only = d->h_summary->seq_overflow != 0 && d->h_summary->header_differs == 0;
+            const bool overflow_only = su->seq_overflow != 0 && su->header_differs == 0;
             if (overflow_only) d->need_planes = true; /* (the header was the assumed one: it stays cached, the next frames launch on it with the other kernels) */
             else d->hdr_cache_valid = false;
-            free(host_copy);
-            return decoder_decode(d, image, image_size, output, overflow_only);
+            k->careful = overflow_only;
+            return DEC_AGAIN;
         }
-        for (int sc = 0; sc < GJ_MAX_COMP; sc++)
-            d->last_scan_bytes[sc] = sc < (int)d->h_summary->scan_count ? d->h_summary->scan_end[sc] - d->h_summary->scan_start[sc] : 0;
-        d->last_max_seg_len = d->h_summary->max_seg_len;
-        if ((int)d->h_summary->segment_count != g->segment_count && c->param.verbose >= 0)
-            GJ_WARN("%d segments read, expected %d. Broken JPEG?\n", (int)d->h_summary->segment_count, g->segment_count);
-    } else if (device_scan && r.scan_begin[0] <= GJ_HDR_WINDOW && r.scan_begin[0] < image_size) {
+        remember_summary(d, su);
+        if ((int)su->segment_count != g->segment_count && c->param.verbose >= 0)
+            GJ_WARN("%d segments read, expected %d. Broken JPEG?\n", (int)su->segment_count, g->segment_count);
+    } else if (k->device_scan && k->r.scan_begin[0] <= GJ_HDR_WINDOW && k->r.scan_begin[0] < k->image_size) {
         /* remember this header (SOI .. first SOS header) for the next call */
-        const size_t n = r.scan_begin[0];
+        const size_t n = k->r.scan_begin[0];
         if (!d->hdr_cache) d->hdr_cache = malloc(GJ_HDR_WINDOW);
         if (!d->d_hdr_cache) d->d_hdr_cache = gj_hip_malloc(GJ_HDR_WINDOW);
         if (d->hdr_cache && d->d_hdr_cache) {
             /* another header than the cached one: what was learnt about the old one's frames does not apply (unless this very call is the
              * second attempt that learnt it) */
-            if (!careful && !(d->hdr_cache_len == n && memcmp(d->hdr_cache, himage, n) == 0)) d->need_planes = false;
-            memcpy(d->hdr_cache, himage, n);
+            if (!k->careful && !(d->hdr_cache_len == n && memcmp(d->hdr_cache, k->himage, n) == 0)) d->need_planes = false;
+            memcpy(d->hdr_cache, k->himage, n);
             if (gj_hip_memcpy_h2d(d->d_hdr_cache, d->hdr_cache, n, c->stream) == 0 && gj_hip_stream_sync(c->stream) == 0) {
                 d->hdr_cache_len = n;
-                d->hdr_cache_r = r;
+                d->hdr_cache_r = k->r;
                 d->hdr_cache_r.comment = NULL;
                 d->hdr_cache_valid = true;
-                d->last_max_seg_len = d->h_summary->max_seg_len;
-                for (int sc = 0; sc < GJ_MAX_COMP; sc++)
-                    d->last_scan_bytes[sc] = sc < (int)d->h_summary->scan_count ? d->h_summary->scan_end[sc] - d->h_summary->scan_start[sc] : 0;
+                remember_summary(d, su);
             }
         }
     } else {
         d->hdr_cache_valid = false;
     }
-    if (stats) {
+    return DEC_DONE;
+}
+
+static void dec_stats(struct gpujpeg_decoder* d, const struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    const struct gpujpeg_decoder_output* output = k->output;
+    if (k->stats) {
         struct gpujpeg_duration_stats* s = &c->stats;
         s->duration_huffman_coder = gj_hip_event_elapsed_ms(c->timers.ev[0], c->timers.ev[1]);
         s->duration_dct_quantization = gj_hip_event_elapsed_ms(c->timers.ev[1], c->timers.ev[2]);
         s->duration_preprocessor = gj_hip_event_elapsed_ms(c->timers.ev[2], c->timers.ev[3]);
         s->duration_in_gpu = gj_hip_event_elapsed_ms(c->timers.ev[0], c->timers.ev[3]);
-        for (int k = 0; k < GJ_DEC_EVENTS - 1; k++) c->kernel_ms[k] = gj_hip_event_elapsed_ms(c->timers.ev[k], c->timers.ev[k + 1]);
+        for (int i = 0; i < GJ_DEC_EVENTS - 1; i++) c->kernel_ms[i] = gj_hip_event_elapsed_ms(c->timers.ev[i], c->timers.ev[i + 1]);
         c->kernel_ms[3] = d->scan_timed ? gj_hip_event_elapsed_ms(c->timers.ev[4], c->timers.ev[5]) : 0.0f; /* the marker scan, when the device did it */
         s->duration_in_gpu += c->kernel_ms[3];
         c->timers.valid = true;
@@ -653,22 +710,73 @@ static int decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t imag
         if (output->type == GPUJPEG_DECODER_OUTPUT_INTERNAL_BUFFER || output->type == GPUJPEG_DECODER_OUTPUT_CUSTOM_BUFFER)
             s->duration_memory_from = gj_hip_event_elapsed_ms(c->timers.copy_out[0], c->timers.copy_out[1]);
     }
-    gj_coder_process_stats(c, stats);
+    gj_coder_process_stats(c, k->stats);
     if (c->param.verbose >= GPUJPEG_LL_STATUS)
         fprintf(stderr, "Decompressed Size:%13zu bytes %dx%d %s %s\n", output->data_size, output->param_image.width, output->param_image.height,
                 gpujpeg_pixel_format_get_name(output->param_image.pixel_format), gpujpeg_color_space_get_name(output->param_image.color_space));
-    output->metadata = &d->metadata;
-    rc = 0;
+}
+
+/* one attempt: the stages in the order their work goes onto the stream */
+static int dec_attempt(struct gpujpeg_decoder* d, struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    GJ_HT_START(c);
+    k->stats = c->param.perf_stats != 0 || c->param.verbose >= GPUJPEG_LL_STATUS;
+    c->start_time = k->stats ? gpujpeg_get_time() : 0;
+    memset(&c->stats, 0, sizeof c->stats);
+    k->t_read0 = k->stats ? gpujpeg_get_time() : 0;
+
+    int rc = dec_headers(d, k);
+    if (rc != 0) return rc;
+    for (int i = 0; i < GPUJPEG_METADATA_COUNT; i++) d->metadata.vals[i] = k->r.metadata.vals[i];
+    if (decoder_configure(d, &k->r.param, &k->r.param_image) != 0) return DEC_FAILED;
+    c->init_end_time = k->stats ? gpujpeg_get_time() : 0;
+    if (dec_upload(d, k) != 0) return DEC_FAILED;
+    if ((rc = dec_segment_table(d, k)) != 0) return rc;
+    if (dec_tables(d, k) != 0) return DEC_FAILED;
+    if (k->stats) gj_hip_event_record(c->timers.copy_in[1], c->stream);
+    if (dec_destination(d, k) != 0 || dec_launch(d, k) != 0 || dec_download(d, k) != 0) return DEC_FAILED;
+    if (d->last_folded) d->n_folded++;
+    GJ_HT(c, 1);
+    if (gj_hip_stream_sync(c->stream) != 0) {
+        GJ_ERROR("Decoder failed: %s\n", gj_hip_last_error());
+        return DEC_FAILED;
+    }
+    GJ_HT(c, 2);
+    if (dec_after(d, k) == DEC_AGAIN) return DEC_AGAIN;
+    dec_stats(d, k);
+    k->output->metadata = &d->metadata;
     GJ_HT(c, 3);
     c->ht_calls++;
-out:
-    free(host_copy);
-    return rc;
+    return DEC_DONE;
+}
+
+/* At most three attempts: on the cached header; rejected for its header or scan structure, the plain way; and when that meets a segment too
+ * long for the LDS stage, the careful way (an attempt that is careful already never asks for another). */
+static int decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t image_size, struct gpujpeg_decoder_output* output)
+{
+    struct dec_call k; /* (not cleared as a whole: it holds a parse result of several KiB) */
+    k.image = image;
+    k.image_size = image_size;
+    k.output = output;
+    k.jpeg_on_device = gj_hip_is_device_ptr(image) != 0;
+    k.careful = false;
+    k.host_io = false;
+    k.host_copy = NULL;
+    int rc = DEC_AGAIN;
+    for (int attempt = 0; attempt < 3 && rc == DEC_AGAIN; attempt++) {
+        rc = dec_attempt(d, &k);
+        free(k.host_copy);
+        k.host_copy = NULL;
+    }
+    if (rc == DEC_DONE) return 0;
+    if (k.host_io) gj_hip_stream_sync(d->coder.stream); /* (what this call queued on its stream must not read or write the caller's memory after the error has left; a copy stranded on a copy lane by a failing event is not covered) */
+    return rc < 0 ? rc : -1;
 }
 
 int gpujpeg_decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t image_size, struct gpujpeg_decoder_output* output)
 {
-    return decoder_decode(d, image, image_size, output, false);
+    return decoder_decode(d, image, image_size, output);
 }
 
 int gpujpeg_decoder_get_stats(struct gpujpeg_decoder* d, struct gpujpeg_duration_stats* stats)
@@ -677,7 +785,6 @@ int gpujpeg_decoder_get_stats(struct gpujpeg_decoder* d, struct gpujpeg_duration
     *stats = d->coder.stats;
     return 0;
 }
-
 
 /* ------------------------------------------------------------------ frame batches (MI355X extension, include/gpujpeg_amd_ext.h) */
 /* Streams with ONE header (a sequence from one encoder) decoded by one set of launches per chunk of frames -- marker scan, marker table, entropy
@@ -688,30 +795,214 @@ int gpujpeg_decoder_get_stats(struct gpujpeg_decoder* d, struct gpujpeg_duration
 #define GJ_DEC_BATCH_CHUNK_MAX 256
 #define GJ_DEC_BATCH_BYTES ((size_t)8 << 30) /* work buffers of one chunk */
 
-static int pinned_ensure(void** p, size_t* cap, size_t need)
-{
-    if (need <= *cap) return 0;
-    gj_hip_host_free(*p);
-    *p = gj_hip_host_alloc(need + need / 2);
-    *cap = *p ? need + need / 2 : 0;
-    return *p ? 0 : -1;
-}
+/* what the parts of a batch call share */
+struct dec_batch {
+    const uint8_t* streams; size_t stream_stride; const size_t* sizes; int count;
+    size_t output_stride;
+    bool streams_on_device, out_on_device;
+    uint8_t* d_out; size_t d_out_stride; /* where the pixels go on the device: the caller's buffer, or a staging area that is copied out at the end */
+    size_t frame_raw;                    /* what every frame decodes to (0: not known yet) */
+    int first;                           /* 1: frame 0 went the ordinary way ahead of the batched launches */
+    uint8_t* frame_done;
+    bool host_io;                        /* copies from or into the caller's host memory have been queued */
+};
 
 /* one frame of a batch the ordinary way: into the decoder's own buffer first -- a stream that is not what the caller promised (other dimensions) must
- * not be written over the neighbours' slots --, then into its slot; *frame_raw = the size every frame of the batch decodes to (0: not known yet) */
-static int batch_decode_one(struct gpujpeg_decoder* d, const uint8_t* stream, size_t size, uint8_t* d_out, size_t out_stride, size_t* frame_raw)
+ * not be written over the neighbours' slots --, then into its slot. `ahead`: frame 0 in front of the batched launches, which tells what every
+ * frame decodes to and with that where the pixels go on the device (the output size is known once a frame has been parsed) */
+static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int f, bool ahead)
 {
+    struct gj_coder* c = &d->coder;
     struct gpujpeg_decoder_output o;
     gpujpeg_decoder_output_set_cuda_buffer(&o);
-    if (decoder_decode(d, (uint8_t*)(uintptr_t)stream, size, &o, false) != 0) return -1;
-    const size_t raw = d->coder.geom.raw_size;
-    if (*frame_raw == 0) *frame_raw = raw;
-    if (raw != *frame_raw || raw > out_stride) {
-        GJ_ERROR("A frame of the batch decodes to %zu B, the others to %zu B (output stride %zu)!\n", raw, *frame_raw, out_stride);
+    if (decoder_decode(d, (uint8_t*)(uintptr_t)(b->streams + (size_t)f * b->stream_stride), b->sizes[f], &o) != 0) return -1;
+    const size_t raw = c->geom.raw_size;
+    if (ahead) {
+        b->frame_raw = raw;
+        if (b->output_stride < raw) {
+            GJ_ERROR("Output stride %zu is smaller than a decoded frame (%zu B)!\n", b->output_stride, raw);
+            return -1;
+        }
+        if (!b->out_on_device) {
+            if (gj_ensure_device_buffer((void**)&d->b_raw, &d->b_raw_cap, raw * (size_t)b->count) != 0) return -1;
+            b->d_out = d->b_raw;
+            b->d_out_stride = raw;
+        }
+    } else {
+        if (b->frame_raw == 0) b->frame_raw = raw;
+        if (raw != b->frame_raw || raw > b->d_out_stride) {
+            GJ_ERROR("A frame of the batch decodes to %zu B, the others to %zu B (output stride %zu)!\n", raw, b->frame_raw, b->d_out_stride);
+            return -1;
+        }
+    }
+    if (gj_hip_memcpy_d2d(b->d_out + (size_t)f * b->d_out_stride, o.data, raw, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) return -1;
+    return 0;
+}
+
+/* The work buffers of one chunk of frames: what a frame takes of each (into B), how many frames fit a chunk (the return value, 0 on error),
+ * the buffers and the job's pointers to them. */
+static int batch_chunk_buffers(struct gpujpeg_decoder* d, gj_dec_job* job, gj_batch* B, int n_all, size_t begin, size_t max_size)
+{
+    struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    const size_t S = (size_t)g->segment_count + GJ_MAX_COMP;
+    const size_t seg_frame = (3 * S + 8 + 3) & ~(size_t)3;                                                                   /* words */
+    const size_t scratch_frame = (gj_hip_find_segments_scratch_words(begin, max_size, (uint32_t)g->segment_count) + 3) & ~(size_t)3; /* words */
+    const size_t coefs_frame = ((size_t)g->data_size + 63) & ~(size_t)63;                                                   /* int16 */
+    const int chunk_cap = d->b_chunk > 0 && d->b_chunk < GJ_DEC_BATCH_CHUNK_MAX ? d->b_chunk : GJ_DEC_BATCH_CHUNK_MAX;
+    job->g.fb.frames = (uint32_t)(n_all < chunk_cap ? n_all : chunk_cap); /* (what the token / plane choice looks at) */
+    const bool tokens = gj_hip_decode_wants_tokens(&job->g, max_size, &d->tune) != 0;
+    const size_t tok_frame = tokens ? (max_size * 4 + 64 + 63) & ~(size_t)63 : 0;                                            /* tokens */
+    const size_t rec_frame = tokens ? ((size_t)g->block_count + 8 + 7) & ~(size_t)7 : 0;                                    /* records */
+    const bool planes = gj_hip_decode_uses_planes(g, job->use_fused) != 0;
+    const size_t frame_bytes = seg_frame * 4 + scratch_frame * 4 + coefs_frame * 2 + tok_frame * 2 + rec_frame * 8 + (planes ? coefs_frame : 0);
+    int chunk = (int)(GJ_DEC_BATCH_BYTES / frame_bytes);
+    if (chunk > chunk_cap) chunk = chunk_cap;
+    if (chunk > n_all) chunk = n_all;
+    if (chunk < 1) chunk = 1;
+    if (gj_ensure_device_buffer((void**)&d->b_seg, &d->b_seg_cap, seg_frame * 4 * (size_t)chunk) != 0) return 0;
+    if (gj_ensure_device_buffer((void**)&d->b_scratch, &d->b_scratch_cap, scratch_frame * 4 * (size_t)chunk + 64) != 0) return 0;
+    if (gj_ensure_device_buffer((void**)&d->b_coefs, &d->b_coefs_cap, coefs_frame * 2 * (size_t)chunk) != 0) return 0;
+    if (planes && gj_ensure_device_buffer((void**)&d->b_planes, &d->b_planes_cap, coefs_frame * (size_t)chunk) != 0) return 0;
+    if (planes) job->d_planes = d->b_planes;
+    if (tokens) {
+        if (gj_ensure_device_buffer((void**)&d->b_tok, &d->b_tok_cap, tok_frame * 2 * (size_t)chunk) != 0) return 0;
+        const size_t had = d->b_rec_cap;
+        if (gj_ensure_device_buffer((void**)&d->b_rec, &d->b_rec_cap, rec_frame * 8 * (size_t)chunk) != 0) return 0;
+        if (d->b_rec_cap != had && gj_hip_memset(d->b_rec, 0, d->b_rec_cap, c->stream) != 0) return 0;
+    }
+    job->d_seg_pos = d->b_seg;
+    job->d_seg_len = d->b_seg + S;
+    job->d_seg_index = d->b_seg + 2 * S;
+    job->d_coefs = d->b_coefs;
+    job->tokens = tokens ? 1 : 0;
+    job->d_tok = tokens ? d->b_tok : NULL;
+    job->tok_cap = tokens ? (uint32_t)(max_size * 4) : 0;
+    job->d_blkrec = tokens ? d->b_rec : NULL;
+    B->coefs = coefs_frame;
+    B->tok = tok_frame;
+    B->rec = rec_frame;
+    B->seg = (uint32_t)seg_frame;
+    B->scratch = (uint32_t)scratch_frame;
+    return chunk;
+}
+
+/* The batched launches for the frames from b->first on, if the decoder's state and the streams allow them, and every frame's verdict in
+ * b->frame_done. Returns 0, -1 on error, or 1: the cached header turned out to be another sequence's -- frame 0 has to go the ordinary way
+ * (which replaces the cache) and the batch is planned again (asked for only while !force_first and frame 0 has not gone ahead). */
+static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool force_first)
+{
+    struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    const int first = b->first, count = b->count, n_all = count - first;
+    const size_t* sizes = b->sizes;
+    bool batched = d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
+                   (b->streams_on_device ? (b->stream_stride & 15u) == 0 : true) && d->tab2_ok;
+    size_t max_size = 0;
+    for (int f = first; f < count; f++) {
+        if (sizes[f] > max_size) max_size = sizes[f];
+        if (sizes[f] <= d->hdr_cache_len + 2 || sizes[f] > 0x1FFFFFF0u) batched = false;
+    }
+    if (!batched || n_all < 1) return 0;
+    const struct gj_reader_result* r = &d->hdr_cache_r;
+    if (decoder_configure(d, &r->param, &r->param_image) != 0) return -1; /* (the geometry of the cached header, whatever the coder was last set up for) */
+    if (b->output_stride < g->raw_size || (b->frame_raw != 0 && b->frame_raw != g->raw_size)) {
+        /* the cached header is an OLDER sequence's (a larger image than the caller's slots, ADVICE r4: this used to fail the call): these
+         * streams are strangers to it */
+        return first == 0 && !force_first ? 1 : 0;
+    }
+    b->frame_raw = g->raw_size;
+    geom_take_tables(&c->geom, r);
+    gj_dec_job job;
+    dec_job_base(d, true, &job);
+    job.seg_count = g->segment_count;
+    job.tune.dec_careful = 0;
+    job.max_seg_len = d->last_max_seg_len;
+    memcpy(job.scan_bytes, d->last_scan_bytes, sizeof job.scan_bytes);
+    job.jpeg_size = max_size;
+    /* (the two pointers only have to be non-null for the question; they are set per chunk below) */
+    job.d_seg_count = &d->d_summary->segment_count;
+    job.d_overflow = &d->h_summary->seq_overflow;
+    if (!gj_hip_decode_batchable(&job)) return 0;
+
+    const size_t begin = r->scan_begin[0];
+    /* streams in host memory: one staging area, slots on 16-byte addresses */
+    const uint8_t* d_streams = b->streams + (size_t)first * b->stream_stride;
+    size_t d_stride = b->stream_stride;
+    if (!b->streams_on_device) {
+        d_stride = (max_size + 64 + 15) & ~(size_t)15;
+        if (gj_ensure_device_buffer((void**)&d->b_jpeg, &d->b_jpeg_cap, d_stride * (size_t)n_all) != 0) return -1;
+        gj_hip_event_record(c->timers.copy_in[0], c->stream); /* (copy marker, see gj_internal.h) */
+        b->host_io = true;
+        for (int f = first; f < count; f++)
+            if (gj_hip_memcpy_h2d(d->b_jpeg + (size_t)(f - first) * d_stride, b->streams + (size_t)f * b->stream_stride, sizes[f], c->stream) != 0) return -1;
+        d_streams = d->b_jpeg;
+    }
+    /* per-frame words of all frames */
+    const size_t max_chunks = gj_hip_find_segments_max_chunks(begin, max_size);
+    const size_t sizes_bytes = (size_t)n_all * sizeof(uint32_t), sum_bytes = (size_t)n_all * sizeof(gj_scan_summary);
+    const size_t maxlen_bytes = (size_t)n_all * max_chunks * sizeof(uint32_t);
+    if (gj_ensure_device_buffer((void**)&d->b_sizes, &d->b_sizes_cap, sizes_bytes) != 0) return -1;
+    if (gj_ensure_pinned_buffer((void**)&d->bh_sizes, &d->bh_sizes_cap, sizes_bytes, sizes_bytes + sizes_bytes / 2) != 0) return -1;
+    if (gj_ensure_pinned_buffer((void**)&d->bh_sum, &d->bh_sum_cap, sum_bytes, sum_bytes + sum_bytes / 2) != 0) return -1;
+    if (gj_ensure_pinned_buffer((void**)&d->bh_maxlen, &d->bh_maxlen_cap, maxlen_bytes, maxlen_bytes + maxlen_bytes / 2) != 0) return -1;
+    {
+        const size_t had = d->b_dsum_cap;
+        if (gj_ensure_device_buffer((void**)&d->b_dsum, &d->b_dsum_cap, sum_bytes) != 0) return -1;
+        if (d->b_dsum_cap != had && gj_hip_memset(d->b_dsum, 0, d->b_dsum_cap, c->stream) != 0) return -1;
+    }
+    memset(d->bh_sum, 0, sum_bytes);
+    for (int i = 0; i < n_all; i++) d->bh_sizes[i] = (uint32_t)sizes[first + i];
+    if (gj_hip_memcpy_h2d(d->b_sizes, d->bh_sizes, sizes_bytes, c->stream) != 0) return -1;
+    gj_batch B;
+    memset(&B, 0, sizeof B);
+    const int chunk = batch_chunk_buffers(d, &job, &B, n_all, begin, max_size);
+    if (chunk < 1) return -1;
+    const size_t S = (size_t)g->segment_count + GJ_MAX_COMP;
+    B.jpeg = d_stride;
+    B.raw = b->d_out_stride;
+    B.maxlen = (uint32_t)max_chunks;
+    job.g.fb.jpeg = B.jpeg;
+    job.g.fb.raw = B.raw;
+    job.g.fb.coefs = B.coefs;
+    job.g.fb.tok = B.tok;
+    job.g.fb.rec = B.rec;
+    job.g.fb.seg = B.seg;
+    for (int a = 0; a < n_all; a += chunk) {
+        B.count = (uint32_t)(n_all - a < chunk ? n_all - a : chunk);
+        B.d_sizes = d->b_sizes + a;
+        job.batch = B;
+        job.g.fb.sizes = B.d_sizes;
+        job.d_jpeg = d_streams + (size_t)a * d_stride;
+        job.d_raw = b->d_out + (size_t)(first + a) * b->d_out_stride;
+        job.d_seg_count = &d->b_dsum[a].segment_count;
+        job.d_overflow = &d->bh_sum[a].seq_overflow;
+        uint32_t parts = 0;
+        if (gj_hip_find_segments_batch(g, job.d_jpeg, begin, max_size, d->b_seg, d->b_seg + S, d->b_seg + 2 * S, (uint32_t)g->segment_count, d->b_scratch,
+                                       d->b_dsum + a, d->d_hdr_cache, (uint32_t)d->hdr_cache_len, d->bh_sum + a, d->bh_maxlen + (size_t)a * max_chunks,
+                                       (uint32_t)max_chunks, &parts, c->stream, &d->tune, &B) != 0 ||
+            gj_hip_decode(&job, c->stream, NULL) != 0) {
+            GJ_ERROR("Decoder kernels failed: %s\n", gj_hip_last_error());
+            return -1;
+        }
+        d->maxlen_parts = parts;
+    }
+    if (gj_hip_stream_sync(c->stream) != 0) {
+        GJ_ERROR("Decoder failed: %s\n", gj_hip_last_error());
         return -1;
     }
-    if (gj_hip_memcpy_d2d(d_out, o.data, raw, d->coder.stream) != 0 || gj_hip_stream_sync(d->coder.stream) != 0) return -1;
-    return 0;
+    /* every frame's summary: was the stream what the launch assumed? */
+    int accepted = 0;
+    for (int i = 0; i < n_all; i++) {
+        gj_scan_summary* su = d->bh_sum + i;
+        summary_take_maxlen(su, d->bh_maxlen + (size_t)i * max_chunks, d->maxlen_parts);
+        if (!spec_summary_ok(d, su, g)) continue;
+        b->frame_done[first + i] = 1;
+        accepted++;
+        remember_summary(d, su);
+    }
+    /* not one frame passed: the cached header (an older sequence's, of dimensions the slots happen to hold) is not these streams' */
+    return accepted == 0 && first == 0 && !force_first ? 1 : 0;
 }
 
 int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count,
@@ -719,237 +1010,42 @@ int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* d, const uint8_t* s
 {
     if (!d || !streams || !sizes || count < 1 || !output) return -1;
     struct gj_coder* c = &d->coder;
-    const bool streams_on_device = gj_hip_is_device_ptr(streams) != 0, out_on_device = gj_hip_is_device_ptr(output) != 0;
+    struct dec_batch b = {.streams = streams, .stream_stride = stream_stride, .sizes = sizes, .count = count, .output_stride = output_stride,
+                          .d_out = output, .d_out_stride = output_stride};
+    b.streams_on_device = gj_hip_is_device_ptr(streams) != 0;
+    b.out_on_device = gj_hip_is_device_ptr(output) != 0;
     int rc = -1;
-    uint8_t* frame_done = calloc((size_t)count, 1);
-    if (!frame_done) return -1;
-    /* where the pixels go on the device: the caller's buffer, or a staging area that is copied out at the end */
-    uint8_t* d_out = output;
-    size_t d_out_stride = output_stride;
-    int first = 0;
-    /* the header cache is what a batch launches on: the first frame goes the ordinary way when there is none (or when it has to) */
-    const uint8_t* s0 = streams;
-    size_t frame_raw = 0; /* what every frame decodes to */
-    bool force_first = false; /* the cached header turned out to be another sequence's: frame 0 the ordinary way (which replaces the cache), then the batch */
-again:
-    if (first == 0 && (!out_on_device || !d->hdr_cache_valid || force_first)) {
-        /* (the output size is known once a frame has been parsed: decode frame 0 into the decoder's own buffer first) */
-        struct gpujpeg_decoder_output o;
-        gpujpeg_decoder_output_set_cuda_buffer(&o);
-        if (decoder_decode(d, (uint8_t*)(uintptr_t)s0, sizes[0], &o, false) != 0) goto out;
-        const size_t raw = c->geom.raw_size;
-        frame_raw = raw;
-        if (output_stride < raw) {
-            GJ_ERROR("Output stride %zu is smaller than a decoded frame (%zu B)!\n", output_stride, raw);
-            goto out;
+    b.frame_done = calloc((size_t)count, 1);
+    if (!b.frame_done) return -1;
+    /* The header cache is what a batch launches on: frame 0 goes the ordinary way when there is none (or when it has to). A second pass, with
+     * force_first, when the cached header turned out to be another sequence's: frame 0 replaces the cache, then the batch. */
+    for (int pass = 0; pass < 2; pass++) {
+        const bool force_first = pass == 1;
+        if (b.first == 0 && (!b.out_on_device || !d->hdr_cache_valid || force_first)) {
+            if (batch_decode_one(d, &b, 0, true) != 0) goto out;
+            b.frame_done[0] = 1;
+            b.first = 1;
         }
-        if (!out_on_device) {
-            if (gj_ensure_device_buffer((void**)&d->b_raw, &d->b_raw_cap, raw * (size_t)count) != 0) goto out;
-            d_out = d->b_raw;
-            d_out_stride = raw;
-        }
-        if (gj_hip_memcpy_d2d(d_out, o.data, raw, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) goto out;
-        frame_done[0] = 1;
-        first = 1;
-    }
-    const gj_geom* g = &c->geom;
-    bool batched = d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
-                   (streams_on_device ? (stream_stride & 15u) == 0 : true) && d->tab2_ok;
-    size_t max_size = 0;
-    for (int f = first; f < count; f++) {
-        if (sizes[f] > max_size) max_size = sizes[f];
-        if (sizes[f] <= d->hdr_cache_len + 2 || sizes[f] > 0x1FFFFFF0u) batched = false;
-    }
-    gj_dec_job job;
-    memset(&job, 0, sizeof job);
-    if (batched && first < count) {
-        struct gj_reader_result r = d->hdr_cache_r;
-        if (decoder_configure(d, &r.param, &r.param_image) != 0) goto out; /* (the geometry of the cached header, whatever the coder was last set up for) */
-        if (output_stride < g->raw_size || (frame_raw != 0 && frame_raw != g->raw_size)) {
-            /* the cached header is an OLDER sequence's (a larger image than the caller's slots, ADVICE r4: this used to fail the call): these
-             * streams are strangers to it. Frame 0 goes the ordinary way, which replaces the cache, and the batch is planned again */
-            if (first == 0 && !force_first) {
-                force_first = true;
-                frame_raw = 0;
-                goto again;
-            }
-            batched = false;
-        }
-    }
-    if (batched && first < count) {
-        struct gj_reader_result r = d->hdr_cache_r;
-        frame_raw = g->raw_size;
-        for (int i = 0; i < c->geom.comp_count; i++) {
-            c->geom.comp[i].q_table = r.quant_map[i];
-            c->geom.comp[i].dc_table = r.huff_map[i][0];
-            c->geom.comp[i].ac_table = r.huff_map[i][1];
-        }
-        job.g = *g;
-        job.seg_count = g->segment_count;
-        job.d_huff_tab = d->d_huff_tab;
-        job.d_qtab = d->d_qtab;
-        job.d_qtabf = (const float*)(const void*)(d->d_huff_tab + GJ_TABS_QF_OFFSET);
-        job.d_huff_tab2 = d->d_qtab + 4 * 64;
-        job.d_planes = c->d_planes;
-        job.use_fused = d->use_fused && !d->flipped;
-        job.flipped = d->flipped;
-        job.channel_remap = d->channel_remap;
-        job.tune = d->tune;
-        job.tune.dec_careful = 0;
-        job.max_seg_len = d->last_max_seg_len;
-        memcpy(job.scan_bytes, d->last_scan_bytes, sizeof job.scan_bytes);
-        job.jpeg_size = max_size;
-        /* (the two pointers only have to be non-null for the question; they are set per chunk below) */
-        job.d_seg_count = &d->d_summary->segment_count;
-        job.d_overflow = &d->h_summary->seq_overflow;
-        if (!gj_hip_decode_batchable(&job)) batched = false;
-    }
-    if (batched && first < count) {
-        const int n_all = count - first;
-        const size_t begin = d->hdr_cache_r.scan_begin[0];
-        /* streams in host memory: one staging area, slots on 16-byte addresses */
-        const uint8_t* d_streams = streams + (size_t)first * stream_stride;
-        size_t d_stride = stream_stride;
-        if (!streams_on_device) {
-            d_stride = (max_size + 64 + 15) & ~(size_t)15;
-            if (gj_ensure_device_buffer((void**)&d->b_jpeg, &d->b_jpeg_cap, d_stride * (size_t)n_all) != 0) goto out;
-            gj_hip_event_record(c->timers.copy_in[0], c->stream); /* (copy marker, see gj_internal.h) */
-            for (int f = first; f < count; f++)
-                if (gj_hip_memcpy_h2d(d->b_jpeg + (size_t)(f - first) * d_stride, streams + (size_t)f * stream_stride, sizes[f], c->stream) != 0) goto out;
-            d_streams = d->b_jpeg;
-        }
-        /* per-frame words of all frames */
-        const size_t max_chunks = gj_hip_find_segments_max_chunks(begin, max_size);
-        if (gj_ensure_device_buffer((void**)&d->b_sizes, &d->b_sizes_cap, (size_t)n_all * sizeof(uint32_t)) != 0) goto out;
-        if (pinned_ensure((void**)&d->bh_sizes, &d->bh_sizes_cap, (size_t)n_all * sizeof(uint32_t)) != 0) goto out;
-        if (pinned_ensure((void**)&d->bh_sum, &d->bh_sum_cap, (size_t)n_all * sizeof(gj_scan_summary)) != 0) goto out;
-        if (pinned_ensure((void**)&d->bh_maxlen, &d->bh_maxlen_cap, (size_t)n_all * max_chunks * sizeof(uint32_t)) != 0) goto out;
-        {
-            const size_t had = d->b_dsum_cap;
-            if (gj_ensure_device_buffer((void**)&d->b_dsum, &d->b_dsum_cap, (size_t)n_all * sizeof(gj_scan_summary)) != 0) goto out;
-            if (d->b_dsum_cap != had && gj_hip_memset(d->b_dsum, 0, d->b_dsum_cap, c->stream) != 0) goto out;
-        }
-        memset(d->bh_sum, 0, (size_t)n_all * sizeof(gj_scan_summary));
-        for (int i = 0; i < n_all; i++) d->bh_sizes[i] = (uint32_t)sizes[first + i];
-        if (gj_hip_memcpy_h2d(d->b_sizes, d->bh_sizes, (size_t)n_all * sizeof(uint32_t), c->stream) != 0) goto out;
-        /* work buffers of a chunk */
-        const size_t S = (size_t)g->segment_count + GJ_MAX_COMP;
-        const size_t seg_frame = (3 * S + 8 + 3) & ~(size_t)3;                                                                   /* words */
-        const size_t scratch_frame = (gj_hip_find_segments_scratch_words(begin, max_size, (uint32_t)g->segment_count) + 3) & ~(size_t)3; /* words */
-        const size_t coefs_frame = ((size_t)g->data_size + 63) & ~(size_t)63;                                                   /* int16 */
-        const int chunk_cap = d->b_chunk > 0 && d->b_chunk < GJ_DEC_BATCH_CHUNK_MAX ? d->b_chunk : GJ_DEC_BATCH_CHUNK_MAX;
-        job.g.fb.frames = (uint32_t)(n_all < chunk_cap ? n_all : chunk_cap); /* (what the token / plane choice looks at) */
-        const bool tokens = gj_hip_decode_wants_tokens(&job.g, max_size, &d->tune) != 0;
-        const size_t tok_frame = tokens ? (max_size * 4 + 64 + 63) & ~(size_t)63 : 0;                                            /* tokens */
-        const size_t rec_frame = tokens ? ((size_t)g->block_count + 8 + 7) & ~(size_t)7 : 0;                                    /* records */
-        const bool planes = gj_hip_decode_uses_planes(g, job.use_fused) != 0;
-        const size_t frame_bytes = seg_frame * 4 + scratch_frame * 4 + coefs_frame * 2 + tok_frame * 2 + rec_frame * 8 + (planes ? coefs_frame : 0);
-        int chunk = (int)(GJ_DEC_BATCH_BYTES / frame_bytes);
-        if (chunk > chunk_cap) chunk = chunk_cap;
-        if (chunk > n_all) chunk = n_all;
-        if (chunk < 1) chunk = 1;
-        if (gj_ensure_device_buffer((void**)&d->b_seg, &d->b_seg_cap, seg_frame * 4 * (size_t)chunk) != 0) goto out;
-        if (gj_ensure_device_buffer((void**)&d->b_scratch, &d->b_scratch_cap, scratch_frame * 4 * (size_t)chunk + 64) != 0) goto out;
-        if (gj_ensure_device_buffer((void**)&d->b_coefs, &d->b_coefs_cap, coefs_frame * 2 * (size_t)chunk) != 0) goto out;
-        if (planes && gj_ensure_device_buffer((void**)&d->b_planes, &d->b_planes_cap, coefs_frame * (size_t)chunk) != 0) goto out;
-        if (planes) job.d_planes = d->b_planes;
-        if (tokens) {
-            if (gj_ensure_device_buffer((void**)&d->b_tok, &d->b_tok_cap, tok_frame * 2 * (size_t)chunk) != 0) goto out;
-            const size_t had = d->b_rec_cap;
-            if (gj_ensure_device_buffer((void**)&d->b_rec, &d->b_rec_cap, rec_frame * 8 * (size_t)chunk) != 0) goto out;
-            if (d->b_rec_cap != had && gj_hip_memset(d->b_rec, 0, d->b_rec_cap, c->stream) != 0) goto out;
-        }
-        job.d_seg_pos = d->b_seg;
-        job.d_seg_len = d->b_seg + S;
-        job.d_seg_index = d->b_seg + 2 * S;
-        job.d_coefs = d->b_coefs;
-        job.tokens = tokens ? 1 : 0;
-        job.d_tok = tokens ? d->b_tok : NULL;
-        job.tok_cap = tokens ? (uint32_t)(max_size * 4) : 0;
-        job.d_blkrec = tokens ? d->b_rec : NULL;
-        for (int a = 0; a < n_all; a += chunk) {
-            const int n = n_all - a < chunk ? n_all - a : chunk;
-            gj_batch B;
-            memset(&B, 0, sizeof B);
-            B.count = (uint32_t)n;
-            B.jpeg = d_stride;
-            B.raw = d_out_stride;
-            B.coefs = coefs_frame;
-            B.tok = tok_frame;
-            B.rec = rec_frame;
-            B.seg = (uint32_t)seg_frame;
-            B.scratch = (uint32_t)scratch_frame;
-            B.maxlen = (uint32_t)max_chunks;
-            B.d_sizes = d->b_sizes + a;
-            job.batch = B;
-            job.g.fb.sizes = B.d_sizes;
-            job.g.fb.jpeg = B.jpeg;
-            job.g.fb.raw = B.raw;
-            job.g.fb.coefs = B.coefs;
-            job.g.fb.tok = B.tok;
-            job.g.fb.rec = B.rec;
-            job.g.fb.seg = B.seg;
-            job.d_jpeg = d_streams + (size_t)a * d_stride;
-            job.d_raw = d_out + (size_t)(first + a) * d_out_stride;
-            job.d_seg_count = &d->b_dsum[a].segment_count;
-            job.d_overflow = &d->bh_sum[a].seq_overflow;
-            uint32_t parts = 0;
-            if (gj_hip_find_segments_batch(g, job.d_jpeg, begin, max_size, d->b_seg, d->b_seg + S, d->b_seg + 2 * S, (uint32_t)g->segment_count, d->b_scratch,
-                                           d->b_dsum + a, d->d_hdr_cache, (uint32_t)d->hdr_cache_len, d->bh_sum + a, d->bh_maxlen + (size_t)a * max_chunks,
-                                           (uint32_t)max_chunks, &parts, c->stream, &d->tune, &B) != 0 ||
-                gj_hip_decode(&job, c->stream, NULL) != 0) {
-                GJ_ERROR("Decoder kernels failed: %s\n", gj_hip_last_error());
-                goto out;
-            }
-            d->maxlen_parts = parts;
-        }
-        if (gj_hip_stream_sync(c->stream) != 0) {
-            GJ_ERROR("Decoder failed: %s\n", gj_hip_last_error());
-            goto out;
-        }
-        /* every frame's summary: was the stream what the launch assumed? (the checks of decoder_decode's speculative path) */
-        for (int i = 0; i < n_all; i++) {
-            gj_scan_summary* su = d->bh_sum + i;
-            uint32_t m = 0;
-            for (uint32_t k = 0; k < d->maxlen_parts; k++)
-                if (d->bh_maxlen[(size_t)i * max_chunks + k] > m) m = d->bh_maxlen[(size_t)i * max_chunks + k];
-            su->max_seg_len = m;
-            struct gj_reader_result chk = d->hdr_cache_r;
-            bool ok = su->header_differs == 0 && su->seq_overflow == 0 && accept_device_scan(su, &chk, g) == 0 && (int)su->segment_count == g->segment_count;
-            for (int k = 0; ok && k < g->comp_count; k++)
-                if (chk.huff_map[k][0] != d->hdr_cache_r.huff_map[k][0] || chk.huff_map[k][1] != d->hdr_cache_r.huff_map[k][1]) ok = false;
-            if (ok) {
-                frame_done[first + i] = 1;
-                for (int sc = 0; sc < GJ_MAX_COMP; sc++) d->last_scan_bytes[sc] = sc < (int)su->scan_count ? su->scan_end[sc] - su->scan_start[sc] : 0;
-                d->last_max_seg_len = su->max_seg_len;
-            }
-        }
-    }
-    if (batched && first == 0 && !force_first) {
-        /* not one frame passed: the cached header (an older sequence's, of dimensions the slots happen to hold) is not these streams' */
-        int accepted = 0;
-        for (int f = 0; f < count; f++) accepted += frame_done[f];
-        if (accepted == 0) {
-            force_first = true;
-            frame_raw = 0;
-            goto again;
-        }
+        const int again = batch_launches(d, &b, force_first);
+        if (again < 0) goto out;
+        if (again == 0) break;
+        b.frame_raw = 0;
     }
     /* whatever is left: the ordinary call, frame by frame */
     d->b_last_batched = 0;
-    for (int f = first; f < count; f++) d->b_last_batched += frame_done[f] ? 1 : 0;
+    for (int f = b.first; f < count; f++) d->b_last_batched += b.frame_done[f] ? 1 : 0;
     d->b_last_single = count - d->b_last_batched;
-    for (int f = 0; f < count; f++) {
-        if (frame_done[f]) continue;
-        if (batch_decode_one(d, streams + (size_t)f * stream_stride, sizes[f], d_out + (size_t)f * d_out_stride, d_out_stride, &frame_raw) != 0) goto out;
-    }
-    if (!out_on_device) {
+    for (int f = 0; f < count; f++)
+        if (!b.frame_done[f] && batch_decode_one(d, &b, f, false) != 0) goto out;
+    if (!b.out_on_device) {
         gj_hip_event_record(c->timers.copy_out[0], c->stream); /* (copy marker) */
-        const gj_stream_t down = gj_hip_lane_begin(1, frame_raw, c->stream); /* (the process's download lane for frames of 1 MiB and more) */
+        const gj_stream_t down = gj_hip_lane_begin(1, b.frame_raw, c->stream); /* (the process's download lane for frames of 1 MiB and more) */
+        b.host_io = true;
         int copies = 0;
         for (int f = 0; f < count && copies == 0; f++)
-            copies = gj_hip_memcpy_d2h(output + (size_t)f * output_stride, d_out + (size_t)f * d_out_stride, frame_raw, down);
-        /* (a copy that could not be queued: the ones before it are still on their way INTO THE CALLER'S BUFFERS -- wait for the lane before the error leaves) */
+            copies = gj_hip_memcpy_d2h(output + (size_t)f * output_stride, b.d_out + (size_t)f * b.d_out_stride, b.frame_raw, down);
+        /* (a copy that could not be queued: the ones before it are still on their way INTO THE CALLER'S BUFFERS -- the lane is waited for here,
+         * the coder's stream at the exit) */
         if (gj_hip_lane_end(down, c->stream, c->timers.lane_out) != 0 || copies != 0 || gj_hip_stream_sync(c->stream) != 0) goto out;
     }
     if (param_image) {
@@ -958,7 +1054,8 @@ again:
     }
     rc = 0; /* (c->frames counts the frames TIMED with perf_stats, src/gpujpeg_common.c:2238-2254: a batch adds none) */
 out:
-    free(frame_done);
+    if (rc != 0 && b.host_io) gj_hip_stream_sync(c->stream); /* (what is queued on the stream must not read the caller's streams or write its frames after the error has left) */
+    free(b.frame_done);
     return rc;
 }
 

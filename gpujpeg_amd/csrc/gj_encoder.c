@@ -280,22 +280,17 @@ static int ensure_optimal_buffers(struct gpujpeg_encoder* e)
 }
 
 /* ------------------------------------------------------------------ encode (src/gpujpeg_encoder.c:352-644) */
-int gpujpeg_encoder_encode(struct gpujpeg_encoder* e, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi,
-                           const struct gpujpeg_encoder_input* input, uint8_t** image_compressed, size_t* image_compressed_size)
-{
-    assert(param->comp_count <= GPUJPEG_MAX_COMPONENT_COUNT);
-    assert(param->quality >= 0 && param->quality <= 100);
-    assert(param->restart_interval >= RESTART_AUTO);
-    assert(param->interleaved == 0 || param->interleaved == 1);
-    struct gj_coder* c = &e->coder;
-    GJ_HT_START(c);
-    const bool img_changed = !c->configured || !gj_image_parameters_equal(&c->param_image, pi);
-    struct gpujpeg_parameters p = adjust_params(c, param, pi, img_changed);
-    p.perf_stats = param->perf_stats || param->verbose >= GPUJPEG_LL_STATUS;
-    const bool stats = p.perf_stats != 0;
-    c->start_time = stats ? gpujpeg_get_time() : 0;
 
-    if (e->table_quality != param->quality) { /* :369-380 */
+/* What a call does before it touches the image: the parameters as they apply to this image (into *p), the quantisation tables of a new
+ * quality (:369-380), the coder set up for parameters and image. */
+static int encoder_prepare(struct gpujpeg_encoder* e, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi, int perf_stats,
+                           struct gpujpeg_parameters* p)
+{
+    struct gj_coder* c = &e->coder;
+    const bool img_changed = !c->configured || !gj_image_parameters_equal(&c->param_image, pi);
+    *p = adjust_params(c, param, pi, img_changed);
+    p->perf_stats = perf_stats;
+    if (e->table_quality != param->quality) {
         for (int t = 0; t < 2; t++) {
             float fwd[64];
             gj_quant_table_raw(t, param->quality, e->qraw[t]);
@@ -305,7 +300,97 @@ int gpujpeg_encoder_encode(struct gpujpeg_encoder* e, const struct gpujpeg_param
         if (gj_hip_stream_sync(c->stream) != 0) return -1; /* stack source */
         e->table_quality = param->quality;
     }
-    if (encoder_configure(e, &p, pi) != 0) return -1;
+    return encoder_configure(e, p, pi);
+}
+
+/* everything of a job that comes from the encoder's state and options; the caller adds where the pixels are and where tile streams, segment
+ * words, result words and the file go */
+static void enc_job_base(const struct gpujpeg_encoder* e, const struct gpujpeg_parameters* p, gj_enc_job* job)
+{
+    const struct gj_coder* c = &e->coder;
+    memset(job, 0, sizeof *job);
+    job->g = c->geom;
+    job->flipped = e->flipped;
+    job->channel_remap = e->channel_remap;
+    job->d_planes = c->d_planes;
+    job->d_coefs = c->d_coefs;
+    job->d_fwd_q[0] = e->d_fwd_q[0];
+    job->d_fwd_q[1] = e->d_fwd_q[1];
+    job->d_huff_lut = e->d_huff_lut;
+    job->jpeg_capacity = e->d_jpeg_cap;
+    job->d_scan_partial = e->d_scan_partial;
+    job->tune = e->tune;
+    job->d_scan_hdr = e->d_scan_hdr;
+    memcpy(job->scan_hdr_offset, e->scan_hdrs.offset, sizeof job->scan_hdr_offset);
+    memcpy(job->scan_info_payload, e->scan_hdrs.info_payload, sizeof job->scan_info_payload);
+    job->segment_info = p->segment_info;
+    job->use_fused = e->use_fused && !e->flipped;
+    job->keep_coefs = e->keep_coefs;
+}
+
+/* enc_opt_huffman=optimal, everything in front of the second launch: 1. pixels -> coefficient planes + the frame's symbol counts; 2. the counts
+ * to the host (the one wait this mode adds); 3. the tables; 4. header and tables up (the tables into a buffer of their own: d_huff_lut keeps
+ * Annex K.3 for every other call). Leaves the job set up for 5. the planes -> entropy-coded segments -> the file with those tables.
+ * *staged: copies from the encoder's pinned staging may be in flight. */
+static int encode_optimal_tables(struct gpujpeg_encoder* e, const struct gpujpeg_parameters* p, gj_enc_job* job, bool stats, bool* staged)
+{
+    struct gj_coder* c = &e->coder;
+    if (ensure_optimal_buffers(e) != 0) return -1;
+    job->stage = GJ_ENC_STAGE_COUNT;
+    job->d_huff_freq = e->d_huff_freq;
+    GJ_HT(c, 0);
+    if (gj_hip_encode(job, c->stream, stats ? c->timers.ev : NULL) != 0 ||
+        gj_hip_memcpy_d2h(e->h_huff_freq, e->d_huff_freq, 1024 * sizeof(uint32_t), c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) {
+        GJ_ERROR("Encoder kernels failed: %s\n", gj_hip_last_error());
+        c->configured = false;
+        return -1;
+    }
+    struct gj_huff_spec spec;
+    if (build_optimal_tables(&c->geom, e->h_huff_freq, &spec) != 0) return -1;
+    gj_huffman_encoder_lut(&spec, e->h_opt_lut);
+    *staged = true;
+    if (gj_hip_memcpy_h2d(e->d_opt_lut, e->h_opt_lut, (GJ_CODER_LUT_OFFSET + GJ_CODER_LUT_WORDS) * sizeof(uint32_t), c->stream) != 0) return -1;
+    const size_t hdr = place_main_header(e, p, &spec);
+    if (hdr == 0) return -1;
+    job->main_hdr_size = (uint32_t)hdr;
+    job->stage = GJ_ENC_STAGE_CODE;
+    job->d_huff_lut = e->d_opt_lut;
+    return 0;
+}
+
+static void encoder_stats(struct gpujpeg_encoder* e, bool optimal, bool uploaded)
+{
+    struct gj_coder* c = &e->coder;
+    struct gpujpeg_duration_stats* s = &c->stats;
+    /* (optimal tables: the DCT ends at event 6, k_huffman_count runs from 6 to 7, the second call starts at 2; duration_in_gpu includes the
+     * host's round trip in between) */
+    for (int k = 0; k < 5; k++) c->kernel_ms[k] = gj_hip_event_elapsed_ms(c->timers.ev[k], c->timers.ev[optimal && k == 1 ? 6 : k + 1]);
+    c->kernel_ms[5] = optimal ? gj_hip_event_elapsed_ms(c->timers.ev[6], c->timers.ev[7]) : 0.0f;
+    c->kernel_ms[6] = c->kernel_ms[7] = 0.0f;
+    s->duration_preprocessor = c->kernel_ms[0];
+    s->duration_dct_quantization = c->kernel_ms[1];
+    s->duration_huffman_coder = gj_hip_event_elapsed_ms(c->timers.ev[2], c->timers.ev[5]) + c->kernel_ms[5];
+    s->duration_in_gpu = gj_hip_event_elapsed_ms(c->timers.ev[0], c->timers.ev[5]);
+    if (uploaded) s->duration_memory_to = gj_hip_event_elapsed_ms(c->timers.copy_in[0], c->timers.copy_in[1]);
+    if (e->out_location != GJ_OUT_DEVICE) s->duration_memory_from = gj_hip_event_elapsed_ms(c->timers.copy_out[0], c->timers.copy_out[1]);
+    c->timers.valid = true;
+}
+
+int gpujpeg_encoder_encode(struct gpujpeg_encoder* e, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi,
+                           const struct gpujpeg_encoder_input* input, uint8_t** image_compressed, size_t* image_compressed_size)
+{
+    assert(param->comp_count <= GPUJPEG_MAX_COMPONENT_COUNT);
+    assert(param->quality >= 0 && param->quality <= 100);
+    assert(param->restart_interval >= RESTART_AUTO);
+    assert(param->interleaved == 0 || param->interleaved == 1);
+    struct gj_coder* c = &e->coder;
+    GJ_HT_START(c);
+    const bool stats = param->perf_stats || param->verbose >= GPUJPEG_LL_STATUS;
+    c->start_time = stats ? gpujpeg_get_time() : 0;
+    struct gpujpeg_parameters p;
+    int rc = -1;
+    bool in_flight = false; /* copies that read the caller's image or the encoder's pinned staging have been queued on the coder's stream */
+    if (encoder_prepare(e, param, pi, stats, &p) != 0) goto out;
     const gj_geom* g = &c->geom;
     c->init_end_time = stats ? gpujpeg_get_time() : 0;
     memset(&c->stats, 0, sizeof c->stats);
@@ -315,145 +400,86 @@ int gpujpeg_encoder_encode(struct gpujpeg_encoder* e, const struct gpujpeg_param
     if (input->type == GPUJPEG_ENCODER_INPUT_GPU_IMAGE || (input->type == GPUJPEG_ENCODER_INPUT_IMAGE && gj_hip_is_device_ptr(input->image))) {
         d_raw = input->image;
     } else if (input->type == GPUJPEG_ENCODER_INPUT_IMAGE) {
-        if (gj_ensure_device_buffer((void**)&c->d_raw_own, &c->d_raw_cap, g->raw_size) != 0) return -1;
+        if (gj_ensure_device_buffer((void**)&c->d_raw_own, &c->d_raw_cap, g->raw_size) != 0) goto out;
         gj_hip_event_record(c->timers.copy_in[0], c->stream); /* (also without perf_stats: see gj_internal.h, copy markers) */
+        in_flight = true;
         /* (through the process's upload lane unless the copy is timed on the coder's stream) */
         if (gj_hip_upload(c->d_raw_own, input->image, g->raw_size, c->stream, stats ? NULL : c->timers.lane_in) != 0) {
             GJ_ERROR("Encoder raw data copy failed: %s\n", gj_hip_last_error());
-            return -1;
+            goto out;
         }
         if (stats) gj_hip_event_record(c->timers.copy_in[1], c->stream);
         d_raw = c->d_raw_own;
     } else {
         GJ_ERROR("OpenGL texture input is not supported by the MI355X build.\n");
-        return -1;
+        goto out;
     }
 
     /* main header (with optimal tables: once the frame's tables are known) */
     const bool optimal = e->huff_optimal != 0;
     size_t hdr = 0;
-    if (!optimal && (hdr = place_main_header(e, &p, NULL)) == 0) return -1;
+    if (!optimal && (hdr = place_main_header(e, &p, NULL)) == 0) goto out;
+    if (gj_channel_remap_check(e->channel_remap, c->param_image.pixel_format) != 0) goto out;
 
     gj_enc_job job;
-    memset(&job, 0, sizeof job);
-    job.g = *g;
+    enc_job_base(e, &p, &job);
     job.d_raw = d_raw;
-    job.flipped = e->flipped;
-    job.channel_remap = e->channel_remap;
-    if (e->channel_remap) {
-        const enum gpujpeg_pixel_format pf = c->param_image.pixel_format;
-        if ((int)(e->channel_remap >> 24) != gpujpeg_pixel_format_get_comp_count(pf)) {
-            GJ_ERROR("Wrong channel remapping given, given %u channels but pixel format has %d!\n", e->channel_remap >> 24, gpujpeg_pixel_format_get_comp_count(pf));
-            return -1;
-        }
-        if (pf != GPUJPEG_U8 && pf != GPUJPEG_444_U8_P012 && pf != GPUJPEG_4444_U8_P0123 && pf != GPUJPEG_444_U8_P0P1P2) {
-            GJ_ERROR("Channel remapping is implemented for pixel formats whose pixels do not share samples (u8, 444-u8-p012, 4444-u8-p0123, 444-u8-p0p1p2).\n");
-            return -1;
-        }
-    }
-    job.d_planes = c->d_planes;
-    job.d_coefs = c->d_coefs;
-    job.d_fwd_q[0] = e->d_fwd_q[0];
-    job.d_fwd_q[1] = e->d_fwd_q[1];
-    job.d_huff_lut = e->d_huff_lut;
     job.d_temp = e->d_temp;
     job.d_seg_bytes = e->d_seg;
     job.d_seg_ff = e->d_seg + g->segment_count;
     job.d_seg_out = e->d_seg + 2 * (size_t)g->segment_count;
     job.d_jpeg = e->d_jpeg;
-    job.jpeg_capacity = e->d_jpeg_cap;
     job.d_result = e->d_result;
     job.h_result = e->h_result;
-    job.d_scan_partial = e->d_scan_partial;
     job.d_tail = e->d_tail;
     job.tail_set = e->tail_set;
     if (++e->epoch == 0) e->epoch = 1;
     job.epoch = e->epoch;
-    job.tune = e->tune;
-    job.d_scan_hdr = e->d_scan_hdr;
-    memcpy(job.scan_hdr_offset, e->scan_hdrs.offset, sizeof job.scan_hdr_offset);
-    memcpy(job.scan_info_payload, e->scan_hdrs.info_payload, sizeof job.scan_info_payload);
     job.main_hdr_size = (uint32_t)hdr;
-    job.segment_info = p.segment_info;
-    job.use_fused = e->use_fused && !e->flipped;
-    job.keep_coefs = e->keep_coefs;
-    /* the sets of group totals alternate only between calls that end in k_gather, which clears the idle one: a call that takes the
-     * coefficient planes (flip, kept coefficients, fused path off) leaves both as they are (it used to flip, and the next
-     * tile-path call added its sizes to an older frame's totals) */
     if (optimal) {
-        /* 1. pixels -> coefficient planes + the frame's symbol counts; 2. the counts to the host (the one wait this mode adds); 3. the
-         * tables; 4. header and tables up (the tables into a buffer of their own: d_huff_lut keeps Annex K.3 for every other call);
-         * 5. the planes -> entropy-coded segments -> the file with those tables */
-        if (ensure_optimal_buffers(e) != 0) return -1;
-        job.stage = GJ_ENC_STAGE_COUNT;
-        job.d_huff_freq = e->d_huff_freq;
-        GJ_HT(c, 0);
-        if (gj_hip_encode(&job, c->stream, stats ? c->timers.ev : NULL) != 0 ||
-            gj_hip_memcpy_d2h(e->h_huff_freq, e->d_huff_freq, 1024 * sizeof(uint32_t), c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) {
-            GJ_ERROR("Encoder kernels failed: %s\n", gj_hip_last_error());
-            c->configured = false;
-            return -1;
-        }
-        struct gj_huff_spec spec;
-        if (build_optimal_tables(g, e->h_huff_freq, &spec) != 0) return -1;
-        gj_huffman_encoder_lut(&spec, e->h_opt_lut);
-        if (gj_hip_memcpy_h2d(e->d_opt_lut, e->h_opt_lut, (GJ_CODER_LUT_OFFSET + GJ_CODER_LUT_WORDS) * sizeof(uint32_t), c->stream) != 0) return -1;
-        if ((hdr = place_main_header(e, &p, &spec)) == 0) return -1;
-        job.main_hdr_size = (uint32_t)hdr;
-        job.stage = GJ_ENC_STAGE_CODE;
-        job.d_huff_lut = e->d_opt_lut;
+        if (encode_optimal_tables(e, &p, &job, stats, &in_flight) != 0) goto out;
     } else {
+        /* the sets of group totals alternate only between calls that end in k_gather, which clears the idle one: a call that takes the
+         * coefficient planes (flip, kept coefficients, fused path off) leaves both as they are (it used to flip, and the next
+         * tile-path call added its sizes to an older frame's totals) */
         if (gj_hip_encode_tiles(&job)) e->tail_set ^= 1;
         GJ_HT(c, 0);
     }
     if (gj_hip_encode(&job, c->stream, stats ? c->timers.ev : NULL) != 0) {
         GJ_ERROR("Encoder kernels failed: %s\n", gj_hip_last_error());
-        if (optimal) gj_hip_stream_sync(c->stream); /* (copies from the pinned staging may still be in flight) */
         c->configured = false; /* (the next call sets the device-side state up again) */
-        return -1;
+        goto out;
     }
     GJ_HT(c, 1);
     /* size first, then the bytes (:550-563) */
     if (gj_hip_stream_sync(c->stream) != 0) { /* (the two result words are in host memory once the kernels have run) */
         GJ_ERROR("Encoder failed: %s\n", gj_hip_last_error());
         c->configured = false;
-        return -1;
+        goto out;
     }
     GJ_HT(c, 2);
+    in_flight = false;
     const size_t size = e->h_result[0];
     if (e->h_result[1]) {
         GJ_ERROR("Compressed stream (%zu B) does not fit the output buffer (%zu B)!\n", size, e->d_jpeg_cap);
-        return -1;
+        goto out;
     }
     if (e->out_location == GJ_OUT_DEVICE) {
         *image_compressed = e->d_jpeg;
     } else {
-        if (ensure_out_buffer(e, e->d_jpeg_cap) != 0) return -1;
+        if (ensure_out_buffer(e, e->d_jpeg_cap) != 0) goto out;
         gj_hip_event_record(c->timers.copy_out[0], c->stream); /* (copy marker) */
+        in_flight = true;
         /* (the compressed stream stays on the coder's own stream: queued behind other coders' images in the download lane it came out 10-40 %
          * slower with four coders, profiles/r5_07) */
-        if (gj_hip_memcpy_d2h(e->out_buf, e->d_jpeg, size, c->stream) != 0) return -1;
+        if (gj_hip_memcpy_d2h(e->out_buf, e->d_jpeg, size, c->stream) != 0) goto out;
         if (stats) gj_hip_event_record(c->timers.copy_out[1], c->stream);
-        if (gj_hip_stream_sync(c->stream) != 0) return -1;
+        if (gj_hip_stream_sync(c->stream) != 0) goto out;
         *image_compressed = e->out_buf;
     }
     *image_compressed_size = size;
 
-    if (stats) {
-        struct gpujpeg_duration_stats* s = &c->stats;
-        /* (optimal tables: the DCT ends at event 6, k_huffman_count runs from 6 to 7, the second call starts at 2; duration_in_gpu includes the
-         * host's round trip in between) */
-        for (int k = 0; k < 5; k++) c->kernel_ms[k] = gj_hip_event_elapsed_ms(c->timers.ev[k], c->timers.ev[optimal && k == 1 ? 6 : k + 1]);
-        c->kernel_ms[5] = optimal ? gj_hip_event_elapsed_ms(c->timers.ev[6], c->timers.ev[7]) : 0.0f;
-        c->kernel_ms[6] = c->kernel_ms[7] = 0.0f;
-        s->duration_preprocessor = c->kernel_ms[0];
-        s->duration_dct_quantization = c->kernel_ms[1];
-        s->duration_huffman_coder = gj_hip_event_elapsed_ms(c->timers.ev[2], c->timers.ev[5]) + c->kernel_ms[5];
-        s->duration_in_gpu = gj_hip_event_elapsed_ms(c->timers.ev[0], c->timers.ev[5]);
-        if (d_raw == c->d_raw_own) s->duration_memory_to = gj_hip_event_elapsed_ms(c->timers.copy_in[0], c->timers.copy_in[1]);
-        if (e->out_location != GJ_OUT_DEVICE) s->duration_memory_from = gj_hip_event_elapsed_ms(c->timers.copy_out[0], c->timers.copy_out[1]);
-        c->timers.valid = true;
-    }
+    if (stats) encoder_stats(e, optimal, d_raw == c->d_raw_own);
     gj_coder_process_stats(c, stats);
     if (c->param.verbose >= GPUJPEG_LL_STATUS) {
         const char* il = p.comp_count == 1 ? "" : (p.interleaved ? " interleaved" : " non-interleaved");
@@ -462,7 +488,10 @@ int gpujpeg_encoder_encode(struct gpujpeg_encoder* e, const struct gpujpeg_param
     }
     GJ_HT(c, 3);
     c->ht_calls++;
-    return 0;
+    rc = 0;
+out:
+    if (rc != 0 && in_flight) gj_hip_stream_sync(c->stream); /* (what this call queued on its stream must not read the caller's image or the staging after the error has left) */
+    return rc;
 }
 
 int gpujpeg_encoder_get_stats(struct gpujpeg_encoder* e, struct gpujpeg_duration_stats* stats)
@@ -482,101 +511,126 @@ int gpujpeg_encoder_get_stats(struct gpujpeg_encoder* e, struct gpujpeg_duration
                                    frames are bounded by the bytes below) */
 #define GJ_BATCH_TEMP_BYTES ((size_t)6 << 30) /* tile areas of one chunk (address space: only the streams' bytes are touched) */
 
+/* another configuration than the batched kernels', or tables per frame: frame by frame, every stream copied to its slot */
+static int batch_encode_singly(struct gpujpeg_encoder* e, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi,
+                               const uint8_t* frames, size_t frame_stride, bool frames_on_device, int count, size_t slot)
+{
+    struct gj_coder* c = &e->coder;
+    for (int f = 0; f < count; f++) {
+        struct gpujpeg_encoder_input in;
+        if (frames_on_device) gpujpeg_encoder_input_set_gpu_image(&in, (uint8_t*)(uintptr_t)(frames + (size_t)f * frame_stride));
+        else gpujpeg_encoder_input_set_image(&in, (uint8_t*)(uintptr_t)(frames + (size_t)f * frame_stride));
+        const int loc = e->out_location;
+        e->out_location = GJ_OUT_DEVICE;
+        uint8_t* one = NULL;
+        size_t n = 0;
+        const int rc = gpujpeg_encoder_encode(e, param, pi, &in, &one, &n);
+        e->out_location = loc;
+        if (rc != 0 || n > slot) return -1;
+        if (gj_hip_memcpy_d2d(e->b_jpeg + (size_t)f * slot, one, n, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) return -1;
+        e->bh_result[2 * f] = (uint32_t)n;
+        e->bh_result[2 * f + 1] = 0;
+    }
+    e->b_hdr_to = NULL; /* (the slots' headers were overwritten by whole streams) */
+    return 0;
+}
+
+/* main header of a batch: the same bytes at the start of every slot, uploaded when they change (as place_main_header does for the one buffer
+ * of gpujpeg_encoder_encode). Returns its size, 0 on error. */
+static size_t place_batch_headers(struct gpujpeg_encoder* e, const struct gpujpeg_parameters* p, int count, size_t slot)
+{
+    struct gj_coder* c = &e->coder;
+    const size_t hdr = gj_write_main_header(e->h_header, GJ_MAIN_HEADER_CAP, &c->geom, p, e->header_type, (const uint8_t(*)[64])e->qraw, &e->metadata,
+                                            e->exif_tags, NULL);
+    if (hdr > GJ_MAIN_HEADER_CAP) {
+        GJ_ERROR("The main header (%zu B: Exif tags, metadata) does not fit its %d B staging buffer.\n", hdr, GJ_MAIN_HEADER_CAP);
+        return 0;
+    }
+    if (!e->b_hdr_sent) e->b_hdr_sent = malloc(GJ_MAIN_HEADER_CAP);
+    if (!e->b_hdr_sent) return 0;
+    if (e->b_hdr_to != e->b_jpeg || e->b_hdr_slot != slot || e->b_hdr_frames < count || e->b_hdr_len != hdr || memcmp(e->b_hdr_sent, e->h_header, hdr) != 0) {
+        for (int f = 0; f < count; f++)
+            if (gj_hip_memcpy_h2d(e->b_jpeg + (size_t)f * slot, e->h_header, hdr, c->stream) != 0) return 0;
+        if (gj_hip_stream_sync(c->stream) != 0) return 0;
+        memcpy(e->b_hdr_sent, e->h_header, hdr);
+        e->b_hdr_len = hdr;
+        e->b_hdr_to = e->b_jpeg;
+        e->b_hdr_slot = slot;
+        e->b_hdr_frames = count;
+    }
+    return hdr;
+}
+
+/* the sizes of the streams (from the result words) and the streams where the caller wants them */
+static int batch_streams_out(struct gpujpeg_encoder* e, int count, size_t slot, uint8_t** images_compressed, size_t* images_compressed_size)
+{
+    struct gj_coder* c = &e->coder;
+    size_t longest = 0;
+    for (int f = 0; f < count; f++) {
+        if (e->bh_result[2 * f + 1]) {
+            GJ_ERROR("Compressed stream (%u B) of frame %d does not fit the output buffer (%zu B)!\n", e->bh_result[2 * f], f, e->d_jpeg_cap);
+            return -1;
+        }
+        images_compressed_size[f] = e->bh_result[2 * f];
+        if (e->bh_result[2 * f] > longest) longest = e->bh_result[2 * f];
+    }
+    if (e->out_location == GJ_OUT_DEVICE) {
+        for (int f = 0; f < count; f++) images_compressed[f] = e->b_jpeg + (size_t)f * slot;
+        return 0;
+    }
+    /* (host copies too lie a constant number of bytes apart -- images_compressed[1] - images_compressed[0], a multiple of 16 --, so that the
+     * pointers can go straight into gpujpeg_amd_decoder_decode_batch) */
+    const size_t host_stride = (longest + 64 + 15) & ~(size_t)15, total = host_stride * (size_t)count;
+    const bool want_pinned = e->out_location == GJ_OUT_PINNED;
+    if (total > e->b_out_cap || want_pinned != e->b_out_pinned) {
+        if (e->b_out_pinned) gj_hip_host_free(e->b_out); else free(e->b_out);
+        e->b_out = want_pinned ? gj_hip_host_alloc(total + total / 4) : malloc(total + total / 4);
+        e->b_out_pinned = want_pinned;
+        e->b_out_cap = e->b_out ? total + total / 4 : 0;
+        if (!e->b_out) return -1;
+    }
+    gj_hip_event_record(c->timers.copy_out[0], c->stream); /* (copy marker) */
+    int copies = 0;
+    for (int f = 0; f < count && copies == 0; f++) {
+        copies = gj_hip_memcpy_d2h(e->b_out + (size_t)f * host_stride, e->b_jpeg + (size_t)f * slot, images_compressed_size[f], c->stream);
+        images_compressed[f] = e->b_out + (size_t)f * host_stride;
+    }
+    return gj_hip_stream_sync(c->stream) != 0 || copies != 0 ? -1 : 0; /* (waited for also when a copy could not be queued) */
+}
+
 int gpujpeg_amd_encoder_encode_batch(struct gpujpeg_encoder* e, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi,
                                      const uint8_t* frames, size_t frame_stride, int count, uint8_t** images_compressed, size_t* images_compressed_size)
 {
     if (!e || !param || !pi || !frames || count < 1 || !images_compressed || !images_compressed_size) return -1;
     struct gj_coder* c = &e->coder;
-    const bool img_changed = !c->configured || !gj_image_parameters_equal(&c->param_image, pi);
-    struct gpujpeg_parameters p = adjust_params(c, param, pi, img_changed);
-    p.perf_stats = 0;
-    if (e->table_quality != param->quality) {
-        for (int t = 0; t < 2; t++) {
-            float fwd[64];
-            gj_quant_table_raw(t, param->quality, e->qraw[t]);
-            gj_quant_table_forward(e->qraw[t], fwd);
-            if (gj_hip_memcpy_h2d(e->d_fwd_q[t], fwd, sizeof fwd, c->stream) != 0) return -1;
-        }
-        if (gj_hip_stream_sync(c->stream) != 0) return -1;
-        e->table_quality = param->quality;
-    }
-    if (encoder_configure(e, &p, pi) != 0) return -1;
+    struct gpujpeg_parameters p;
+    int rc = -1;
+    bool in_flight = false; /* copies that read the caller's frames have been queued on the coder's stream */
+    if (encoder_prepare(e, param, pi, 0, &p) != 0) goto out;
     const gj_geom* g = &c->geom;
     if (frame_stride < g->raw_size) {
         GJ_ERROR("Frame stride %zu is smaller than a frame (%zu B)!\n", frame_stride, (size_t)g->raw_size);
-        return -1;
+        goto out;
     }
     const bool frames_on_device = gj_hip_is_device_ptr(frames) != 0;
     /* the streams of ALL frames stay valid until the next call: a slot per frame, sized like the single-frame buffer */
-    const size_t slot = (e->d_jpeg_cap + 255) & ~(size_t)255;
-    if (gj_ensure_device_buffer((void**)&e->b_jpeg, &e->b_jpeg_cap, slot * (size_t)count) != 0) return -1;
-    if (gj_ensure_device_buffer((void**)&e->b_result, &e->b_result_cap, (size_t)count * 2 * sizeof(uint32_t)) != 0) return -1;
-    if ((size_t)count * 2 * sizeof(uint32_t) > e->bh_result_cap) {
-        gj_hip_host_free(e->bh_result);
-        e->bh_result_cap = (size_t)count * 2 * sizeof(uint32_t) * 2;
-        e->bh_result = gj_hip_host_alloc(e->bh_result_cap);
-        if (!e->bh_result) { e->bh_result_cap = 0; return -1; }
-    }
+    const size_t slot = (e->d_jpeg_cap + 255) & ~(size_t)255, result_bytes = (size_t)count * 2 * sizeof(uint32_t);
+    if (gj_ensure_device_buffer((void**)&e->b_jpeg, &e->b_jpeg_cap, slot * (size_t)count) != 0) goto out;
+    if (gj_ensure_device_buffer((void**)&e->b_result, &e->b_result_cap, result_bytes) != 0) goto out;
+    if (gj_ensure_pinned_buffer((void**)&e->bh_result, &e->bh_result_cap, result_bytes, result_bytes * 2) != 0) goto out;
 
     gj_enc_job job;
-    memset(&job, 0, sizeof job);
-    job.g = *g;
-    job.flipped = e->flipped;
-    job.channel_remap = e->channel_remap;
-    job.d_planes = c->d_planes;
-    job.d_coefs = c->d_coefs;
-    job.d_fwd_q[0] = e->d_fwd_q[0];
-    job.d_fwd_q[1] = e->d_fwd_q[1];
-    job.d_huff_lut = e->d_huff_lut;
-    job.tune = e->tune;
-    job.d_scan_hdr = e->d_scan_hdr;
-    memcpy(job.scan_hdr_offset, e->scan_hdrs.offset, sizeof job.scan_hdr_offset);
-    memcpy(job.scan_info_payload, e->scan_hdrs.info_payload, sizeof job.scan_info_payload);
-    job.segment_info = p.segment_info;
-    job.use_fused = e->use_fused && !e->flipped;
-    job.keep_coefs = e->keep_coefs;
-
-    if (e->huff_optimal || !gj_hip_encode_batchable(&job)) {
-        /* another configuration than the fully fused kernel's, or tables per frame: frame by frame, every stream copied to its slot */
-        for (int f = 0; f < count; f++) {
-            struct gpujpeg_encoder_input in;
-            if (frames_on_device) gpujpeg_encoder_input_set_gpu_image(&in, (uint8_t*)(uintptr_t)(frames + (size_t)f * frame_stride));
-            else gpujpeg_encoder_input_set_image(&in, (uint8_t*)(uintptr_t)(frames + (size_t)f * frame_stride));
-            const int loc = e->out_location;
-            e->out_location = GJ_OUT_DEVICE;
-            uint8_t* one = NULL;
-            size_t n = 0;
-            const int rc = gpujpeg_encoder_encode(e, param, pi, &in, &one, &n);
-            e->out_location = loc;
-            if (rc != 0 || n > slot) return -1;
-            if (gj_hip_memcpy_d2d(e->b_jpeg + (size_t)f * slot, one, n, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) return -1;
-            e->bh_result[2 * f] = (uint32_t)n;
-            e->bh_result[2 * f + 1] = 0;
-        }
-        e->b_hdr_to = NULL; /* (the slots' headers were overwritten by whole streams) */
+    enc_job_base(e, &p, &job);
+    const bool batched = !e->huff_optimal && gj_hip_encode_batchable(&job);
+    if (!batched) {
+        if (batch_encode_singly(e, param, pi, frames, frame_stride, frames_on_device, count, slot) != 0) goto out;
         e->b_last_batched = 0;
         e->b_last_single = count;
     } else {
         e->b_last_batched = count;
         e->b_last_single = 0;
-        /* main header: the same bytes at the start of every slot, uploaded when they change (as gpujpeg_encoder_encode does for its one buffer) */
-        const size_t hdr = gj_write_main_header(e->h_header, GJ_MAIN_HEADER_CAP, g, &p, e->header_type, (const uint8_t(*)[64])e->qraw, &e->metadata, e->exif_tags, NULL);
-        if (hdr > GJ_MAIN_HEADER_CAP) {
-            GJ_ERROR("The main header (%zu B: Exif tags, metadata) does not fit its %d B staging buffer.\n", hdr, GJ_MAIN_HEADER_CAP);
-            return -1;
-        }
-        if (!e->b_hdr_sent) e->b_hdr_sent = malloc(GJ_MAIN_HEADER_CAP);
-        if (!e->b_hdr_sent) return -1;
-        if (e->b_hdr_to != e->b_jpeg || e->b_hdr_slot != slot || e->b_hdr_frames < count || e->b_hdr_len != hdr || memcmp(e->b_hdr_sent, e->h_header, hdr) != 0) {
-            for (int f = 0; f < count; f++)
-                if (gj_hip_memcpy_h2d(e->b_jpeg + (size_t)f * slot, e->h_header, hdr, c->stream) != 0) return -1;
-            if (gj_hip_stream_sync(c->stream) != 0) return -1;
-            memcpy(e->b_hdr_sent, e->h_header, hdr);
-            e->b_hdr_len = hdr;
-            e->b_hdr_to = e->b_jpeg;
-            e->b_hdr_slot = slot;
-            e->b_hdr_frames = count;
-        }
+        const size_t hdr = place_batch_headers(e, &p, count, slot);
+        if (hdr == 0) goto out;
         /* chunks: as many frames per launch as their tile areas may take */
         const size_t temp_frame = (((size_t)g->block_count * GJ_TEMP_BYTES_PER_BLOCK + 256) + 255) & ~(size_t)255;
         const size_t seg_frame = ((size_t)g->segment_count * 2 + 16 + 3) & ~(size_t)3;          /* words: bytes | ff */
@@ -586,30 +640,30 @@ int gpujpeg_amd_encoder_encode_batch(struct gpujpeg_encoder* e, const struct gpu
         if (e->b_chunk > 0 && chunk > e->b_chunk) chunk = e->b_chunk;
         if (chunk > count) chunk = count;
         if (chunk < 1) chunk = 1;
-        if (gj_ensure_device_buffer((void**)&e->b_temp, &e->b_temp_cap, temp_frame * (size_t)chunk) != 0) return -1;
-        if (gj_ensure_device_buffer((void**)&e->b_seg, &e->b_seg_cap, seg_frame * (size_t)chunk * sizeof(uint32_t)) != 0) return -1;
-        if (gj_ensure_device_buffer((void**)&e->b_tail, &e->b_tail_cap, tail_frame * (size_t)chunk * sizeof(uint32_t)) != 0) return -1;
+        if (gj_ensure_device_buffer((void**)&e->b_temp, &e->b_temp_cap, temp_frame * (size_t)chunk) != 0) goto out;
+        if (gj_ensure_device_buffer((void**)&e->b_seg, &e->b_seg_cap, seg_frame * (size_t)chunk * sizeof(uint32_t)) != 0) goto out;
+        if (gj_ensure_device_buffer((void**)&e->b_tail, &e->b_tail_cap, tail_frame * (size_t)chunk * sizeof(uint32_t)) != 0) goto out;
         const uint8_t* d_frames = frames;
         size_t d_stride = frame_stride;
         if (!frames_on_device) {
-            if (gj_ensure_device_buffer((void**)&e->b_raw, &e->b_raw_cap, (size_t)g->raw_size * (size_t)count) != 0) return -1;
+            if (gj_ensure_device_buffer((void**)&e->b_raw, &e->b_raw_cap, (size_t)g->raw_size * (size_t)count) != 0) goto out;
             gj_hip_event_record(c->timers.copy_in[0], c->stream); /* (copy marker, see gj_internal.h) */
             const gj_stream_t up = gj_hip_lane_begin(0, g->raw_size, c->stream); /* (the process's upload lane for frames of 1 MiB and more) */
+            in_flight = true;
             int copies = 0;
             for (int f = 0; f < count && copies == 0; f++)
                 copies = gj_hip_memcpy_h2d(e->b_raw + (size_t)f * g->raw_size, frames + (size_t)f * frame_stride, g->raw_size, up);
-            /* (a copy that could not be queued: the ones before it still read THE CALLER'S BUFFERS -- wait for the lane before the error leaves) */
-            if (gj_hip_lane_end(up, c->stream, c->timers.lane_in) != 0 || copies != 0) return -1;
+            /* (a copy that could not be queued: the ones before it still read THE CALLER'S BUFFERS -- the lane is waited for here, the coder's
+             * stream at the exit) */
+            if (gj_hip_lane_end(up, c->stream, c->timers.lane_in) != 0 || copies != 0) goto out;
             d_frames = e->b_raw;
             d_stride = g->raw_size;
         }
         job.main_hdr_size = (uint32_t)hdr;
-        job.jpeg_capacity = e->d_jpeg_cap;
         job.d_temp = e->b_temp;
         job.d_seg_bytes = e->b_seg;
         job.d_seg_ff = e->b_seg + g->segment_count;
         job.d_seg_out = NULL;
-        job.d_scan_partial = e->d_scan_partial;
         job.d_tail = e->b_tail;
         job.tail_set = 0;
         job.batch.raw = d_stride;
@@ -620,7 +674,7 @@ int gpujpeg_amd_encoder_encode_batch(struct gpujpeg_encoder* e, const struct gpu
         for (int f0 = 0; f0 < count; f0 += chunk) {
             const int n = count - f0 < chunk ? count - f0 : chunk;
             /* (the group totals a launch adds to: zero for every frame of the chunk, whatever the chunks before it looked like) */
-            if (gj_hip_memset(e->b_tail, 0, tail_frame * (size_t)n * sizeof(uint32_t), c->stream) != 0) return -1;
+            if (gj_hip_memset(e->b_tail, 0, tail_frame * (size_t)n * sizeof(uint32_t), c->stream) != 0) goto out;
             job.d_raw = d_frames + (size_t)f0 * d_stride;
             job.d_jpeg = e->b_jpeg + (size_t)f0 * slot;
             job.d_result = e->b_result + 2 * (size_t)f0;
@@ -631,46 +685,21 @@ int gpujpeg_amd_encoder_encode_batch(struct gpujpeg_encoder* e, const struct gpu
             if (gj_hip_encode(&job, c->stream, NULL) != 0) {
                 GJ_ERROR("Encoder kernels failed: %s\n", gj_hip_last_error());
                 c->configured = false;
-                return -1;
+                goto out;
             }
         }
         if (gj_hip_stream_sync(c->stream) != 0) {
             GJ_ERROR("Encoder failed: %s\n", gj_hip_last_error());
             c->configured = false;
-            return -1;
+            goto out;
         }
+        in_flight = false;
     }
-    size_t longest = 0;
-    for (int f = 0; f < count; f++) {
-        if (e->bh_result[2 * f + 1]) {
-            GJ_ERROR("Compressed stream (%u B) of frame %d does not fit the output buffer (%zu B)!\n", e->bh_result[2 * f], f, e->d_jpeg_cap);
-            return -1;
-        }
-        images_compressed_size[f] = e->bh_result[2 * f];
-        if (e->bh_result[2 * f] > longest) longest = e->bh_result[2 * f];
-    }
-    /* (host copies too lie a constant number of bytes apart -- images_compressed[1] - images_compressed[0], a multiple of 16 --, so that the
-     * pointers can go straight into gpujpeg_amd_decoder_decode_batch) */
-    const size_t host_stride = (longest + 64 + 15) & ~(size_t)15, total = host_stride * (size_t)count;
-    if (e->out_location == GJ_OUT_DEVICE) {
-        for (int f = 0; f < count; f++) images_compressed[f] = e->b_jpeg + (size_t)f * slot;
-    } else {
-        const bool want_pinned = e->out_location == GJ_OUT_PINNED;
-        if (total > e->b_out_cap || want_pinned != e->b_out_pinned) {
-            if (e->b_out_pinned) gj_hip_host_free(e->b_out); else free(e->b_out);
-            e->b_out = want_pinned ? gj_hip_host_alloc(total + total / 4) : malloc(total + total / 4);
-            e->b_out_pinned = want_pinned;
-            e->b_out_cap = e->b_out ? total + total / 4 : 0;
-            if (!e->b_out) return -1;
-        }
-        gj_hip_event_record(c->timers.copy_out[0], c->stream); /* (copy marker) */
-        for (int f = 0; f < count; f++) {
-            if (gj_hip_memcpy_d2h(e->b_out + (size_t)f * host_stride, e->b_jpeg + (size_t)f * slot, images_compressed_size[f], c->stream) != 0) return -1;
-            images_compressed[f] = e->b_out + (size_t)f * host_stride;
-        }
-        if (gj_hip_stream_sync(c->stream) != 0) return -1;
-    }
-    return 0; /* (c->frames counts the frames timed with perf_stats: a batch adds none, see gj_coder_process_stats_overall) */
+    rc = batch_streams_out(e, count, slot, images_compressed, images_compressed_size);
+    /* (c->frames counts the frames timed with perf_stats: a batch adds none, see gj_coder_process_stats_overall) */
+out:
+    if (rc != 0 && in_flight) gj_hip_stream_sync(c->stream); /* (what is queued on the stream must not read the caller's frames after the error has left) */
+    return rc;
 }
 
 /* The same for frames that are separate buffers (device or host memory, mixed if need be). Buffers that happen to lie a constant distance apart

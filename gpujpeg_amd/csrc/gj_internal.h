@@ -106,6 +106,8 @@ void gj_coder_process_stats_overall(struct gj_coder* c);
 int gj_timers_create(struct gj_timers* t);
 void gj_timers_destroy(struct gj_timers* t);
 int gj_ensure_device_buffer(void** p, size_t* cap, size_t need);
+int gj_ensure_pinned_buffer(void** p, size_t* cap, size_t need, size_t grow_to); /* grow_to >= need: what a buffer that has to grow is replaced by */
+int gj_channel_remap_check(unsigned remap, enum gpujpeg_pixel_format pixel_format);
 
 /* ---- writer (src/gpujpeg_writer.c) ---- */
 struct gj_scan_headers {
