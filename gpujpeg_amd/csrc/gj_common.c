@@ -496,6 +496,46 @@ int gj_geom_init(gj_geom* g, const struct gpujpeg_parameters* param, const struc
     return 0;
 }
 
+/* Reduced-size decode (dec_opt_scale = 1/s, DESIGN "Reduced-size decode"): the geometry of the ceil(W / s) x ceil(H / s) image the pixel kernels
+ * work on, and that image's parameters. Every block leaves N = 8 / s samples per edge, so a component's reduced plane is the full one's
+ * data_width * N / 8 x data_height * N / 8 samples (its pitch and offset here); width / height of the components are what the stream's sampling
+ * factors make of the reduced image, as in gj_geom_init. `alignment`: dec_opt_alignment_bytes, applied to the reduced line. -1: no such image
+ * (packed 4:2:2 output of odd width, see tests/conftest.py CASES). */
+int gj_geom_init_scaled(gj_geom* gs, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi, int s,
+                        unsigned alignment, struct gpujpeg_image_parameters* pi_scaled)
+{
+    if (s != 2 && s != 4 && s != 8) return -1;
+    const int N = 8 / s;
+    struct gpujpeg_image_parameters rp = *pi;
+    rp.width = GPUJPEG_AMD_SCALED_DIM(pi->width, s);
+    rp.height = GPUJPEG_AMD_SCALED_DIM(pi->height, s);
+    if (alignment != 0) {
+        const unsigned linesize = (unsigned)gj_pixfmt_unit_size(rp.pixel_format) * (unsigned)rp.width;
+        rp.width_padding = (int)((linesize + alignment - 1) / alignment * alignment - linesize);
+    }
+    if (rp.pixel_format == GPUJPEG_422_U8_P1020 && (rp.width & 1)) {
+        GJ_ERROR("Packed 4:2:2 output needs an even width: %dx%d at scale 1/%d is %dx%d!\n", pi->width, pi->height, s, rp.width, rp.height);
+        return -1;
+    }
+    if (gj_geom_init(gs, param, &rp, false) != 0) return -1;
+    uint64_t offset = 0;
+    for (int c = 0; c < gs->comp_count; c++) {
+        gj_comp_geom* k = &gs->comp[c];
+        const gj_comp_geom* f = &full->comp[c];
+        k->data_width = f->data_width * N / 8;
+        k->data_height = f->data_height * N / 8;
+        k->blocks_x = f->blocks_x;
+        k->blocks_y = f->blocks_y;
+        k->data_offset = offset;
+        offset += (uint64_t)k->data_width * k->data_height;
+        if (k->width > k->data_width || k->height > k->data_height) return -1; /* (cannot happen: data_width * sub_h >= W) */
+    }
+    gs->data_size = offset;
+    gs->block_count = full->block_count;
+    if (pi_scaled) *pi_scaled = rp;
+    return 0;
+}
+
 /* ------------------------------------------------------------------ buffers / timers / statistics */
 int gj_ensure_device_buffer(void** p, size_t* cap, size_t need)
 {

@@ -187,8 +187,6 @@ __global__ __launch_bounds__(256, 3) void k_idct_fused_rgb444(const gj_geom g, i
 // there is no workgroup barrier. Blocks of segments too long for the decoder's LDS stage arrive through the coefficient
 // planes as before (count 0xFFFF in the record). Non-interleaved scans only (plane order == coding order).
 // ================================================================================================
-#define GJ_TOK_STAGE 832 // tokens per wave in LDS (with the 32 KiB tile: four workgroups per CU)
-
 // a lane's 128-byte slot of the block tile: row r (16 bytes) sits at (r ^ (lane & 7)) * 16, which spreads the row reads and
 // writes of the 64 lanes over all banks without padding the slot. A token carries its natural position = row << 3 | column in its low
 // 6 bits and the value above them: its place in the slot is 2 x (position XOR (lane & 7) << 3), and what is stored there is the token
@@ -202,32 +200,6 @@ __device__ __forceinline__ uint4* gj_slot_row(uint8_t* slot, const int lane, con
 __device__ __forceinline__ void gj_slot_put(uint8_t* slot, const uint32_t swz /* (lane & 7) << 3 */, const uint32_t tok)
 {
     reinterpret_cast<uint16_t*>(slot)[(tok & 63u) ^ swz] = (uint16_t)(tok & 0xFFC0u);
-}
-
-// the wave's token range of one component: dense and small enough for the stage (the normal case), with the two 16-byte
-// loads per lane that fetch it
-struct GjTokRange {
-    uint32_t S, E;
-    bool fast;
-    uint4 t0, t1;
-};
-
-__device__ __forceinline__ GjTokRange gj_tok_fetch(const uint16_t* __restrict__ d_tok, const uint32_t start, const uint32_t cnt, const int lane)
-{
-    GjTokRange r;
-    const uint32_t end = start + cnt;
-    const uint32_t prev_end = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)end, 0x138, 0xF, 0xF, false); // wave_shr:1
-    const unsigned long long breaks = __ballot(lane != 0 && start != prev_end);
-    r.S = (uint32_t)__builtin_amdgcn_readlane((int)start, 0) & ~7u; // (16-byte pieces of 8 tokens)
-    r.E = (uint32_t)__builtin_amdgcn_readlane((int)end, 63);
-    r.fast = breaks == 0 && r.E - r.S <= GJ_TOK_STAGE;
-    r.t0 = r.t1 = make_uint4(0, 0, 0, 0);
-    if (r.fast) {
-        const uint32_t i0 = (uint32_t)lane * 8u, i1 = i0 + 512u;
-        if (r.S + i0 < r.E) r.t0 = *reinterpret_cast<const uint4*>(d_tok + r.S + i0);
-        if (i1 < GJ_TOK_STAGE && r.S + i1 < r.E) r.t1 = *reinterpret_cast<const uint4*>(d_tok + r.S + i1);
-    }
-    return r;
 }
 
 // One block per lane: zeros, the DC term and the lane's tokens go into its tile slot. `fast`: the wave's tokens are in the stage
@@ -699,8 +671,31 @@ extern "C" int gj_hip_decode_uses_planes(const gj_geom* g, int use_fused)
     return !(use_fused && (gj_is_uyvy422(*g) || gj_idct_fused_kernel(*g) != nullptr));
 }
 
+// component planes -> pixels of the image `g` describes (the stream's, or the reduced one of a reduced-size decode)
+static void gj_launch_postprocess(const gj_geom& g, const gj_dec_job* job, hipStream_t st, const unsigned frames)
+{
+    if (g.no_transform) {
+        hipLaunchKernelGGL(k_copy_planes_out, dim3(2048, 1, frames), dim3(256), 0, st, g, job->d_planes, job->d_raw);
+    } else {
+        const unsigned n = (unsigned)g.raw_width * (unsigned)g.height;
+        hipLaunchKernelGGL(k_postprocess, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, g, job->d_planes, job->d_raw);
+    }
+}
+
 void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_tok, gj_event_t* ev)
 {
+    if (job->scale > 1) { // reduced-size decode (gj_dec_idct_scaled.hip): the pixel kernels work on the reduced image's geometry
+        const gj_geom& gs = job->gs;
+        const bool done = gj_launch_idct_scaled(job, st, idct_tok != nullptr);
+        if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
+        if (!done) gj_launch_postprocess(gs, job, st, 1u);
+        gj_debug_stage(job->tune.debug_sync != 0, st, "idct / postprocess (reduced size)");
+        if (job->channel_remap) {
+            const unsigned n = (unsigned)gs.width * (unsigned)gs.height;
+            hipLaunchKernelGGL(k_channel_remap, dim3((n + 255) / 256), dim3(256), 0, st, gs, job->d_raw, job->channel_remap & 0xFFFFu);
+        }
+        return;
+    }
     const gj_geom& g = job->g;
     const bool uyvy = job->use_fused && gj_is_uyvy422(g);
     gj_idct_fused_t fused = job->use_fused ? gj_idct_fused_kernel(g) : nullptr;
@@ -723,12 +718,7 @@ void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_to
                            job->d_planes, job->zero_coefs);
         if (job->flipped) hipLaunchKernelGGL(k_flip_planes, dim3(1024), dim3(256), 0, st, g, job->d_planes); // src/gpujpeg_postprocessor.cu:447
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
-        if (g.no_transform) {
-            hipLaunchKernelGGL(k_copy_planes_out, dim3(2048, 1, frames), dim3(256), 0, st, g, job->d_planes, job->d_raw);
-        } else {
-            const unsigned n = (unsigned)g.raw_width * (unsigned)g.height;
-            hipLaunchKernelGGL(k_postprocess, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, g, job->d_planes, job->d_raw);
-        }
+        gj_launch_postprocess(g, job, st, frames);
     }
     gj_debug_stage(job->tune.debug_sync != 0, st, "idct / postprocess");
     if (job->channel_remap) { // src/gpujpeg_postprocessor.cu:450,493: the finished image is permuted in place

@@ -9,6 +9,7 @@
 //                               lane refills itself (token mode), k_huffman_decode_seq over an LDS stage (plane mode)
 //   gj_dec_entropy_serial.hip   k_huffman_decode: one lane per restart segment, stream windows (Huffman tables that do not fit the two-level layout)
 //   gj_dec_idct.hip             k_idct_fused_* (from the planes), k_idct_tok_* (from tokens), k_idct / k_postprocess / k_copy_planes_out (generic)
+//   gj_dec_idct_scaled.hip      reduced-size output (dec_opt_scale): k_idct_scaled (from the planes), k_idct_tok_scaled_rgb444 (from tokens)
 //   gj_bitreader.h              unstuffing of a restart segment into an LDS stage, two-level table look-up
 //
 // Restates src/gpujpeg_huffman_gpu_decoder.cu:135-495 (entropy decoding semantics; identical results to
@@ -236,3 +237,37 @@ gj_idct_tok_t gj_idct_tok_for(const gj_geom& g); // the token-fed IDCT kernel fo
 bool gj_is_uyvy422(const gj_geom& g);
 // dequantisation + IDCT + postprocessing of the frame; ev (may be null): events 2 and 3 of gj_hip_decode
 void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_tok, gj_event_t* ev);
+// reduced-size decode (gj_dec_idct_scaled.hip): is there a token-fed kernel for this configuration; the IDCT side of the frame -- true: the pixels
+// are in d_raw, false: the reduced component planes are in d_planes and the pixel kernels follow with job->gs
+bool gj_idct_tok_scaled_for(const gj_geom& g);
+bool gj_launch_idct_scaled(const gj_dec_job* job, hipStream_t st, bool tokens);
+
+// ---- token-fed IDCT kernels (gj_dec_idct.hip, gj_dec_idct_scaled.hip): the wave's tokens on their way into LDS
+#define GJ_TOK_STAGE 832 // tokens per wave in LDS (with the 32 KiB tile: four workgroups per CU)
+
+// the wave's token range of one component: dense and small enough for the stage (the normal case), with the two 16-byte
+// loads per lane that fetch it
+struct GjTokRange {
+    uint32_t S, E;
+    bool fast;
+    uint4 t0, t1;
+};
+
+__device__ __forceinline__ GjTokRange gj_tok_fetch(const uint16_t* __restrict__ d_tok, const uint32_t start, const uint32_t cnt, const int lane)
+{
+    GjTokRange r;
+    const uint32_t end = start + cnt;
+    const uint32_t prev_end = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)end, 0x138, 0xF, 0xF, false); // wave_shr:1
+    const unsigned long long breaks = __ballot(lane != 0 && start != prev_end);
+    r.S = (uint32_t)__builtin_amdgcn_readlane((int)start, 0) & ~7u; // (16-byte pieces of 8 tokens)
+    r.E = (uint32_t)__builtin_amdgcn_readlane((int)end, 63);
+    r.fast = breaks == 0 && r.E - r.S <= GJ_TOK_STAGE;
+    r.t0 = r.t1 = make_uint4(0, 0, 0, 0);
+    if (r.fast) {
+        const uint32_t i0 = (uint32_t)lane * 8u, i1 = i0 + 512u;
+        if (r.S + i0 < r.E) r.t0 = *reinterpret_cast<const uint4*>(d_tok + r.S + i0);
+        if (i1 < GJ_TOK_STAGE && r.S + i1 < r.E) r.t1 = *reinterpret_cast<const uint4*>(d_tok + r.S + i1);
+    }
+    return r;
+}
+

@@ -43,6 +43,7 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     const gj_geom& g = job->g;
     if (g.blocks_per_mcu > GJ_MAX_MCU_BLOCKS) return -1;
     if ((job->batch.count > 1 || g.fb.sizes != nullptr) && (!gj_hip_decode_batchable(job) || g.fb.sizes == nullptr || job->batch.count > 65535u)) return -1;
+    if (job->scale > 1 && ((job->scale != 2 && job->scale != 4 && job->scale != 8) || g.fb.sizes != nullptr || job->flipped)) return -1; // (single frames, no flip)
     gj_hip_note_reset();
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[0], st));
     bool par = job->d_huff_tab2 != nullptr && job->seg_count > 0;
@@ -58,7 +59,9 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     // token mode: the entropy decoder hands the non-zero coefficients to the fused IDCT as a dense token array plus one
     // record per block instead of through the coefficient planes: k_huffman_decode_tok for non-interleaved scans (every segment has to
     // fit its LDS stage), the lane-per-segment kernel for interleaved ones
-    const bool tok_wanted = fast_ok && job->tokens && job->use_fused && job->d_tok && job->d_blkrec && gj_hip_decode_wants_tokens(&g, job->jpeg_size, &job->tune);
+    // (a reduced-size decode, gj_dec_job::scale: token mode where the token-fed reduced-size kernel exists -- not for the interleaved 4:2:2 scan)
+    const bool tok_wanted = fast_ok && job->tokens && job->use_fused && job->d_tok && job->d_blkrec && gj_hip_decode_wants_tokens(&g, job->jpeg_size, &job->tune) &&
+                            (job->scale <= 1 || gj_idct_tok_scaled_for(g));
     const bool tok_sub = tok_wanted && !g.interleaved && !seq && job->max_seg_len != 0 && job->max_seg_len + 12u <= (uint32_t)GJ_TOK_CAP_U;
     const bool tok_seq = tok_wanted && seq;
     gj_idct_tok_t idct_tok = (tok_sub || tok_seq) ? gj_idct_tok_for(g) : nullptr;

@@ -77,7 +77,36 @@ struct gpujpeg_decoder {
     int last_folded;                               /* the last decode call did without the k_marker_table launch (gj_scan_deferred) */
     long n_spec, n_folded, n_again;                /* calls launched on the cached header / of those without the table launch / decoded again the careful way */
     int b_chunk;                                   /* gpujpeg_amd_decoder_set_batch_chunk: frames per launch at most, 0 = the default */
+    /* reduced-size decode (dec_opt_scale). The option is read once per attempt (dec_scale_geometry); the header cache and the speculative launch
+     * hold nothing that depends on it: the parse result and the entropy side are the full-size ones at every scale. */
+    int scale;                                     /* the option: 0 / 1 = full size, else 2, 4, 8 */
+    int call_scale;                                /* what the decode call in progress (and, after it, the last one) used */
+    gj_geom geom_s;                                /* call_scale > 1: geometry and parameters of the reduced image */
+    struct gpujpeg_image_parameters pi_s;
+    int last_idct_path;                            /* gj_dec_job::idct_path of the last call */
 };
+
+/* what a call decodes to: the stream's image, or the reduced one */
+static size_t dec_raw_size(const struct gpujpeg_decoder* d) { return d->call_scale > 1 ? d->geom_s.raw_size : d->coder.geom.raw_size; }
+static struct gpujpeg_image_parameters dec_out_param_image(const struct gpujpeg_decoder* d)
+{
+    struct gpujpeg_image_parameters pi = d->call_scale > 1 ? d->pi_s : d->coder.param_image;
+    if (pi.color_space == GPUJPEG_NONE) pi.color_space = d->coder.param.color_space_internal;
+    return pi;
+}
+
+/* the scale of this call and the geometry of the reduced image, once the coder is configured for the stream; 0 or -1 (no such image / option clash) */
+static int dec_scale_geometry(struct gpujpeg_decoder* d)
+{
+    struct gj_coder* c = &d->coder;
+    d->call_scale = d->scale > 1 ? d->scale : 1;
+    if (d->call_scale == 1) return 0;
+    if (d->flipped) {
+        GJ_ERROR(GPUJPEG_DEC_OPT_FLIPPED_BOOL " is not available together with " GPUJPEG_AMD_DEC_OPT_SCALE "=1/%d!\n", d->call_scale);
+        return -1;
+    }
+    return gj_geom_init_scaled(&d->geom_s, &c->geom, &c->param, &c->param_image, d->call_scale, d->req_alignment, &d->pi_s);
+}
 
 #define GJ_HDR_WINDOW 65536
 
@@ -298,6 +327,10 @@ static void dec_job_base(const struct gpujpeg_decoder* d, bool tab2_ok, gj_dec_j
     job->flipped = d->flipped;
     job->channel_remap = d->channel_remap;
     job->tune = d->tune;
+    if (d->call_scale > 1) {
+        job->scale = d->call_scale;
+        job->gs = d->geom_s;
+    }
 }
 
 /* One call = up to three attempts (decoder_decode). What the stages of an attempt share: */
@@ -540,7 +573,7 @@ static int dec_destination(struct gpujpeg_decoder* d, struct dec_call* k)
         GJ_ERROR("OpenGL texture output is not supported by the MI355X build.\n");
         return -1;
     } else {
-        if (gj_ensure_device_buffer((void**)&c->d_raw_own, &c->d_raw_cap, c->geom.raw_size) != 0) return -1;
+        if (gj_ensure_device_buffer((void**)&c->d_raw_own, &c->d_raw_cap, dec_raw_size(d)) != 0) return -1;
         k->d_raw = c->d_raw_own;
     }
     return 0;
@@ -564,6 +597,8 @@ static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
     job.scan = k->scan_deferred;
     d->last_folded = 0;
     job.scan.folded = &d->last_folded;
+    d->last_idct_path = 0;
+    job.idct_path = &d->last_idct_path;
     if (k->spec) d->n_spec++;
     job.d_raw = k->d_raw;
     if (gj_channel_remap_check(d->channel_remap, c->param_image.pixel_format) != 0) return -1;
@@ -619,24 +654,23 @@ static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
 static int dec_download(struct gpujpeg_decoder* d, struct dec_call* k)
 {
     struct gj_coder* c = &d->coder;
-    const gj_geom* g = &c->geom;
+    const size_t raw_size = dec_raw_size(d);
     struct gpujpeg_decoder_output* output = k->output;
-    output->data_size = g->raw_size;
-    output->param_image = c->param_image;
-    if (output->param_image.color_space == GPUJPEG_NONE) output->param_image.color_space = c->param.color_space_internal;
+    output->data_size = raw_size;
+    output->param_image = dec_out_param_image(d);
     if (output->type != GPUJPEG_DECODER_OUTPUT_INTERNAL_BUFFER && output->type != GPUJPEG_DECODER_OUTPUT_CUSTOM_BUFFER) {
         output->data = k->d_raw;
         return 0;
     }
     if (output->type == GPUJPEG_DECODER_OUTPUT_INTERNAL_BUFFER) {
-        if (gj_ensure_pinned_buffer((void**)&d->h_raw, &d->h_raw_cap, g->raw_size, g->raw_size) != 0) return -1;
+        if (gj_ensure_pinned_buffer((void**)&d->h_raw, &d->h_raw_cap, raw_size, raw_size) != 0) return -1;
         output->data = d->h_raw;
     } else {
         assert(output->data != NULL);
     }
     gj_hip_event_record(c->timers.copy_out[0], c->stream);
     k->host_io = true;
-    if (gj_hip_download(output->data, k->d_raw, g->raw_size, c->stream, k->stats ? NULL : c->timers.lane_out) != 0) return -1; /* (the process's download lane) */
+    if (gj_hip_download(output->data, k->d_raw, raw_size, c->stream, k->stats ? NULL : c->timers.lane_out) != 0) return -1; /* (the process's download lane) */
     if (k->stats) gj_hip_event_record(c->timers.copy_out[1], c->stream);
     return 0;
 }
@@ -705,6 +739,7 @@ static void dec_stats(struct gpujpeg_decoder* d, const struct dec_call* k)
         for (int i = 0; i < GJ_DEC_EVENTS - 1; i++) c->kernel_ms[i] = gj_hip_event_elapsed_ms(c->timers.ev[i], c->timers.ev[i + 1]);
         c->kernel_ms[3] = d->scan_timed ? gj_hip_event_elapsed_ms(c->timers.ev[4], c->timers.ev[5]) : 0.0f; /* the marker scan, when the device did it */
         s->duration_in_gpu += c->kernel_ms[3];
+        c->kernel_ms[4] = (float)d->last_idct_path; /* (not a duration: which IDCT side ran, gpujpeg_amd_ext.h) */
         c->timers.valid = true;
         s->duration_memory_to = gj_hip_event_elapsed_ms(c->timers.copy_in[0], c->timers.copy_in[1]);
         if (output->type == GPUJPEG_DECODER_OUTPUT_INTERNAL_BUFFER || output->type == GPUJPEG_DECODER_OUTPUT_CUSTOM_BUFFER)
@@ -729,7 +764,7 @@ static int dec_attempt(struct gpujpeg_decoder* d, struct dec_call* k)
     int rc = dec_headers(d, k);
     if (rc != 0) return rc;
     for (int i = 0; i < GPUJPEG_METADATA_COUNT; i++) d->metadata.vals[i] = k->r.metadata.vals[i];
-    if (decoder_configure(d, &k->r.param, &k->r.param_image) != 0) return DEC_FAILED;
+    if (decoder_configure(d, &k->r.param, &k->r.param_image) != 0 || dec_scale_geometry(d) != 0) return DEC_FAILED;
     c->init_end_time = k->stats ? gpujpeg_get_time() : 0;
     if (dec_upload(d, k) != 0) return DEC_FAILED;
     if ((rc = dec_segment_table(d, k)) != 0) return rc;
@@ -816,7 +851,7 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
     struct gpujpeg_decoder_output o;
     gpujpeg_decoder_output_set_cuda_buffer(&o);
     if (decoder_decode(d, (uint8_t*)(uintptr_t)(b->streams + (size_t)f * b->stream_stride), b->sizes[f], &o) != 0) return -1;
-    const size_t raw = c->geom.raw_size;
+    const size_t raw = dec_raw_size(d);
     if (ahead) {
         b->frame_raw = raw;
         if (b->output_stride < raw) {
@@ -896,7 +931,8 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     const gj_geom* g = &c->geom;
     const int first = b->first, count = b->count, n_all = count - first;
     const size_t* sizes = b->sizes;
-    bool batched = d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
+    /* (a reduced-size decode goes frame by frame: the scaled kernels do not know the frame dimension) */
+    bool batched = d->scale <= 1 && d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
                    (b->streams_on_device ? (b->stream_stride & 15u) == 0 : true) && d->tab2_ok;
     size_t max_size = 0;
     for (int f = first; f < count; f++) {
@@ -904,6 +940,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         if (sizes[f] <= d->hdr_cache_len + 2 || sizes[f] > 0x1FFFFFF0u) batched = false;
     }
     if (!batched || n_all < 1) return 0;
+    d->call_scale = 1;
     const struct gj_reader_result* r = &d->hdr_cache_r;
     if (decoder_configure(d, &r->param, &r->param_image) != 0) return -1; /* (the geometry of the cached header, whatever the coder was last set up for) */
     if (b->output_stride < g->raw_size || (b->frame_raw != 0 && b->frame_raw != g->raw_size)) {
@@ -1048,10 +1085,7 @@ int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* d, const uint8_t* s
          * the coder's stream at the exit) */
         if (gj_hip_lane_end(down, c->stream, c->timers.lane_out) != 0 || copies != 0 || gj_hip_stream_sync(c->stream) != 0) goto out;
     }
-    if (param_image) {
-        *param_image = c->param_image;
-        if (param_image->color_space == GPUJPEG_NONE) param_image->color_space = c->param.color_space_internal;
-    }
+    if (param_image) *param_image = dec_out_param_image(d);
     rc = 0; /* (c->frames counts the frames TIMED with perf_stats, src/gpujpeg_common.c:2238-2254: a batch adds none) */
 out:
     if (rc != 0 && b.host_io) gj_hip_stream_sync(c->stream); /* (what is queued on the stream must not read the caller's streams or write its frames after the error has left) */
@@ -1107,7 +1141,7 @@ int gpujpeg_amd_decoder_decode_batch_ptrs(struct gpujpeg_decoder* d, const uint8
     }
     if (gj_ensure_device_buffer((void**)&d->b_scatter, &d->b_scatter_cap, frame_bytes * (size_t)count) != 0) return -1;
     if (gpujpeg_amd_decoder_decode_batch(d, src, in_stride, sizes, count, d->b_scatter, frame_bytes, &pi) != 0) return -1;
-    const size_t raw = c->geom.raw_size;
+    const size_t raw = dec_raw_size(d);
     for (int f = 0; f < count; f++) {
         const int rc = gj_hip_is_device_ptr(outputs[f]) ? gj_hip_memcpy_d2d(outputs[f], d->b_scatter + (size_t)f * frame_bytes, raw, c->stream)
                                                         : gj_hip_memcpy_d2h(outputs[f], d->b_scatter + (size_t)f * frame_bytes, raw, c->stream);
@@ -1172,6 +1206,13 @@ int gpujpeg_decoder_set_option(struct gpujpeg_decoder* d, const char* opt, const
         return GPUJPEG_NOERR;
     }
     if (strcmp(opt, GPUJPEG_DEC_OPT_CHANNEL_REMAP) == 0) return gj_parse_channel_remap(&d->channel_remap, val, opt);
+    if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_SCALE) == 0) { /* holds from the next decode call on */
+        static const char* const names[4] = {"1", "1/2", "1/4", "1/8"};
+        for (int i = 0; i < 4; i++)
+            if (strcmp(val, names[i]) == 0) { d->scale = 1 << i; return GPUJPEG_NOERR; }
+        GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_SCALE " (1, 1/2, 1/4 or 1/8)\n", val);
+        return GPUJPEG_ERROR;
+    }
     GJ_ERROR("Invalid decoder option: %s!\n", opt);
     return GPUJPEG_ERROR;
 }
@@ -1181,6 +1222,7 @@ void gpujpeg_decoder_print_options(void)
     printf("\t" GPUJPEG_DEC_OPT_ALIGNMENT_BYTES_INT "=<n> - required line alignment of the decoded image in bytes\n");
     printf("\t" GPUJPEG_DEC_OPT_FLIPPED_BOOL "=[" GPUJPEG_VAL_TRUE "|" GPUJPEG_VAL_FALSE "] - whether the output image should be vertically flipped\n");
     printf("\t" GPUJPEG_DEC_OPT_CHANNEL_REMAP "=XYZ[W] - output channel remapping, 'help' for details\n");
+    printf("\t" GPUJPEG_AMD_DEC_OPT_SCALE "=[1|1/2|1/4|1/8] - decode to a reduced-size image (MI355X extension)\n");
 }
 
 /* ------------------------------------------------------------------ MI355X extensions (include/gpujpeg_amd_ext.h) */
@@ -1214,7 +1256,7 @@ size_t gpujpeg_amd_decoder_read_coefficients(struct gpujpeg_decoder* d, int16_t*
 
 size_t gpujpeg_amd_decoder_read_planes(struct gpujpeg_decoder* d, uint8_t* dst, size_t capacity)
 {
-    const size_t n = d->coder.geom.data_size;
+    const size_t n = d->call_scale > 1 ? d->geom_s.data_size : d->coder.geom.data_size; /* (the reduced planes of a reduced-size decode) */
     if (!d->coder.configured || capacity < n) return 0;
     if (gj_hip_memcpy_d2h(dst, d->coder.d_planes, n, d->coder.stream) != 0 || gj_hip_stream_sync(d->coder.stream) != 0) return 0;
     return n;

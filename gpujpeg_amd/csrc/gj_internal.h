@@ -40,6 +40,9 @@ bool gj_image_parameters_equal(const struct gpujpeg_image_parameters* a, const s
 
 /* ---- geometry (src/gpujpeg_common.c:675-870, 1040-1085) ---- */
 int gj_geom_init(gj_geom* g, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image, bool encoder);
+/* geometry and image parameters of the reduced image of a decode at scale 1/s (s = 2, 4, 8); -1 when the output format has no such image */
+int gj_geom_init_scaled(gj_geom* gs, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image, int s,
+                        unsigned alignment, struct gpujpeg_image_parameters* param_image_scaled);
 
 /* ---- tables ---- */
 extern const uint8_t gj_zigzag[64];

@@ -330,6 +330,11 @@ class Decoder:
     def set_output_format(self, color_space, pixel_format):
         self.lib.L.gpujpeg_decoder_set_output_format(self.h, color_space, pixel_format)
 
+    def set_option(self, opt, val):
+        """gpujpeg_decoder_set_option, e.g. ("dec_opt_scale", "1/4"): the decode calls that follow return the reduced image (their
+        ImageParameters and sizes are the reduced image's). Returns the library's code (0 = accepted)."""
+        return self.lib.L.gpujpeg_decoder_set_option(self.h, opt.encode(), val.encode())
+
     def init(self, param, param_image):
         return self.lib.L.gpujpeg_decoder_init(self.h, C.byref(param), C.byref(param_image))
 
@@ -440,6 +445,13 @@ class Decoder:
         if self.lib.L.gpujpeg_amd_decoder_get_kernel_times(self.h, ms) != 0:
             return None
         return list(ms)[:4]
+
+    def idct_path(self):
+        """IDCT side of the last perf_stats call: 0 full size, 1 reduced size from the coefficient planes, 2 reduced size from tokens"""
+        ms = (C.c_float * 8)()
+        if self.lib.L.gpujpeg_amd_decoder_get_kernel_times(self.h, ms) != 0:
+            return None
+        return int(ms[4])
 
     def coefficients(self, count):
         a = np.empty(count, np.int16)

@@ -297,6 +297,12 @@ typedef struct gj_dec_job {
     gj_scan_deferred scan;         /* valid: the segment table has not been written yet (see gj_scan_deferred) */
     gj_batch batch;                /* count > 1: a batch of frames with the same header (speculative launches only: d_seg_count and d_overflow
                                       point to frame 0's words inside arrays of gj_scan_summary) */
+    /* reduced-size decode (dec_opt_scale): scale = 2, 4, 8 (0 or 1: full size). The entropy decoders work on g as ever; the IDCT side leaves
+     * 8 / scale samples per block edge and the pixel kernels behind it work on gs, the geometry of the reduced image (gj_geom_init_scaled: d_planes
+     * holds the reduced planes, d_raw the reduced image). Single frames only. */
+    int scale;
+    gj_geom gs;
+    int* idct_path;                /* host, may be NULL: which IDCT side ran -- 0 full size, 1 k_idct_scaled, 2 k_idct_tok_scaled_rgb444 */
 } gj_dec_job;
 /* 1 when gj_hip_decode takes a batch (gj_dec_job::batch.count > 1) of this job's configuration */
 GJ_HIP_API int gj_hip_decode_batchable(const gj_dec_job* job);

@@ -77,6 +77,14 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
 #define GPUJPEG_AMD_ENC_OPT_HUFFMAN "enc_opt_huffman"
 #define GPUJPEG_AMD_ENC_HUFFMAN_VAL_STANDARD "standard"
 #define GPUJPEG_AMD_ENC_HUFFMAN_VAL_OPTIMAL "optimal"
+/* Decoder option (gpujpeg_decoder_set_option): reduced-size output. "1" (default), "1/2", "1/4", "1/8": the decode calls return the image of
+ * GPUJPEG_AMD_SCALED_DIM(width, s) x GPUJPEG_AMD_SCALED_DIM(height, s) pixels that the N x N low-frequency corner (N = 8 / s) of every block gives
+ * (integer N-point inverse DCT, DESIGN "Reduced-size decode"); output->param_image, output->data_size and the buffer layout are those of an image of
+ * that size, gpujpeg_decoder_get_image_info keeps reporting the stream's own size. May be changed between two calls of a decoder. Packed 4:2:2 output
+ * of odd reduced width and dec_opt_flipped together with a scale are refused by the decode call; batch calls decode such frames one by one.
+ * Outside reference parity by construction (the reference has no reduced decode). */
+#define GPUJPEG_AMD_DEC_OPT_SCALE "dec_opt_scale"
+#define GPUJPEG_AMD_SCALED_DIM(v, s) (((v) + (s) - 1) / (s))
 /* Host-only: the table enc_opt_huffman=optimal builds for one class from symbol counts freq[256] (ITU T.81 Annex K.2: Figures K.1, K.3, K.4;
  * reserved code point, ties to the larger symbol value), code lengths limited to the largest L of 16 .. 10 whose table the library's
  * two-level decode tables take. Writes BITS (bits[1..16]) and HUFFVAL; returns L, or -1 when no count is non-zero. */
@@ -85,7 +93,9 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_optimal(const uint32_t freq[256], uint8
 /* per-kernel durations (ms, hipEvents on the coder's stream) of the last call made with perf_stats != 0:
  * encoder: [0] preprocess, [1] DCT+quant (fused path: preprocess included), [2] k_huffman or k_encode_*, [3] k_gather (behind k_huffman:
  *          k_scan_segments), [4] k_assemble (behind k_huffman only), [5] k_huffman_count (enc_opt_huffman=optimal; 0 otherwise)
- * decoder: [0] entropy decoder, [1] IDCT (fused path: postprocess included), [2] postprocess, [3] marker scan (k_markers; 0 when the host walked the stream) */
+ * decoder: [0] entropy decoder, [1] IDCT (fused path: postprocess included), [2] postprocess, [3] marker scan (k_markers; 0 when the host walked the stream),
+ *          [4] not a duration: the IDCT side of that call -- 0 full size, 1 reduced size from the coefficient planes (k_idct_scaled), 2 reduced size from
+ *          tokens (k_idct_tok_scaled_rgb444) */
 GPUJPEG_API int gpujpeg_amd_encoder_get_kernel_times(struct gpujpeg_encoder* encoder, float ms[8]);
 GPUJPEG_API int gpujpeg_amd_decoder_get_kernel_times(struct gpujpeg_decoder* decoder, float ms[8]);
 
