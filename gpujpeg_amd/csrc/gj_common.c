@@ -536,6 +536,75 @@ int gj_geom_init_scaled(gj_geom* gs, const gj_geom* full, const struct gpujpeg_p
     return 0;
 }
 
+/* Region decode (dec_opt_region). The region's pixels x .. x + w - 1 (packed 4:2:2: up to the end of the last pixel pair) need
+ * samples x / sub_h .. of component c; the cover is the rectangle of blocks that holds them -- for an interleaved scan widened to whole MCUs,
+ * which is the same MCU rectangle for every component. gr is gj_geom_init of the w x h image with the components' planes replaced by the
+ * cover-sized ones (k_idct_region writes them, the region's pixel kernels read them). */
+int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi,
+                        const int region[4], unsigned alignment, struct gpujpeg_image_parameters* pi_region)
+{
+    const int x = region[0], y = region[1], w = region[2], h = region[3];
+    if (x < 0 || y < 0 || w < 1 || h < 1 || x >= pi->width || y >= pi->height || w > pi->width - x || h > pi->height - y) {
+        GJ_ERROR("Region %d,%d,%d,%d is not inside the %dx%d image!\n", x, y, w, h, pi->width, pi->height);
+        return -1;
+    }
+    /* output formats whose pixels share samples: the region starts and ends on their sampling grid (or at the image's edge) */
+    const enum gpujpeg_pixel_format pf = pi->pixel_format;
+    const int ah = (pf == GPUJPEG_422_U8_P1020 || pf == GPUJPEG_422_U8_P0P1P2 || pf == GPUJPEG_420_U8_P0P1P2) ? 2 : 1;
+    const int av = pf == GPUJPEG_420_U8_P0P1P2 ? 2 : 1;
+    if (x % ah || y % av || (w % ah && x + w != pi->width) || (h % av && y + h != pi->height)) {
+        GJ_ERROR("Region %d,%d,%d,%d is misaligned for %s output: X and W must be multiples of %d, Y and H of %d (W, H: unless the region ends at the image's edge)!\n",
+                 x, y, w, h, gpujpeg_pixel_format_get_name(pf), ah, av);
+        return -1;
+    }
+    struct gpujpeg_image_parameters rp = *pi;
+    rp.width = w;
+    rp.height = h;
+    if (alignment != 0) {
+        const unsigned linesize = (unsigned)gj_pixfmt_unit_size(rp.pixel_format) * (unsigned)rp.width;
+        rp.width_padding = (int)((linesize + alignment - 1) / alignment * alignment - linesize);
+    }
+    if (gj_geom_init(gr, param, &rp, false) != 0) return -1;
+    memset(r, 0, sizeof *r);
+    r->on = 1;
+    r->x = x; r->y = y; r->w = w; r->h = h;
+    const int px1 = x + gr->raw_width - 1, py1 = y + h - 1; /* the last pixel column / row whose samples are read */
+    if (full->interleaved) {
+        r->mx0 = x / (8 * full->max_h);
+        r->my0 = y / (8 * full->max_v);
+        r->mx1 = px1 / (8 * full->max_h) + 1;
+        r->my1 = py1 / (8 * full->max_v) + 1;
+        const int mcu_rows = full->mcu_count_x > 0 ? full->mcu_count / full->mcu_count_x : 0;
+        if (r->mx1 > full->mcu_count_x) r->mx1 = full->mcu_count_x;
+        if (r->my1 > mcu_rows) r->my1 = mcu_rows;
+    }
+    uint64_t offset = 0;
+    for (int c = 0; c < gr->comp_count; c++) {
+        gj_comp_geom* k = &gr->comp[c];
+        const gj_comp_geom* f = &full->comp[c];
+        if (full->interleaved) {
+            r->bx0[c] = r->mx0 * f->samp_h; r->bx1[c] = r->mx1 * f->samp_h;
+            r->by0[c] = r->my0 * f->samp_v; r->by1[c] = r->my1 * f->samp_v;
+        } else {
+            r->bx0[c] = x / f->sub_h / 8; r->bx1[c] = px1 / f->sub_h / 8 + 1;
+            r->by0[c] = y / f->sub_v / 8; r->by1[c] = py1 / f->sub_v / 8 + 1;
+        }
+        if (r->bx1[c] > f->blocks_x) r->bx1[c] = f->blocks_x;
+        if (r->by1[c] > f->blocks_y) r->by1[c] = f->blocks_y;
+        if (r->bx0[c] >= r->bx1[c] || r->by0[c] >= r->by1[c]) return -1; /* (cannot happen: the region lies inside the image) */
+        k->blocks_x = r->bx1[c] - r->bx0[c];
+        k->blocks_y = r->by1[c] - r->by0[c];
+        k->data_width = k->blocks_x * 8;
+        k->data_height = k->blocks_y * 8;
+        k->data_offset = offset;
+        offset += (uint64_t)k->data_width * k->data_height;
+    }
+    gr->data_size = offset;
+    gr->block_count = (int)(offset / 64);
+    if (pi_region) *pi_region = rp;
+    return 0;
+}
+
 /* ------------------------------------------------------------------ buffers / timers / statistics */
 int gj_ensure_device_buffer(void** p, size_t* cap, size_t need)
 {

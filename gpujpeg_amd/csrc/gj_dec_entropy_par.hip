@@ -648,8 +648,11 @@ GjBatchPlan gj_plan_batches(const gj_dec_job* job, const unsigned cap_u, const u
         return max(1, min(G, (int)min(gmax, max_blocks / (unsigned)max(1, g.seg_blocks))));
     };
     GjBatchPlan plan = {};
-    bool per_scan = !g.interleaved && g.comp_count > 1 && job->seg_count == g.segment_count;
-    for (int c = 0; per_scan && c < g.comp_count; c++) per_scan = job->scan_bytes[c] != 0 && g.comp[c].segment_count > 0;
+    // (a region's selection, gj_region: the compacted table holds sel_count[c] entries of scan c, in stream order)
+    const bool sel = job->region.select != 0;
+    auto scan_segs = [&](int c) { return sel ? job->region.sel_count[c] : g.comp[c].segment_count; };
+    bool per_scan = !g.interleaved && g.comp_count > 1 && (sel || job->seg_count == g.segment_count);
+    for (int c = 0; per_scan && c < g.comp_count; c++) per_scan = job->scan_bytes[c] != 0 && scan_segs(c) > 0;
     // 23/32 of the stage on average is the measured optimum; when that gives a little more than one generation of resident
     // workgroups, fuller batches (up to 27/32) that fit into one are better than a second generation of a few
     // (a batch of frames is dozens of generations of workgroups: measured best at 26/32 -- 256 x 4K 21 030 frames/s against 20 860 at 23 and 20 700 at
@@ -661,7 +664,7 @@ GjBatchPlan gj_plan_batches(const gj_dec_job* job, const unsigned cap_u, const u
             int first = 0;
             for (int c = 0; c < g.comp_count; c++) {
                 plan.first[c] = first;
-                plan.count[c] = g.comp[c].segment_count;
+                plan.count[c] = scan_segs(c);
                 plan.g[c] = batch_size(job->scan_bytes[c], plan.count[c], fill);
                 plan.batch0[c + 1] = plan.batch0[c] + (plan.count[c] + plan.g[c] - 1) / plan.g[c];
                 first += plan.count[c];

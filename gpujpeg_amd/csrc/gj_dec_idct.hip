@@ -364,6 +364,116 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_rgb444(const gj_geom g, con
 }
 
 // ================================================================================================
+// Token-fed IDCT of a REGION (dec_opt_region, gj_region): k_idct_tok_rgb444 over the cover's blocks only, pixels into the W x H image.
+// A wave takes up to 64 consecutive blocks of ONE block row of the cover -- a row piece, not 64 blocks of a linearised cover: consecutive blocks
+// of a row are consecutive in coding order, so their tokens are one dense range and gj_tok_fetch keeps its fast path; a wave that ran over the
+// cover's row end would see a break there in every wave. Lanes behind the end of the piece carry an empty range that continues the last block's.
+// The region's origin falls anywhere inside a block: a pixel row of a block is 24 bytes at any byte alignment, stored as dwords where the
+// address allows it and byte by byte with bounds checks at the region's edges.
+// ================================================================================================
+template <int CS_FROM, int CS_TO>
+__global__ __launch_bounds__(256, 4) void k_idct_tok_region_rgb444(const gj_geom g, const gj_geom gr, const gj_region rg, const int16_t* __restrict__ coefs,
+                                                                   const uint2* __restrict__ d_rec, const uint16_t* __restrict__ d_tok,
+                                                                   const uint32_t tok_cap, const float* __restrict__ qtab, uint8_t* __restrict__ raw)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_blk[256 * 128];
+    __shared__ __attribute__((aligned(16))) uint16_t s_stage[4][GJ_TOK_STAGE];
+    __shared__ __attribute__((aligned(8))) float s_q[2][3][64]; // (as in k_idct_tok_rgb444)
+    if (threadIdx.x < 192) {
+        const float q = qtab[g.comp[threadIdx.x >> 6].q_table * 64 + (threadIdx.x & 63)];
+        s_q[0][threadIdx.x >> 6][threadIdx.x & 63] = (threadIdx.x & 63) ? q * 0.015625f : q;
+        s_q[1][threadIdx.x >> 6][threadIdx.x & 63] = q;
+    }
+    const int lane = threadIdx.x & 63;
+    // the wave's row piece of the cover (the three components' covers are the same rectangle: 4:4:4)
+    const unsigned cbx = (unsigned)(rg.bx1[0] - rg.bx0[0]), cby = (unsigned)(rg.by1[0] - rg.by0[0]);
+    const unsigned pieces = (cbx + 63u) / 64u;
+    const unsigned gw = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const unsigned crow = gw / pieces, piece = gw - crow * pieces;
+    const unsigned in_piece = crow < cby ? min(64u, cbx - piece * 64u) : 0u; // blocks of this wave
+    const bool valid = (unsigned)lane < in_piece;
+    const unsigned fby = (unsigned)rg.by0[0] + min(crow, cby - 1u);
+    const unsigned fbx = (unsigned)rg.bx0[0] + piece * 64u + (valid ? (unsigned)lane : (in_piece ? in_piece - 1u : 0u));
+    const unsigned lb = fby * (unsigned)g.comp[0].blocks_x + fbx; // (inside the component's grid: the cover is)
+    uint8_t* slot = s_blk + threadIdx.x * 128;
+    uint16_t* stage = s_stage[threadIdx.x >> 6];
+
+    uint32_t start[3], cd[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const uint2 r = d_rec[g.comp[c].data_offset / 64 + lb];
+        start[c] = r.x;
+        uint32_t n = r.y >> 16;
+        const bool planes = n == 0xFFFFu;
+        if (planes || n > 63u || start[c] > tok_cap || n > tok_cap - start[c]) n = 0;
+        cd[c] = (r.y & 0xFFFFu) | (n << 16) | (planes ? 0x80000000u : 0u);
+        if (!valid) { // an empty range behind the piece's last block
+            start[c] += n;
+            cd[c] = 0;
+        }
+    }
+    auto cnt_of = [](const uint32_t x) { return (x >> 16) & 0x7FFFu; };
+    __syncthreads(); // (s_q; everything below is private to a wave)
+
+    uint32_t pk[3][16];
+    GjTokRange cur = gj_tok_fetch(d_tok, start[0], cnt_of(cd[0]), lane);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const bool fast = cur.fast;
+        const uint32_t S = cur.S;
+        if (fast) {
+            *reinterpret_cast<uint4*>(stage + lane * 8) = cur.t0;
+            if (lane * 8 + 512 < GJ_TOK_STAGE) *reinterpret_cast<uint4*>(stage + lane * 8 + 512) = cur.t1;
+        }
+        if (c < 2) cur = gj_tok_fetch(d_tok, start[c + 1], cnt_of(cd[c + 1]), lane);
+        const bool in_plane = (int32_t)cd[c] < 0;
+        gj_tok_to_slot<false>(slot, stage, lane, fast, S, start[c], cnt_of(cd[c]), cd[c] & 0xFFFFu, in_plane,
+                       reinterpret_cast<const uint4*>(coefs + g.comp[c].data_offset + (size_t)lb * 64), d_tok);
+        uint32_t wb[32];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const uint4 v = *gj_slot_row(slot, lane, r);
+            wb[r * 4] = v.x; wb[r * 4 + 1] = v.y; wb[r * 4 + 2] = v.z; wb[r * 4 + 3] = v.w;
+        }
+        gj_idct_pk(wb, s_q[in_plane ? 1 : 0][c], pk[c]);
+#pragma unroll
+        for (int i = 0; i < 16; i++) GJ_KEEP(pk[c][i]);
+    }
+    if (!valid) return;
+    // the block's 8 x 8 pixels at (x0, y0) of the region image, of which any part may lie outside it
+    const int W = gr.width, H = gr.height;
+    const size_t pitch = (size_t)W * 3 + gr.width_padding;
+    const int x0 = (int)(fbx * 8u) - rg.x, y0 = (int)(fby * 8u) - rg.y;
+    const bool inside = x0 >= 0 && x0 + 8 <= W;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        uint32_t px[6] = {0, 0, 0, 0, 0, 0};
+        const uint32_t c0[2] = {pk[0][2 * r], pk[0][2 * r + 1]}, c1[2] = {pk[1][2 * r], pk[1][2 * r + 1]}, c2[2] = {pk[2][2 * r], pk[2][2 * r + 1]};
+        gj_store_pair<CS_FROM, CS_TO, 0>(c0, c1, c2, px);
+        gj_store_pair<CS_FROM, CS_TO, 2>(c0, c1, c2, px);
+        gj_store_pair<CS_FROM, CS_TO, 4>(c0, c1, c2, px);
+        gj_store_pair<CS_FROM, CS_TO, 6>(c0, c1, c2, px);
+        const int y = y0 + r;
+        if (y >= 0 && y < H) {
+            uint8_t* row = raw + (size_t)y * pitch;
+            uint8_t* p = row + (ptrdiff_t)x0 * 3;
+            if (inside && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
+                uint32_t* q = reinterpret_cast<uint32_t*>(p);
+#pragma unroll
+                for (int i = 0; i < 6; i++) q[i] = px[i];
+            } else {
+#pragma unroll
+                for (int byte = 0; byte < 24; byte++) {
+                    const int x = x0 + byte / 3;
+                    if (x >= 0 && x < W) row[(size_t)x * 3 + byte % 3] = (uint8_t)(px[byte >> 2] >> ((byte & 3) * 8));
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// ================================================================================================
 // Token-fed IDCT for interleaved 4:2:2 scans with packed UYVY output and no colour transform (BASELINE config 4): one lane
 // per BLOCK in coding order (Y0 Y1 Cb Cr of MCU 0, of MCU 1, ...), so a workgroup's 256 records and its tokens are dense
 // ranges. After the transform the four lanes of an MCU exchange their rows with quad-permute DPP moves and every lane
@@ -550,45 +660,7 @@ __global__ __launch_bounds__(256) void k_postprocess(const gj_geom g, const uint
         const gj_comp_geom& k = g.comp[c];
         v[c] = planes[k.data_offset + (size_t)(y / (unsigned)k.sub_v) * k.data_width + x / (unsigned)k.sub_h];
     }
-    if (g.comp_count == 1) { // single channel expanded for the colour transform (:127-170)
-        if (g.color_space_internal == GJ_CS_RGB) v[1] = v[2] = v[0];
-        else v[1] = v[2] = 128;
-    }
-    gj_color_transform(g.color_space_internal, g.color_space, v[0], v[1], v[2]);
-    switch (g.pixel_format) {
-    case GJ_PF_U8: raw[(size_t)pos + (size_t)g.width_padding * y] = (uint8_t)v[0]; break;
-    case GJ_PF_444_P012: {
-        uint8_t* p = raw + (size_t)pos * 3 + (size_t)g.width_padding * y;
-        p[0] = (uint8_t)v[0]; p[1] = (uint8_t)v[1]; p[2] = (uint8_t)v[2];
-        break; }
-    case GJ_PF_4444_P0123: {
-        uint8_t* p = raw + (size_t)pos * 4 + (size_t)g.width_padding * y;
-        p[0] = (uint8_t)v[0]; p[1] = (uint8_t)v[1]; p[2] = (uint8_t)v[2]; p[3] = (uint8_t)v[3];
-        break; }
-    case GJ_PF_444_P0P1P2:
-        raw[pos] = (uint8_t)v[0]; raw[(size_t)W * H + pos] = (uint8_t)v[1]; raw[(size_t)2 * W * H + pos] = (uint8_t)v[2];
-        break;
-    case GJ_PF_422_P0P1P2:
-        raw[pos] = (uint8_t)v[0];
-        if ((x & 1) == 0) {
-            raw[(size_t)W * H + pos / 2] = (uint8_t)v[1];
-            raw[(size_t)W * H + (size_t)H * ((W + 1) / 2) + pos / 2] = (uint8_t)v[2];
-        }
-        break;
-    case GJ_PF_422_P1020: {
-        const size_t off = (size_t)pos * 2 + (size_t)g.width_padding * y;
-        raw[off + 1] = (uint8_t)v[0];
-        raw[off] = (uint8_t)((x & 1) == 0 ? v[1] : v[2]);
-        break; }
-    case GJ_PF_420_P0P1P2:
-        raw[pos] = (uint8_t)v[0];
-        if ((pos & 1) == 0 && (y & 1) == 0) {
-            raw[(size_t)W * H + (size_t)(y / 2) * ((W + 1) / 2) + x / 2] = (uint8_t)v[1];
-            raw[(size_t)W * H + (size_t)((H + 1) / 2 + y / 2) * ((W + 1) / 2) + x / 2] = (uint8_t)v[2];
-        }
-        break;
-    default: break;
-    }
+    gj_store_pixel(g, raw, W, H, x, y, pos, v);
 }
 
 // planar output whose layout equals the component layout (src/gpujpeg_postprocessor.cu:404-434)
@@ -645,6 +717,25 @@ static gj_idct_tok_t gj_idct_tok_kernel(const gj_geom& g)
     return nullptr;
 }
 
+typedef void (*gj_idct_tok_region_t)(const gj_geom, const gj_geom, const gj_region, const int16_t*, const uint2*, const uint16_t*, uint32_t, const float*, uint8_t*);
+// the token-fed IDCT side of a region call (gj_launch_idct_region; the configuration of k_idct_tok_rgb444, non-interleaved scans)
+void gj_launch_idct_tok_region(const gj_dec_job* job, hipStream_t st)
+{
+    const gj_geom& g = job->g;
+    const int from = g.color_space_internal, to = g.color_space;
+    gj_idct_tok_region_t k = k_idct_tok_region_rgb444<GJ_CS_NONE, GJ_CS_NONE>;
+    if (from == to || from == GJ_CS_NONE || to == GJ_CS_NONE) k = k_idct_tok_region_rgb444<GJ_CS_NONE, GJ_CS_NONE>;
+    else if (from == GJ_CS_BT601_256 && to == GJ_CS_RGB) k = k_idct_tok_region_rgb444<GJ_CS_BT601_256, GJ_CS_RGB>;
+    else if (from == GJ_CS_BT601 && to == GJ_CS_RGB) k = k_idct_tok_region_rgb444<GJ_CS_BT601, GJ_CS_RGB>;
+    else if (from == GJ_CS_BT709 && to == GJ_CS_RGB) k = k_idct_tok_region_rgb444<GJ_CS_BT709, GJ_CS_RGB>;
+    else if (from == GJ_CS_RGB && to == GJ_CS_BT601_256) k = k_idct_tok_region_rgb444<GJ_CS_RGB, GJ_CS_BT601_256>;
+    const gj_region& r = job->region;
+    const unsigned cbx = (unsigned)(r.bx1[0] - r.bx0[0]), cby = (unsigned)(r.by1[0] - r.by0[0]);
+    const unsigned waves = (cbx + 63u) / 64u * cby;
+    hipLaunchKernelGGL(k, dim3((waves + 3u) / 4u), dim3(256), 0, st, g, job->gs, r, job->d_coefs, (const uint2*)job->d_blkrec, (const uint16_t*)job->d_tok,
+                       job->tok_cap, job->d_qtabf, job->d_raw);
+}
+
 bool gj_is_uyvy422(const gj_geom& g)
 {
     return g.pixel_format == GJ_PF_422_P1020 && g.comp_count == 3 &&
@@ -684,6 +775,10 @@ static void gj_launch_postprocess(const gj_geom& g, const gj_dec_job* job, hipSt
 
 void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_tok, gj_event_t* ev)
 {
+    if (job->region.on) { // region decode (gj_dec_region.hip): the cover's blocks, the region's pixels
+        gj_launch_idct_region(job, st, idct_tok != nullptr, ev);
+        return;
+    }
     if (job->scale > 1) { // reduced-size decode (gj_dec_idct_scaled.hip): the pixel kernels work on the reduced image's geometry
         const gj_geom& gs = job->gs;
         const bool done = gj_launch_idct_scaled(job, st, idct_tok != nullptr);

@@ -10,6 +10,8 @@
 //   gj_dec_entropy_serial.hip   k_huffman_decode: one lane per restart segment, stream windows (Huffman tables that do not fit the two-level layout)
 //   gj_dec_idct.hip             k_idct_fused_* (from the planes), k_idct_tok_* (from tokens), k_idct / k_postprocess / k_copy_planes_out (generic)
 //   gj_dec_idct_scaled.hip      reduced-size output (dec_opt_scale): k_idct_scaled (from the planes), k_idct_tok_scaled_rgb444 (from tokens)
+//   gj_dec_region.hip           region decode (dec_opt_region): k_segment_select (table -> the entries that touch the region's cover), k_idct_region,
+//                               k_postprocess_region / k_copy_planes_region (cover blocks -> cover planes -> the region's pixels)
 //   gj_bitreader.h              unstuffing of a restart segment into an LDS stage, two-level table look-up
 //
 // Restates src/gpujpeg_huffman_gpu_decoder.cu:135-495 (entropy decoding semantics; identical results to
@@ -241,6 +243,57 @@ void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_to
 // are in d_raw, false: the reduced component planes are in d_planes and the pixel kernels follow with job->gs
 bool gj_idct_tok_scaled_for(const gj_geom& g);
 bool gj_launch_idct_scaled(const gj_dec_job* job, hipStream_t st, bool tokens);
+
+// the generic pixel kernels' second half (k_postprocess, k_postprocess_region): the samples v of pixel (x, y) = number `pos` of a W x H image ->
+// colour transform -> the stores of the pixel format (src/gpujpeg_postprocessor.cu:193-217, src/gpujpeg_preprocessor_common.cuh:118-203)
+__device__ __forceinline__ void gj_store_pixel(const gj_geom& g, uint8_t* __restrict__ raw, const unsigned W, const unsigned H, const unsigned x,
+                                               const unsigned y, const unsigned pos, int (&v)[4])
+{
+    if (g.comp_count == 1) { // single channel expanded for the colour transform (:127-170)
+        if (g.color_space_internal == GJ_CS_RGB) v[1] = v[2] = v[0];
+        else v[1] = v[2] = 128;
+    }
+    gj_color_transform(g.color_space_internal, g.color_space, v[0], v[1], v[2]);
+    switch (g.pixel_format) {
+    case GJ_PF_U8: raw[(size_t)pos + (size_t)g.width_padding * y] = (uint8_t)v[0]; break;
+    case GJ_PF_444_P012: {
+        uint8_t* p = raw + (size_t)pos * 3 + (size_t)g.width_padding * y;
+        p[0] = (uint8_t)v[0]; p[1] = (uint8_t)v[1]; p[2] = (uint8_t)v[2];
+        break; }
+    case GJ_PF_4444_P0123: {
+        uint8_t* p = raw + (size_t)pos * 4 + (size_t)g.width_padding * y;
+        p[0] = (uint8_t)v[0]; p[1] = (uint8_t)v[1]; p[2] = (uint8_t)v[2]; p[3] = (uint8_t)v[3];
+        break; }
+    case GJ_PF_444_P0P1P2:
+        raw[pos] = (uint8_t)v[0]; raw[(size_t)W * H + pos] = (uint8_t)v[1]; raw[(size_t)2 * W * H + pos] = (uint8_t)v[2];
+        break;
+    case GJ_PF_422_P0P1P2:
+        raw[pos] = (uint8_t)v[0];
+        if ((x & 1) == 0) {
+            raw[(size_t)W * H + pos / 2] = (uint8_t)v[1];
+            raw[(size_t)W * H + (size_t)H * ((W + 1) / 2) + pos / 2] = (uint8_t)v[2];
+        }
+        break;
+    case GJ_PF_422_P1020: {
+        const size_t off = (size_t)pos * 2 + (size_t)g.width_padding * y;
+        raw[off + 1] = (uint8_t)v[0];
+        raw[off] = (uint8_t)((x & 1) == 0 ? v[1] : v[2]);
+        break; }
+    case GJ_PF_420_P0P1P2:
+        raw[pos] = (uint8_t)v[0];
+        if ((pos & 1) == 0 && (y & 1) == 0) {
+            raw[(size_t)W * H + (size_t)(y / 2) * ((W + 1) / 2) + x / 2] = (uint8_t)v[1];
+            raw[(size_t)W * H + (size_t)((H + 1) / 2 + y / 2) * ((W + 1) / 2) + x / 2] = (uint8_t)v[2];
+        }
+        break;
+    default: break;
+    }
+}
+
+// region decode (gj_dec_region.hip): the compacted segment table of job->region (from job's table, which has been written), and the IDCT side
+void gj_launch_segment_select(const gj_dec_job* job, hipStream_t st);
+void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, bool tokens, gj_event_t* ev);
+void gj_launch_idct_tok_region(const gj_dec_job* job, hipStream_t st); // (gj_dec_idct.hip: beside k_idct_tok_rgb444, whose LDS helpers it shares)
 
 // ---- token-fed IDCT kernels (gj_dec_idct.hip, gj_dec_idct_scaled.hip): the wave's tokens on their way into LDS
 #define GJ_TOK_STAGE 832 // tokens per wave in LDS (with the 32 KiB tile: four workgroups per CU)

@@ -1,0 +1,221 @@
+// gj_dec_region.hip -- MI355X (gfx950, wave64) JPEG decoder: region-of-interest decode (dec_opt_region = X,Y,W,H). The result is the crop of
+// the full decode, byte for byte; what a region call saves is work:
+//
+//   k_segment_select        segment table -> compacted table of the entries whose restart segment touches the region's cover
+//                           (gj_segment_in_cover, gj_device.h), in stream order, and their number per scan in pinned host memory. Every entropy
+//                           decoder reads the table, so every one of them decodes the selection without a change to its symbol loop.
+//   k_idct_region           dequantisation + IDCT of the cover's blocks from the coefficient planes into COVER-SIZED component planes
+//                           (one lane per block like k_idct, the same arithmetic: gj_idct_pk)
+//   k_postprocess_region    the region's pixels from those planes: k_postprocess with the region's origin inside the cover
+//   k_copy_planes_region    the same for planar output whose layout equals the component layout (k_copy_planes_out)
+//
+// Every configuration can go this way; three-component 4:4:4 streams with non-interleaved scans and packed 3-byte output in token mode go
+// through k_idct_tok_region_rgb444 (gj_dec_idct.hip, beside k_idct_tok_rgb444 whose LDS helpers it shares) instead of the last three: same bytes.
+// (part of the decoder's device code, see gj_dec_internal.h for the map of the files)
+#include "gj_dec_internal.h"
+
+extern "C" int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s) { return gj_segment_in_cover(*g, *r, s) ? 1 : 0; }
+
+// ================================================================================================
+// Selection
+// ================================================================================================
+#define GJ_SEL_CHUNK 1024 // table entries per workgroup = its lanes
+
+// scan of the stream a geometric segment index belongs to (0 for an interleaved scan)
+__device__ __forceinline__ int gj_segment_scan(const gj_geom& g, const uint32_t s)
+{
+    int c = 0;
+    if (!g.interleaved)
+        for (int i = 1; i < GJ_MAX_COMP; i++)
+            if (i < g.comp_count && (int)s >= g.comp[i].first_segment) c = i;
+    return c;
+}
+
+// One launch, no ordering between workgroups: workgroup w takes entries [w * 1024, (w + 1) * 1024) of the table, one per lane, and finds where its
+// selected entries go by counting the selected ones in front of its chunk itself -- reads of 4-byte indices that stay in L2 and a predicate of two
+// 32-bit divisions each; the table of an 8K frame has 43 200 entries, the last workgroup evaluates all of them, 43 trips of its 1024 lanes. Counting is a ballot
+// per wave and trip (every lane of a wave holds the wave's count), the order of the table (stream order) is kept: the batch plan's and the token
+// decoder's arguments need batches in increasing stream position.
+// The last workgroup has counted everything: it leaves the totals, per scan too, for the entropy decoders (device word) and for the host (pinned).
+__global__ __launch_bounds__(GJ_SEL_CHUNK) void k_segment_select(const gj_geom g, const gj_region r, const uint32_t* __restrict__ seg_pos,
+                                                                 const uint32_t* __restrict__ seg_len, const uint32_t* __restrict__ seg_index,
+                                                                 const int seg_count_max, const uint32_t* __restrict__ seg_count_ptr,
+                                                                 uint32_t* __restrict__ out, const uint32_t out_stride, uint32_t* __restrict__ d_count,
+                                                                 uint32_t* __restrict__ h_count)
+{
+    __shared__ uint32_t s_before, s_scan[GJ_MAX_COMP], s_wave[GJ_SEL_CHUNK / GJ_WAVE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = seg_count_ptr ? min((int)*seg_count_ptr, seg_count_max) : seg_count_max;
+    const int begin = (int)blockIdx.x * GJ_SEL_CHUNK;
+    const bool last_wg = blockIdx.x == gridDim.x - 1;
+    if (begin >= n && !last_wg) return;
+    if (tid == 0) s_before = 0;
+    if (tid < GJ_MAX_COMP) s_scan[tid] = 0;
+    __syncthreads();
+    // selected entries in front of the chunk (the last workgroup: per scan as well); every lane makes every trip
+    uint32_t before = 0, per[GJ_MAX_COMP] = {0, 0, 0, 0};
+    const int front = min(begin, n);
+    for (int base = 0; base < front; base += GJ_SEL_CHUNK) {
+        const int i = base + tid;
+        const uint32_t s = i < front ? seg_index[i] : 0xFFFFFFFFu;
+        const bool in = i < front && gj_segment_in_cover(g, r, (int)s);
+        before += (uint32_t)__popcll(__ballot(in));
+        if (last_wg) {
+            const int sc = in ? gj_segment_scan(g, s) : -1;
+#pragma unroll
+            for (int c = 0; c < GJ_MAX_COMP; c++) per[c] += (uint32_t)__popcll(__ballot(sc == c));
+        }
+    }
+    // the chunk
+    const int i = begin + tid;
+    const uint32_t s = i < n ? seg_index[i] : 0xFFFFFFFFu;
+    const bool in = i < n && gj_segment_in_cover(g, r, (int)s);
+    const unsigned long long b = __ballot(in);
+    if (last_wg) {
+        const int sc = in ? gj_segment_scan(g, s) : -1;
+#pragma unroll
+        for (int c = 0; c < GJ_MAX_COMP; c++) per[c] += (uint32_t)__popcll(__ballot(sc == c));
+    }
+    if (lane == 0) {
+        s_wave[wave] = (uint32_t)__popcll(b);
+        if (before) atomicAdd(&s_before, before);
+#pragma unroll
+        for (int c = 0; c < GJ_MAX_COMP; c++)
+            if (last_wg && per[c]) atomicAdd(&s_scan[c], per[c]);
+    }
+    __syncthreads();
+    uint32_t at = s_before, total = s_before;
+    for (int w = 0; w < GJ_SEL_CHUNK / GJ_WAVE; w++) {
+        if (w < wave) at += s_wave[w];
+        total += s_wave[w];
+    }
+    at += (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+    if (in && at < out_stride) { // (cannot fail: the compacted table has room for every entry of the table)
+        out[at] = seg_pos[i];
+        out[out_stride + at] = seg_len[i];
+        out[2 * out_stride + at] = s;
+    }
+    if (last_wg) {
+        if (tid == 0) {
+            *d_count = total;
+            h_count[0] = total;
+        }
+        if (tid < GJ_MAX_COMP) h_count[1 + tid] = s_scan[tid];
+    }
+}
+
+// the table of this job behind the selection: what the entropy decoders are launched with (gj_hip_decode)
+void gj_launch_segment_select(const gj_dec_job* job, hipStream_t st)
+{
+    const gj_geom& g = job->g;
+    const gj_region& r = job->region;
+    const uint32_t stride = (uint32_t)g.segment_count + GJ_MAX_COMP;
+    const unsigned wgs = ((unsigned)max(job->seg_count, 1) + GJ_SEL_CHUNK - 1) / GJ_SEL_CHUNK;
+    hipLaunchKernelGGL(k_segment_select, dim3(wgs), dim3(GJ_SEL_CHUNK), 0, st, g, r, job->d_seg_pos, job->d_seg_len, job->d_seg_index, job->seg_count,
+                       job->d_seg_count, r.d_sel, stride, r.d_sel_count, r.h_sel_count);
+}
+
+// ================================================================================================
+// IDCT side
+// ================================================================================================
+// gr: the region image's geometry whose component planes are the COVER (gj_geom_init_region): blocks_x / blocks_y, data_width / data_height and
+// data_offset of every component describe the cover-sized planes. One lane per block of the cover; a block of the cover is block
+// (bx0 + bx, by0 + by) of the component's coefficient plane, which holds its blocks in raster order for every kind of scan.
+__global__ __launch_bounds__(256) void k_idct_region(const gj_geom g, const gj_geom gr, const gj_region r, const int16_t* __restrict__ coefs,
+                                                     const float* __restrict__ qtab, uint8_t* __restrict__ planes)
+{
+    const unsigned gb = blockIdx.x * 256u + threadIdx.x;
+    if (gb >= (unsigned)gr.block_count) return;
+    int c = 0;
+#pragma unroll
+    for (int i = 1; i < GJ_MAX_COMP; i++)
+        if (i < gr.comp_count && (uint64_t)gb * 64 >= gr.comp[i].data_offset) c = i;
+    const gj_comp_geom& k = gr.comp[c];
+    const unsigned lb = gb - (unsigned)(k.data_offset / 64);
+    const unsigned by = lb / (unsigned)k.blocks_x, bx = lb - by * (unsigned)k.blocks_x;
+    const gj_comp_geom& kf = g.comp[c];
+    const unsigned fbx = (unsigned)r.bx0[c] + bx, fby = (unsigned)r.by0[c] + by;
+    if (fbx >= (unsigned)kf.blocks_x || fby >= (unsigned)kf.blocks_y) return; // (cannot happen: the cover lies inside the component's grid)
+    uint32_t w[32];
+    {
+        const uint4* p = reinterpret_cast<const uint4*>(coefs + kf.data_offset + ((size_t)fby * kf.blocks_x + fbx) * 64);
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const uint4 v = p[q];
+            w[q * 4] = v.x; w[q * 4 + 1] = v.y; w[q * 4 + 2] = v.z; w[q * 4 + 3] = v.w;
+        }
+    }
+    uint32_t px[16];
+    gj_idct_pk(w, qtab + kf.q_table * 64, px);
+    uint8_t* dst = planes + k.data_offset + (size_t)by * 8 * k.data_width + bx * 8;
+#pragma unroll
+    for (int q = 0; q < 8; q++) *reinterpret_cast<uint2*>(dst + (size_t)q * k.data_width) = make_uint2(px[2 * q], px[2 * q + 1]);
+}
+
+// sample of component c that pixel (x, y) of the REGION needs, in the cover-sized plane: pixel (r.x + x, r.y + y) of the stream's image
+__device__ __forceinline__ size_t gj_region_sample(const gj_comp_geom& k, const gj_region& r, const int c, const unsigned x, const unsigned y)
+{
+    const unsigned sx = ((unsigned)r.x + x) / (unsigned)k.sub_h - (unsigned)r.bx0[c] * 8u;
+    const unsigned sy = ((unsigned)r.y + y) / (unsigned)k.sub_v - (unsigned)r.by0[c] * 8u;
+    return k.data_offset + (size_t)min(sy, (unsigned)k.data_height - 1u) * k.data_width + min(sx, (unsigned)k.data_width - 1u); // (the cover holds them)
+}
+
+// k_postprocess for a region: one lane per pixel of the W x H image (raw_width x height of gr)
+__global__ __launch_bounds__(256) void k_postprocess_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    const unsigned W = (unsigned)gr.raw_width, H = (unsigned)gr.height;
+    const unsigned pos = blockIdx.x * 256u + threadIdx.x;
+    if (pos >= W * H) return;
+    const unsigned y = pos / W, x = pos - y * W;
+    int v[4] = {0, 0, 0, gr.pixel_format == GJ_PF_4444_P0123 ? 0xFF : 0};
+#pragma unroll
+    for (int c = 0; c < GJ_MAX_COMP; c++) {
+        if (c >= gr.comp_count) break;
+        v[c] = planes[gj_region_sample(gr.comp[c], r, c, x, y)];
+    }
+    gj_store_pixel(gr, raw, W, H, x, y, pos, v);
+}
+
+// k_copy_planes_out for a region: plane c of the result is the crop of plane c at (r.x / sub_h, r.y / sub_v), k.width x k.height samples
+__global__ __launch_bounds__(256) void k_copy_planes_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    size_t dst_off = 0;
+    for (int c = 0; c < gr.comp_count; c++) {
+        const gj_comp_geom& k = gr.comp[c];
+        const size_t dpitch = (size_t)k.width + gr.width_padding;
+        const size_t n = (size_t)k.width * k.height;
+        const size_t ox = (size_t)(r.x / k.sub_h - r.bx0[c] * 8), oy = (size_t)(r.y / k.sub_v - r.by0[c] * 8);
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+            const size_t y = i / k.width, x = i - y * k.width;
+            raw[dst_off + y * dpitch + x] = planes[k.data_offset + (oy + y) * k.data_width + ox + x];
+        }
+        dst_off += dpitch * k.height;
+    }
+}
+
+// The IDCT side of a region call: cover blocks -> cover planes -> region pixels (+ channel remap on the region image).
+void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tokens, gj_event_t* ev)
+{
+    const gj_geom& gr = job->gs;
+    const gj_region& r = job->region;
+    if (tokens) { // token mode: records and tokens of the cover's blocks -> region pixels (k_idct_tok_region_rgb444)
+        gj_launch_idct_tok_region(job, st);
+        if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
+    } else {
+        hipLaunchKernelGGL(k_idct_region, dim3(((unsigned)gr.block_count + 255) / 256), dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtabf, job->d_planes);
+        if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
+        if (gr.no_transform) {
+            const size_t n = (size_t)gr.comp[0].width * gr.comp[0].height;
+            hipLaunchKernelGGL(k_copy_planes_region, dim3((unsigned)min((n + 255) / 256, (size_t)2048)), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
+        } else {
+            const unsigned n = (unsigned)gr.raw_width * (unsigned)gr.height;
+            hipLaunchKernelGGL(k_postprocess_region, dim3((n + 255) / 256), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
+        }
+    }
+    gj_debug_stage(job->tune.debug_sync != 0, st, "idct / postprocess (region)");
+    if (job->channel_remap) {
+        const unsigned n = (unsigned)gr.width * (unsigned)gr.height;
+        hipLaunchKernelGGL(k_channel_remap, dim3((n + 255) / 256), dim3(256), 0, st, gr, job->d_raw, job->channel_remap & 0xFFFFu);
+    }
+    if (job->idct_path) *job->idct_path = tokens ? 4 : 3;
+}

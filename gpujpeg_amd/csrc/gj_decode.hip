@@ -44,6 +44,11 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     if (g.blocks_per_mcu > GJ_MAX_MCU_BLOCKS) return -1;
     if ((job->batch.count > 1 || g.fb.sizes != nullptr) && (!gj_hip_decode_batchable(job) || g.fb.sizes == nullptr || job->batch.count > 65535u)) return -1;
     if (job->scale > 1 && ((job->scale != 2 && job->scale != 4 && job->scale != 8) || g.fb.sizes != nullptr || job->flipped)) return -1; // (single frames, no flip)
+    const gj_region& rg = job->region;
+    // (a region call: a single frame, no scale, no flip; with a selection, room for the compacted table and its counts)
+    if (rg.on && (job->scale > 1 || g.fb.sizes != nullptr || job->batch.count > 1 || job->flipped ||
+                  (rg.select && (!rg.d_sel || !rg.d_sel_count || !rg.h_sel_count || g.restart_interval <= 0))))
+        return -1;
     gj_hip_note_reset();
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[0], st));
     bool par = job->d_huff_tab2 != nullptr && job->seg_count > 0;
@@ -61,7 +66,7 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     // fit its LDS stage), the lane-per-segment kernel for interleaved ones
     // (a reduced-size decode, gj_dec_job::scale: token mode where the token-fed reduced-size kernel exists -- not for the interleaved 4:2:2 scan)
     const bool tok_wanted = fast_ok && job->tokens && job->use_fused && job->d_tok && job->d_blkrec && gj_hip_decode_wants_tokens(&g, job->jpeg_size, &job->tune) &&
-                            (job->scale <= 1 || gj_idct_tok_scaled_for(g));
+                            (job->scale <= 1 || gj_idct_tok_scaled_for(g)) && (!job->region.on || gj_idct_tok_scaled_for(g)); // (region: the same configuration)
     const bool tok_sub = tok_wanted && !g.interleaved && !seq && job->max_seg_len != 0 && job->max_seg_len + 12u <= (uint32_t)GJ_TOK_CAP_U;
     const bool tok_seq = tok_wanted && seq;
     gj_idct_tok_t idct_tok = (tok_sub || tok_seq) ? gj_idct_tok_for(g) : nullptr;
@@ -76,9 +81,26 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     }
     // a marker scan whose table launch was left to us (gj_scan_deferred): the token decoder reads the scan's records itself, everything else needs the table
     const bool takes_par = !(tokens && tok_sub) && !seq && par;
-    const bool folded = job->scan.valid && ((tokens && tok_sub && gj_tok_folds_table(job)) || (takes_par && gj_par_folds_table(job)));
+    // (a selection reads the table: its launch is not folded into the entropy decoder)
+    const bool folded = job->scan.valid && !rg.select && ((tokens && tok_sub && gj_tok_folds_table(job)) || (takes_par && gj_par_folds_table(job)));
     if (job->scan.valid && !folded) gj_launch_marker_table_deferred(job, st);
     if (job->scan.valid && job->scan.folded) *job->scan.folded = folded ? 1 : 0;
+    // region call with a selection: the entropy decoder gets the compacted table -- as many entries as the geometry says touch the cover (the plan),
+    // bounded by what k_segment_select found in this stream's table
+    gj_dec_job sel;
+    if (rg.select) {
+        gj_launch_segment_select(job, st);
+        sel = *job;
+        const uint32_t stride = (uint32_t)g.segment_count + GJ_MAX_COMP;
+        sel.d_seg_pos = rg.d_sel;
+        sel.d_seg_len = rg.d_sel + stride;
+        sel.d_seg_index = rg.d_sel + 2 * stride;
+        sel.d_seg_count = rg.d_sel_count;
+        sel.seg_count = 0;
+        for (int c = 0; c < g.scan_count && c < GJ_MAX_COMP; c++) sel.seg_count += rg.sel_count[c];
+        sel.scan.valid = 0;
+        job = &sel;
+    }
     if (tokens && tok_sub) gj_launch_huffman_tok(job, st);
     else if (seq) gj_launch_huffman_seq(job, st, tokens);
     else if (par) gj_launch_huffman_par(job, st);

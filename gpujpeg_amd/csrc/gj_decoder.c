@@ -36,7 +36,6 @@ struct gpujpeg_decoder {
     int keep_coefs;               /* 1: leave the coefficients in HBM after the call (gpujpeg_amd_decoder_keep_coefficients) */
     uint16_t* d_tok; size_t d_tok_cap;     /* token mode (gj_hip.h): non-zero AC coefficients of the frame */
     void* d_blkrec; size_t d_blkrec_cap;   /* token mode: one record per block */
-    bool coefs_clean;             /* d_coefs is all zero: the previous call's IDCT cleared what it read */
     /* device-side segment discovery */
     uint8_t* h_hdr;               /* pinned: first bytes of a device-resident stream, for header parsing */
     uint32_t* d_scan_scratch; size_t d_scan_scratch_cap;
@@ -84,13 +83,23 @@ struct gpujpeg_decoder {
     gj_geom geom_s;                                /* call_scale > 1: geometry and parameters of the reduced image */
     struct gpujpeg_image_parameters pi_s;
     int last_idct_path;                            /* gj_dec_job::idct_path of the last call */
+    /* region decode (dec_opt_region). Like the scale, the option is read once per attempt (dec_region_geometry) and nothing cached depends on it.
+     * A region call shares geom_s / pi_s with the reduced-size decode (the two exclude each other): the W x H image over the cover's planes. */
+    bool region_on; int region[4];                 /* the option: x, y, w, h */
+    bool call_region;                              /* what the decode call in progress (and, after it, the last one) used */
+    gj_region rg;                                  /* call_region: pixel rectangle, cover, planned selection */
+    uint32_t* d_sel; size_t d_sel_cap;             /* the compacted segment table of a selection */
+    uint32_t* d_sel_count; uint32_t* h_sel_count;  /* its entry count on the device; pinned: [0] the same, [1 + c] entries of scan c */
+    gj_region plan_rg; bool plan_valid;            /* the region whose sel_count is in plan_rg (the count is a loop over the geometry's segments) */
+    long region_stats[4];                          /* gpujpeg_amd_decoder_get_region_stats */
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
-static size_t dec_raw_size(const struct gpujpeg_decoder* d) { return d->call_scale > 1 ? d->geom_s.raw_size : d->coder.geom.raw_size; }
+static bool dec_reduced_or_region(const struct gpujpeg_decoder* d) { return d->call_scale > 1 || d->call_region; }
+static size_t dec_raw_size(const struct gpujpeg_decoder* d) { return dec_reduced_or_region(d) ? d->geom_s.raw_size : d->coder.geom.raw_size; }
 static struct gpujpeg_image_parameters dec_out_param_image(const struct gpujpeg_decoder* d)
 {
-    struct gpujpeg_image_parameters pi = d->call_scale > 1 ? d->pi_s : d->coder.param_image;
+    struct gpujpeg_image_parameters pi = dec_reduced_or_region(d) ? d->pi_s : d->coder.param_image;
     if (pi.color_space == GPUJPEG_NONE) pi.color_space = d->coder.param.color_space_internal;
     return pi;
 }
@@ -106,6 +115,44 @@ static int dec_scale_geometry(struct gpujpeg_decoder* d)
         return -1;
     }
     return gj_geom_init_scaled(&d->geom_s, &c->geom, &c->param, &c->param_image, d->call_scale, d->req_alignment, &d->pi_s);
+}
+
+/* the region of this call, once the coder is configured for the stream and the scale is known: validated against the stream, cover and geometry
+ * of the W x H image derived (gj_geom_init_region), segments per scan that touch the cover counted; 0 or -1 (refused, with a message) */
+static int dec_region_geometry(struct gpujpeg_decoder* d)
+{
+    struct gj_coder* c = &d->coder;
+    d->call_region = d->region_on;
+    if (!d->call_region) return 0;
+    d->call_region = false; /* (a refused call decodes nothing: what it leaves describes no region image) */
+    if (d->call_scale > 1) {
+        GJ_ERROR(GPUJPEG_AMD_DEC_OPT_REGION " is not available together with " GPUJPEG_AMD_DEC_OPT_SCALE "=1/%d!\n", d->call_scale);
+        return -1;
+    }
+    if (d->flipped) {
+        GJ_ERROR(GPUJPEG_AMD_DEC_OPT_REGION " is not available together with " GPUJPEG_DEC_OPT_FLIPPED_BOOL "!\n");
+        return -1;
+    }
+    gj_region rg;
+    if (gj_geom_init_region(&d->geom_s, &rg, &c->geom, &c->param, &c->param_image, d->region, d->req_alignment, &d->pi_s) != 0) return -1;
+    /* the plan of a selection: one question per segment of the geometry, asked again only when the region or the stream's geometry changes */
+    if (c->geom.restart_interval > 0) {
+        /* (keyed on the cover itself -- the pixel rectangle alone does not fix it: packed 4:2:2 output widens it to the pixel pair --; a new geometry
+         * drops the plan in decoder_configure) */
+        if (!d->plan_valid || memcmp(d->plan_rg.bx0, rg.bx0, (size_t)((const char*)rg.sel_count - (const char*)rg.bx0)) != 0) {
+            memset(rg.sel_count, 0, sizeof rg.sel_count);
+            for (int sc = 0, s = 0; sc < c->geom.scan_count && sc < GJ_MAX_COMP; sc++) {
+                const int n = c->geom.interleaved ? c->geom.segment_count : c->geom.comp[sc].segment_count;
+                for (int i = 0; i < n; i++, s++) rg.sel_count[sc] += gj_hip_segment_in_cover(&c->geom, &rg, s);
+            }
+            d->plan_rg = rg;
+            d->plan_valid = true;
+        }
+        memcpy(rg.sel_count, d->plan_rg.sel_count, sizeof rg.sel_count);
+    }
+    d->rg = rg;
+    d->call_region = true;
+    return 0;
 }
 
 #define GJ_HDR_WINDOW 65536
@@ -145,7 +192,9 @@ struct gpujpeg_decoder* gpujpeg_decoder_create(cudaStream_t stream)
     d->h_hdr = gj_hip_host_alloc(GJ_HDR_WINDOW);
     d->d_summary = gj_hip_malloc(sizeof(gj_scan_summary));
     d->h_summary = gj_hip_host_alloc(sizeof(gj_scan_summary));
-    if (!d->h_hdr || !d->d_summary || !d->h_summary) goto fail;
+    d->d_sel_count = gj_hip_malloc(sizeof(uint32_t));
+    d->h_sel_count = gj_hip_host_alloc((1 + GJ_MAX_COMP) * sizeof(uint32_t));
+    if (!d->h_hdr || !d->d_summary || !d->h_summary || !d->d_sel_count || !d->h_sel_count) goto fail;
     if (gj_hip_memset(d->d_summary, 0, sizeof(gj_scan_summary), d->coder.stream) != 0 || gj_hip_stream_sync(d->coder.stream) != 0) goto fail;
     d->host_scan = d->tune.host_scan;
     return d;
@@ -182,6 +231,7 @@ int gpujpeg_decoder_destroy(struct gpujpeg_decoder* d)
     free(d->hdr_cache); gj_hip_free(d->d_hdr_cache);
     gj_hip_host_free(d->h_hdr); gj_hip_host_free(d->h_summary); gj_hip_host_free(d->h_maxlen); gj_hip_free(d->d_summary); gj_hip_free(d->d_scan_scratch);
     free(d->segs.pos); free(d->segs.len); free(d->segs.index);
+    gj_hip_free(d->d_sel); gj_hip_free(d->d_sel_count); gj_hip_host_free(d->h_sel_count);
     gj_hip_free(d->b_dsum); gj_hip_free(d->b_sizes); gj_hip_free(d->b_seg); gj_hip_free(d->b_scratch); gj_hip_free(d->b_coefs); gj_hip_free(d->b_planes); gj_hip_free(d->b_tok);
     gj_hip_free(d->b_rec); gj_hip_free(d->b_jpeg); gj_hip_free(d->b_raw); gj_hip_free(d->b_gather); gj_hip_free(d->b_scatter);
     gj_hip_host_free(d->bh_sum); gj_hip_host_free(d->bh_maxlen); gj_hip_host_free(d->bh_sizes);
@@ -204,7 +254,7 @@ static int decoder_configure(struct gpujpeg_decoder* d, const struct gpujpeg_par
     if (c->configured && gj_parameters_equal(&c->param, p) && gj_image_parameters_equal(&c->param_image, pi)) return 0;
     if (c->configured && verbose >= GPUJPEG_LL_INFO) fprintf(stderr, "[GPUJPEG] [Info] Reinitializing decoder.\n");
     c->configured = false;
-    d->coefs_clean = false;
+    d->plan_valid = false;
     c->param = *p;
     c->param.verbose = verbose;
     c->param.perf_stats = perf;
@@ -331,6 +381,11 @@ static void dec_job_base(const struct gpujpeg_decoder* d, bool tab2_ok, gj_dec_j
         job->scale = d->call_scale;
         job->gs = d->geom_s;
     }
+    if (d->call_region) {
+        job->region = d->rg;
+        job->region.on = 1;
+        job->gs = d->geom_s;
+    }
 }
 
 /* One call = up to three attempts (decoder_decode). What the stages of an attempt share: */
@@ -352,6 +407,8 @@ struct dec_call {
     const uint32_t* d_seg_count;
     gj_scan_deferred scan_deferred;
     bool tab2_ok;
+    bool no_select;      /* region call: a previous attempt's selection did not match its plan -- this one entropy-decodes every segment */
+    bool select;         /* region call: this attempt entropy-decodes the segments that touch the cover only */
     struct gj_reader_result r;
 };
 /* what an attempt and its stages return: 0, a negative error code of the call, or DEC_AGAIN (dec_after only: another attempt, with k->careful as
@@ -607,6 +664,18 @@ static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
      * which is validated and repeated then */
     job.clear_coefs = !k->spec && k->seg_count != g->segment_count;
     job.zero_coefs = 0;
+    /* region call: where the stream is (or, on the cached header, is assumed to be) the regular one of the geometry, only the segments that touch
+     * the cover are entropy-decoded. The selected table has fewer entries than the geometry by design; no clear is needed for it -- every block of
+     * the cover belongs to a selected segment, and the decoders zero-fill the blocks of the segments they decode. */
+    k->select = d->call_region && !k->no_select && g->restart_interval > 0 && (k->spec || k->seg_count == g->segment_count);
+    if (k->select) {
+        if (gj_ensure_device_buffer((void**)&d->d_sel, &d->d_sel_cap, 3 * S * sizeof(uint32_t)) != 0) return -1;
+        job.region.select = 1;
+        job.region.d_sel = d->d_sel;
+        job.region.d_sel_count = d->d_sel_count;
+        job.region.h_sel_count = d->h_sel_count;
+        memset(d->h_sel_count, 0xFF, (1 + GJ_MAX_COMP) * sizeof(uint32_t));
+    }
     /* token mode buffers (gj_hip.h): one record per block, 4 tokens per stream byte at most */
     if (!d->keep_coefs && job.use_fused && k->tab2_ok && k->image_size < ((size_t)1 << 29) && gj_hip_decode_wants_tokens(&job.g, k->image_size, &d->tune)) {
         const size_t tok_need = (k->image_size * 4 + 64) * sizeof(uint16_t);
@@ -642,6 +711,11 @@ static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
         }
     }
     if (!k->spec && k->seg_count != g->segment_count) memset(job.scan_bytes, 0, sizeof job.scan_bytes); /* (table and geometry out of step: one batch size) */
+    if (k->select) /* (the selected share of every scan's bytes: an estimate, it only sizes the batches) */
+        for (int sc = 0; sc < g->scan_count && sc < GJ_MAX_COMP; sc++) {
+            const int all = g->interleaved ? g->segment_count : g->comp[sc].segment_count;
+            if (all > 0) job.scan_bytes[sc] = (uint32_t)((uint64_t)job.scan_bytes[sc] * (uint64_t)d->rg.sel_count[sc] / (uint64_t)all);
+        }
     if (gj_hip_decode(&job, c->stream, k->stats ? c->timers.ev : NULL) != 0) {
         GJ_ERROR("Decoder kernels failed: %s\n", gj_hip_last_error());
         return -1;
@@ -675,12 +749,29 @@ static int dec_download(struct gpujpeg_decoder* d, struct dec_call* k)
     return 0;
 }
 
+/* a region's selection: did k_segment_select find in this stream's table what the plan took from the geometry? */
+static bool dec_selection_ok(const struct gpujpeg_decoder* d, const struct dec_call* k)
+{
+    if (!k->select) return true;
+    uint32_t sum = 0;
+    for (int sc = 0; sc < GJ_MAX_COMP; sc++) {
+        if (d->h_sel_count[1 + sc] != (uint32_t)d->rg.sel_count[sc]) return false;
+        sum += (uint32_t)d->rg.sel_count[sc];
+    }
+    return d->h_sel_count[0] == sum;
+}
+
 /* ---- 8. everything has run: was a launch on the cached header justified? Which header do the next calls launch on? ---- */
 static int dec_after(struct gpujpeg_decoder* d, struct dec_call* k)
 {
     struct gj_coder* c = &d->coder;
     const gj_geom* g = &c->geom;
     const gj_scan_summary* su = d->h_summary;
+    if (!k->spec && !dec_selection_ok(d, k)) {
+        GJ_DEBUG(c->param.verbose, "the region's selection found other segments than planned: decoding again with every segment\n");
+        k->no_select = true;
+        return DEC_AGAIN;
+    }
     if (!k->spec && su->seq_overflow && !k->careful) { /* (a kernel forced on a stream with segments it cannot stage; or, after a host
                                                            walk, a table whose longest segment the host did not foresee) */
         GJ_DEBUG(c->param.verbose, "a restart segment did not fit the entropy decoder's LDS stage: decoding again through the coefficient planes\n");
@@ -690,6 +781,11 @@ static int dec_after(struct gpujpeg_decoder* d, struct dec_call* k)
     }
     if (k->spec) { /* now the summary of this stream is on the host: was it what we assumed? */
         summary_take_maxlen(d->h_summary, d->h_maxlen, d->maxlen_parts);
+        if (spec_summary_ok(d, su, g) && !dec_selection_ok(d, k)) { /* (cannot happen for a stream the rule accepts: its table is the geometry's) */
+            d->n_again++;
+            k->no_select = true;
+            return DEC_AGAIN;
+        }
         if (!spec_summary_ok(d, su, g)) { /* different header or unusual scan structure: decode again the careful way */
             d->n_again++;
             if (d->last_folded) d->n_folded--; /* (counted at the launch: only accepted launches count as folded) */
@@ -764,7 +860,7 @@ static int dec_attempt(struct gpujpeg_decoder* d, struct dec_call* k)
     int rc = dec_headers(d, k);
     if (rc != 0) return rc;
     for (int i = 0; i < GPUJPEG_METADATA_COUNT; i++) d->metadata.vals[i] = k->r.metadata.vals[i];
-    if (decoder_configure(d, &k->r.param, &k->r.param_image) != 0 || dec_scale_geometry(d) != 0) return DEC_FAILED;
+    if (decoder_configure(d, &k->r.param, &k->r.param_image) != 0 || dec_scale_geometry(d) != 0 || dec_region_geometry(d) != 0) return DEC_FAILED;
     c->init_end_time = k->stats ? gpujpeg_get_time() : 0;
     if (dec_upload(d, k) != 0) return DEC_FAILED;
     if ((rc = dec_segment_table(d, k)) != 0) return rc;
@@ -779,6 +875,12 @@ static int dec_attempt(struct gpujpeg_decoder* d, struct dec_call* k)
     }
     GJ_HT(c, 2);
     if (dec_after(d, k) == DEC_AGAIN) return DEC_AGAIN;
+    /* what this call did (gpujpeg_amd_decoder_get_region_stats): from what was launched and what the selection found */
+    const long stream_segs = k->spec ? (long)d->h_summary->segment_count : (long)k->seg_count;
+    d->region_stats[0] = !d->call_region ? 0 : k->select ? 1 : 2;
+    d->region_stats[1] = k->select ? (long)d->h_sel_count[0] : stream_segs;
+    d->region_stats[2] = d->call_region ? (long)d->geom_s.block_count : (long)c->geom.block_count;
+    d->region_stats[3] = stream_segs;
     dec_stats(d, k);
     k->output->metadata = &d->metadata;
     GJ_HT(c, 3);
@@ -796,10 +898,12 @@ static int decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t imag
     k.output = output;
     k.jpeg_on_device = gj_hip_is_device_ptr(image) != 0;
     k.careful = false;
+    k.no_select = false;
+    k.select = false;
     k.host_io = false;
     k.host_copy = NULL;
     int rc = DEC_AGAIN;
-    for (int attempt = 0; attempt < 3 && rc == DEC_AGAIN; attempt++) {
+    for (int attempt = 0; attempt < 4 && rc == DEC_AGAIN; attempt++) { /* (the fourth: a region's selection that did not match its plan) */
         rc = dec_attempt(d, &k);
         free(k.host_copy);
         k.host_copy = NULL;
@@ -931,8 +1035,8 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     const gj_geom* g = &c->geom;
     const int first = b->first, count = b->count, n_all = count - first;
     const size_t* sizes = b->sizes;
-    /* (a reduced-size decode goes frame by frame: the scaled kernels do not know the frame dimension) */
-    bool batched = d->scale <= 1 && d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
+    /* (a reduced-size decode and a region decode go frame by frame: their kernels do not know the frame dimension) */
+    bool batched = d->scale <= 1 && !d->region_on && d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
                    (b->streams_on_device ? (b->stream_stride & 15u) == 0 : true) && d->tab2_ok;
     size_t max_size = 0;
     for (int f = first; f < count; f++) {
@@ -941,6 +1045,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     }
     if (!batched || n_all < 1) return 0;
     d->call_scale = 1;
+    d->call_region = false;
     const struct gj_reader_result* r = &d->hdr_cache_r;
     if (decoder_configure(d, &r->param, &r->param_image) != 0) return -1; /* (the geometry of the cached header, whatever the coder was last set up for) */
     if (b->output_stride < g->raw_size || (b->frame_raw != 0 && b->frame_raw != g->raw_size)) {
@@ -1213,6 +1318,26 @@ int gpujpeg_decoder_set_option(struct gpujpeg_decoder* d, const char* opt, const
         GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_SCALE " (1, 1/2, 1/4 or 1/8)\n", val);
         return GPUJPEG_ERROR;
     }
+    if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_REGION) == 0) { /* syntax only: the decode call checks the region against its stream */
+        if (strcmp(val, "full") == 0) { d->region_on = false; return GPUJPEG_NOERR; }
+        long v[4];
+        const char* p = val;
+        bool ok = true;
+        for (int i = 0; i < 4 && ok; i++) {
+            int digits = 0;
+            v[i] = 0;
+            while (*p >= '0' && *p <= '9' && digits < 9) { v[i] = v[i] * 10 + (*p - '0'); p++; digits++; }
+            ok = digits > 0 && !(*p >= '0' && *p <= '9') && *p == (i < 3 ? ',' : '\0');
+            if (ok && i < 3) p++;
+        }
+        if (!ok || v[2] < 1 || v[3] < 1) {
+            GJ_ERROR("Wrong value %s for " GPUJPEG_AMD_DEC_OPT_REGION " (X,Y,W,H in pixels with W, H >= 1, or full)\n", val);
+            return GPUJPEG_ERROR;
+        }
+        for (int i = 0; i < 4; i++) d->region[i] = (int)v[i];
+        d->region_on = true;
+        return GPUJPEG_NOERR;
+    }
     GJ_ERROR("Invalid decoder option: %s!\n", opt);
     return GPUJPEG_ERROR;
 }
@@ -1223,6 +1348,7 @@ void gpujpeg_decoder_print_options(void)
     printf("\t" GPUJPEG_DEC_OPT_FLIPPED_BOOL "=[" GPUJPEG_VAL_TRUE "|" GPUJPEG_VAL_FALSE "] - whether the output image should be vertically flipped\n");
     printf("\t" GPUJPEG_DEC_OPT_CHANNEL_REMAP "=XYZ[W] - output channel remapping, 'help' for details\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_SCALE "=[1|1/2|1/4|1/8] - decode to a reduced-size image (MI355X extension)\n");
+    printf("\t" GPUJPEG_AMD_DEC_OPT_REGION "=[X,Y,W,H|full] - decode the W x H pixels at (X, Y) only (MI355X extension)\n");
 }
 
 /* ------------------------------------------------------------------ MI355X extensions (include/gpujpeg_amd_ext.h) */
@@ -1256,10 +1382,17 @@ size_t gpujpeg_amd_decoder_read_coefficients(struct gpujpeg_decoder* d, int16_t*
 
 size_t gpujpeg_amd_decoder_read_planes(struct gpujpeg_decoder* d, uint8_t* dst, size_t capacity)
 {
-    const size_t n = d->call_scale > 1 ? d->geom_s.data_size : d->coder.geom.data_size; /* (the reduced planes of a reduced-size decode) */
+    const size_t n = dec_reduced_or_region(d) ? d->geom_s.data_size : d->coder.geom.data_size; /* (the reduced planes of a reduced-size decode, the cover's of a region decode) */
     if (!d->coder.configured || capacity < n) return 0;
     if (gj_hip_memcpy_d2h(dst, d->coder.d_planes, n, d->coder.stream) != 0 || gj_hip_stream_sync(d->coder.stream) != 0) return 0;
     return n;
+}
+
+int gpujpeg_amd_decoder_get_region_stats(struct gpujpeg_decoder* d, long out[4])
+{
+    if (!d || !out) return -1;
+    memcpy(out, d->region_stats, sizeof d->region_stats);
+    return 0;
 }
 
 void gpujpeg_amd_decoder_set_fused(struct gpujpeg_decoder* d, int enabled) { d->use_fused = enabled != 0; }

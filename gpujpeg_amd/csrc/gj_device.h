@@ -98,6 +98,38 @@ __device__ __forceinline__ uint64_t gj_segment_block(const gj_geom& g, const GjS
     return kc.data_offset + ((uint64_t)by * kc.blocks_x + bx) * 64;
 }
 
+// Region decode (gj_region): does restart segment s have a block (non-interleaved scan: of its component's grid) or an MCU (interleaved scan)
+// inside the region's cover? A segment is a run of consecutive cells [first, last] of a raster whose rows are `gridx` cells long; it meets the
+// rectangle [x0, x1) x [y0, y1) in its first row (cells xa .. end of the row), in its last row (0 .. xb) or in any whole row between them.
+// The ONE statement of the selection: k_segment_select (for every kind of table, a host-walked one included) and -- through gj_hip_segment_in_cover -- the host's count of the
+// batch plan ask here.
+__host__ __device__ inline bool gj_segment_in_cover(const gj_geom& g, const gj_region& r, const int s)
+{
+    if (s < 0 || s >= g.segment_count) return false;
+    int c = 0, gridx, total, x0, y0, x1, y1, k = s;
+    if (g.interleaved) {
+        gridx = g.mcu_count_x; total = g.mcu_count;
+        x0 = r.mx0; y0 = r.my0; x1 = r.mx1; y1 = r.my1;
+    } else {
+        for (int i = 1; i < GJ_MAX_COMP; i++)
+            if (i < g.comp_count && s >= g.comp[i].first_segment) c = i;
+        gridx = g.comp[c].blocks_x; total = g.comp[c].mcu_count;
+        x0 = r.bx0[c]; y0 = r.by0[c]; x1 = r.bx1[c]; y1 = r.by1[c];
+        k = s - g.comp[c].first_segment;
+    }
+    if (g.restart_interval <= 0) return true; // one segment per scan
+    // (32-bit throughout: k * restart_interval < total + restart_interval, and a 64-bit division costs the selection kernel ten times this one)
+    const unsigned ri = (unsigned)g.restart_interval, first = (unsigned)k * ri;
+    if (first >= (unsigned)total || gridx <= 0 || x0 >= x1 || y0 >= y1) return false;
+    const unsigned last = (first + ri < (unsigned)total ? first + ri : (unsigned)total) - 1u;
+    const int ya = (int)(first / (unsigned)gridx), yb = (int)(last / (unsigned)gridx);
+    const int xa = (int)(first - (unsigned)ya * (unsigned)gridx), xb = (int)(last - (unsigned)yb * (unsigned)gridx);
+    const int mid_lo = ya + 1 > y0 ? ya + 1 : y0, mid_hi = yb - 1 < y1 - 1 ? yb - 1 : y1 - 1;
+    if (mid_lo <= mid_hi) return true;
+    if (ya >= y0 && ya < y1 && xa < x1 && (ya == yb ? xb : gridx - 1) >= x0) return true;
+    return yb != ya && yb >= y0 && yb < y1 && xb >= x0;
+}
+
 // LDS written by some lanes of a wave is read by other lanes of the SAME wave: the hardware keeps a wave's LDS operations in
 // order, the compiler only has to be told not to move them across this point (no instruction is emitted for the barrier).
 __device__ __forceinline__ void gj_wave_sync()

@@ -43,6 +43,10 @@ int gj_geom_init(gj_geom* g, const struct gpujpeg_parameters* param, const struc
 /* geometry and image parameters of the reduced image of a decode at scale 1/s (s = 2, 4, 8); -1 when the output format has no such image */
 int gj_geom_init_scaled(gj_geom* gs, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image, int s,
                         unsigned alignment, struct gpujpeg_image_parameters* param_image_scaled);
+/* region decode (dec_opt_region): region[4] = x, y, w, h validated against the stream's image and the output format; r: the rectangle and its cover;
+ * gr: the geometry of the w x h image whose component planes are the cover's; -1 (with a message) when the region is refused */
+int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
+                        const int region[4], unsigned alignment, struct gpujpeg_image_parameters* pi_region);
 
 /* ---- tables ---- */
 extern const uint8_t gj_zigzag[64];

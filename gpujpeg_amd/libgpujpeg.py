@@ -332,7 +332,9 @@ class Decoder:
 
     def set_option(self, opt, val):
         """gpujpeg_decoder_set_option, e.g. ("dec_opt_scale", "1/4"): the decode calls that follow return the reduced image (their
-        ImageParameters and sizes are the reduced image's). Returns the library's code (0 = accepted)."""
+        ImageParameters and sizes are the reduced image's), or ("dec_opt_region", "x,y,w,h"): they return the w x h pixels at (x, y) of the
+        stream's image ("full": the whole image again; a region that does not fit the stream or the output format's sampling grid is refused by
+        the decode call). Returns the library's code (0 = accepted)."""
         return self.lib.L.gpujpeg_decoder_set_option(self.h, opt.encode(), val.encode())
 
     def init(self, param, param_image):
@@ -421,6 +423,14 @@ class Decoder:
         raw = self.lib.image_size(pi)
         return [out[i * bound:i * bound + raw].copy() for i in range(n)], pi
 
+    def region_stats(self):
+        """gpujpeg_amd_decoder_get_region_stats of the last decode call: (mode 0 none / 1 selected segments / 2 every segment, restart segments
+        entropy-decoded, 8x8 blocks transformed, segments in the stream)"""
+        a = (C.c_long * 4)()
+        self.lib.L.gpujpeg_amd_decoder_get_region_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        assert self.lib.L.gpujpeg_amd_decoder_get_region_stats(self.h, a) == 0
+        return tuple(int(x) for x in a)
+
     def path_counters(self):
         """(speculative launches, of those without the k_marker_table launch, decoded again the careful way) of this decoder so far"""
         a = (C.c_long * 3)()
@@ -447,7 +457,8 @@ class Decoder:
         return list(ms)[:4]
 
     def idct_path(self):
-        """IDCT side of the last perf_stats call: 0 full size, 1 reduced size from the coefficient planes, 2 reduced size from tokens"""
+        """IDCT side of the last perf_stats call: 0 full size, 1 reduced size from the coefficient planes, 2 reduced size from tokens,
+        3 region from the coefficient planes, 4 region from tokens"""
         ms = (C.c_float * 8)()
         if self.lib.L.gpujpeg_amd_decoder_get_kernel_times(self.h, ms) != 0:
             return None

@@ -258,6 +258,22 @@ typedef struct gj_scan_deferred {
     int* folded;                   /* host, may be NULL: set to 1 by gj_hip_decode when the table launch was folded into the entropy decoder, to 0 otherwise */
 } gj_scan_deferred;
 
+/* Region-of-interest decode (dec_opt_region): the W x H pixels at (x, y) of the stream's image. The COVER of the region is, per component, the
+ * smallest rectangle of 8x8 blocks -- whole MCUs of an interleaved scan -- that holds every sample the region's pixels need. */
+typedef struct gj_region {
+    int on;                        /* 1: this call decodes a region */
+    int select;                    /* 1: only the restart segments that touch the cover are entropy-decoded (k_segment_select compacts the table) */
+    int x, y, w, h;                /* pixels of the stream's image */
+    int bx0[GJ_MAX_COMP], by0[GJ_MAX_COMP], bx1[GJ_MAX_COMP], by1[GJ_MAX_COMP]; /* cover: blocks [bx0, bx1) x [by0, by1) of the component's grid */
+    int mx0, my0, mx1, my1;        /* interleaved scan: the cover in MCUs */
+    int sel_count[GJ_MAX_COMP];    /* select: segments of every scan that touch the cover, as the geometry gives them (the batch plan) */
+    uint32_t* d_sel;               /* select: the compacted table, three arrays of (g.segment_count + GJ_MAX_COMP) words: pos | len | index */
+    uint32_t* d_sel_count;         /* select: device word, entries of the compacted table (what the entropy decoders bound their work with) */
+    uint32_t* h_sel_count;         /* select: pinned host words written by k_segment_select: [0] entries of the compacted table, [1 + c] of scan c */
+} gj_region;
+/* the predicate of the selection (gj_device.h: gj_segment_in_cover) for host code: does restart segment s have a block / an MCU inside the cover? */
+GJ_HIP_API int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s);
+
 typedef struct gj_dec_job {
     gj_geom g;                     /* pixel_format / color_space describe the requested output */
     const uint8_t* d_jpeg;         /* whole file in HBM */
@@ -302,7 +318,11 @@ typedef struct gj_dec_job {
      * holds the reduced planes, d_raw the reduced image). Single frames only. */
     int scale;
     gj_geom gs;
-    int* idct_path;                /* host, may be NULL: which IDCT side ran -- 0 full size, 1 k_idct_scaled, 2 k_idct_tok_scaled_rgb444 */
+    int* idct_path;                /* host, may be NULL: which IDCT side ran -- 0 full size, 1 k_idct_scaled, 2 k_idct_tok_scaled_rgb444, 3 k_idct_region, 4 k_idct_tok_region_rgb444 */
+    /* region decode (dec_opt_region, region.on): the entropy decoders work on g -- with region.select on the compacted table --, the IDCT side
+     * transforms the cover's blocks -- from tokens straight into d_raw, or into cover-sized planes in d_planes from which the region's pixels go to d_raw --; gs is the geometry of the W x H image
+     * with the cover's planes (gj_geom_init_region). Single frames, no scale, no flip. */
+    gj_region region;
 } gj_dec_job;
 /* 1 when gj_hip_decode takes a batch (gj_dec_job::batch.count > 1) of this job's configuration */
 GJ_HIP_API int gj_hip_decode_batchable(const gj_dec_job* job);

@@ -85,6 +85,27 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
  * Outside reference parity by construction (the reference has no reduced decode). */
 #define GPUJPEG_AMD_DEC_OPT_SCALE "dec_opt_scale"
 #define GPUJPEG_AMD_SCALED_DIM(v, s) (((v) + (s) - 1) / (s))
+/* Decoder option (gpujpeg_decoder_set_option): region-of-interest decode. "X,Y,W,H" in pixels of the stream's full-size image, or "full" (default):
+ * no region. set_option checks the syntax only (four decimal integers, W, H >= 1; anything else returns GPUJPEG_ERROR and leaves the setting as it
+ * was); the option holds from the next decode call on and may be changed between two calls of a decoder.
+ * A decode call with a region returns the W x H image whose pixel (i, j) is pixel (X + i, Y + j) of the image the same decoder returns without
+ * the option -- same pixel format, colour space and dec_opt_channel_remap; output->param_image.width / height are W and H, output->data_size and
+ * the buffer layout those of a W x H image of that format (dec_opt_alignment_bytes applies to the region's line),
+ * gpujpeg_decoder_get_image_info keeps reporting the stream's own size. Planar output: plane c is the crop of plane c of the full result at
+ * (X / hs_c, Y / vs_c), ceil(W / hs_c) x ceil(H / vs_c) samples.
+ * Grey, packed 4:4:4 / 4:4:4:4 and planar 4:4:4 output take any rectangle inside the image, whatever the stream's sampling. Packed 4:2:2, planar
+ * 4:2:2 and planar 4:2:0 output need X (4:2:0: and Y) even, and W (H) even unless the region ends at the image's right (bottom) edge.
+ * Refused by the DECODE CALL with a message (the decoder stays usable): a region that is not inside the stream's image, those misalignments, a
+ * region together with dec_opt_flipped or with a dec_opt_scale other than 1.
+ * What a region call skips: on a stream with a restart interval whose segments are all there, only the restart segments that touch the region's
+ * cover (per component the smallest rectangle of 8x8 blocks, whole MCUs of an interleaved scan, that holds the samples the region needs) are
+ * entropy-decoded; otherwise (restart interval 0, missing segments) all of them. Either way only the cover's blocks are transformed, only W x H pixels
+ * are written and downloaded. Token mode serves a region call where it serves the full frame's packed 4:4:4 output (k_idct_tok_region_rgb444),
+ * every other configuration goes through the coefficient planes and cover-sized component planes; the bytes are the same. Batch calls decode the frames
+ * of a decoder that has a region one by one. After a region call gpujpeg_amd_decoder_read_planes returns the cover-sized component planes (cover
+ * of component c: see DESIGN 4.2) and gpujpeg_amd_decoder_read_coefficients the full planes, of which only the blocks of the entropy-decoded
+ * segments are this frame's. */
+#define GPUJPEG_AMD_DEC_OPT_REGION "dec_opt_region"
 /* Host-only: the table enc_opt_huffman=optimal builds for one class from symbol counts freq[256] (ITU T.81 Annex K.2: Figures K.1, K.3, K.4;
  * reserved code point, ties to the larger symbol value), code lengths limited to the largest L of 16 .. 10 whose table the library's
  * two-level decode tables take. Writes BITS (bits[1..16]) and HUFFVAL; returns L, or -1 when no count is non-zero. */
@@ -95,7 +116,7 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_optimal(const uint32_t freq[256], uint8
  *          k_scan_segments), [4] k_assemble (behind k_huffman only), [5] k_huffman_count (enc_opt_huffman=optimal; 0 otherwise)
  * decoder: [0] entropy decoder, [1] IDCT (fused path: postprocess included), [2] postprocess, [3] marker scan (k_markers; 0 when the host walked the stream),
  *          [4] not a duration: the IDCT side of that call -- 0 full size, 1 reduced size from the coefficient planes (k_idct_scaled), 2 reduced size from
- *          tokens (k_idct_tok_scaled_rgb444) */
+ *          tokens (k_idct_tok_scaled_rgb444), 3 region from the coefficient planes (k_idct_region), 4 region from tokens (k_idct_tok_region_rgb444) */
 GPUJPEG_API int gpujpeg_amd_encoder_get_kernel_times(struct gpujpeg_encoder* encoder, float ms[8]);
 GPUJPEG_API int gpujpeg_amd_decoder_get_kernel_times(struct gpujpeg_decoder* decoder, float ms[8]);
 
@@ -139,6 +160,10 @@ GPUJPEG_API int gpujpeg_amd_decoder_last_batch(struct gpujpeg_decoder* decoder, 
 GPUJPEG_API int gpujpeg_amd_decoder_get_path_counters(struct gpujpeg_decoder* decoder, long counters[3]);
 GPUJPEG_API int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* decoder, const uint8_t* streams, size_t stream_stride, const size_t* sizes,
                                                  int count, uint8_t* output, size_t output_stride, struct gpujpeg_image_parameters* param_image);
+/* what the last decode call did with dec_opt_region (taken from what was launched and from the device's selection result): out[0] mode: 0 = no
+ * region, 1 = region, entropy-decoded the selected restart segments only, 2 = region, every segment entropy-decoded (fallback); out[1] restart
+ * segments handed to the entropy decoder; out[2] 8x8 blocks the IDCT side transformed; out[3] segments in the stream */
+GPUJPEG_API int gpujpeg_amd_decoder_get_region_stats(struct gpujpeg_decoder* decoder, long out[4]);
 
 #ifdef __cplusplus
 }
