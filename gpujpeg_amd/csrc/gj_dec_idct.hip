@@ -371,11 +371,21 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_rgb444(const gj_geom g, con
 // The region's origin falls anywhere inside a block: a pixel row of a block is 24 bytes at any byte alignment, stored as dwords where the
 // address allows it and byte by byte with bounds checks at the region's edges.
 // ================================================================================================
-template <int CS_FROM, int CS_TO>
-__global__ __launch_bounds__(256, 4) void k_idct_tok_region_rgb444(const gj_geom g, const gj_geom gr, const gj_region rg, const int16_t* __restrict__ coefs,
+// BATCH (a batch of regions, gj_region::d_frames): frame blockIdx.z -- its records, tokens and pixels, its rectangle and cover from device memory; the grid
+// is the one of the largest cover of the batch, waves behind the frame's own cover carry no block.
+template <int CS_FROM, int CS_TO, bool BATCH>
+__global__ __launch_bounds__(256, 4) void k_idct_tok_region_rgb444(const gj_geom g, const gj_geom gr, const gj_region rg_in, const int16_t* __restrict__ coefs,
                                                                    const uint2* __restrict__ d_rec, const uint16_t* __restrict__ d_tok,
                                                                    const uint32_t tok_cap, const float* __restrict__ qtab, uint8_t* __restrict__ raw)
 {
+    gj_region rg_frame;
+    if (BATCH) {
+        const size_t z = blockIdx.z;
+        coefs += z * g.fb.coefs; d_rec += z * g.fb.rec; d_tok += z * g.fb.tok;
+        raw += z * g.fb.raw;
+        rg_frame = gj_region_of_frame(rg_in, rg_in.d_frames[z]);
+    }
+    const gj_region& rg = BATCH ? rg_frame : rg_in;
     __shared__ __attribute__((aligned(16))) uint8_t s_blk[256 * 128];
     __shared__ __attribute__((aligned(16))) uint16_t s_stage[4][GJ_TOK_STAGE];
     __shared__ __attribute__((aligned(8))) float s_q[2][3][64]; // (as in k_idct_tok_rgb444)
@@ -723,17 +733,22 @@ void gj_launch_idct_tok_region(const gj_dec_job* job, hipStream_t st)
 {
     const gj_geom& g = job->g;
     const int from = g.color_space_internal, to = g.color_space;
-    gj_idct_tok_region_t k = k_idct_tok_region_rgb444<GJ_CS_NONE, GJ_CS_NONE>;
-    if (from == to || from == GJ_CS_NONE || to == GJ_CS_NONE) k = k_idct_tok_region_rgb444<GJ_CS_NONE, GJ_CS_NONE>;
-    else if (from == GJ_CS_BT601_256 && to == GJ_CS_RGB) k = k_idct_tok_region_rgb444<GJ_CS_BT601_256, GJ_CS_RGB>;
-    else if (from == GJ_CS_BT601 && to == GJ_CS_RGB) k = k_idct_tok_region_rgb444<GJ_CS_BT601, GJ_CS_RGB>;
-    else if (from == GJ_CS_BT709 && to == GJ_CS_RGB) k = k_idct_tok_region_rgb444<GJ_CS_BT709, GJ_CS_RGB>;
-    else if (from == GJ_CS_RGB && to == GJ_CS_BT601_256) k = k_idct_tok_region_rgb444<GJ_CS_RGB, GJ_CS_BT601_256>;
     const gj_region& r = job->region;
-    const unsigned cbx = (unsigned)(r.bx1[0] - r.bx0[0]), cby = (unsigned)(r.by1[0] - r.by0[0]);
+    const bool batch = r.d_frames != nullptr;
+#define GJ_TOK_REGION_K(F, T) (batch ? k_idct_tok_region_rgb444<F, T, true> : k_idct_tok_region_rgb444<F, T, false>)
+    gj_idct_tok_region_t k = GJ_TOK_REGION_K(GJ_CS_NONE, GJ_CS_NONE);
+    if (from == to || from == GJ_CS_NONE || to == GJ_CS_NONE) k = GJ_TOK_REGION_K(GJ_CS_NONE, GJ_CS_NONE);
+    else if (from == GJ_CS_BT601_256 && to == GJ_CS_RGB) k = GJ_TOK_REGION_K(GJ_CS_BT601_256, GJ_CS_RGB);
+    else if (from == GJ_CS_BT601 && to == GJ_CS_RGB) k = GJ_TOK_REGION_K(GJ_CS_BT601, GJ_CS_RGB);
+    else if (from == GJ_CS_BT709 && to == GJ_CS_RGB) k = GJ_TOK_REGION_K(GJ_CS_BT709, GJ_CS_RGB);
+    else if (from == GJ_CS_RGB && to == GJ_CS_BT601_256) k = GJ_TOK_REGION_K(GJ_CS_RGB, GJ_CS_BT601_256);
+#undef GJ_TOK_REGION_K
+    // (a batch: the largest cover of its frames is the one of job->gs, gj_dec_job::region)
+    const unsigned cbx = batch ? (unsigned)job->gs.comp[0].blocks_x : (unsigned)(r.bx1[0] - r.bx0[0]);
+    const unsigned cby = batch ? (unsigned)job->gs.comp[0].blocks_y : (unsigned)(r.by1[0] - r.by0[0]);
     const unsigned waves = (cbx + 63u) / 64u * cby;
-    hipLaunchKernelGGL(k, dim3((waves + 3u) / 4u), dim3(256), 0, st, g, job->gs, r, job->d_coefs, (const uint2*)job->d_blkrec, (const uint16_t*)job->d_tok,
-                       job->tok_cap, job->d_qtabf, job->d_raw);
+    hipLaunchKernelGGL(k, dim3((waves + 3u) / 4u, 1, batch ? job->batch.count : 1u), dim3(256), 0, st, g, job->gs, r, job->d_coefs, (const uint2*)job->d_blkrec,
+                       (const uint16_t*)job->d_tok, job->tok_cap, job->d_qtabf, job->d_raw);
 }
 
 bool gj_is_uyvy422(const gj_geom& g)

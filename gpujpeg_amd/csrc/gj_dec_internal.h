@@ -292,6 +292,7 @@ __device__ __forceinline__ void gj_store_pixel(const gj_geom& g, uint8_t* __rest
 
 // region decode (gj_dec_region.hip): the compacted segment table of job->region (from job's table, which has been written), and the IDCT side
 void gj_launch_segment_select(const gj_dec_job* job, hipStream_t st);
+void gj_launch_segment_select_batch(const gj_dec_job* job, hipStream_t st); // (a batch of regions: every frame's table against its own cover)
 void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, bool tokens, gj_event_t* ev);
 void gj_launch_idct_tok_region(const gj_dec_job* job, hipStream_t st); // (gj_dec_idct.hip: beside k_idct_tok_rgb444, whose LDS helpers it shares)
 

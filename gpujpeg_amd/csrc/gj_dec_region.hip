@@ -11,6 +11,10 @@
 //
 // Every configuration can go this way; three-component 4:4:4 streams with non-interleaved scans and packed 3-byte output in token mode go
 // through k_idct_tok_region_rgb444 (gj_dec_idct.hip, beside k_idct_tok_rgb444 whose LDS helpers it shares) instead of the last three: same bytes.
+//
+// A BATCH of regions (gj_region::d_frames: one rectangle per frame, gpujpeg_amd_decoder_decode_batch_regions) runs the same code with blockIdx.z =
+// frame: k_segment_select_batch, k_idct_region_batch, k_postprocess_region_batch, k_copy_planes_region_batch and the batched instantiation of
+// k_idct_tok_region_rgb444 read their frame's rectangle and cover from device memory and share the bodies of the single-frame kernels.
 // (part of the decoder's device code, see gj_dec_internal.h for the map of the files)
 #include "gj_dec_internal.h"
 
@@ -115,14 +119,95 @@ void gj_launch_segment_select(const gj_dec_job* job, hipStream_t st)
                        job->d_seg_count, r.d_sel, stride, r.d_sel_count, r.h_sel_count);
 }
 
+// The selection of a batch of regions: frame blockIdx.z's table (at gj_frame_strides::seg words, entries counted by its marker scan) against ITS
+// cover. All frames are decoded behind ONE batch plan, which the host makes for the largest selection of every scan among them (r.sel_count): the
+// entries of scan c go to the fixed offset sum(sel_count[0 .. c)) of the frame's compacted table in stream order, and what the frame's own
+// selection leaves of the range is filled with null entries -- index 0xFFFFFFFF, length 0: a segment without blocks for both batchable entropy
+// decoders. One workgroup per frame walks the table in trips of its 1024 lanes and keeps the running count per scan (a ballot per scan and wave,
+// the waves' counts through LDS); what it found per scan goes to pinned host memory, where the host compares it with the frame's plan.
+__global__ __launch_bounds__(GJ_SEL_CHUNK) void k_segment_select_batch(const gj_geom g, const gj_region rb, const uint32_t* __restrict__ seg_pos,
+                                                                       const uint32_t* __restrict__ seg_len, const uint32_t* __restrict__ seg_index,
+                                                                       const int seg_count_max, const uint32_t* __restrict__ seg_count_ptr,
+                                                                       uint32_t* __restrict__ out, const uint32_t out_stride, uint32_t* __restrict__ h_found)
+{
+    __shared__ uint32_t s_wave[GJ_MAX_COMP][GJ_SEL_CHUNK / GJ_WAVE];
+    const size_t z = blockIdx.z;
+    seg_pos += z * g.fb.seg; seg_len += z * g.fb.seg; seg_index += z * g.fb.seg;
+    out += z * g.fb.seg;
+    h_found += z * GJ_MAX_COMP;
+    const gj_region_frame& r = rb.d_frames[z]; // (read where it lies: a copy indexed by component would live in scratch memory)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min((int)seg_count_ptr[z * (sizeof(gj_scan_summary) / 4)], seg_count_max);
+    uint32_t first[GJ_MAX_COMP], run[GJ_MAX_COMP];
+    {
+        uint32_t at = 0;
+#pragma unroll
+        for (int c = 0; c < GJ_MAX_COMP; c++) { first[c] = at; run[c] = 0; at += (uint32_t)rb.sel_count[c]; }
+    }
+    for (int base = 0; base < n; base += GJ_SEL_CHUNK) { // (n is the same in every lane: every lane makes every trip)
+        const int i = base + tid;
+        const uint32_t s = i < n ? seg_index[i] : 0xFFFFFFFFu;
+        const bool in = i < n && gj_segment_in_cover(g, r, (int)s);
+        const int sc = in ? gj_segment_scan(g, s) : -1;
+        uint32_t below = 0; // selected entries of this lane's scan in front of it inside its wave
+#pragma unroll
+        for (int c = 0; c < GJ_MAX_COMP; c++) {
+            const unsigned long long b = __ballot(sc == c);
+            if (lane == 0) s_wave[c][wave] = (uint32_t)__popcll(b);
+            if (sc == c) below = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < GJ_MAX_COMP; c++) {
+            uint32_t front = 0, all = 0;
+            for (int w = 0; w < GJ_SEL_CHUNK / GJ_WAVE; w++) {
+                if (w < wave) front += s_wave[c][w];
+                all += s_wave[c][w];
+            }
+            if (sc == c) {
+                const uint32_t k = run[c] + front + below;
+                if (k < (uint32_t)rb.sel_count[c] && first[c] + k < out_stride) { // (more than planned: another stream than the geometry's -- the host sees the count)
+                    out[first[c] + k] = seg_pos[i];
+                    out[out_stride + first[c] + k] = seg_len[i];
+                    out[2 * out_stride + first[c] + k] = s;
+                }
+            }
+            run[c] += all;
+        }
+        __syncthreads(); // (s_wave is rewritten by the next trip)
+    }
+#pragma unroll
+    for (int c = 0; c < GJ_MAX_COMP; c++)
+        for (uint32_t k = run[c] + (uint32_t)tid; k < (uint32_t)rb.sel_count[c] && first[c] + k < out_stride; k += GJ_SEL_CHUNK) {
+            out[first[c] + k] = 0u;
+            out[out_stride + first[c] + k] = 0u;
+            out[2 * out_stride + first[c] + k] = 0xFFFFFFFFu;
+        }
+#pragma unroll
+    for (int c = 0; c < GJ_MAX_COMP; c++)
+        if (tid == c) h_found[c] = run[c];
+}
+
+void gj_launch_segment_select_batch(const gj_dec_job* job, hipStream_t st)
+{
+    const gj_geom& g = job->g;
+    const gj_region& r = job->region;
+    const uint32_t stride = (uint32_t)g.segment_count + GJ_MAX_COMP;
+    hipLaunchKernelGGL(k_segment_select_batch, dim3(1, 1, job->batch.count), dim3(GJ_SEL_CHUNK), 0, st, g, r, job->d_seg_pos, job->d_seg_len, job->d_seg_index,
+                       job->seg_count, job->d_seg_count, r.d_sel, stride, r.h_sel_count);
+}
+
 // ================================================================================================
 // IDCT side
 // ================================================================================================
 // gr: the region image's geometry whose component planes are the COVER (gj_geom_init_region): blocks_x / blocks_y, data_width / data_height and
 // data_offset of every component describe the cover-sized planes. One lane per block of the cover; a block of the cover is block
 // (bx0 + bx, by0 + by) of the component's coefficient plane, which holds its blocks in raster order for every kind of scan.
-__global__ __launch_bounds__(256) void k_idct_region(const gj_geom g, const gj_geom gr, const gj_region r, const int16_t* __restrict__ coefs,
-                                                     const float* __restrict__ qtab, uint8_t* __restrict__ planes)
+// (BATCH: gr holds the planes of the largest cover of the batch, r is the frame's: lanes beyond the frame's own cover leave)
+// (R: gj_region, or a frame's gj_region_frame where it lies in device memory)
+template <bool BATCH, class R>
+__device__ __forceinline__ void gj_idct_region_body(const gj_geom& g, const gj_geom& gr, const R& r, const int16_t* __restrict__ coefs,
+                                                    const float* __restrict__ qtab, uint8_t* __restrict__ planes)
 {
     const unsigned gb = blockIdx.x * 256u + threadIdx.x;
     if (gb >= (unsigned)gr.block_count) return;
@@ -133,6 +218,7 @@ __global__ __launch_bounds__(256) void k_idct_region(const gj_geom g, const gj_g
     const gj_comp_geom& k = gr.comp[c];
     const unsigned lb = gb - (unsigned)(k.data_offset / 64);
     const unsigned by = lb / (unsigned)k.blocks_x, bx = lb - by * (unsigned)k.blocks_x;
+    if (BATCH && (bx >= (unsigned)(r.bx1[c] - r.bx0[c]) || by >= (unsigned)(r.by1[c] - r.by0[c]))) return;
     const gj_comp_geom& kf = g.comp[c];
     const unsigned fbx = (unsigned)r.bx0[c] + bx, fby = (unsigned)r.by0[c] + by;
     if (fbx >= (unsigned)kf.blocks_x || fby >= (unsigned)kf.blocks_y) return; // (cannot happen: the cover lies inside the component's grid)
@@ -152,16 +238,34 @@ __global__ __launch_bounds__(256) void k_idct_region(const gj_geom g, const gj_g
     for (int q = 0; q < 8; q++) *reinterpret_cast<uint2*>(dst + (size_t)q * k.data_width) = make_uint2(px[2 * q], px[2 * q + 1]);
 }
 
+__global__ __launch_bounds__(256) void k_idct_region(const gj_geom g, const gj_geom gr, const gj_region r, const int16_t* __restrict__ coefs,
+                                                     const float* __restrict__ qtab, uint8_t* __restrict__ planes)
+{
+    gj_idct_region_body<false>(g, gr, r, coefs, qtab, planes);
+}
+
+// frame blockIdx.z of a batch of regions (the planes of a frame take as many bytes as its coefficients take elements at most)
+__global__ __launch_bounds__(256) void k_idct_region_batch(const gj_geom g, const gj_geom gr, const gj_region rb, const int16_t* __restrict__ coefs,
+                                                           const float* __restrict__ qtab, uint8_t* __restrict__ planes)
+{
+    const size_t z = blockIdx.z;
+    gj_idct_region_body<true>(g, gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, planes + z * g.fb.coefs);
+}
+
 // sample of component c that pixel (x, y) of the REGION needs, in the cover-sized plane: pixel (r.x + x, r.y + y) of the stream's image
-__device__ __forceinline__ size_t gj_region_sample(const gj_comp_geom& k, const gj_region& r, const int c, const unsigned x, const unsigned y)
+template <class R>
+__device__ __forceinline__ size_t gj_region_sample(const gj_comp_geom& k, const R& r, const int c, const unsigned x, const unsigned y)
 {
     const unsigned sx = ((unsigned)r.x + x) / (unsigned)k.sub_h - (unsigned)r.bx0[c] * 8u;
     const unsigned sy = ((unsigned)r.y + y) / (unsigned)k.sub_v - (unsigned)r.by0[c] * 8u;
-    return k.data_offset + (size_t)min(sy, (unsigned)k.data_height - 1u) * k.data_width + min(sx, (unsigned)k.data_width - 1u); // (the cover holds them)
+    // (the cover holds them; its own size bounds them -- the planes of a frame of a batch are laid out for the largest cover, the frame's own may be smaller)
+    const unsigned cw = (unsigned)(r.bx1[c] - r.bx0[c]) * 8u, ch = (unsigned)(r.by1[c] - r.by0[c]) * 8u;
+    return k.data_offset + (size_t)min(sy, ch - 1u) * k.data_width + min(sx, cw - 1u);
 }
 
 // k_postprocess for a region: one lane per pixel of the W x H image (raw_width x height of gr)
-__global__ __launch_bounds__(256) void k_postprocess_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+template <class R>
+__device__ __forceinline__ void gj_postprocess_region_body(const gj_geom& gr, const R& r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
 {
     const unsigned W = (unsigned)gr.raw_width, H = (unsigned)gr.height;
     const unsigned pos = blockIdx.x * 256u + threadIdx.x;
@@ -176,8 +280,21 @@ __global__ __launch_bounds__(256) void k_postprocess_region(const gj_geom gr, co
     gj_store_pixel(gr, raw, W, H, x, y, pos, v);
 }
 
+__global__ __launch_bounds__(256) void k_postprocess_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    gj_postprocess_region_body(gr, r, planes, raw);
+}
+
+// frame blockIdx.z of a batch of regions: its rectangle, its cover planes (laid out for the largest cover: gr), its pixels
+__global__ __launch_bounds__(256) void k_postprocess_region_batch(const gj_geom gr, const gj_region rb, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    const size_t z = blockIdx.z;
+    gj_postprocess_region_body(gr, rb.d_frames[z], planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
+}
+
 // k_copy_planes_out for a region: plane c of the result is the crop of plane c at (r.x / sub_h, r.y / sub_v), k.width x k.height samples
-__global__ __launch_bounds__(256) void k_copy_planes_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+template <class R>
+__device__ __forceinline__ void gj_copy_planes_region_body(const gj_geom& gr, const R& r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
 {
     size_t dst_off = 0;
     for (int c = 0; c < gr.comp_count; c++) {
@@ -193,11 +310,43 @@ __global__ __launch_bounds__(256) void k_copy_planes_region(const gj_geom gr, co
     }
 }
 
+__global__ __launch_bounds__(256) void k_copy_planes_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    gj_copy_planes_region_body(gr, r, planes, raw);
+}
+
+__global__ __launch_bounds__(256) void k_copy_planes_region_batch(const gj_geom gr, const gj_region rb, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    const size_t z = blockIdx.z;
+    gj_copy_planes_region_body(gr, rb.d_frames[z], planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
+}
+
 // The IDCT side of a region call: cover blocks -> cover planes -> region pixels (+ channel remap on the region image).
 void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tokens, gj_event_t* ev)
 {
     const gj_geom& gr = job->gs;
     const gj_region& r = job->region;
+    if (r.d_frames != nullptr) { // a batch of regions: the same stages with blockIdx.z = frame, grids for the largest cover (gr)
+        const unsigned frames = job->batch.count;
+        if (tokens) {
+            gj_launch_idct_tok_region(job, st);
+            if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
+        } else {
+            hipLaunchKernelGGL(k_idct_region_batch, dim3(((unsigned)gr.block_count + 255) / 256, 1, frames), dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtabf,
+                               job->d_planes);
+            if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
+            if (gr.no_transform) {
+                const size_t n = (size_t)gr.comp[0].width * gr.comp[0].height;
+                hipLaunchKernelGGL(k_copy_planes_region_batch, dim3((unsigned)min((n + 255) / 256, (size_t)2048), 1, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
+            } else {
+                const unsigned n = (unsigned)gr.raw_width * (unsigned)gr.height;
+                hipLaunchKernelGGL(k_postprocess_region_batch, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
+            }
+        }
+        gj_debug_stage(job->tune.debug_sync != 0, st, "idct / postprocess (batch of regions)");
+        if (job->idct_path) *job->idct_path = tokens ? 4 : 3;
+        return;
+    }
     if (tokens) { // token mode: records and tokens of the cover's blocks -> region pixels (k_idct_tok_region_rgb444)
         gj_launch_idct_tok_region(job, st);
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));

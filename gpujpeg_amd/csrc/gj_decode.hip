@@ -45,9 +45,11 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     if ((job->batch.count > 1 || g.fb.sizes != nullptr) && (!gj_hip_decode_batchable(job) || g.fb.sizes == nullptr || job->batch.count > 65535u)) return -1;
     if (job->scale > 1 && ((job->scale != 2 && job->scale != 4 && job->scale != 8) || g.fb.sizes != nullptr || job->flipped)) return -1; // (single frames, no flip)
     const gj_region& rg = job->region;
-    // (a region call: a single frame, no scale, no flip; with a selection, room for the compacted table and its counts)
-    if (rg.on && (job->scale > 1 || g.fb.sizes != nullptr || job->batch.count > 1 || job->flipped ||
-                  (rg.select && (!rg.d_sel || !rg.d_sel_count || !rg.h_sel_count || g.restart_interval <= 0))))
+    // (a region call: no scale, no flip; with a selection, room for the compacted table and its counts. A single frame -- or a batch of regions,
+    // gj_region::d_frames: always with a selection, compacted tables at the frames' table stride, the found counts of every frame)
+    const bool rg_batch = rg.on && rg.d_frames != nullptr;
+    if (rg.on && (job->scale > 1 || job->flipped || (rg.select && (!rg.d_sel || !rg.h_sel_count || g.restart_interval <= 0)) ||
+                  (rg_batch ? (g.fb.sizes == nullptr || !rg.select || job->channel_remap) : (g.fb.sizes != nullptr || job->batch.count > 1 || (rg.select && !rg.d_sel_count)))))
         return -1;
     gj_hip_note_reset();
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[0], st));
@@ -89,13 +91,14 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     // bounded by what k_segment_select found in this stream's table
     gj_dec_job sel;
     if (rg.select) {
-        gj_launch_segment_select(job, st);
+        if (rg_batch) gj_launch_segment_select_batch(job, st);
+        else gj_launch_segment_select(job, st);
         sel = *job;
         const uint32_t stride = (uint32_t)g.segment_count + GJ_MAX_COMP;
         sel.d_seg_pos = rg.d_sel;
         sel.d_seg_len = rg.d_sel + stride;
         sel.d_seg_index = rg.d_sel + 2 * stride;
-        sel.d_seg_count = rg.d_sel_count;
+        sel.d_seg_count = rg_batch ? nullptr : rg.d_sel_count; // (a batch: every frame's compacted table is padded to the plan's entries)
         sel.seg_count = 0;
         for (int c = 0; c < g.scan_count && c < GJ_MAX_COMP; c++) sel.seg_count += rg.sel_count[c];
         sel.scan.valid = 0;

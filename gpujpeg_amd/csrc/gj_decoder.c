@@ -92,6 +92,11 @@ struct gpujpeg_decoder {
     uint32_t* d_sel_count; uint32_t* h_sel_count;  /* its entry count on the device; pinned: [0] the same, [1 + c] entries of scan c */
     gj_region plan_rg; bool plan_valid;            /* the region whose sel_count is in plan_rg (the count is a loop over the geometry's segments) */
     long region_stats[4];                          /* gpujpeg_amd_decoder_get_region_stats */
+    /* batches of regions (gpujpeg_amd_decoder_decode_batch_regions): one rectangle per frame */
+    uint32_t* b_sel; size_t b_sel_cap;             /* device: the compacted segment tables of one chunk of frames, laid out like b_seg */
+    gj_region_frame* b_rgn; size_t b_rgn_cap;      /* device: origin and covers of every frame of a call */
+    gj_region_frame* bh_rgn; size_t bh_rgn_cap;    /* pinned staging of the same */
+    uint32_t* bh_found; size_t bh_found_cap;       /* pinned: [frame][GJ_MAX_COMP] entries per scan the selection found */
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
@@ -235,6 +240,7 @@ int gpujpeg_decoder_destroy(struct gpujpeg_decoder* d)
     gj_hip_free(d->b_dsum); gj_hip_free(d->b_sizes); gj_hip_free(d->b_seg); gj_hip_free(d->b_scratch); gj_hip_free(d->b_coefs); gj_hip_free(d->b_planes); gj_hip_free(d->b_tok);
     gj_hip_free(d->b_rec); gj_hip_free(d->b_jpeg); gj_hip_free(d->b_raw); gj_hip_free(d->b_gather); gj_hip_free(d->b_scatter);
     gj_hip_host_free(d->bh_sum); gj_hip_host_free(d->bh_maxlen); gj_hip_host_free(d->bh_sizes);
+    gj_hip_free(d->b_sel); gj_hip_free(d->b_rgn); gj_hip_host_free(d->bh_rgn); gj_hip_host_free(d->bh_found);
     free(d);
     return 0;
 }
@@ -944,7 +950,92 @@ struct dec_batch {
     int first;                           /* 1: frame 0 went the ordinary way ahead of the batched launches */
     uint8_t* frame_done;
     bool host_io;                        /* copies from or into the caller's host memory have been queued */
+    /* a batch of regions (gpujpeg_amd_decoder_decode_batch_regions; origins == NULL: the decoder's own options hold for every frame) */
+    const int* origins; int rw, rh;      /* frame f: the rw x rh pixels at (origins[2f], origins[2f + 1]) */
+    bool planned;                        /* the rectangles have been checked against the streams' geometry; what follows is valid then */
+    int* plan;                           /* [count][GJ_MAX_COMP] restart segments of every scan that touch frame f's cover */
+    int plan_max[GJ_MAX_COMP];           /* the largest of them per scan */
+    gj_geom gs_max;                      /* geometry of the rw x rh image with the planes of the largest cover (per component the widest and the highest) */
+    gj_geom gs_one; gj_region rg_one;    /* the same for one of the frames, and its region */
+    struct gpujpeg_image_parameters pi_r;
+    int img_w, img_h;                    /* the streams' image, as the rectangles were checked against it */
+    long stats[4];                       /* gpujpeg_amd_decoder_get_region_stats of the call: sums over the frames */
+    bool unselected;                     /* a frame was entropy-decoded in full */
 };
+
+/* restart segments of scan sc with a block / an MCU inside the cover: what counting gj_hip_segment_in_cover over the scan's segments gives, in closed
+ * form -- a row of the cover is a run of cells, cell i belongs to segment i / restart_interval, and the rows' runs of segments follow each other
+ * (a segment that wraps from one row's end to the next row's start is counted once) */
+static int region_scan_segments(const gj_geom* g, const gj_region* r, int sc)
+{
+    const int gridx = g->interleaved ? g->mcu_count_x : g->comp[sc].blocks_x, ri = g->restart_interval;
+    const int x0 = g->interleaved ? r->mx0 : r->bx0[sc], x1 = g->interleaved ? r->mx1 : r->bx1[sc];
+    const int y0 = g->interleaved ? r->my0 : r->by0[sc], y1 = g->interleaved ? r->my1 : r->by1[sc];
+    if (ri <= 0 || gridx <= 0 || x0 >= x1) return 0;
+    long n = 0, prev_hi = -1;
+    for (int y = y0; y < y1; y++) {
+        long lo = ((long)y * gridx + x0) / ri;
+        const long hi = ((long)y * gridx + x1 - 1) / ri;
+        if (lo <= prev_hi) lo = prev_hi + 1;
+        if (hi >= lo) n += hi - lo + 1;
+        if (hi > prev_hi) prev_hi = hi;
+    }
+    return (int)n;
+}
+
+/* A batch of regions, once the coder is configured for the streams' geometry: every frame's rectangle checked against it (gj_geom_init_region; a
+ * refusal names the frame), its origin and covers into the pinned records, its selection counted; the largest cover and the largest selection
+ * per scan of the call. 0 or -1. Nothing has been launched and nothing of the caller's output has been written when this runs. */
+static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b)
+{
+    struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    b->planned = false;
+    if (gj_ensure_pinned_buffer((void**)&d->bh_rgn, &d->bh_rgn_cap, (size_t)b->count * sizeof(gj_region_frame), (size_t)b->count * sizeof(gj_region_frame) * 2) != 0) return -1;
+    memset(b->plan_max, 0, sizeof b->plan_max);
+    int wmax[GJ_MAX_COMP] = {0, 0, 0, 0}, hmax[GJ_MAX_COMP] = {0, 0, 0, 0};
+    for (int f = 0; f < b->count; f++) {
+        const int region[4] = {b->origins[2 * f], b->origins[2 * f + 1], b->rw, b->rh};
+        gj_region rg;
+        if (gj_geom_init_region(&b->gs_one, &rg, g, &c->param, &c->param_image, region, d->req_alignment, &b->pi_r) != 0) {
+            GJ_ERROR("Frame %d of the batch: the region %d,%d,%d,%d was refused!\n", f, region[0], region[1], region[2], region[3]);
+            return -1;
+        }
+        b->rg_one = rg;
+        gj_region_frame* rf = d->bh_rgn + f;
+        rf->x = rg.x; rf->y = rg.y;
+        memcpy(rf->bx0, rg.bx0, sizeof rf->bx0); memcpy(rf->by0, rg.by0, sizeof rf->by0);
+        memcpy(rf->bx1, rg.bx1, sizeof rf->bx1); memcpy(rf->by1, rg.by1, sizeof rf->by1);
+        rf->mx0 = rg.mx0; rf->my0 = rg.my0; rf->mx1 = rg.mx1; rf->my1 = rg.my1;
+        for (int i = 0; i < g->comp_count && i < GJ_MAX_COMP; i++) {
+            if (rg.bx1[i] - rg.bx0[i] > wmax[i]) wmax[i] = rg.bx1[i] - rg.bx0[i];
+            if (rg.by1[i] - rg.by0[i] > hmax[i]) hmax[i] = rg.by1[i] - rg.by0[i];
+        }
+        for (int sc = 0; sc < GJ_MAX_COMP; sc++) {
+            const int n = sc < g->scan_count && g->restart_interval > 0 ? region_scan_segments(g, &rg, sc) : 0;
+            b->plan[f * GJ_MAX_COMP + sc] = n;
+            if (n > b->plan_max[sc]) b->plan_max[sc] = n;
+        }
+    }
+    /* the planes of the largest cover: every frame's cover planes are laid out like this */
+    b->gs_max = b->gs_one;
+    uint64_t offset = 0;
+    for (int i = 0; i < g->comp_count && i < GJ_MAX_COMP; i++) {
+        gj_comp_geom* k = &b->gs_max.comp[i];
+        k->blocks_x = wmax[i];
+        k->blocks_y = hmax[i];
+        k->data_width = wmax[i] * 8;
+        k->data_height = hmax[i] * 8;
+        k->data_offset = offset;
+        offset += (uint64_t)k->data_width * k->data_height;
+    }
+    b->gs_max.data_size = offset;
+    b->gs_max.block_count = (int)(offset / 64);
+    b->img_w = c->param_image.width;
+    b->img_h = c->param_image.height;
+    b->planned = true;
+    return 0;
+}
 
 /* one frame of a batch the ordinary way: into the decoder's own buffer first -- a stream that is not what the caller promised (other dimensions) must
  * not be written over the neighbours' slots --, then into its slot. `ahead`: frame 0 in front of the batched launches, which tells what every
@@ -954,7 +1045,21 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
     struct gj_coder* c = &d->coder;
     struct gpujpeg_decoder_output o;
     gpujpeg_decoder_output_set_cuda_buffer(&o);
+    if (b->origins) { /* (a batch of regions: the single-frame region call with this frame's rectangle -- the definition of the frame's result) */
+        d->region_on = true;
+        d->region[0] = b->origins[2 * f]; d->region[1] = b->origins[2 * f + 1]; d->region[2] = b->rw; d->region[3] = b->rh;
+    }
     if (decoder_decode(d, (uint8_t*)(uintptr_t)(b->streams + (size_t)f * b->stream_stride), b->sizes[f], &o) != 0) return -1;
+    if (b->origins) {
+        if (d->region_stats[0] != 1) b->unselected = true;
+        for (int i = 1; i < 4; i++) b->stats[i] += d->region_stats[i];
+        /* (frame 0 ahead of everything: the streams' geometry is known now -- every rectangle is checked before a pixel goes to the caller's slots) */
+        if (ahead && batch_regions_plan(d, b) != 0) return -1;
+        if (!ahead && b->planned && (c->param_image.width != b->img_w || c->param_image.height != b->img_h)) {
+            GJ_ERROR("Frame %d of the batch is a %dx%d image, the others %dx%d!\n", f, c->param_image.width, c->param_image.height, b->img_w, b->img_h);
+            return -1;
+        }
+    }
     const size_t raw = dec_raw_size(d);
     if (ahead) {
         b->frame_raw = raw;
@@ -980,7 +1085,7 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
 
 /* The work buffers of one chunk of frames: what a frame takes of each (into B), how many frames fit a chunk (the return value, 0 on error),
  * the buffers and the job's pointers to them. */
-static int batch_chunk_buffers(struct gpujpeg_decoder* d, gj_dec_job* job, gj_batch* B, int n_all, size_t begin, size_t max_size)
+static int batch_chunk_buffers(struct gpujpeg_decoder* d, gj_dec_job* job, gj_batch* B, int n_all, size_t begin, size_t max_size, bool regions)
 {
     struct gj_coder* c = &d->coder;
     const gj_geom* g = &c->geom;
@@ -993,13 +1098,15 @@ static int batch_chunk_buffers(struct gpujpeg_decoder* d, gj_dec_job* job, gj_ba
     const bool tokens = gj_hip_decode_wants_tokens(&job->g, max_size, &d->tune) != 0;
     const size_t tok_frame = tokens ? (max_size * 4 + 64 + 63) & ~(size_t)63 : 0;                                            /* tokens */
     const size_t rec_frame = tokens ? ((size_t)g->block_count + 8 + 7) & ~(size_t)7 : 0;                                    /* records */
-    const bool planes = gj_hip_decode_uses_planes(g, job->use_fused) != 0;
-    const size_t frame_bytes = seg_frame * 4 + scratch_frame * 4 + coefs_frame * 2 + tok_frame * 2 + rec_frame * 8 + (planes ? coefs_frame : 0);
+    /* (a batch of regions: the cover planes of every configuration that does not take the token-fed region kernel, and a compacted table per frame) */
+    const bool planes = regions || gj_hip_decode_uses_planes(g, job->use_fused) != 0;
+    const size_t frame_bytes = seg_frame * 4 * (regions ? 2 : 1) + scratch_frame * 4 + coefs_frame * 2 + tok_frame * 2 + rec_frame * 8 + (planes ? coefs_frame : 0);
     int chunk = (int)(GJ_DEC_BATCH_BYTES / frame_bytes);
     if (chunk > chunk_cap) chunk = chunk_cap;
     if (chunk > n_all) chunk = n_all;
     if (chunk < 1) chunk = 1;
     if (gj_ensure_device_buffer((void**)&d->b_seg, &d->b_seg_cap, seg_frame * 4 * (size_t)chunk) != 0) return 0;
+    if (regions && gj_ensure_device_buffer((void**)&d->b_sel, &d->b_sel_cap, seg_frame * 4 * (size_t)chunk) != 0) return 0;
     if (gj_ensure_device_buffer((void**)&d->b_scratch, &d->b_scratch_cap, scratch_frame * 4 * (size_t)chunk + 64) != 0) return 0;
     if (gj_ensure_device_buffer((void**)&d->b_coefs, &d->b_coefs_cap, coefs_frame * 2 * (size_t)chunk) != 0) return 0;
     if (planes && gj_ensure_device_buffer((void**)&d->b_planes, &d->b_planes_cap, coefs_frame * (size_t)chunk) != 0) return 0;
@@ -1035,8 +1142,10 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     const gj_geom* g = &c->geom;
     const int first = b->first, count = b->count, n_all = count - first;
     const size_t* sizes = b->sizes;
-    /* (a reduced-size decode and a region decode go frame by frame: their kernels do not know the frame dimension) */
-    bool batched = d->scale <= 1 && !d->region_on && d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
+    /* (a reduced-size decode and the region of the decoder's own option go frame by frame: their kernels do not know the frame dimension; a batch
+     * of regions -- b->origins -- has kernels that do) */
+    const bool regions = b->origins != NULL;
+    bool batched = d->scale <= 1 && (regions || !d->region_on) && d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
                    (b->streams_on_device ? (b->stream_stride & 15u) == 0 : true) && d->tab2_ok;
     size_t max_size = 0;
     for (int f = first; f < count; f++) {
@@ -1048,13 +1157,23 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     d->call_region = false;
     const struct gj_reader_result* r = &d->hdr_cache_r;
     if (decoder_configure(d, &r->param, &r->param_image) != 0) return -1; /* (the geometry of the cached header, whatever the coder was last set up for) */
-    if (b->output_stride < g->raw_size || (b->frame_raw != 0 && b->frame_raw != g->raw_size)) {
+    /* a batch of regions: the rectangles against the cached header's geometry, unless frame 0 went ahead and they have been checked against its own.
+     * A rectangle the CACHED header refuses may be one the streams' own header takes (an older sequence's cache): frame 0 goes ahead and decides. */
+    if (regions && !b->planned && batch_regions_plan(d, b) != 0) return first == 0 && !force_first ? 1 : -1;
+    const size_t frame_raw = regions ? (size_t)b->gs_one.raw_size : (size_t)g->raw_size;
+    if (b->output_stride < frame_raw || (b->frame_raw != 0 && b->frame_raw != frame_raw)) {
         /* the cached header is an OLDER sequence's (a larger image than the caller's slots, ADVICE r4: this used to fail the call): these
          * streams are strangers to it */
         return first == 0 && !force_first ? 1 : 0;
     }
-    b->frame_raw = g->raw_size;
+    b->frame_raw = frame_raw;
     geom_take_tables(&c->geom, r);
+    if (regions) { /* (what a region call leaves for dec_raw_size / dec_out_param_image and what dec_job_base reads) */
+        d->call_region = true;
+        d->geom_s = b->gs_one;
+        d->pi_s = b->pi_r;
+        d->rg = b->rg_one;
+    }
     gj_dec_job job;
     dec_job_base(d, true, &job);
     job.seg_count = g->segment_count;
@@ -1098,9 +1217,30 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     if (gj_hip_memcpy_h2d(d->b_sizes, d->bh_sizes, sizes_bytes, c->stream) != 0) return -1;
     gj_batch B;
     memset(&B, 0, sizeof B);
-    const int chunk = batch_chunk_buffers(d, &job, &B, n_all, begin, max_size);
+    const int chunk = batch_chunk_buffers(d, &job, &B, n_all, begin, max_size, regions);
     if (chunk < 1) return -1;
     const size_t S = (size_t)g->segment_count + GJ_MAX_COMP;
+    if (regions) {
+        /* the per-frame records, uploaded once; ONE selection plan for all frames: the largest selection of every scan (gj_region) */
+        const size_t rgn_bytes = (size_t)count * sizeof(gj_region_frame), found_bytes = (size_t)count * GJ_MAX_COMP * sizeof(uint32_t);
+        if (gj_ensure_device_buffer((void**)&d->b_rgn, &d->b_rgn_cap, rgn_bytes) != 0) return -1;
+        if (gj_ensure_pinned_buffer((void**)&d->bh_found, &d->bh_found_cap, found_bytes, found_bytes * 2) != 0) return -1;
+        if (gj_hip_memcpy_h2d(d->b_rgn, d->bh_rgn, rgn_bytes, c->stream) != 0) return -1;
+        memset(d->bh_found, 0xFF, found_bytes);
+        job.gs = b->gs_max;
+        job.region.select = 1;
+        job.region.x = job.region.y = 0;
+        memcpy(job.region.sel_count, b->plan_max, sizeof job.region.sel_count);
+        job.region.d_sel = d->b_sel;
+        job.region.d_sel_count = NULL;
+        job.seg_count = g->segment_count; /* (entries of a frame's table at most; gj_hip_decode hands the entropy decoders the plan's) */
+        d->last_idct_path = 0;
+        job.idct_path = &d->last_idct_path;
+        for (int sc = 0; sc < g->scan_count && sc < GJ_MAX_COMP; sc++) { /* (the selected share of every scan's bytes: it only sizes the batches) */
+            const int all = g->interleaved ? g->segment_count : g->comp[sc].segment_count;
+            if (all > 0) job.scan_bytes[sc] = (uint32_t)((uint64_t)job.scan_bytes[sc] * (uint64_t)b->plan_max[sc] / (uint64_t)all);
+        }
+    }
     B.jpeg = d_stride;
     B.raw = b->d_out_stride;
     B.maxlen = (uint32_t)max_chunks;
@@ -1110,11 +1250,17 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     job.g.fb.tok = B.tok;
     job.g.fb.rec = B.rec;
     job.g.fb.seg = B.seg;
+    if (regions) job.gs.fb = job.g.fb; /* (the pixel kernels of a batch of regions take gs only) */
     for (int a = 0; a < n_all; a += chunk) {
         B.count = (uint32_t)(n_all - a < chunk ? n_all - a : chunk);
         B.d_sizes = d->b_sizes + a;
         job.batch = B;
         job.g.fb.sizes = B.d_sizes;
+        if (regions) {
+            job.gs.fb.sizes = B.d_sizes;
+            job.region.d_frames = d->b_rgn + first + a;
+            job.region.h_sel_count = d->bh_found + (size_t)(first + a) * GJ_MAX_COMP;
+        }
         job.d_jpeg = d_streams + (size_t)a * d_stride;
         job.d_raw = b->d_out + (size_t)(first + a) * b->d_out_stride;
         job.d_seg_count = &d->b_dsum[a].segment_count;
@@ -1133,12 +1279,21 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         GJ_ERROR("Decoder failed: %s\n", gj_hip_last_error());
         return -1;
     }
+    if (regions) c->kernel_ms[4] = (float)d->last_idct_path; /* (which IDCT side the batched launches took, gpujpeg_amd_ext.h) */
     /* every frame's summary: was the stream what the launch assumed? */
     int accepted = 0;
     for (int i = 0; i < n_all; i++) {
         gj_scan_summary* su = d->bh_sum + i;
         summary_take_maxlen(su, d->bh_maxlen + (size_t)i * max_chunks, d->maxlen_parts);
         if (!spec_summary_ok(d, su, g)) continue;
+        if (regions) { /* did the selection find in this stream's table what the plan took from the geometry? (cannot fail for a stream the rule accepts) */
+            const int f = first + i;
+            if (memcmp(d->bh_found + (size_t)f * GJ_MAX_COMP, b->plan + (size_t)f * GJ_MAX_COMP, GJ_MAX_COMP * sizeof(uint32_t)) != 0) continue;
+            const gj_region_frame* rf = d->bh_rgn + f;
+            for (int sc = 0; sc < GJ_MAX_COMP; sc++) b->stats[1] += b->plan[f * GJ_MAX_COMP + sc];
+            for (int k = 0; k < g->comp_count && k < GJ_MAX_COMP; k++) b->stats[2] += (long)(rf->bx1[k] - rf->bx0[k]) * (rf->by1[k] - rf->by0[k]);
+            b->stats[3] += (long)su->segment_count;
+        }
         b->frame_done[first + i] = 1;
         accepted++;
         remember_summary(d, su);
@@ -1147,18 +1302,19 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     return accepted == 0 && first == 0 && !force_first ? 1 : 0;
 }
 
-int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count,
-                                     uint8_t* output, size_t output_stride, struct gpujpeg_image_parameters* param_image)
+/* the batch call proper; origins (with width, height): a batch of regions */
+static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count, const int* origins,
+                        int width, int height, uint8_t* output, size_t output_stride, struct gpujpeg_image_parameters* param_image)
 {
-    if (!d || !streams || !sizes || count < 1 || !output) return -1;
     struct gj_coder* c = &d->coder;
     struct dec_batch b = {.streams = streams, .stream_stride = stream_stride, .sizes = sizes, .count = count, .output_stride = output_stride,
-                          .d_out = output, .d_out_stride = output_stride};
+                          .d_out = output, .d_out_stride = output_stride, .origins = origins, .rw = width, .rh = height};
     b.streams_on_device = gj_hip_is_device_ptr(streams) != 0;
     b.out_on_device = gj_hip_is_device_ptr(output) != 0;
     int rc = -1;
     b.frame_done = calloc((size_t)count, 1);
-    if (!b.frame_done) return -1;
+    if (origins) b.plan = calloc((size_t)count * GJ_MAX_COMP, sizeof(int));
+    if (!b.frame_done || (origins && !b.plan)) goto out;
     /* The header cache is what a batch launches on: frame 0 goes the ordinary way when there is none (or when it has to). A second pass, with
      * force_first, when the cached header turned out to be another sequence's: frame 0 replaces the cache, then the batch. */
     for (int pass = 0; pass < 2; pass++) {
@@ -1172,6 +1328,15 @@ int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* d, const uint8_t* s
         if (again < 0) goto out;
         if (again == 0) break;
         b.frame_raw = 0;
+        b.planned = false;
+    }
+    /* a batch of regions none of whose rectangles has been looked at (nothing has been launched: no header to launch on that these streams share,
+     * or a decoder state without batched launches): frame 0 the ordinary way tells the streams' geometry, and every rectangle is checked against it
+     * before the first pixel goes to the caller's slots */
+    if (origins && !b.planned && b.first == 0) {
+        if (batch_decode_one(d, &b, 0, true) != 0) goto out;
+        b.frame_done[0] = 1;
+        b.first = 1;
     }
     /* whatever is left: the ordinary call, frame by frame */
     d->b_last_batched = 0;
@@ -1191,10 +1356,50 @@ int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* d, const uint8_t* s
         if (gj_hip_lane_end(down, c->stream, c->timers.lane_out) != 0 || copies != 0 || gj_hip_stream_sync(c->stream) != 0) goto out;
     }
     if (param_image) *param_image = dec_out_param_image(d);
+    if (origins) { /* (gpujpeg_amd_decoder_get_region_stats of the call: sums over its frames) */
+        b.stats[0] = b.unselected ? 2 : 1;
+        memcpy(d->region_stats, b.stats, sizeof d->region_stats);
+    }
     rc = 0; /* (c->frames counts the frames TIMED with perf_stats, src/gpujpeg_common.c:2238-2254: a batch adds none) */
 out:
     if (rc != 0 && b.host_io) gj_hip_stream_sync(c->stream); /* (what is queued on the stream must not read the caller's streams or write its frames after the error has left) */
     free(b.frame_done);
+    free(b.plan);
+    return rc;
+}
+
+int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count,
+                                     uint8_t* output, size_t output_stride, struct gpujpeg_image_parameters* param_image)
+{
+    if (!d || !streams || !sizes || count < 1 || !output) return -1;
+    return decode_batch(d, streams, stream_stride, sizes, count, NULL, 0, 0, output, output_stride, param_image);
+}
+
+/* A batch of regions: one width x height rectangle per frame, each at its own origin. The decoder's own dec_opt_region is neither read nor changed
+ * (frames that go the ordinary way borrow the option's fields for their call). */
+int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count,
+                                             const int* origins, int width, int height, uint8_t* output, size_t output_stride,
+                                             struct gpujpeg_image_parameters* param_image)
+{
+    if (!d || !streams || !sizes || count < 1 || !output || !origins) return -1;
+    if (width < 1 || height < 1) {
+        GJ_ERROR("A batch of regions needs a width and a height of at least 1 (given: %d x %d)!\n", width, height);
+        return -1;
+    }
+    if (d->scale > 1) {
+        GJ_ERROR("A batch of regions is not available together with " GPUJPEG_AMD_DEC_OPT_SCALE "=1/%d!\n", d->scale);
+        return -1;
+    }
+    if (d->flipped) {
+        GJ_ERROR("A batch of regions is not available together with " GPUJPEG_DEC_OPT_FLIPPED_BOOL "!\n");
+        return -1;
+    }
+    const bool own_on = d->region_on;
+    int own[4];
+    memcpy(own, d->region, sizeof own);
+    const int rc = decode_batch(d, streams, stream_stride, sizes, count, origins, width, height, output, output_stride, param_image);
+    d->region_on = own_on;
+    memcpy(d->region, own, sizeof own);
     return rc;
 }
 

@@ -157,6 +157,9 @@ class Library:
                                                                 C.POINTER(ImageParameters)]
         if hasattr(L, "gpujpeg_amd_decoder_decode_batch"):
             L.gpujpeg_amd_decoder_decode_batch.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, vp, C.c_size_t, C.POINTER(ImageParameters)]
+        if hasattr(L, "gpujpeg_amd_decoder_decode_batch_regions"):
+            L.gpujpeg_amd_decoder_decode_batch_regions.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
+                                                                   vp, C.c_size_t, C.POINTER(ImageParameters)]
 
     # ---- developer settings (include/gpujpeg_amd_ext.h: gpujpeg_amd_tuning) ----
     def tuning(self, setting):
@@ -420,6 +423,40 @@ class Decoder:
         rc = self.lib.L.gpujpeg_amd_decoder_decode_batch(self.h, base, in_stride, csz, n, out.ctypes.data, bound, C.byref(pi))
         if rc != 0:
             raise RuntimeError(f"gpujpeg_amd_decoder_decode_batch failed ({rc})")
+        raw = self.lib.image_size(pi)
+        return [out[i * bound:i * bound + raw].copy() for i in range(n)], pi
+
+    def decode_batch_regions(self, streams, origins, width, height, device_out=None, out_stride=None, device_in=None, in_stride=None, sizes=None):
+        """gpujpeg_amd_decoder_decode_batch_regions: decode_batch with one crop per frame -- frame f is the width x height pixels at origins[f] = (x, y)
+        of stream f's image. streams / device_in, in_stride, sizes and device_out, out_stride as for decode_batch; without device_out the crops come
+        back as a list of numpy arrays. Returns (pixels or None, ImageParameters)."""
+        if device_in is None:
+            sizes = [int(x.size) for x in streams]
+            in_stride = (max(sizes) + 64 + 15) & ~15
+            buf = np.zeros(in_stride * len(sizes), np.uint8)
+            for i, x in enumerate(streams):
+                buf[i * in_stride:i * in_stride + x.size] = x
+            self._keep = buf
+            base = buf.ctypes.data
+        else:
+            base = int(device_in)
+        n = len(sizes)
+        if len(origins) != n:
+            raise ValueError("decode_batch_regions needs one origin per stream")
+        csz = (C.c_size_t * n)(*sizes)
+        org = (C.c_int * (2 * n))(*[int(v) for xy in origins for v in xy])
+        pi = ImageParameters()
+        call = self.lib.L.gpujpeg_amd_decoder_decode_batch_regions
+        if device_out is not None:
+            rc = call(self.h, base, in_stride, csz, n, org, int(width), int(height), int(device_out), out_stride, C.byref(pi))
+            if rc != 0:
+                raise RuntimeError(f"gpujpeg_amd_decoder_decode_batch_regions failed ({rc})")
+            return None, pi
+        bound = max(int(width), 1) * max(int(height), 1) * 4 + 4096 * max(int(height), 1)  # (room for any format and line alignment up to 4 KiB)
+        out = np.empty(bound * n, np.uint8)
+        rc = call(self.h, base, in_stride, csz, n, org, int(width), int(height), out.ctypes.data, bound, C.byref(pi))
+        if rc != 0:
+            raise RuntimeError(f"gpujpeg_amd_decoder_decode_batch_regions failed ({rc})")
         raw = self.lib.image_size(pi)
         return [out[i * bound:i * bound + raw].copy() for i in range(n)], pi
 

@@ -260,6 +260,7 @@ typedef struct gj_scan_deferred {
 
 /* Region-of-interest decode (dec_opt_region): the W x H pixels at (x, y) of the stream's image. The COVER of the region is, per component, the
  * smallest rectangle of 8x8 blocks -- whole MCUs of an interleaved scan -- that holds every sample the region's pixels need. */
+struct gj_region_frame;
 typedef struct gj_region {
     int on;                        /* 1: this call decodes a region */
     int select;                    /* 1: only the restart segments that touch the cover are entropy-decoded (k_segment_select compacts the table) */
@@ -270,7 +271,20 @@ typedef struct gj_region {
     uint32_t* d_sel;               /* select: the compacted table, three arrays of (g.segment_count + GJ_MAX_COMP) words: pos | len | index */
     uint32_t* d_sel_count;         /* select: device word, entries of the compacted table (what the entropy decoders bound their work with) */
     uint32_t* h_sel_count;         /* select: pinned host words written by k_segment_select: [0] entries of the compacted table, [1 + c] of scan c */
+    /* a batch of regions (gj_dec_job::batch together with region.on: gpujpeg_amd_decoder_decode_batch_regions) -- one w x h for all frames, the
+     * origin and with it the cover PER FRAME: x, y, the covers and the MCU rectangle above are not used, frame f's are d_frames[f]. select is 1.
+     * sel_count[c] is the LARGEST selection of scan c among the frames: frame f's compacted table (d_sel + f x gj_frame_strides::seg words, laid out
+     * like the frame's segment table) holds its own selection of scan c from entry sum(sel_count[0 .. c)) on and null entries (index 0xFFFFFFFF,
+     * length 0: a segment without blocks for the entropy decoders) up to the next scan's, so that ONE batch plan serves every frame. d_sel_count is
+     * not used (every compacted table has sum(sel_count) entries); h_sel_count holds GJ_MAX_COMP words per frame: the entries found per scan. */
+    const struct gj_region_frame* d_frames; /* device memory, [gj_batch::count]; NULL: a single frame */
 } gj_region;
+/* what gj_region carries per frame of a batch of regions */
+typedef struct gj_region_frame {
+    int x, y;
+    int bx0[GJ_MAX_COMP], by0[GJ_MAX_COMP], bx1[GJ_MAX_COMP], by1[GJ_MAX_COMP];
+    int mx0, my0, mx1, my1;
+} gj_region_frame;
 /* the predicate of the selection (gj_device.h: gj_segment_in_cover) for host code: does restart segment s have a block / an MCU inside the cover? */
 GJ_HIP_API int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s);
 
@@ -321,7 +335,9 @@ typedef struct gj_dec_job {
     int* idct_path;                /* host, may be NULL: which IDCT side ran -- 0 full size, 1 k_idct_scaled, 2 k_idct_tok_scaled_rgb444, 3 k_idct_region, 4 k_idct_tok_region_rgb444 */
     /* region decode (dec_opt_region, region.on): the entropy decoders work on g -- with region.select on the compacted table --, the IDCT side
      * transforms the cover's blocks -- from tokens straight into d_raw, or into cover-sized planes in d_planes from which the region's pixels go to d_raw --; gs is the geometry of the W x H image
-     * with the cover's planes (gj_geom_init_region). Single frames, no scale, no flip. */
+     * with the cover's planes (gj_geom_init_region). No scale, no flip. A single frame, or (region.d_frames) a batch of frames with one
+     * rectangle each: gs then holds the planes of the LARGEST cover of the batch -- per component the widest and the highest one --, every frame's
+     * cover planes are laid out like that (gj_frame_strides::coefs bytes apart in d_planes) and gs.fb = g.fb. */
     gj_region region;
 } gj_dec_job;
 /* 1 when gj_hip_decode takes a batch (gj_dec_job::batch.count > 1) of this job's configuration */

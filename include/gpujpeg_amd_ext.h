@@ -102,7 +102,7 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
  * entropy-decoded; otherwise (restart interval 0, missing segments) all of them. Either way only the cover's blocks are transformed, only W x H pixels
  * are written and downloaded. Token mode serves a region call where it serves the full frame's packed 4:4:4 output (k_idct_tok_region_rgb444),
  * every other configuration goes through the coefficient planes and cover-sized component planes; the bytes are the same. Batch calls decode the frames
- * of a decoder that has a region one by one. After a region call gpujpeg_amd_decoder_read_planes returns the cover-sized component planes (cover
+ * of a decoder that has a region one by one (one crop per frame behind batched launches: gpujpeg_amd_decoder_decode_batch_regions). After a region call gpujpeg_amd_decoder_read_planes returns the cover-sized component planes (cover
  * of component c: see DESIGN 4.2) and gpujpeg_amd_decoder_read_coefficients the full planes, of which only the blocks of the entropy-decoded
  * segments are this frame's. */
 #define GPUJPEG_AMD_DEC_OPT_REGION "dec_opt_region"
@@ -116,7 +116,8 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_optimal(const uint32_t freq[256], uint8
  *          k_scan_segments), [4] k_assemble (behind k_huffman only), [5] k_huffman_count (enc_opt_huffman=optimal; 0 otherwise)
  * decoder: [0] entropy decoder, [1] IDCT (fused path: postprocess included), [2] postprocess, [3] marker scan (k_markers; 0 when the host walked the stream),
  *          [4] not a duration: the IDCT side of that call -- 0 full size, 1 reduced size from the coefficient planes (k_idct_scaled), 2 reduced size from
- *          tokens (k_idct_tok_scaled_rgb444), 3 region from the coefficient planes (k_idct_region), 4 region from tokens (k_idct_tok_region_rgb444) */
+ *          tokens (k_idct_tok_scaled_rgb444), 3 region from the coefficient planes (k_idct_region), 4 region from tokens (k_idct_tok_region_rgb444);
+ *          gpujpeg_amd_decoder_decode_batch_regions leaves the side its batched launches took here (3 or 4) and no durations */
 GPUJPEG_API int gpujpeg_amd_encoder_get_kernel_times(struct gpujpeg_encoder* encoder, float ms[8]);
 GPUJPEG_API int gpujpeg_amd_decoder_get_kernel_times(struct gpujpeg_decoder* decoder, float ms[8]);
 
@@ -164,6 +165,22 @@ GPUJPEG_API int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* decoder
  * region, 1 = region, entropy-decoded the selected restart segments only, 2 = region, every segment entropy-decoded (fallback); out[1] restart
  * segments handed to the entropy decoder; out[2] 8x8 blocks the IDCT side transformed; out[3] segments in the stream */
 GPUJPEG_API int gpujpeg_amd_decoder_get_region_stats(struct gpujpeg_decoder* decoder, long out[4]);
+/* A batch of regions: gpujpeg_amd_decoder_decode_batch with one crop per frame -- frame f is the `width` x `height` pixels at
+ * (origins[2f], origins[2f + 1]) of stream f's image. The bytes at output + f * output_stride are exactly what gpujpeg_decoder_decode of this decoder
+ * returns for stream f with dec_opt_region = "X_f,Y_f,width,height" (every output format and colour space, dec_opt_alignment_bytes, the planar crop
+ * rules); param_image and the frame size are those of a width x height image. streams, stream_stride, sizes, output (device or host memory) and
+ * output_stride as for gpujpeg_amd_decoder_decode_batch. The decoder's own dec_opt_region is neither read nor changed by the call.
+ * Every configuration the full-frame batch covers goes through batched launches: the frame is a grid dimension of the region kernels, every frame's
+ * restart segments are selected against its own cover, and the host waits once per chunk of frames. Restart interval 0, a stream with another header
+ * or with damaged markers: that frame goes through the single-frame region call inside this one.
+ * Refused with a message, -1 returned, nothing of `output` written, the decoder usable as before: width or height < 1; an origin whose rectangle
+ * the single-frame call would refuse (outside the image, off the output format's sampling grid: the message names the frame); a dec_opt_scale other
+ * than 1; dec_opt_flipped.
+ * Afterwards gpujpeg_amd_decoder_last_batch counts the frames as for decode_batch, and gpujpeg_amd_decoder_get_region_stats gives out[1..3] as sums
+ * over the call's frames, out[0] = 1 when every frame was entropy-decoded from its selected segments only, else 2. */
+GPUJPEG_API int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder* decoder, const uint8_t* streams, size_t stream_stride,
+                                                         const size_t* sizes, int count, const int* origins, int width, int height, uint8_t* output,
+                                                         size_t output_stride, struct gpujpeg_image_parameters* param_image);
 
 #ifdef __cplusplus
 }
