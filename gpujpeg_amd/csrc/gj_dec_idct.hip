@@ -798,7 +798,7 @@ void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_to
         const gj_geom& gs = job->gs;
         const bool done = gj_launch_idct_scaled(job, st, idct_tok != nullptr);
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
-        if (!done) gj_launch_postprocess(gs, job, st, 1u);
+        if (!done) gj_launch_postprocess(gs, job, st, job->batch.count > 1 ? job->batch.count : 1u); // (a batch: gs.fb = g.fb)
         gj_debug_stage(job->tune.debug_sync != 0, st, "idct / postprocess (reduced size)");
         if (job->channel_remap) {
             const unsigned n = (unsigned)gs.width * (unsigned)gs.height;

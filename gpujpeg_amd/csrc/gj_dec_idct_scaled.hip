@@ -16,6 +16,8 @@
 //   k_idct_tok_scaled_rgb444<N, ..>    from the entropy decoder's tokens and block records to packed 3-byte pixels, one lane per block position
 //                                      (the configuration of k_idct_tok_rgb444: three components 4:4:4, non-interleaved scans). N = 1 reads the
 //                                      records only: the DC term is in them.
+// Both know the frame dimension of a batch (blockIdx.z, gj_frame_strides): frame z's reduced planes lie z x gj_frame_strides::coefs bytes into
+// d_planes -- where k_postprocess / k_copy_planes_out look for them with gs.fb = g.fb --, its pixels z x gj_frame_strides::raw bytes into d_raw.
 // (part of the decoder's device code, see gj_dec_internal.h for the map of the files)
 #include "gj_dec_internal.h"
 
@@ -89,6 +91,10 @@ template <int N>
 __global__ __launch_bounds__(256) void k_idct_scaled(const gj_geom g, int16_t* __restrict__ coefs, const uint16_t* __restrict__ qtab,
                                                      uint8_t* __restrict__ planes, const int zero)
 {
+    if (g.fb.sizes != nullptr) { // frame blockIdx.z of a batch (the reduced planes of a frame lie as far apart as the full-size ones: k_postprocess)
+        coefs += (size_t)blockIdx.z * g.fb.coefs;
+        planes += (size_t)blockIdx.z * g.fb.coefs;
+    }
     const unsigned gb = blockIdx.x * 256u + threadIdx.x;
     if (gb >= (unsigned)g.block_count) return;
     int c = 0;
@@ -153,6 +159,12 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_scaled_rgb444(const gj_geom
                                                                     const uint16_t* __restrict__ qtab, uint8_t* __restrict__ raw, const int out_w,
                                                                     const int out_h, const int out_padding)
 {
+    if (g.fb.sizes != nullptr) { // frame blockIdx.z of a batch (tok_cap is a frame's; a reduced frame need not end on a dword: the stores below take
+                                 // their alignment from the row's address, so from the frame's own base)
+        const size_t z = blockIdx.z;
+        coefs += z * g.fb.coefs; d_rec += z * g.fb.rec; d_tok += z * g.fb.tok;
+        raw += z * g.fb.raw;
+    }
     constexpr int ROWB = 64 * 3 * N;                                               // bytes of a wave's blocks in one pixel row
     __shared__ __attribute__((aligned(16))) uint16_t s_stage[4][N > 1 ? GJ_TOK_STAGE : 8];
     __shared__ __attribute__((aligned(16))) uint32_t s_tile[4][N][ROWB / 4 + 1];   // (+ 1: the dword past the end that the shifted read touches)
@@ -317,15 +329,16 @@ bool gj_launch_idct_scaled(const gj_dec_job* job, hipStream_t st, const bool tok
 {
     const gj_geom& g = job->g;
     const int N = 8 / job->scale;
+    const unsigned frames = job->batch.count > 1 ? job->batch.count : 1u; // (a batch: blockIdx.z = frame)
     if (tokens) {
         const gj_idct_tok_scaled_t k = N == 4 ? gj_idct_tok_scaled_kernel<4>(g) : N == 2 ? gj_idct_tok_scaled_kernel<2>(g) : gj_idct_tok_scaled_kernel<1>(g);
         const unsigned nb = (unsigned)(g.comp[0].blocks_x * g.comp[0].blocks_y);
-        hipLaunchKernelGGL(k, dim3((nb + 255) / 256), dim3(256), 0, st, g, job->d_coefs, (const uint2*)job->d_blkrec, (const uint16_t*)job->d_tok, job->tok_cap,
-                           job->d_qtab, job->d_raw, job->gs.width, job->gs.height, job->gs.width_padding);
+        hipLaunchKernelGGL(k, dim3((nb + 255) / 256, 1, frames), dim3(256), 0, st, g, job->d_coefs, (const uint2*)job->d_blkrec, (const uint16_t*)job->d_tok,
+                           job->tok_cap, job->d_qtab, job->d_raw, job->gs.width, job->gs.height, job->gs.width_padding);
         if (job->idct_path) *job->idct_path = 2;
         return true;
     }
-    const dim3 grid(((unsigned)g.block_count + 255) / 256);
+    const dim3 grid(((unsigned)g.block_count + 255) / 256, 1, frames);
     if (N == 4) hipLaunchKernelGGL(k_idct_scaled<4>, grid, dim3(256), 0, st, g, job->d_coefs, job->d_qtab, job->d_planes, job->zero_coefs);
     else if (N == 2) hipLaunchKernelGGL(k_idct_scaled<2>, grid, dim3(256), 0, st, g, job->d_coefs, job->d_qtab, job->d_planes, job->zero_coefs);
     else hipLaunchKernelGGL(k_idct_scaled<1>, grid, dim3(256), 0, st, g, job->d_coefs, job->d_qtab, job->d_planes, job->zero_coefs);

@@ -43,7 +43,10 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     const gj_geom& g = job->g;
     if (g.blocks_per_mcu > GJ_MAX_MCU_BLOCKS) return -1;
     if ((job->batch.count > 1 || g.fb.sizes != nullptr) && (!gj_hip_decode_batchable(job) || g.fb.sizes == nullptr || job->batch.count > 65535u)) return -1;
-    if (job->scale > 1 && ((job->scale != 2 && job->scale != 4 && job->scale != 8) || g.fb.sizes != nullptr || job->flipped)) return -1; // (single frames, no flip)
+    // (a reduced-size decode: no flip; a batch: the pixel kernels find frame z's reduced planes and pixels through gs.fb, which must be g.fb)
+    if (job->scale > 1 && ((job->scale != 2 && job->scale != 4 && job->scale != 8) || job->flipped ||
+                           (g.fb.sizes != nullptr && (job->gs.fb.sizes != g.fb.sizes || job->gs.fb.coefs != g.fb.coefs || job->gs.fb.raw != g.fb.raw))))
+        return -1;
     const gj_region& rg = job->region;
     // (a region call: no scale, no flip; with a selection, room for the compacted table and its counts. A single frame -- or a batch of regions,
     // gj_region::d_frames: always with a selection, compacted tables at the frames' table stride, the found counts of every frame)

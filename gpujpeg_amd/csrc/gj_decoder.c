@@ -1098,8 +1098,10 @@ static int batch_chunk_buffers(struct gpujpeg_decoder* d, gj_dec_job* job, gj_ba
     const bool tokens = gj_hip_decode_wants_tokens(&job->g, max_size, &d->tune) != 0;
     const size_t tok_frame = tokens ? (max_size * 4 + 64 + 63) & ~(size_t)63 : 0;                                            /* tokens */
     const size_t rec_frame = tokens ? ((size_t)g->block_count + 8 + 7) & ~(size_t)7 : 0;                                    /* records */
-    /* (a batch of regions: the cover planes of every configuration that does not take the token-fed region kernel, and a compacted table per frame) */
-    const bool planes = regions || gj_hip_decode_uses_planes(g, job->use_fused) != 0;
+    /* (a batch of regions: the cover planes of every configuration that does not take the token-fed region kernel, and a compacted table per frame;
+     * a reduced-size batch: the reduced planes of every configuration, also of those whose full-size IDCT is fused and has none -- the token route
+     * does not touch them, but whether a chunk takes it is gj_hip_decode's decision, made with the longest segment of the streams) */
+    const bool planes = regions || job->scale > 1 || gj_hip_decode_uses_planes(g, job->use_fused) != 0;
     const size_t frame_bytes = seg_frame * 4 * (regions ? 2 : 1) + scratch_frame * 4 + coefs_frame * 2 + tok_frame * 2 + rec_frame * 8 + (planes ? coefs_frame : 0);
     int chunk = (int)(GJ_DEC_BATCH_BYTES / frame_bytes);
     if (chunk > chunk_cap) chunk = chunk_cap;
@@ -1142,10 +1144,10 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     const gj_geom* g = &c->geom;
     const int first = b->first, count = b->count, n_all = count - first;
     const size_t* sizes = b->sizes;
-    /* (a reduced-size decode and the region of the decoder's own option go frame by frame: their kernels do not know the frame dimension; a batch
-     * of regions -- b->origins -- has kernels that do) */
+    /* (the region of the decoder's own option goes frame by frame: the single-frame region kernels do not know the frame dimension; a batch of
+     * regions -- b->origins -- has kernels that do, and so has a reduced-size decode, dec_opt_scale) */
     const bool regions = b->origins != NULL;
-    bool batched = d->scale <= 1 && (regions || !d->region_on) && d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
+    bool batched = (regions || !d->region_on) && d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
                    (b->streams_on_device ? (b->stream_stride & 15u) == 0 : true) && d->tab2_ok;
     size_t max_size = 0;
     for (int f = first; f < count; f++) {
@@ -1156,11 +1158,15 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     d->call_scale = 1;
     d->call_region = false;
     const struct gj_reader_result* r = &d->hdr_cache_r;
+    /* a scale the single call refuses for this header (a flip; packed 4:2:2 output of odd reduced width, gj_geom_init_scaled): nothing is launched,
+     * the frames go the ordinary way and that call says why */
+    if (d->scale > 1 && (d->flipped || (r->param_image.pixel_format == GPUJPEG_422_U8_P1020 && (GPUJPEG_AMD_SCALED_DIM(r->param_image.width, d->scale) & 1)))) return 0;
     if (decoder_configure(d, &r->param, &r->param_image) != 0) return -1; /* (the geometry of the cached header, whatever the coder was last set up for) */
+    if (dec_scale_geometry(d) != 0) return -1; /* (call_scale, and with a scale geom_s / pi_s: the reduced image of the cached header's geometry) */
     /* a batch of regions: the rectangles against the cached header's geometry, unless frame 0 went ahead and they have been checked against its own.
      * A rectangle the CACHED header refuses may be one the streams' own header takes (an older sequence's cache): frame 0 goes ahead and decides. */
     if (regions && !b->planned && batch_regions_plan(d, b) != 0) return first == 0 && !force_first ? 1 : -1;
-    const size_t frame_raw = regions ? (size_t)b->gs_one.raw_size : (size_t)g->raw_size;
+    const size_t frame_raw = regions ? (size_t)b->gs_one.raw_size : d->call_scale > 1 ? (size_t)d->geom_s.raw_size : (size_t)g->raw_size;
     if (b->output_stride < frame_raw || (b->frame_raw != 0 && b->frame_raw != frame_raw)) {
         /* the cached header is an OLDER sequence's (a larger image than the caller's slots, ADVICE r4: this used to fail the call): these
          * streams are strangers to it */
@@ -1241,6 +1247,10 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
             if (all > 0) job.scan_bytes[sc] = (uint32_t)((uint64_t)job.scan_bytes[sc] * (uint64_t)b->plan_max[sc] / (uint64_t)all);
         }
     }
+    if (job.scale > 1) { /* (a reduced-size batch: dec_job_base has set scale and gs = geom_s) */
+        d->last_idct_path = 0;
+        job.idct_path = &d->last_idct_path;
+    }
     B.jpeg = d_stride;
     B.raw = b->d_out_stride;
     B.maxlen = (uint32_t)max_chunks;
@@ -1250,14 +1260,14 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     job.g.fb.tok = B.tok;
     job.g.fb.rec = B.rec;
     job.g.fb.seg = B.seg;
-    if (regions) job.gs.fb = job.g.fb; /* (the pixel kernels of a batch of regions take gs only) */
+    if (regions || job.scale > 1) job.gs.fb = job.g.fb; /* (the pixel kernels of a batch of regions and of a reduced-size batch take gs only) */
     for (int a = 0; a < n_all; a += chunk) {
         B.count = (uint32_t)(n_all - a < chunk ? n_all - a : chunk);
         B.d_sizes = d->b_sizes + a;
         job.batch = B;
         job.g.fb.sizes = B.d_sizes;
+        if (regions || job.scale > 1) job.gs.fb.sizes = B.d_sizes;
         if (regions) {
-            job.gs.fb.sizes = B.d_sizes;
             job.region.d_frames = d->b_rgn + first + a;
             job.region.h_sel_count = d->bh_found + (size_t)(first + a) * GJ_MAX_COMP;
         }
@@ -1279,7 +1289,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         GJ_ERROR("Decoder failed: %s\n", gj_hip_last_error());
         return -1;
     }
-    if (regions) c->kernel_ms[4] = (float)d->last_idct_path; /* (which IDCT side the batched launches took, gpujpeg_amd_ext.h) */
+    if (regions || job.scale > 1) c->kernel_ms[4] = (float)d->last_idct_path; /* (which IDCT side the batched launches took, gpujpeg_amd_ext.h) */
     /* every frame's summary: was the stream what the launch assumed? */
     int accepted = 0;
     for (int i = 0; i < n_all; i++) {

@@ -329,7 +329,9 @@ typedef struct gj_dec_job {
                                       point to frame 0's words inside arrays of gj_scan_summary) */
     /* reduced-size decode (dec_opt_scale): scale = 2, 4, 8 (0 or 1: full size). The entropy decoders work on g as ever; the IDCT side leaves
      * 8 / scale samples per block edge and the pixel kernels behind it work on gs, the geometry of the reduced image (gj_geom_init_scaled: d_planes
-     * holds the reduced planes, d_raw the reduced image). Single frames only. */
+     * holds the reduced planes, d_raw the reduced image). No flip. A single frame, or a batch of frames (gj_dec_job::batch): frame z's reduced planes
+     * lie z x gj_frame_strides::coefs bytes into d_planes -- the full-size planes' stride --, its reduced image z x gj_frame_strides::raw bytes into
+     * d_raw, and gs.fb = g.fb. */
     int scale;
     gj_geom gs;
     int* idct_path;                /* host, may be NULL: which IDCT side ran -- 0 full size, 1 k_idct_scaled, 2 k_idct_tok_scaled_rgb444, 3 k_idct_region, 4 k_idct_tok_region_rgb444 */

@@ -81,7 +81,11 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
  * GPUJPEG_AMD_SCALED_DIM(width, s) x GPUJPEG_AMD_SCALED_DIM(height, s) pixels that the N x N low-frequency corner (N = 8 / s) of every block gives
  * (integer N-point inverse DCT, DESIGN "Reduced-size decode"); output->param_image, output->data_size and the buffer layout are those of an image of
  * that size, gpujpeg_decoder_get_image_info keeps reporting the stream's own size. May be changed between two calls of a decoder. Packed 4:2:2 output
- * of odd reduced width and dec_opt_flipped together with a scale are refused by the decode call; batch calls decode such frames one by one.
+ * of odd reduced width and dec_opt_flipped together with a scale are refused by the decode call. The batch calls (gpujpeg_amd_decoder_decode_batch,
+ * _decode_batch_ptrs) take the scale into their batched launches -- the frame is a grid dimension of the reduced-size kernels, output_stride and
+ * frame_bytes count in reduced frames --; what still goes frame by frame inside the call is what does so at full size (restart interval 0, channel
+ * remap, another header, damaged markers, a segment too long for the fast entropy decoders, the first frame of a decoder's life, frame 0 of a call
+ * whose pixels go to host memory). A scale together with gpujpeg_amd_decoder_decode_batch_regions is refused.
  * Outside reference parity by construction (the reference has no reduced decode). */
 #define GPUJPEG_AMD_DEC_OPT_SCALE "dec_opt_scale"
 #define GPUJPEG_AMD_SCALED_DIM(v, s) (((v) + (s) - 1) / (s))
@@ -117,7 +121,8 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_optimal(const uint32_t freq[256], uint8
  * decoder: [0] entropy decoder, [1] IDCT (fused path: postprocess included), [2] postprocess, [3] marker scan (k_markers; 0 when the host walked the stream),
  *          [4] not a duration: the IDCT side of that call -- 0 full size, 1 reduced size from the coefficient planes (k_idct_scaled), 2 reduced size from
  *          tokens (k_idct_tok_scaled_rgb444), 3 region from the coefficient planes (k_idct_region), 4 region from tokens (k_idct_tok_region_rgb444);
- *          gpujpeg_amd_decoder_decode_batch_regions leaves the side its batched launches took here (3 or 4) and no durations */
+ *          gpujpeg_amd_decoder_decode_batch_regions leaves the side its batched launches took here (3 or 4) and no durations, and so does
+ *          gpujpeg_amd_decoder_decode_batch with a dec_opt_scale (1 or 2) */
 GPUJPEG_API int gpujpeg_amd_encoder_get_kernel_times(struct gpujpeg_encoder* encoder, float ms[8]);
 GPUJPEG_API int gpujpeg_amd_decoder_get_kernel_times(struct gpujpeg_decoder* decoder, float ms[8]);
 
