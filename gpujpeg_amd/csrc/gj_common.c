@@ -567,33 +567,35 @@ int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const st
     if (gj_geom_init(gr, param, &rp, false) != 0) return -1;
     memset(r, 0, sizeof *r);
     r->on = 1;
-    r->x = x; r->y = y; r->w = w; r->h = h;
+    r->w = w; r->h = h;
+    gj_region_frame* const rf = &r->frame;
+    rf->x = x; rf->y = y;
     const int px1 = x + gr->raw_width - 1, py1 = y + h - 1; /* the last pixel column / row whose samples are read */
     if (full->interleaved) {
-        r->mx0 = x / (8 * full->max_h);
-        r->my0 = y / (8 * full->max_v);
-        r->mx1 = px1 / (8 * full->max_h) + 1;
-        r->my1 = py1 / (8 * full->max_v) + 1;
+        rf->mx0 = x / (8 * full->max_h);
+        rf->my0 = y / (8 * full->max_v);
+        rf->mx1 = px1 / (8 * full->max_h) + 1;
+        rf->my1 = py1 / (8 * full->max_v) + 1;
         const int mcu_rows = full->mcu_count_x > 0 ? full->mcu_count / full->mcu_count_x : 0;
-        if (r->mx1 > full->mcu_count_x) r->mx1 = full->mcu_count_x;
-        if (r->my1 > mcu_rows) r->my1 = mcu_rows;
+        if (rf->mx1 > full->mcu_count_x) rf->mx1 = full->mcu_count_x;
+        if (rf->my1 > mcu_rows) rf->my1 = mcu_rows;
     }
     uint64_t offset = 0;
     for (int c = 0; c < gr->comp_count; c++) {
         gj_comp_geom* k = &gr->comp[c];
         const gj_comp_geom* f = &full->comp[c];
         if (full->interleaved) {
-            r->bx0[c] = r->mx0 * f->samp_h; r->bx1[c] = r->mx1 * f->samp_h;
-            r->by0[c] = r->my0 * f->samp_v; r->by1[c] = r->my1 * f->samp_v;
+            rf->bx0[c] = rf->mx0 * f->samp_h; rf->bx1[c] = rf->mx1 * f->samp_h;
+            rf->by0[c] = rf->my0 * f->samp_v; rf->by1[c] = rf->my1 * f->samp_v;
         } else {
-            r->bx0[c] = x / f->sub_h / 8; r->bx1[c] = px1 / f->sub_h / 8 + 1;
-            r->by0[c] = y / f->sub_v / 8; r->by1[c] = py1 / f->sub_v / 8 + 1;
+            rf->bx0[c] = x / f->sub_h / 8; rf->bx1[c] = px1 / f->sub_h / 8 + 1;
+            rf->by0[c] = y / f->sub_v / 8; rf->by1[c] = py1 / f->sub_v / 8 + 1;
         }
-        if (r->bx1[c] > f->blocks_x) r->bx1[c] = f->blocks_x;
-        if (r->by1[c] > f->blocks_y) r->by1[c] = f->blocks_y;
-        if (r->bx0[c] >= r->bx1[c] || r->by0[c] >= r->by1[c]) return -1; /* (cannot happen: the region lies inside the image) */
-        k->blocks_x = r->bx1[c] - r->bx0[c];
-        k->blocks_y = r->by1[c] - r->by0[c];
+        if (rf->bx1[c] > f->blocks_x) rf->bx1[c] = f->blocks_x;
+        if (rf->by1[c] > f->blocks_y) rf->by1[c] = f->blocks_y;
+        if (rf->bx0[c] >= rf->bx1[c] || rf->by0[c] >= rf->by1[c]) return -1; /* (cannot happen: the region lies inside the image) */
+        k->blocks_x = rf->bx1[c] - rf->bx0[c];
+        k->blocks_y = rf->by1[c] - rf->by0[c];
         k->data_width = k->blocks_x * 8;
         k->data_height = k->blocks_y * 8;
         k->data_offset = offset;

@@ -17,13 +17,8 @@ __global__ __launch_bounds__(256) void k_idct(const gj_geom g, int16_t* __restri
     }
     const unsigned gb = blockIdx.x * 256u + threadIdx.x;
     if (gb >= (unsigned)g.block_count) return;
-    int c = 0;
-#pragma unroll
-    for (int i = 1; i < GJ_MAX_COMP; i++)
-        if (i < g.comp_count && (uint64_t)gb * 64 >= g.comp[i].data_offset) c = i;
-    const gj_comp_geom& k = g.comp[c];
-    const unsigned lb = gb - (unsigned)(k.data_offset / 64);
-    const unsigned by = lb / (unsigned)k.blocks_x, bx = lb - by * (unsigned)k.blocks_x;
+    unsigned bx, by;
+    const gj_comp_geom& k = g.comp[gj_block_of(g, gb, bx, by)];
     uint32_t w[32];
     {
         uint4* p = reinterpret_cast<uint4*>(coefs + (size_t)gb * 64);
@@ -286,6 +281,60 @@ __device__ __forceinline__ void gj_tok_to_slot(uint8_t* slot, uint16_t* stage, c
     gj_wave_sync(); // (the stage is rewritten by the next component)
 }
 
+// The LDS of a token-fed workgroup (32 KiB tile + stages + tables = 40 KiB: four workgroups per CU)
+struct __attribute__((aligned(16))) GjTokLds {
+    uint8_t blk[256 * 128];          // a lane's 128-byte slot (gj_slot_row)
+    uint16_t stage[4][GJ_TOK_STAGE]; // a wave's tokens
+    // dequantisation tables: [0] for blocks rebuilt from tokens (AC entries / 64: the slot holds 64 x the value, see gj_slot_put; the DC term is
+    // stored as it is), [1] for blocks that arrive through the coefficient planes; read as VGPR pairs for v_pk_mul_f32
+    float q[2][3][64];
+};
+
+// ... its tables (visible to the workgroup behind the caller's __syncthreads)
+__device__ __forceinline__ void gj_tok_tables(GjTokLds& s, const gj_geom& g, const float* __restrict__ qtab)
+{
+    if (threadIdx.x < 192) {
+        const float q = qtab[g.comp[threadIdx.x >> 6].q_table * 64 + (threadIdx.x & 63)];
+        s.q[0][threadIdx.x >> 6][threadIdx.x & 63] = (threadIdx.x & 63) ? q * 0.015625f : q;
+        s.q[1][threadIdx.x >> 6][threadIdx.x & 63] = q;
+    }
+}
+
+// The core of the 4:4:4 kernels: records (gj_tok_record) of the lane's block position lb -> the three components' samples, byte-packed. Per
+// component the tokens of the wave's 64 blocks go through the LDS stage (consecutive blocks of a scan have consecutive tokens); the loads of the
+// next component are in flight while this one is transformed. Everything is private to a wave.
+__device__ __forceinline__ void gj_tok_idct3(GjTokLds& s, const gj_geom& g, const int16_t* __restrict__ coefs, const uint16_t* __restrict__ d_tok,
+                                             const unsigned lb, const uint32_t (&start)[3], const uint32_t (&cd)[3], uint32_t (&pk)[3][16])
+{
+    const int lane = threadIdx.x & 63;
+    uint8_t* slot = s.blk + threadIdx.x * 128;
+    uint16_t* stage = s.stage[threadIdx.x >> 6];
+    GjTokRange cur = gj_tok_fetch(d_tok, start[0], gj_rec_count(cd[0]), lane);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const bool fast = cur.fast;
+        const uint32_t S = cur.S;
+        if (fast) {
+            *reinterpret_cast<uint4*>(stage + lane * 8) = cur.t0;
+            if (lane * 8 + 512 < GJ_TOK_STAGE) *reinterpret_cast<uint4*>(stage + lane * 8 + 512) = cur.t1;
+        }
+        if (c < 2) cur = gj_tok_fetch(d_tok, start[c + 1], gj_rec_count(cd[c + 1]), lane);
+        const bool in_plane = (int32_t)cd[c] < 0;
+        gj_tok_to_slot<false>(slot, stage, lane, fast, S, start[c], gj_rec_count(cd[c]), cd[c] & 0xFFFFu, in_plane,
+                       reinterpret_cast<const uint4*>(coefs + g.comp[c].data_offset + (size_t)lb * 64), d_tok);
+        // the block as rows; dequantisation + IDCT
+        uint32_t wb[32];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const uint4 v = *gj_slot_row(slot, lane, r);
+            wb[r * 4] = v.x; wb[r * 4 + 1] = v.y; wb[r * 4 + 2] = v.z; wb[r * 4 + 3] = v.w;
+        }
+        gj_idct_pk(wb, s.q[in_plane ? 1 : 0][c], pk[c]);
+#pragma unroll
+        for (int i = 0; i < 16; i++) GJ_KEEP(pk[c][i]); // one transform at a time (see k_idct_fused_rgb444)
+    }
+}
+
 template <int CS_FROM, int CS_TO>
 __global__ __launch_bounds__(256, 4) void k_idct_tok_rgb444(const gj_geom g, const int16_t* __restrict__ coefs, const uint2* __restrict__ d_rec,
                                                             const uint16_t* __restrict__ d_tok, const uint32_t tok_cap,
@@ -296,70 +345,18 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_rgb444(const gj_geom g, con
         coefs += z * g.fb.coefs; d_rec += z * g.fb.rec; d_tok += z * g.fb.tok;
         raw += z * g.fb.raw;
     }
-    __shared__ __attribute__((aligned(16))) uint8_t s_blk[256 * 128];
-    __shared__ __attribute__((aligned(16))) uint16_t s_stage[4][GJ_TOK_STAGE];
-    // dequantisation tables: [0] for blocks rebuilt from tokens (AC entries / 64: the slot holds 64 x the value, see gj_slot_put; the DC term is
-    // stored as it is), [1] for blocks that arrive through the coefficient planes
-    __shared__ __attribute__((aligned(8))) float s_q[2][3][64];
-    if (threadIdx.x < 192) {
-        const float q = qtab[g.comp[threadIdx.x >> 6].q_table * 64 + (threadIdx.x & 63)];
-        s_q[0][threadIdx.x >> 6][threadIdx.x & 63] = (threadIdx.x & 63) ? q * 0.015625f : q;
-        s_q[1][threadIdx.x >> 6][threadIdx.x & 63] = q;
-    }
+    __shared__ GjTokLds s;
+    gj_tok_tables(s, g, qtab);
     const gj_comp_geom& k0 = g.comp[0];
     const unsigned nb = (unsigned)(k0.blocks_x * k0.blocks_y);
     const unsigned lb = blockIdx.x * 256u + threadIdx.x;
     const unsigned by = lb / (unsigned)k0.blocks_x, bx = lb - by * (unsigned)k0.blocks_x;
-    const int lane = threadIdx.x & 63;
-    uint8_t* slot = s_blk + threadIdx.x * 128;
-    uint16_t* stage = s_stage[threadIdx.x >> 6];
-
-    // ---- 1. the three block records (independent loads)
-    // (count and DC term stay packed as the record holds them -- count << 16 | DC, bit 31: "the block is in the coefficient planes" -- until their
-    // component is worked on: the kernel has no register to spare, profiles/r5_11)
     uint32_t start[3], cd[3];
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-        start[c] = cd[c] = 0;
-        if (lb < nb) {
-            const uint2 r = d_rec[g.comp[c].data_offset / 64 + lb];
-            start[c] = r.x;
-            uint32_t n = r.y >> 16;
-            const bool planes = n == 0xFFFFu;
-            if (planes || n > 63u || start[c] > tok_cap || n > tok_cap - start[c]) n = 0; // (the second: a record nobody wrote, damaged stream)
-            cd[c] = (r.y & 0xFFFFu) | (n << 16) | (planes ? 0x80000000u : 0u);
-        }
-    }
-    auto cnt_of = [](const uint32_t x) { return (x >> 16) & 0x7FFFu; };
-    __syncthreads(); // (s_q; everything below is private to a wave)
-
-    // ---- 2. per component: the tokens of the wave's 64 blocks go through the LDS stage (consecutive blocks of a scan have
-    //         consecutive tokens); the loads of the next component are in flight while this one is transformed
+    for (int c = 0; c < 3; c++) gj_tok_record(g, d_rec, tok_cap, lb < nb, lb, c, start[c], cd[c]);
+    __syncthreads(); // (s.q; everything below is private to a wave)
     uint32_t pk[3][16];
-    GjTokRange cur = gj_tok_fetch(d_tok, start[0], cnt_of(cd[0]), lane);
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const bool fast = cur.fast;
-        const uint32_t S = cur.S;
-        if (fast) {
-            *reinterpret_cast<uint4*>(stage + lane * 8) = cur.t0;
-            if (lane * 8 + 512 < GJ_TOK_STAGE) *reinterpret_cast<uint4*>(stage + lane * 8 + 512) = cur.t1;
-        }
-        if (c < 2) cur = gj_tok_fetch(d_tok, start[c + 1], cnt_of(cd[c + 1]), lane);
-        const bool in_plane = (int32_t)cd[c] < 0;
-        gj_tok_to_slot<false>(slot, stage, lane, fast, S, start[c], cnt_of(cd[c]), cd[c] & 0xFFFFu, in_plane,
-                       reinterpret_cast<const uint4*>(coefs + g.comp[c].data_offset + (size_t)lb * 64), d_tok);
-        // the block as rows; dequantisation + IDCT
-        uint32_t wb[32];
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const uint4 v = *gj_slot_row(slot, lane, r);
-            wb[r * 4] = v.x; wb[r * 4 + 1] = v.y; wb[r * 4 + 2] = v.z; wb[r * 4 + 3] = v.w;
-        }
-        gj_idct_pk(wb, s_q[in_plane ? 1 : 0][c], pk[c]);
-#pragma unroll
-        for (int i = 0; i < 16; i++) GJ_KEEP(pk[c][i]); // one transform at a time (see k_idct_fused_rgb444)
-    }
+    gj_tok_idct3(s, g, coefs, d_tok, lb, start, cd, pk);
     gj_store_rgb444<CS_FROM, CS_TO>(g, raw, pk, lb, nb, bx, by);
 }
 
@@ -378,22 +375,14 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_region_rgb444(const gj_geom
                                                                    const uint2* __restrict__ d_rec, const uint16_t* __restrict__ d_tok,
                                                                    const uint32_t tok_cap, const float* __restrict__ qtab, uint8_t* __restrict__ raw)
 {
-    gj_region rg_frame;
     if (BATCH) {
         const size_t z = blockIdx.z;
         coefs += z * g.fb.coefs; d_rec += z * g.fb.rec; d_tok += z * g.fb.tok;
         raw += z * g.fb.raw;
-        rg_frame = gj_region_of_frame(rg_in, rg_in.d_frames[z]);
     }
-    const gj_region& rg = BATCH ? rg_frame : rg_in;
-    __shared__ __attribute__((aligned(16))) uint8_t s_blk[256 * 128];
-    __shared__ __attribute__((aligned(16))) uint16_t s_stage[4][GJ_TOK_STAGE];
-    __shared__ __attribute__((aligned(8))) float s_q[2][3][64]; // (as in k_idct_tok_rgb444)
-    if (threadIdx.x < 192) {
-        const float q = qtab[g.comp[threadIdx.x >> 6].q_table * 64 + (threadIdx.x & 63)];
-        s_q[0][threadIdx.x >> 6][threadIdx.x & 63] = (threadIdx.x & 63) ? q * 0.015625f : q;
-        s_q[1][threadIdx.x >> 6][threadIdx.x & 63] = q;
-    }
+    const gj_region_frame& rg = BATCH ? rg_in.d_frames[blockIdx.z] : rg_in.frame; // (a frame's record is read where it lies)
+    __shared__ GjTokLds s;
+    gj_tok_tables(s, g, qtab);
     const int lane = threadIdx.x & 63;
     // the wave's row piece of the cover (the three components' covers are the same rectangle: 4:4:4)
     const unsigned cbx = (unsigned)(rg.bx1[0] - rg.bx0[0]), cby = (unsigned)(rg.by1[0] - rg.by0[0]);
@@ -405,50 +394,19 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_region_rgb444(const gj_geom
     const unsigned fby = (unsigned)rg.by0[0] + min(crow, cby - 1u);
     const unsigned fbx = (unsigned)rg.bx0[0] + piece * 64u + (valid ? (unsigned)lane : (in_piece ? in_piece - 1u : 0u));
     const unsigned lb = fby * (unsigned)g.comp[0].blocks_x + fbx; // (inside the component's grid: the cover is)
-    uint8_t* slot = s_blk + threadIdx.x * 128;
-    uint16_t* stage = s_stage[threadIdx.x >> 6];
-
     uint32_t start[3], cd[3];
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const uint2 r = d_rec[g.comp[c].data_offset / 64 + lb];
-        start[c] = r.x;
-        uint32_t n = r.y >> 16;
-        const bool planes = n == 0xFFFFu;
-        if (planes || n > 63u || start[c] > tok_cap || n > tok_cap - start[c]) n = 0;
-        cd[c] = (r.y & 0xFFFFu) | (n << 16) | (planes ? 0x80000000u : 0u);
-        if (!valid) { // an empty range behind the piece's last block
-            start[c] += n;
+    for (int c = 0; c < 3; c++) gj_tok_record(g, d_rec, tok_cap, true, lb, c, start[c], cd[c]);
+    if (!valid) { // empty ranges behind the piece's last block
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            start[c] += gj_rec_count(cd[c]);
             cd[c] = 0;
         }
     }
-    auto cnt_of = [](const uint32_t x) { return (x >> 16) & 0x7FFFu; };
-    __syncthreads(); // (s_q; everything below is private to a wave)
-
+    __syncthreads(); // (s.q; everything below is private to a wave)
     uint32_t pk[3][16];
-    GjTokRange cur = gj_tok_fetch(d_tok, start[0], cnt_of(cd[0]), lane);
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const bool fast = cur.fast;
-        const uint32_t S = cur.S;
-        if (fast) {
-            *reinterpret_cast<uint4*>(stage + lane * 8) = cur.t0;
-            if (lane * 8 + 512 < GJ_TOK_STAGE) *reinterpret_cast<uint4*>(stage + lane * 8 + 512) = cur.t1;
-        }
-        if (c < 2) cur = gj_tok_fetch(d_tok, start[c + 1], cnt_of(cd[c + 1]), lane);
-        const bool in_plane = (int32_t)cd[c] < 0;
-        gj_tok_to_slot<false>(slot, stage, lane, fast, S, start[c], cnt_of(cd[c]), cd[c] & 0xFFFFu, in_plane,
-                       reinterpret_cast<const uint4*>(coefs + g.comp[c].data_offset + (size_t)lb * 64), d_tok);
-        uint32_t wb[32];
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const uint4 v = *gj_slot_row(slot, lane, r);
-            wb[r * 4] = v.x; wb[r * 4 + 1] = v.y; wb[r * 4 + 2] = v.z; wb[r * 4 + 3] = v.w;
-        }
-        gj_idct_pk(wb, s_q[in_plane ? 1 : 0][c], pk[c]);
-#pragma unroll
-        for (int i = 0; i < 16; i++) GJ_KEEP(pk[c][i]);
-    }
+    gj_tok_idct3(s, g, coefs, d_tok, lb, start, cd, pk);
     if (!valid) return;
     // the block's 8 x 8 pixels at (x0, y0) of the region image, of which any part may lie outside it
     const int W = gr.width, H = gr.height;
@@ -498,15 +456,8 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_uyvy422(const gj_geom g, co
         coefs += z * g.fb.coefs; d_rec += z * g.fb.rec; d_tok += z * g.fb.tok;
         raw += z * g.fb.raw;
     }
-    __shared__ __attribute__((aligned(16))) uint8_t s_blk[256 * 128];
-    __shared__ __attribute__((aligned(16))) uint16_t s_stage[4][GJ_TOK_STAGE];
-    // dequantisation tables: [0] for blocks rebuilt from tokens (AC entries / 64, see gj_slot_put), [1] for blocks from the coefficient planes
-    __shared__ __attribute__((aligned(8))) float s_q[2][3][64];
-    if (threadIdx.x < 192) {
-        const float q = qtab[g.comp[threadIdx.x >> 6].q_table * 64 + (threadIdx.x & 63)];
-        s_q[0][threadIdx.x >> 6][threadIdx.x & 63] = (threadIdx.x & 63) ? q * 0.015625f : q;
-        s_q[1][threadIdx.x >> 6][threadIdx.x & 63] = q;
-    }
+    __shared__ GjTokLds s;
+    gj_tok_tables(s, g, qtab);
     const gj_comp_geom& kc = g.comp[1];
     const unsigned nm = (unsigned)(kc.blocks_x * kc.blocks_y);
     const int p = threadIdx.x & 3; // Y0 Y1 Cb Cr
@@ -514,24 +465,24 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_uyvy422(const gj_geom g, co
     const unsigned my = m / (unsigned)kc.blocks_x, mx = m - my * (unsigned)kc.blocks_x;
     const int c = p < 2 ? 0 : p - 1;
     const int lane = threadIdx.x & 63;
-    uint8_t* slot = s_blk + threadIdx.x * 128;
-    uint16_t* stage = s_stage[threadIdx.x >> 6];
+    uint8_t* slot = s.blk + threadIdx.x * 128;
+    uint16_t* stage = s.stage[threadIdx.x >> 6];
     uint32_t start = 0, cnt = 0, dc = 0;
     bool in_plane = false;
     if (m < nm) {
         const uint2 r = d_rec[(size_t)m * 4 + p];
+        const uint32_t cd = gj_rec_pack(r, tok_cap);
         start = r.x;
-        cnt = r.y >> 16;
-        dc = r.y & 0xFFFFu;
-        if (cnt == 0xFFFFu) { in_plane = true; cnt = 0; }
-        else if (cnt > 63u || start > tok_cap || cnt > tok_cap - start) cnt = 0; // (a record nobody wrote: damaged stream)
+        cnt = gj_rec_count(cd);
+        dc = cd & 0xFFFFu;
+        in_plane = (int32_t)cd < 0;
     }
     const GjTokRange tr = gj_tok_fetch(d_tok, start, cnt, lane);
     if (tr.fast) {
         *reinterpret_cast<uint4*>(stage + lane * 8) = tr.t0;
         if (lane * 8 + 512 < GJ_TOK_STAGE) *reinterpret_cast<uint4*>(stage + lane * 8 + 512) = tr.t1;
     }
-    __syncthreads(); // (s_q)
+    __syncthreads(); // (s.q)
     const size_t blk = p < 2 ? (size_t)my * g.comp[0].blocks_x + 2 * mx + p : (size_t)m; // (plane address: blocks of long segments only)
     gj_tok_to_slot<true>(slot, stage, lane, tr.fast, tr.S, start, cnt, dc, in_plane,
                    reinterpret_cast<const uint4*>(coefs + g.comp[c].data_offset + (m < nm ? blk : 0) * 64), d_tok);
@@ -542,7 +493,7 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_uyvy422(const gj_geom g, co
         wb[r * 4] = v.x; wb[r * 4 + 1] = v.y; wb[r * 4 + 2] = v.z; wb[r * 4 + 3] = v.w;
     }
     uint32_t px[16];
-    gj_idct_pk(wb, s_q[in_plane ? 1 : 0][c], px);
+    gj_idct_pk(wb, s.q[in_plane ? 1 : 0][c], px);
 
     // ---- UYVY: dword k of an MCU row = U_k | Y_2k << 8 | V_k << 16 | Y_2k+1 << 24; lane p writes dwords 2p and 2p + 1
     const size_t pitch = (size_t)g.width * 2 + g.width_padding;
@@ -697,58 +648,49 @@ __global__ __launch_bounds__(256) void k_copy_planes_out(const gj_geom g, const 
 // ================================================================================================
 // Kernel selection and launch
 // ================================================================================================
+// The 4:4:4 kernels of a configuration (gj_is_rgb444): the instantiation for its colour pair out of GJ_COLOR_PAIRS, or nullptr
 typedef void (*gj_idct_fused_t)(const gj_geom, int16_t*, const float*, uint8_t*, int);
 
 static gj_idct_fused_t gj_idct_fused_kernel(const gj_geom& g)
 {
-    if (g.pixel_format != GJ_PF_444_P012 || g.comp_count != 3) return nullptr;
-    for (int c = 0; c < 3; c++)
-        if (g.comp[c].samp_h != 1 || g.comp[c].samp_v != 1) return nullptr;
-    const int from = g.color_space_internal, to = g.color_space;
-    if (from == to || from == GJ_CS_NONE || to == GJ_CS_NONE) return k_idct_fused_rgb444<GJ_CS_NONE, GJ_CS_NONE>;
-    if (from == GJ_CS_BT601_256 && to == GJ_CS_RGB) return k_idct_fused_rgb444<GJ_CS_BT601_256, GJ_CS_RGB>;
-    if (from == GJ_CS_BT601 && to == GJ_CS_RGB) return k_idct_fused_rgb444<GJ_CS_BT601, GJ_CS_RGB>;
-    if (from == GJ_CS_BT709 && to == GJ_CS_RGB) return k_idct_fused_rgb444<GJ_CS_BT709, GJ_CS_RGB>;
-    if (from == GJ_CS_RGB && to == GJ_CS_BT601_256) return k_idct_fused_rgb444<GJ_CS_RGB, GJ_CS_BT601_256>;
-    return nullptr;
+#define GJ_X(F, T) k_idct_fused_rgb444<F, T>,
+    static const gj_idct_fused_t k[] = {GJ_COLOR_PAIRS(GJ_X)};
+#undef GJ_X
+    const int pair = gj_color_pair(g);
+    return gj_is_rgb444(g) && pair >= 0 ? k[pair] : nullptr;
 }
 
 static gj_idct_tok_t gj_idct_tok_kernel(const gj_geom& g)
 {
-    if (g.pixel_format != GJ_PF_444_P012 || g.comp_count != 3) return nullptr;
-    for (int c = 0; c < 3; c++)
-        if (g.comp[c].samp_h != 1 || g.comp[c].samp_v != 1) return nullptr;
-    const int from = g.color_space_internal, to = g.color_space;
-    if (from == to || from == GJ_CS_NONE || to == GJ_CS_NONE) return k_idct_tok_rgb444<GJ_CS_NONE, GJ_CS_NONE>;
-    if (from == GJ_CS_BT601_256 && to == GJ_CS_RGB) return k_idct_tok_rgb444<GJ_CS_BT601_256, GJ_CS_RGB>;
-    if (from == GJ_CS_BT601 && to == GJ_CS_RGB) return k_idct_tok_rgb444<GJ_CS_BT601, GJ_CS_RGB>;
-    if (from == GJ_CS_BT709 && to == GJ_CS_RGB) return k_idct_tok_rgb444<GJ_CS_BT709, GJ_CS_RGB>;
-    if (from == GJ_CS_RGB && to == GJ_CS_BT601_256) return k_idct_tok_rgb444<GJ_CS_RGB, GJ_CS_BT601_256>;
-    return nullptr;
+#define GJ_X(F, T) k_idct_tok_rgb444<F, T>,
+    static const gj_idct_tok_t k[] = {GJ_COLOR_PAIRS(GJ_X)};
+#undef GJ_X
+    const int pair = gj_color_pair(g);
+    return gj_is_rgb444(g) && pair >= 0 ? k[pair] : nullptr;
 }
 
 typedef void (*gj_idct_tok_region_t)(const gj_geom, const gj_geom, const gj_region, const int16_t*, const uint2*, const uint16_t*, uint32_t, const float*, uint8_t*);
-// the token-fed IDCT side of a region call (gj_launch_idct_region; the configuration of k_idct_tok_rgb444, non-interleaved scans)
+// the token-fed IDCT side of a region call (gj_launch_idct_region; the configuration of k_idct_tok_rgb444, non-interleaved scans: gj_hip_decode asks
+// gj_idct_tok_scaled_for before it takes this way)
 void gj_launch_idct_tok_region(const gj_dec_job* job, hipStream_t st)
 {
     const gj_geom& g = job->g;
-    const int from = g.color_space_internal, to = g.color_space;
     const gj_region& r = job->region;
     const bool batch = r.d_frames != nullptr;
-#define GJ_TOK_REGION_K(F, T) (batch ? k_idct_tok_region_rgb444<F, T, true> : k_idct_tok_region_rgb444<F, T, false>)
-    gj_idct_tok_region_t k = GJ_TOK_REGION_K(GJ_CS_NONE, GJ_CS_NONE);
-    if (from == to || from == GJ_CS_NONE || to == GJ_CS_NONE) k = GJ_TOK_REGION_K(GJ_CS_NONE, GJ_CS_NONE);
-    else if (from == GJ_CS_BT601_256 && to == GJ_CS_RGB) k = GJ_TOK_REGION_K(GJ_CS_BT601_256, GJ_CS_RGB);
-    else if (from == GJ_CS_BT601 && to == GJ_CS_RGB) k = GJ_TOK_REGION_K(GJ_CS_BT601, GJ_CS_RGB);
-    else if (from == GJ_CS_BT709 && to == GJ_CS_RGB) k = GJ_TOK_REGION_K(GJ_CS_BT709, GJ_CS_RGB);
-    else if (from == GJ_CS_RGB && to == GJ_CS_BT601_256) k = GJ_TOK_REGION_K(GJ_CS_RGB, GJ_CS_BT601_256);
-#undef GJ_TOK_REGION_K
+#define GJ_X(F, T) {k_idct_tok_region_rgb444<F, T, false>, k_idct_tok_region_rgb444<F, T, true>},
+    static const gj_idct_tok_region_t k[][2] = {GJ_COLOR_PAIRS(GJ_X)};
+#undef GJ_X
+    const int pair = gj_color_pair(g);
+    if (!gj_is_rgb444(g) || pair < 0) { // (cannot happen; a missing kernel is an error, not another way)
+        gj_hip_note((int)hipErrorInvalidValue);
+        return;
+    }
     // (a batch: the largest cover of its frames is the one of job->gs, gj_dec_job::region)
-    const unsigned cbx = batch ? (unsigned)job->gs.comp[0].blocks_x : (unsigned)(r.bx1[0] - r.bx0[0]);
-    const unsigned cby = batch ? (unsigned)job->gs.comp[0].blocks_y : (unsigned)(r.by1[0] - r.by0[0]);
+    const unsigned cbx = batch ? (unsigned)job->gs.comp[0].blocks_x : (unsigned)(r.frame.bx1[0] - r.frame.bx0[0]);
+    const unsigned cby = batch ? (unsigned)job->gs.comp[0].blocks_y : (unsigned)(r.frame.by1[0] - r.frame.by0[0]);
     const unsigned waves = (cbx + 63u) / 64u * cby;
-    hipLaunchKernelGGL(k, dim3((waves + 3u) / 4u, 1, batch ? job->batch.count : 1u), dim3(256), 0, st, g, job->gs, r, job->d_coefs, (const uint2*)job->d_blkrec,
-                       (const uint16_t*)job->d_tok, job->tok_cap, job->d_qtabf, job->d_raw);
+    hipLaunchKernelGGL(k[pair][batch], dim3((waves + 3u) / 4u, 1, batch ? job->batch.count : 1u), dim3(256), 0, st, g, job->gs, r, job->d_coefs,
+                       (const uint2*)job->d_blkrec, (const uint16_t*)job->d_tok, job->tok_cap, job->d_qtabf, job->d_raw);
 }
 
 bool gj_is_uyvy422(const gj_geom& g)
@@ -788,38 +730,34 @@ static void gj_launch_postprocess(const gj_geom& g, const gj_dec_job* job, hipSt
     }
 }
 
+// The IDCT side of a call, whichever kind it is, and what ends every kind: the channel remap of the finished image and the report of the way taken.
 void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_tok, gj_event_t* ev)
 {
-    if (job->region.on) { // region decode (gj_dec_region.hip): the cover's blocks, the region's pixels
-        gj_launch_idct_region(job, st, idct_tok != nullptr, ev);
-        return;
-    }
-    if (job->scale > 1) { // reduced-size decode (gj_dec_idct_scaled.hip): the pixel kernels work on the reduced image's geometry
-        const gj_geom& gs = job->gs;
-        const bool done = gj_launch_idct_scaled(job, st, idct_tok != nullptr);
-        if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
-        if (!done) gj_launch_postprocess(gs, job, st, job->batch.count > 1 ? job->batch.count : 1u); // (a batch: gs.fb = g.fb)
-        gj_debug_stage(job->tune.debug_sync != 0, st, "idct / postprocess (reduced size)");
-        if (job->channel_remap) {
-            const unsigned n = (unsigned)gs.width * (unsigned)gs.height;
-            hipLaunchKernelGGL(k_channel_remap, dim3((n + 255) / 256), dim3(256), 0, st, gs, job->d_raw, job->channel_remap & 0xFFFFu);
-        }
-        return;
-    }
     const gj_geom& g = job->g;
-    const bool uyvy = job->use_fused && gj_is_uyvy422(g);
-    gj_idct_fused_t fused = job->use_fused ? gj_idct_fused_kernel(g) : nullptr;
+    const bool tokens = idct_tok != nullptr;
     const unsigned frames = job->batch.count > 1 ? job->batch.count : 1u; // (batches: every kernel below but the flip and the remap)
-    if (idct_tok) {
+    int path = 0; // gj_dec_job::idct_path
+    const char* what = "idct / postprocess";
+    if (job->region.on) { // region decode (gj_dec_region.hip): the cover's blocks, the region's pixels
+        gj_launch_idct_region(job, st, tokens, ev);
+        path = tokens ? 4 : 3;
+        what = job->region.d_frames ? "idct / postprocess (batch of regions)" : "idct / postprocess (region)";
+    } else if (job->scale > 1) { // reduced-size decode (gj_dec_idct_scaled.hip): the pixel kernels work on the reduced image's geometry
+        const bool done = gj_launch_idct_scaled(job, st, tokens);
+        if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
+        if (!done) gj_launch_postprocess(job->gs, job, st, frames); // (a batch: gs.fb = g.fb)
+        path = done ? 2 : 1;
+        what = "idct / postprocess (reduced size)";
+    } else if (tokens) {
         const unsigned nb = g.interleaved ? (unsigned)g.block_count : (unsigned)(g.comp[0].blocks_x * g.comp[0].blocks_y); // one lane per block (position)
         hipLaunchKernelGGL(idct_tok, dim3((nb + 255) / 256, 1, frames), dim3(256), 0, st, g, job->d_coefs, (const uint2*)job->d_blkrec, (const uint16_t*)job->d_tok, job->tok_cap,
                            job->d_qtabf, job->d_raw);
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
-    } else if (uyvy) {
+    } else if (job->use_fused && gj_is_uyvy422(g)) {
         const unsigned nm = (unsigned)(g.comp[1].blocks_x * g.comp[1].blocks_y);
         hipLaunchKernelGGL(k_idct_fused_uyvy422, dim3((nm + 255) / 256, 1, frames), dim3(256), 0, st, g, job->d_coefs, job->d_qtabf, job->d_raw, job->zero_coefs);
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
-    } else if (fused) {
+    } else if (gj_idct_fused_t fused = job->use_fused ? gj_idct_fused_kernel(g) : nullptr) {
         const unsigned nb = (unsigned)(g.comp[0].blocks_x * g.comp[0].blocks_y);
         hipLaunchKernelGGL(fused, dim3((nb + 255) / 256, 1, frames), dim3(256), 0, st, g, job->d_coefs, job->d_qtabf, job->d_raw, job->zero_coefs);
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
@@ -830,9 +768,11 @@ void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_to
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
         gj_launch_postprocess(g, job, st, frames);
     }
-    gj_debug_stage(job->tune.debug_sync != 0, st, "idct / postprocess");
-    if (job->channel_remap) { // src/gpujpeg_postprocessor.cu:450,493: the finished image is permuted in place
-        const unsigned n = (unsigned)g.width * (unsigned)g.height;
-        hipLaunchKernelGGL(k_channel_remap, dim3((n + 255) / 256), dim3(256), 0, st, g, job->d_raw, job->channel_remap & 0xFFFFu);
+    gj_debug_stage(job->tune.debug_sync != 0, st, what);
+    if (job->channel_remap) { // src/gpujpeg_postprocessor.cu:450,493: the finished image is permuted in place (never a batch's: gj_hip_decode_batchable)
+        const gj_geom& go = job->scale > 1 || job->region.on ? job->gs : g; // the geometry of the image in d_raw
+        const unsigned n = (unsigned)go.width * (unsigned)go.height;
+        hipLaunchKernelGGL(k_channel_remap, dim3((n + 255) / 256), dim3(256), 0, st, go, job->d_raw, job->channel_remap & 0xFFFFu);
     }
+    if (job->idct_path) *job->idct_path = path;
 }

@@ -97,13 +97,8 @@ __global__ __launch_bounds__(256) void k_idct_scaled(const gj_geom g, int16_t* _
     }
     const unsigned gb = blockIdx.x * 256u + threadIdx.x;
     if (gb >= (unsigned)g.block_count) return;
-    int c = 0;
-#pragma unroll
-    for (int i = 1; i < GJ_MAX_COMP; i++)
-        if (i < g.comp_count && (uint64_t)gb * 64 >= g.comp[i].data_offset) c = i;
-    const gj_comp_geom& k = g.comp[c];
-    const unsigned lb = gb - (unsigned)(k.data_offset / 64);
-    const unsigned by = lb / (unsigned)k.blocks_x, bx = lb - by * (unsigned)k.blocks_x;
+    unsigned bx, by;
+    const gj_comp_geom& k = g.comp[gj_block_of(g, gb, bx, by)];
     int16_t* blk = coefs + (size_t)gb * 64;
     int D[N * N];
     gj_corner_from_plane<N>(blk, D);
@@ -183,24 +178,14 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_scaled_rgb444(const gj_geom
     // ---- 1. the three block records
     uint32_t start[3], cd[3]; // count << 16 | DC, bit 31: the block is in the coefficient planes
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-        start[c] = cd[c] = 0;
-        if (lb < nb) {
-            const uint2 r = d_rec[g.comp[c].data_offset / 64 + lb];
-            start[c] = r.x;
-            uint32_t n = r.y >> 16;
-            const bool planes = n == 0xFFFFu;
-            if (planes || n > 63u || start[c] > tok_cap || n > tok_cap - start[c]) n = 0; // (the second: a record nobody wrote, damaged stream)
-            cd[c] = (r.y & 0xFFFFu) | (n << 16) | (planes ? 0x80000000u : 0u);
-        }
-    }
+    for (int c = 0; c < 3; c++) gj_tok_record(g, d_rec, tok_cap, lb < nb, lb, c, start[c], cd[c]);
     __syncthreads(); // (s_q; everything below is private to a wave)
 
     // ---- 2. per component: corner coefficients -> samples
     uint32_t px[3][N];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const uint32_t cnt = (cd[c] >> 16) & 0x7FFFu;
+        const uint32_t cnt = gj_rec_count(cd[c]);
         const bool in_plane = (int32_t)cd[c] < 0;
         int F[N * N];
 #pragma unroll
@@ -302,25 +287,21 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_scaled_rgb444(const gj_geom
 // ================================================================================================
 typedef void (*gj_idct_tok_scaled_t)(const gj_geom, const int16_t*, const uint2*, const uint16_t*, uint32_t, const uint16_t*, uint8_t*, int, int, int);
 
+// the instantiation for the geometry's colour pair (GJ_COLOR_PAIRS), or nullptr
 template <int N>
 static gj_idct_tok_scaled_t gj_idct_tok_scaled_kernel(const gj_geom& g)
 {
-    const int from = g.color_space_internal, to = g.color_space;
-    if (from == to || from == GJ_CS_NONE || to == GJ_CS_NONE) return k_idct_tok_scaled_rgb444<N, GJ_CS_NONE, GJ_CS_NONE>;
-    if (from == GJ_CS_BT601_256 && to == GJ_CS_RGB) return k_idct_tok_scaled_rgb444<N, GJ_CS_BT601_256, GJ_CS_RGB>;
-    if (from == GJ_CS_BT601 && to == GJ_CS_RGB) return k_idct_tok_scaled_rgb444<N, GJ_CS_BT601, GJ_CS_RGB>;
-    if (from == GJ_CS_BT709 && to == GJ_CS_RGB) return k_idct_tok_scaled_rgb444<N, GJ_CS_BT709, GJ_CS_RGB>;
-    if (from == GJ_CS_RGB && to == GJ_CS_BT601_256) return k_idct_tok_scaled_rgb444<N, GJ_CS_RGB, GJ_CS_BT601_256>;
-    return nullptr;
+#define GJ_X(F, T) k_idct_tok_scaled_rgb444<N, F, T>,
+    static const gj_idct_tok_scaled_t k[] = {GJ_COLOR_PAIRS(GJ_X)};
+#undef GJ_X
+    const int pair = gj_color_pair(g);
+    return pair >= 0 ? k[pair] : nullptr;
 }
 
 // does a token-fed reduced-size kernel exist for this configuration? (what gj_idct_tok_for serves with k_idct_tok_rgb444)
 bool gj_idct_tok_scaled_for(const gj_geom& g)
 {
-    if (g.interleaved || g.pixel_format != GJ_PF_444_P012 || g.comp_count != 3) return false;
-    for (int c = 0; c < 3; c++)
-        if (g.comp[c].samp_h != 1 || g.comp[c].samp_v != 1) return false;
-    return gj_idct_tok_scaled_kernel<1>(g) != nullptr;
+    return !g.interleaved && gj_is_rgb444(g) && gj_color_pair(g) >= 0;
 }
 
 // The IDCT side of a reduced-size decode. Returns true when the pixels are in d_raw (token-fed kernel), false when the reduced component planes
@@ -335,13 +316,11 @@ bool gj_launch_idct_scaled(const gj_dec_job* job, hipStream_t st, const bool tok
         const unsigned nb = (unsigned)(g.comp[0].blocks_x * g.comp[0].blocks_y);
         hipLaunchKernelGGL(k, dim3((nb + 255) / 256, 1, frames), dim3(256), 0, st, g, job->d_coefs, (const uint2*)job->d_blkrec, (const uint16_t*)job->d_tok,
                            job->tok_cap, job->d_qtab, job->d_raw, job->gs.width, job->gs.height, job->gs.width_padding);
-        if (job->idct_path) *job->idct_path = 2;
         return true;
     }
     const dim3 grid(((unsigned)g.block_count + 255) / 256, 1, frames);
     if (N == 4) hipLaunchKernelGGL(k_idct_scaled<4>, grid, dim3(256), 0, st, g, job->d_coefs, job->d_qtab, job->d_planes, job->zero_coefs);
     else if (N == 2) hipLaunchKernelGGL(k_idct_scaled<2>, grid, dim3(256), 0, st, g, job->d_coefs, job->d_qtab, job->d_planes, job->zero_coefs);
     else hipLaunchKernelGGL(k_idct_scaled<1>, grid, dim3(256), 0, st, g, job->d_coefs, job->d_qtab, job->d_planes, job->zero_coefs);
-    if (job->idct_path) *job->idct_path = 1;
     return false;
 }

@@ -8,10 +8,14 @@
 //   gj_dec_entropy_seq.hip      one lane per restart segment (interleaved scans with many short segments): k_huffman_decode_win over a ring the
 //                               lane refills itself (token mode), k_huffman_decode_seq over an LDS stage (plane mode)
 //   gj_dec_entropy_serial.hip   k_huffman_decode: one lane per restart segment, stream windows (Huffman tables that do not fit the two-level layout)
-//   gj_dec_idct.hip             k_idct_fused_* (from the planes), k_idct_tok_* (from tokens), k_idct / k_postprocess / k_copy_planes_out (generic)
+//   gj_dec_idct.hip             k_idct_fused_* (from the planes), k_idct_tok_* (from tokens; the full-size and the region kernel around one core:
+//                               gj_tok_tables, gj_tok_idct3), k_idct / k_postprocess / k_copy_planes_out (generic); gj_launch_idct: the IDCT side of
+//                               every kind of call and its one tail (debug stage, channel remap, gj_dec_job::idct_path)
 //   gj_dec_idct_scaled.hip      reduced-size output (dec_opt_scale): k_idct_scaled (from the planes), k_idct_tok_scaled_rgb444 (from tokens)
 //   gj_dec_region.hip           region decode (dec_opt_region): k_segment_select (table -> the entries that touch the region's cover), k_idct_region,
 //                               k_postprocess_region / k_copy_planes_region (cover blocks -> cover planes -> the region's pixels)
+//   this header                 what those share: the 4:4:4 configuration and its colour pairs (gj_is_rgb444, GJ_COLOR_PAIRS), gj_block_of, the block
+//                               records of the token-fed kernels (gj_rec_pack, gj_tok_record) and their token ranges (gj_tok_fetch)
 //   gj_bitreader.h              unstuffing of a restart segment into an LDS stage, two-level table look-up
 //
 // Restates src/gpujpeg_huffman_gpu_decoder.cu:135-495 (entropy decoding semantics; identical results to
@@ -234,10 +238,50 @@ __device__ __forceinline__ bool gj_fold_batch(const GjFold& F, const gj_geom& g,
 }
 
 // ---- IDCT side
+// Three components, 4:4:4, packed 3-byte pixels: the configuration of every k_idct_*_rgb444 kernel
+static inline bool gj_is_rgb444(const gj_geom& g)
+{
+    if (g.pixel_format != GJ_PF_444_P012 || g.comp_count != 3) return false;
+    for (int c = 0; c < 3; c++)
+        if (g.comp[c].samp_h != 1 || g.comp[c].samp_v != 1) return false;
+    return true;
+}
+// ... and the (color_space_internal, color_space) pairs those kernels are instantiated for, the first one for "no transform". A launcher makes its
+// array of instantiations from this list and takes entry gj_color_pair(g), the geometry's place in it (-1: not in the list).
+#define GJ_COLOR_PAIRS(X) \
+    X(GJ_CS_NONE, GJ_CS_NONE) X(GJ_CS_BT601_256, GJ_CS_RGB) X(GJ_CS_BT601, GJ_CS_RGB) X(GJ_CS_BT709, GJ_CS_RGB) X(GJ_CS_RGB, GJ_CS_BT601_256)
+static inline int gj_color_pair(const gj_geom& g)
+{
+    const int from = g.color_space_internal, to = g.color_space;
+    if (from == to || from == GJ_CS_NONE || to == GJ_CS_NONE) return 0;
+    int i = 0;
+#define GJ_X(F, T) \
+    if (from == F && to == T) return i; \
+    i++;
+    GJ_COLOR_PAIRS(GJ_X)
+#undef GJ_X
+    return -1;
+}
+
+// block gb of a geometry's planes (blocks of component 0 in raster order, then component 1's ...): its component, and its place in that component's grid
+__device__ __forceinline__ int gj_block_of(const gj_geom& g, const unsigned gb, unsigned& bx, unsigned& by)
+{
+    int c = 0;
+#pragma unroll
+    for (int i = 1; i < GJ_MAX_COMP; i++)
+        if (i < g.comp_count && (uint64_t)gb * 64 >= g.comp[i].data_offset) c = i;
+    const gj_comp_geom& k = g.comp[c];
+    const unsigned lb = gb - (unsigned)(k.data_offset / 64);
+    by = lb / (unsigned)k.blocks_x;
+    bx = lb - by * (unsigned)k.blocks_x;
+    return c;
+}
+
 typedef void (*gj_idct_tok_t)(const gj_geom, const int16_t*, const uint2*, const uint16_t*, uint32_t, const float*, uint8_t*);
 gj_idct_tok_t gj_idct_tok_for(const gj_geom& g); // the token-fed IDCT kernel for this configuration, or nullptr
 bool gj_is_uyvy422(const gj_geom& g);
-// dequantisation + IDCT + postprocessing of the frame; ev (may be null): events 2 and 3 of gj_hip_decode
+// dequantisation + IDCT + postprocessing of the frame, whichever kind of call it is (full size, reduced size, region); channel remap; the one place
+// that reports gj_dec_job::idct_path. ev (may be null): events 2 and 3 of gj_hip_decode
 void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_tok, gj_event_t* ev);
 // reduced-size decode (gj_dec_idct_scaled.hip): is there a token-fed kernel for this configuration; the IDCT side of the frame -- true: the pixels
 // are in d_raw, false: the reduced component planes are in d_planes and the pixel kernels follow with job->gs
@@ -291,6 +335,7 @@ __device__ __forceinline__ void gj_store_pixel(const gj_geom& g, uint8_t* __rest
 }
 
 // region decode (gj_dec_region.hip): the compacted segment table of job->region (from job's table, which has been written), and the IDCT side
+// up to the region's pixels (gj_launch_idct goes on from there)
 void gj_launch_segment_select(const gj_dec_job* job, hipStream_t st);
 void gj_launch_segment_select_batch(const gj_dec_job* job, hipStream_t st); // (a batch of regions: every frame's table against its own cover)
 void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, bool tokens, gj_event_t* ev);
@@ -325,3 +370,30 @@ __device__ __forceinline__ GjTokRange gj_tok_fetch(const uint16_t* __restrict__ 
     return r;
 }
 
+// A block's record as the token-fed kernels keep it: start = first token, cd = count << 16 | DC term, bit 31: "the block is in the coefficient
+// planes" (count 0xFFFF in the record) -- packed until the block is worked on (k_idct_tok_rgb444 has no register to spare, profiles/r5_11);
+// gj_rec_count takes the count out. The guards are for damaged streams: a record nobody wrote, a range that leaves the token array -- count 0.
+__device__ __forceinline__ uint32_t gj_rec_count(const uint32_t cd) { return (cd >> 16) & 0x7FFFu; }
+
+// a record as the array holds it -> its cd word: the ONE place with the guards
+__device__ __forceinline__ uint32_t gj_rec_pack(const uint2 r, const uint32_t tok_cap)
+{
+    uint32_t n = r.y >> 16;
+    const bool planes = n == 0xFFFFu;
+    if (planes || n > 63u || r.x > tok_cap || n > tok_cap - r.x) n = 0;
+    return (r.y & 0xFFFFu) | (n << 16) | (planes ? 0x80000000u : 0u);
+}
+
+// Component c's record of block position lb (4:4:4, non-interleaved scans: plane order == coding order); a lane without a block gets an empty range.
+// One call per component from the kernel's own unrolled loop: a helper that loads all three lets the compiler put the loads into one branch, which
+// costs k_idct_tok_scaled_rgb444<1> four registers.
+__device__ __forceinline__ void gj_tok_record(const gj_geom& g, const uint2* d_rec, const uint32_t tok_cap, const bool has_block, const unsigned lb,
+                                              const int c, uint32_t& start, uint32_t& cd)
+{
+    start = cd = 0;
+    if (has_block) {
+        const uint2 r = d_rec[g.comp[c].data_offset / 64 + lb];
+        start = r.x;
+        cd = gj_rec_pack(r, tok_cap);
+    }
+}

@@ -18,7 +18,7 @@
 // (part of the decoder's device code, see gj_dec_internal.h for the map of the files)
 #include "gj_dec_internal.h"
 
-extern "C" int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s) { return gj_segment_in_cover(*g, *r, s) ? 1 : 0; }
+extern "C" int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s) { return gj_segment_in_cover(*g, r->frame, s) ? 1 : 0; }
 
 // ================================================================================================
 // Selection
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(GJ_SEL_CHUNK) void k_segment_select(const gj_geom g
     for (int base = 0; base < front; base += GJ_SEL_CHUNK) {
         const int i = base + tid;
         const uint32_t s = i < front ? seg_index[i] : 0xFFFFFFFFu;
-        const bool in = i < front && gj_segment_in_cover(g, r, (int)s);
+        const bool in = i < front && gj_segment_in_cover(g, r.frame, (int)s);
         before += (uint32_t)__popcll(__ballot(in));
         if (last_wg) {
             const int sc = in ? gj_segment_scan(g, s) : -1;
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(GJ_SEL_CHUNK) void k_segment_select(const gj_geom g
     // the chunk
     const int i = begin + tid;
     const uint32_t s = i < n ? seg_index[i] : 0xFFFFFFFFu;
-    const bool in = i < n && gj_segment_in_cover(g, r, (int)s);
+    const bool in = i < n && gj_segment_in_cover(g, r.frame, (int)s);
     const unsigned long long b = __ballot(in);
     if (last_wg) {
         const int sc = in ? gj_segment_scan(g, s) : -1;
@@ -204,20 +204,16 @@ void gj_launch_segment_select_batch(const gj_dec_job* job, hipStream_t st)
 // data_offset of every component describe the cover-sized planes. One lane per block of the cover; a block of the cover is block
 // (bx0 + bx, by0 + by) of the component's coefficient plane, which holds its blocks in raster order for every kind of scan.
 // (BATCH: gr holds the planes of the largest cover of the batch, r is the frame's: lanes beyond the frame's own cover leave)
-// (R: gj_region, or a frame's gj_region_frame where it lies in device memory)
-template <bool BATCH, class R>
-__device__ __forceinline__ void gj_idct_region_body(const gj_geom& g, const gj_geom& gr, const R& r, const int16_t* __restrict__ coefs,
+// (r: gj_region::frame, or the frame's record where it lies in device memory)
+template <bool BATCH>
+__device__ __forceinline__ void gj_idct_region_body(const gj_geom& g, const gj_geom& gr, const gj_region_frame& r, const int16_t* __restrict__ coefs,
                                                     const float* __restrict__ qtab, uint8_t* __restrict__ planes)
 {
     const unsigned gb = blockIdx.x * 256u + threadIdx.x;
     if (gb >= (unsigned)gr.block_count) return;
-    int c = 0;
-#pragma unroll
-    for (int i = 1; i < GJ_MAX_COMP; i++)
-        if (i < gr.comp_count && (uint64_t)gb * 64 >= gr.comp[i].data_offset) c = i;
+    unsigned bx, by;
+    const int c = gj_block_of(gr, gb, bx, by);
     const gj_comp_geom& k = gr.comp[c];
-    const unsigned lb = gb - (unsigned)(k.data_offset / 64);
-    const unsigned by = lb / (unsigned)k.blocks_x, bx = lb - by * (unsigned)k.blocks_x;
     if (BATCH && (bx >= (unsigned)(r.bx1[c] - r.bx0[c]) || by >= (unsigned)(r.by1[c] - r.by0[c]))) return;
     const gj_comp_geom& kf = g.comp[c];
     const unsigned fbx = (unsigned)r.bx0[c] + bx, fby = (unsigned)r.by0[c] + by;
@@ -241,7 +237,7 @@ __device__ __forceinline__ void gj_idct_region_body(const gj_geom& g, const gj_g
 __global__ __launch_bounds__(256) void k_idct_region(const gj_geom g, const gj_geom gr, const gj_region r, const int16_t* __restrict__ coefs,
                                                      const float* __restrict__ qtab, uint8_t* __restrict__ planes)
 {
-    gj_idct_region_body<false>(g, gr, r, coefs, qtab, planes);
+    gj_idct_region_body<false>(g, gr, r.frame, coefs, qtab, planes);
 }
 
 // frame blockIdx.z of a batch of regions (the planes of a frame take as many bytes as its coefficients take elements at most)
@@ -253,8 +249,7 @@ __global__ __launch_bounds__(256) void k_idct_region_batch(const gj_geom g, cons
 }
 
 // sample of component c that pixel (x, y) of the REGION needs, in the cover-sized plane: pixel (r.x + x, r.y + y) of the stream's image
-template <class R>
-__device__ __forceinline__ size_t gj_region_sample(const gj_comp_geom& k, const R& r, const int c, const unsigned x, const unsigned y)
+__device__ __forceinline__ size_t gj_region_sample(const gj_comp_geom& k, const gj_region_frame& r, const int c, const unsigned x, const unsigned y)
 {
     const unsigned sx = ((unsigned)r.x + x) / (unsigned)k.sub_h - (unsigned)r.bx0[c] * 8u;
     const unsigned sy = ((unsigned)r.y + y) / (unsigned)k.sub_v - (unsigned)r.by0[c] * 8u;
@@ -264,8 +259,7 @@ __device__ __forceinline__ size_t gj_region_sample(const gj_comp_geom& k, const 
 }
 
 // k_postprocess for a region: one lane per pixel of the W x H image (raw_width x height of gr)
-template <class R>
-__device__ __forceinline__ void gj_postprocess_region_body(const gj_geom& gr, const R& r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+__device__ __forceinline__ void gj_postprocess_region_body(const gj_geom& gr, const gj_region_frame& r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
 {
     const unsigned W = (unsigned)gr.raw_width, H = (unsigned)gr.height;
     const unsigned pos = blockIdx.x * 256u + threadIdx.x;
@@ -282,7 +276,7 @@ __device__ __forceinline__ void gj_postprocess_region_body(const gj_geom& gr, co
 
 __global__ __launch_bounds__(256) void k_postprocess_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
 {
-    gj_postprocess_region_body(gr, r, planes, raw);
+    gj_postprocess_region_body(gr, r.frame, planes, raw);
 }
 
 // frame blockIdx.z of a batch of regions: its rectangle, its cover planes (laid out for the largest cover: gr), its pixels
@@ -293,8 +287,7 @@ __global__ __launch_bounds__(256) void k_postprocess_region_batch(const gj_geom 
 }
 
 // k_copy_planes_out for a region: plane c of the result is the crop of plane c at (r.x / sub_h, r.y / sub_v), k.width x k.height samples
-template <class R>
-__device__ __forceinline__ void gj_copy_planes_region_body(const gj_geom& gr, const R& r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+__device__ __forceinline__ void gj_copy_planes_region_body(const gj_geom& gr, const gj_region_frame& r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
 {
     size_t dst_off = 0;
     for (int c = 0; c < gr.comp_count; c++) {
@@ -312,7 +305,7 @@ __device__ __forceinline__ void gj_copy_planes_region_body(const gj_geom& gr, co
 
 __global__ __launch_bounds__(256) void k_copy_planes_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
 {
-    gj_copy_planes_region_body(gr, r, planes, raw);
+    gj_copy_planes_region_body(gr, r.frame, planes, raw);
 }
 
 __global__ __launch_bounds__(256) void k_copy_planes_region_batch(const gj_geom gr, const gj_region rb, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
@@ -321,50 +314,29 @@ __global__ __launch_bounds__(256) void k_copy_planes_region_batch(const gj_geom 
     gj_copy_planes_region_body(gr, rb.d_frames[z], planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
 }
 
-// The IDCT side of a region call: cover blocks -> cover planes -> region pixels (+ channel remap on the region image).
+// The IDCT side of a region call: cover blocks -> cover planes -> region pixels. A batch of regions (d_frames) runs the same stages through the
+// _batch kernels with blockIdx.z = frame and grids for the largest cover (gr).
 void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tokens, gj_event_t* ev)
 {
     const gj_geom& gr = job->gs;
     const gj_region& r = job->region;
-    if (r.d_frames != nullptr) { // a batch of regions: the same stages with blockIdx.z = frame, grids for the largest cover (gr)
-        const unsigned frames = job->batch.count;
-        if (tokens) {
-            gj_launch_idct_tok_region(job, st);
-            if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
-        } else {
-            hipLaunchKernelGGL(k_idct_region_batch, dim3(((unsigned)gr.block_count + 255) / 256, 1, frames), dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtabf,
-                               job->d_planes);
-            if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
-            if (gr.no_transform) {
-                const size_t n = (size_t)gr.comp[0].width * gr.comp[0].height;
-                hipLaunchKernelGGL(k_copy_planes_region_batch, dim3((unsigned)min((n + 255) / 256, (size_t)2048), 1, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
-            } else {
-                const unsigned n = (unsigned)gr.raw_width * (unsigned)gr.height;
-                hipLaunchKernelGGL(k_postprocess_region_batch, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
-            }
-        }
-        gj_debug_stage(job->tune.debug_sync != 0, st, "idct / postprocess (batch of regions)");
-        if (job->idct_path) *job->idct_path = tokens ? 4 : 3;
-        return;
-    }
+    const bool batch = r.d_frames != nullptr;
+    const unsigned frames = batch ? job->batch.count : 1u;
     if (tokens) { // token mode: records and tokens of the cover's blocks -> region pixels (k_idct_tok_region_rgb444)
         gj_launch_idct_tok_region(job, st);
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
+        return;
+    }
+    hipLaunchKernelGGL(batch ? k_idct_region_batch : k_idct_region, dim3(((unsigned)gr.block_count + 255) / 256, 1, frames), dim3(256), 0, st, job->g, gr, r,
+                       job->d_coefs, job->d_qtabf, job->d_planes);
+    if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
+    if (gr.no_transform) {
+        const size_t n = (size_t)gr.comp[0].width * gr.comp[0].height;
+        hipLaunchKernelGGL(batch ? k_copy_planes_region_batch : k_copy_planes_region, dim3((unsigned)min((n + 255) / 256, (size_t)2048), 1, frames), dim3(256), 0, st,
+                           gr, r, job->d_planes, job->d_raw);
     } else {
-        hipLaunchKernelGGL(k_idct_region, dim3(((unsigned)gr.block_count + 255) / 256), dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtabf, job->d_planes);
-        if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
-        if (gr.no_transform) {
-            const size_t n = (size_t)gr.comp[0].width * gr.comp[0].height;
-            hipLaunchKernelGGL(k_copy_planes_region, dim3((unsigned)min((n + 255) / 256, (size_t)2048)), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
-        } else {
-            const unsigned n = (unsigned)gr.raw_width * (unsigned)gr.height;
-            hipLaunchKernelGGL(k_postprocess_region, dim3((n + 255) / 256), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
-        }
+        const unsigned n = (unsigned)gr.raw_width * (unsigned)gr.height;
+        hipLaunchKernelGGL(batch ? k_postprocess_region_batch : k_postprocess_region, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, gr, r, job->d_planes,
+                           job->d_raw);
     }
-    gj_debug_stage(job->tune.debug_sync != 0, st, "idct / postprocess (region)");
-    if (job->channel_remap) {
-        const unsigned n = (unsigned)gr.width * (unsigned)gr.height;
-        hipLaunchKernelGGL(k_channel_remap, dim3((n + 255) / 256), dim3(256), 0, st, gr, job->d_raw, job->channel_remap & 0xFFFFu);
-    }
-    if (job->idct_path) *job->idct_path = tokens ? 4 : 3;
 }

@@ -90,7 +90,7 @@ struct gpujpeg_decoder {
     gj_region rg;                                  /* call_region: pixel rectangle, cover, planned selection */
     uint32_t* d_sel; size_t d_sel_cap;             /* the compacted segment table of a selection */
     uint32_t* d_sel_count; uint32_t* h_sel_count;  /* its entry count on the device; pinned: [0] the same, [1 + c] entries of scan c */
-    gj_region plan_rg; bool plan_valid;            /* the region whose sel_count is in plan_rg (the count is a loop over the geometry's segments) */
+    gj_region_frame plan_cover; int plan_sel[GJ_MAX_COMP]; bool plan_valid; /* the cover whose selection plan_sel counts (a loop over the geometry's segments) */
     long region_stats[4];                          /* gpujpeg_amd_decoder_get_region_stats */
     /* batches of regions (gpujpeg_amd_decoder_decode_batch_regions): one rectangle per frame */
     uint32_t* b_sel; size_t b_sel_cap;             /* device: the compacted segment tables of one chunk of frames, laid out like b_seg */
@@ -142,18 +142,21 @@ static int dec_region_geometry(struct gpujpeg_decoder* d)
     if (gj_geom_init_region(&d->geom_s, &rg, &c->geom, &c->param, &c->param_image, d->region, d->req_alignment, &d->pi_s) != 0) return -1;
     /* the plan of a selection: one question per segment of the geometry, asked again only when the region or the stream's geometry changes */
     if (c->geom.restart_interval > 0) {
-        /* (keyed on the cover itself -- the pixel rectangle alone does not fix it: packed 4:2:2 output widens it to the pixel pair --; a new geometry
-         * drops the plan in decoder_configure) */
-        if (!d->plan_valid || memcmp(d->plan_rg.bx0, rg.bx0, (size_t)((const char*)rg.sel_count - (const char*)rg.bx0)) != 0) {
+        /* (keyed on the cover itself -- the pixel rectangle alone does not fix it: packed 4:2:2 output widens it to the pixel pair --, so with the
+         * origin taken out: it moves inside a cover without changing the selection; a new geometry drops the plan in decoder_configure) */
+        gj_region_frame cover = rg.frame;
+        cover.x = cover.y = 0;
+        if (!d->plan_valid || memcmp(&d->plan_cover, &cover, sizeof cover) != 0) {
             memset(rg.sel_count, 0, sizeof rg.sel_count);
             for (int sc = 0, s = 0; sc < c->geom.scan_count && sc < GJ_MAX_COMP; sc++) {
                 const int n = c->geom.interleaved ? c->geom.segment_count : c->geom.comp[sc].segment_count;
                 for (int i = 0; i < n; i++, s++) rg.sel_count[sc] += gj_hip_segment_in_cover(&c->geom, &rg, s);
             }
-            d->plan_rg = rg;
+            d->plan_cover = cover;
+            memcpy(d->plan_sel, rg.sel_count, sizeof d->plan_sel);
             d->plan_valid = true;
         }
-        memcpy(rg.sel_count, d->plan_rg.sel_count, sizeof rg.sel_count);
+        memcpy(rg.sel_count, d->plan_sel, sizeof rg.sel_count);
     }
     d->rg = rg;
     d->call_region = true;
@@ -367,11 +370,22 @@ static void geom_take_tables(gj_geom* g, const struct gj_reader_result* r)
     }
 }
 
+/* a selection's share of every scan's bytes -- sel[sc] of the scan's segments --: an estimate, it only sizes the entropy decoders' batches */
+static void selected_scan_bytes(const gj_geom* g, const int sel[GJ_MAX_COMP], uint32_t scan_bytes[GJ_MAX_COMP])
+{
+    for (int sc = 0; sc < g->scan_count && sc < GJ_MAX_COMP; sc++) {
+        const int all = g->interleaved ? g->segment_count : g->comp[sc].segment_count;
+        if (all > 0) scan_bytes[sc] = (uint32_t)((uint64_t)scan_bytes[sc] * (uint64_t)sel[sc] / (uint64_t)all);
+    }
+}
+
 /* everything of a job that comes from the decoder's state and options (geometry with its table selectors included: set those first) */
-static void dec_job_base(const struct gpujpeg_decoder* d, bool tab2_ok, gj_dec_job* job)
+static void dec_job_base(struct gpujpeg_decoder* d, bool tab2_ok, gj_dec_job* job)
 {
     const struct gj_coder* c = &d->coder;
     memset(job, 0, sizeof *job);
+    d->last_idct_path = 0;
+    job->idct_path = &d->last_idct_path;
     job->g = c->geom;
     job->d_huff_tab = d->d_huff_tab;
     job->d_qtab = d->d_qtab;
@@ -660,8 +674,6 @@ static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
     job.scan = k->scan_deferred;
     d->last_folded = 0;
     job.scan.folded = &d->last_folded;
-    d->last_idct_path = 0;
-    job.idct_path = &d->last_idct_path;
     if (k->spec) d->n_spec++;
     job.d_raw = k->d_raw;
     if (gj_channel_remap_check(d->channel_remap, c->param_image.pixel_format) != 0) return -1;
@@ -717,11 +729,7 @@ static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
         }
     }
     if (!k->spec && k->seg_count != g->segment_count) memset(job.scan_bytes, 0, sizeof job.scan_bytes); /* (table and geometry out of step: one batch size) */
-    if (k->select) /* (the selected share of every scan's bytes: an estimate, it only sizes the batches) */
-        for (int sc = 0; sc < g->scan_count && sc < GJ_MAX_COMP; sc++) {
-            const int all = g->interleaved ? g->segment_count : g->comp[sc].segment_count;
-            if (all > 0) job.scan_bytes[sc] = (uint32_t)((uint64_t)job.scan_bytes[sc] * (uint64_t)d->rg.sel_count[sc] / (uint64_t)all);
-        }
+    if (k->select) selected_scan_bytes(g, d->rg.sel_count, job.scan_bytes);
     if (gj_hip_decode(&job, c->stream, k->stats ? c->timers.ev : NULL) != 0) {
         GJ_ERROR("Decoder kernels failed: %s\n", gj_hip_last_error());
         return -1;
@@ -966,7 +974,7 @@ struct dec_batch {
 /* restart segments of scan sc with a block / an MCU inside the cover: what counting gj_hip_segment_in_cover over the scan's segments gives, in closed
  * form -- a row of the cover is a run of cells, cell i belongs to segment i / restart_interval, and the rows' runs of segments follow each other
  * (a segment that wraps from one row's end to the next row's start is counted once) */
-static int region_scan_segments(const gj_geom* g, const gj_region* r, int sc)
+static int region_scan_segments(const gj_geom* g, const gj_region_frame* r, int sc)
 {
     const int gridx = g->interleaved ? g->mcu_count_x : g->comp[sc].blocks_x, ri = g->restart_interval;
     const int x0 = g->interleaved ? r->mx0 : r->bx0[sc], x1 = g->interleaved ? r->mx1 : r->bx1[sc];
@@ -1002,17 +1010,14 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b)
             return -1;
         }
         b->rg_one = rg;
-        gj_region_frame* rf = d->bh_rgn + f;
-        rf->x = rg.x; rf->y = rg.y;
-        memcpy(rf->bx0, rg.bx0, sizeof rf->bx0); memcpy(rf->by0, rg.by0, sizeof rf->by0);
-        memcpy(rf->bx1, rg.bx1, sizeof rf->bx1); memcpy(rf->by1, rg.by1, sizeof rf->by1);
-        rf->mx0 = rg.mx0; rf->my0 = rg.my0; rf->mx1 = rg.mx1; rf->my1 = rg.my1;
+        const gj_region_frame* rf = &rg.frame;
+        d->bh_rgn[f] = *rf;
         for (int i = 0; i < g->comp_count && i < GJ_MAX_COMP; i++) {
-            if (rg.bx1[i] - rg.bx0[i] > wmax[i]) wmax[i] = rg.bx1[i] - rg.bx0[i];
-            if (rg.by1[i] - rg.by0[i] > hmax[i]) hmax[i] = rg.by1[i] - rg.by0[i];
+            if (rf->bx1[i] - rf->bx0[i] > wmax[i]) wmax[i] = rf->bx1[i] - rf->bx0[i];
+            if (rf->by1[i] - rf->by0[i] > hmax[i]) hmax[i] = rf->by1[i] - rf->by0[i];
         }
         for (int sc = 0; sc < GJ_MAX_COMP; sc++) {
-            const int n = sc < g->scan_count && g->restart_interval > 0 ? region_scan_segments(g, &rg, sc) : 0;
+            const int n = sc < g->scan_count && g->restart_interval > 0 ? region_scan_segments(g, rf, sc) : 0;
             b->plan[f * GJ_MAX_COMP + sc] = n;
             if (n > b->plan_max[sc]) b->plan_max[sc] = n;
         }
@@ -1235,21 +1240,12 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         memset(d->bh_found, 0xFF, found_bytes);
         job.gs = b->gs_max;
         job.region.select = 1;
-        job.region.x = job.region.y = 0;
+        memset(&job.region.frame, 0, sizeof job.region.frame); /* (not used: d_frames) */
         memcpy(job.region.sel_count, b->plan_max, sizeof job.region.sel_count);
         job.region.d_sel = d->b_sel;
         job.region.d_sel_count = NULL;
         job.seg_count = g->segment_count; /* (entries of a frame's table at most; gj_hip_decode hands the entropy decoders the plan's) */
-        d->last_idct_path = 0;
-        job.idct_path = &d->last_idct_path;
-        for (int sc = 0; sc < g->scan_count && sc < GJ_MAX_COMP; sc++) { /* (the selected share of every scan's bytes: it only sizes the batches) */
-            const int all = g->interleaved ? g->segment_count : g->comp[sc].segment_count;
-            if (all > 0) job.scan_bytes[sc] = (uint32_t)((uint64_t)job.scan_bytes[sc] * (uint64_t)b->plan_max[sc] / (uint64_t)all);
-        }
-    }
-    if (job.scale > 1) { /* (a reduced-size batch: dec_job_base has set scale and gs = geom_s) */
-        d->last_idct_path = 0;
-        job.idct_path = &d->last_idct_path;
+        selected_scan_bytes(g, b->plan_max, job.scan_bytes);
     }
     B.jpeg = d_stride;
     B.raw = b->d_out_stride;

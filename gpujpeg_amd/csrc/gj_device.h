@@ -103,9 +103,8 @@ __device__ __forceinline__ uint64_t gj_segment_block(const gj_geom& g, const GjS
 // rectangle [x0, x1) x [y0, y1) in its first row (cells xa .. end of the row), in its last row (0 .. xb) or in any whole row between them.
 // The ONE statement of the selection: k_segment_select (for every kind of table, a host-walked one included) and -- through gj_hip_segment_in_cover -- the host's count of the
 // batch plan ask here.
-// (R: gj_region, or the gj_region_frame of one frame of a batch of regions, read where it lies in device memory)
-template <class R>
-__host__ __device__ inline bool gj_segment_in_cover(const gj_geom& g, const R& r, const int s)
+// (r: gj_region::frame, or one frame's record of a batch of regions, read where it lies in device memory)
+__host__ __device__ inline bool gj_segment_in_cover(const gj_geom& g, const gj_region_frame& r, const int s)
 {
     if (s < 0 || s >= g.segment_count) return false;
     int c = 0, gridx, total, x0, y0, x1, y1, k = s;
@@ -130,16 +129,6 @@ __host__ __device__ inline bool gj_segment_in_cover(const gj_geom& g, const R& r
     if (mid_lo <= mid_hi) return true;
     if (ya >= y0 && ya < y1 && xa < x1 && (ya == yb ? xb : gridx - 1) >= x0) return true;
     return yb != ya && yb >= y0 && yb < y1 && xb >= x0;
-}
-
-// A batch of regions (gj_region::d_frames): the region of one frame -- the batch's (size, selection plan, buffers) with the frame's origin and covers
-__host__ __device__ inline gj_region gj_region_of_frame(const gj_region& batch, const gj_region_frame& f)
-{
-    gj_region r = batch;
-    r.x = f.x; r.y = f.y;
-    for (int c = 0; c < GJ_MAX_COMP; c++) { r.bx0[c] = f.bx0[c]; r.by0[c] = f.by0[c]; r.bx1[c] = f.bx1[c]; r.by1[c] = f.by1[c]; }
-    r.mx0 = f.mx0; r.my0 = f.my0; r.mx1 = f.mx1; r.my1 = f.my1;
-    return r;
 }
 
 // LDS written by some lanes of a wave is read by other lanes of the SAME wave: the hardware keeps a wave's LDS operations in

@@ -260,31 +260,30 @@ typedef struct gj_scan_deferred {
 
 /* Region-of-interest decode (dec_opt_region): the W x H pixels at (x, y) of the stream's image. The COVER of the region is, per component, the
  * smallest rectangle of 8x8 blocks -- whole MCUs of an interleaved scan -- that holds every sample the region's pixels need. */
-struct gj_region_frame;
+/* origin and cover of ONE rectangle: what a single region call has once (gj_region::frame) and a batch of regions once per frame, in device
+ * memory (gj_region::d_frames) */
+typedef struct gj_region_frame {
+    int x, y;                      /* pixels of the stream's image */
+    int bx0[GJ_MAX_COMP], by0[GJ_MAX_COMP], bx1[GJ_MAX_COMP], by1[GJ_MAX_COMP]; /* cover: blocks [bx0, bx1) x [by0, by1) of the component's grid */
+    int mx0, my0, mx1, my1;        /* interleaved scan: the cover in MCUs */
+} gj_region_frame;
 typedef struct gj_region {
     int on;                        /* 1: this call decodes a region */
     int select;                    /* 1: only the restart segments that touch the cover are entropy-decoded (k_segment_select compacts the table) */
-    int x, y, w, h;                /* pixels of the stream's image */
-    int bx0[GJ_MAX_COMP], by0[GJ_MAX_COMP], bx1[GJ_MAX_COMP], by1[GJ_MAX_COMP]; /* cover: blocks [bx0, bx1) x [by0, by1) of the component's grid */
-    int mx0, my0, mx1, my1;        /* interleaved scan: the cover in MCUs */
+    int w, h;                      /* pixels of the region */
+    gj_region_frame frame;         /* where it lies in the stream's image, and its cover */
     int sel_count[GJ_MAX_COMP];    /* select: segments of every scan that touch the cover, as the geometry gives them (the batch plan) */
     uint32_t* d_sel;               /* select: the compacted table, three arrays of (g.segment_count + GJ_MAX_COMP) words: pos | len | index */
     uint32_t* d_sel_count;         /* select: device word, entries of the compacted table (what the entropy decoders bound their work with) */
     uint32_t* h_sel_count;         /* select: pinned host words written by k_segment_select: [0] entries of the compacted table, [1 + c] of scan c */
     /* a batch of regions (gj_dec_job::batch together with region.on: gpujpeg_amd_decoder_decode_batch_regions) -- one w x h for all frames, the
-     * origin and with it the cover PER FRAME: x, y, the covers and the MCU rectangle above are not used, frame f's are d_frames[f]. select is 1.
+     * origin and with it the cover PER FRAME: `frame` above is not used, frame f's is d_frames[f]. select is 1.
      * sel_count[c] is the LARGEST selection of scan c among the frames: frame f's compacted table (d_sel + f x gj_frame_strides::seg words, laid out
      * like the frame's segment table) holds its own selection of scan c from entry sum(sel_count[0 .. c)) on and null entries (index 0xFFFFFFFF,
      * length 0: a segment without blocks for the entropy decoders) up to the next scan's, so that ONE batch plan serves every frame. d_sel_count is
      * not used (every compacted table has sum(sel_count) entries); h_sel_count holds GJ_MAX_COMP words per frame: the entries found per scan. */
-    const struct gj_region_frame* d_frames; /* device memory, [gj_batch::count]; NULL: a single frame */
+    const gj_region_frame* d_frames; /* device memory, [gj_batch::count]; NULL: a single frame */
 } gj_region;
-/* what gj_region carries per frame of a batch of regions */
-typedef struct gj_region_frame {
-    int x, y;
-    int bx0[GJ_MAX_COMP], by0[GJ_MAX_COMP], bx1[GJ_MAX_COMP], by1[GJ_MAX_COMP];
-    int mx0, my0, mx1, my1;
-} gj_region_frame;
 /* the predicate of the selection (gj_device.h: gj_segment_in_cover) for host code: does restart segment s have a block / an MCU inside the cover? */
 GJ_HIP_API int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s);
 
