@@ -202,8 +202,12 @@ static int encoder_configure(struct gpujpeg_encoder* e, const struct gpujpeg_par
     if (gj_ensure_device_buffer((void**)&e->d_scan_hdr, &e->d_scan_hdr_cap, e->scan_hdrs.size + 16) != 0) return -1;
     if (gj_hip_memcpy_h2d(e->d_scan_hdr, e->scan_hdrs.bytes, e->scan_hdrs.size, c->stream) != 0) return -1;
     if (gj_hip_stream_sync(c->stream) != 0) return -1; /* scan_hdrs.bytes is pageable: finish before it can change */
-    /* same sizing rule as the reference writer (writer.c:66-69) plus the scan headers */
-    const size_t jpeg_cap = 1000 + e->scan_hdrs.size + (size_t)pi->width * pi->height * p->comp_count * 2 + 4096;
+    /* The reference writer's rule (writer.c:66-69: 1000 + 2 bytes per sample of the image) plus the scan headers -- but over the samples that
+     * are CODED: whole padded blocks (g->data_size), of which a thin image has many times its own samples (65535x1: eight rows of blocks for
+     * one of pixels), where the reference's count of real samples is too small for ordinary content. An image of whole MCUs keeps the
+     * reference's size; with chroma subsampling the real samples of all components outnumber the coded ones anyway. */
+    const size_t real_samples = (size_t)pi->width * pi->height * p->comp_count;
+    const size_t jpeg_cap = 1000 + e->scan_hdrs.size + 2 * (real_samples > g->data_size ? real_samples : g->data_size) + 4096;
     if (gj_ensure_device_buffer((void**)&e->d_jpeg, &e->d_jpeg_cap, jpeg_cap) != 0) return -1;
     e->hdr_sent_to = NULL; /* (the buffer may be a new one: the main header has to be uploaded again) */
     c->configured = true;
@@ -303,6 +307,13 @@ static int encoder_prepare(struct gpujpeg_encoder* e, const struct gpujpeg_param
     return encoder_configure(e, p, pi);
 }
 
+/* The capacity the assembly kernels are told and the host reports: the stream buffer's, or less under the developer setting GJ_ENC_OUT_CAP=<bytes>
+ * (tests: the kernels' overflow guard, which no image reaches through the public API) -- never more than the buffer holds */
+static size_t enc_out_capacity(const struct gpujpeg_encoder* e)
+{
+    return e->tune.enc_out_cap > 0 && (size_t)e->tune.enc_out_cap < e->d_jpeg_cap ? (size_t)e->tune.enc_out_cap : e->d_jpeg_cap;
+}
+
 /* everything of a job that comes from the encoder's state and options; the caller adds where the pixels are and where tile streams, segment
  * words, result words and the file go */
 static void enc_job_base(const struct gpujpeg_encoder* e, const struct gpujpeg_parameters* p, gj_enc_job* job)
@@ -317,7 +328,7 @@ static void enc_job_base(const struct gpujpeg_encoder* e, const struct gpujpeg_p
     job->d_fwd_q[0] = e->d_fwd_q[0];
     job->d_fwd_q[1] = e->d_fwd_q[1];
     job->d_huff_lut = e->d_huff_lut;
-    job->jpeg_capacity = e->d_jpeg_cap;
+    job->jpeg_capacity = enc_out_capacity(e);
     job->d_scan_partial = e->d_scan_partial;
     job->tune = e->tune;
     job->d_scan_hdr = e->d_scan_hdr;
@@ -461,7 +472,7 @@ int gpujpeg_encoder_encode(struct gpujpeg_encoder* e, const struct gpujpeg_param
     in_flight = false;
     const size_t size = e->h_result[0];
     if (e->h_result[1]) {
-        GJ_ERROR("Compressed stream (%zu B) does not fit the output buffer (%zu B)!\n", size, e->d_jpeg_cap);
+        GJ_ERROR("Compressed stream (%zu B) does not fit the output buffer (%zu B)!\n", size, enc_out_capacity(e));
         goto out;
     }
     if (e->out_location == GJ_OUT_DEVICE) {
@@ -568,7 +579,7 @@ static int batch_streams_out(struct gpujpeg_encoder* e, int count, size_t slot, 
     size_t longest = 0;
     for (int f = 0; f < count; f++) {
         if (e->bh_result[2 * f + 1]) {
-            GJ_ERROR("Compressed stream (%u B) of frame %d does not fit the output buffer (%zu B)!\n", e->bh_result[2 * f], f, e->d_jpeg_cap);
+            GJ_ERROR("Compressed stream (%u B) of frame %d does not fit the output buffer (%zu B)!\n", e->bh_result[2 * f], f, enc_out_capacity(e));
             return -1;
         }
         images_compressed_size[f] = e->bh_result[2 * f];
@@ -749,8 +760,9 @@ size_t gpujpeg_encoder_max_memory(struct gpujpeg_parameters* param, struct gpujp
     if (p.restart_interval == RESTART_AUTO) p.restart_interval = gpujpeg_encoder_suggest_restart_interval(&t, gj_make_sampling_factor(p.comp_count, p.sampling_factor), p.interleaved, -1);
     gj_geom g;
     if (gj_geom_init(&g, &p, &t, true) != 0) return 0;
+    const size_t real_samples = (size_t)t.width * t.height * p.comp_count; /* (the stream buffer: as encoder_configure sizes it) */
     size_t total = g.data_size * 3 + (size_t)g.block_count * GJ_TEMP_BYTES_PER_BLOCK + (size_t)g.segment_count * 20 +
-                   1000 + (size_t)t.width * t.height * p.comp_count * 2;
+                   1000 + 2 * (real_samples > g.data_size ? real_samples : g.data_size);
     if (type == GPUJPEG_ENCODER_INPUT_IMAGE) total += g.raw_size;
     return total;
 }

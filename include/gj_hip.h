@@ -157,6 +157,8 @@ typedef struct gj_tuning {
                             workgroups, a third of the work each) 1 = always, -1 = never, 0 = small frames only */
     int dec_fill;        /* GJ_DEC_FILL=<32nds>: how full the sub-sequence decoders' LDS stage is planned on average (default 23, up to 27 when that keeps
                             a single frame within one generation of workgroups); A/B runs of the batch plan */
+    int enc_out_cap;     /* GJ_ENC_OUT_CAP=<bytes>: the assembly kernels and the host's checks take min(the stream buffer's size, bytes) as the output
+                            capacity (0: the buffer's size); tests of the overflow guard, which no image reaches through the public API */
     int dec_careful;     /* set by the host for ONE call, never from the environment: a kernel that takes whole segments into LDS met one that
                             does not fit (overflow flag) -- this call uses the kernels without that limit */
 } gj_tuning;

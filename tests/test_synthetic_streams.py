@@ -12,12 +12,17 @@ the Python writer without any product code; (c) pixels are oracle.decode (reduce
 regions: a numpy crop); (d) CPU tier only, where oracle/_ref is built: the reference's own library decodes every synthetic stream to the oracle's
 pixels. Every comparison of a decode is byte for byte.
 
+The encoder's own limit, the size of its output buffer, is the last section but one: thin frames whose stream the reference's sizing rule does not
+hold, frames of 65535 pixels in one dimension, and the assembly kernels' overflow guard on both sides of its boundary (GJ_ENC_OUT_CAP).
+
 Two tiers with the same bodies: the CPU tier runs the product's kernels on tests/hipemu, the -m gpu tier the product library on the MI355X. One test
 re-runs the CPU tier on the AddressSanitizer + UBSan build of the execution model. tests/MUTATIONS.md records which of these tests fail for which
-deliberate defect of the decoder.
+deliberate defect of the decoder and of the encoder's output limit.
 
 Times: the CPU tier of this file takes about 95 s on 8 cores (pytest -n 8), its slowest test 29 s (test_mixed_batches_in_token_mode); the sanitizer
-re-run 7 min 20 s. The -m gpu tier had not been timed on an MI355X when this file was written."""
+re-run 7 min 20 s. The -m gpu tier had not been timed on an MI355X when this file was written. With the output-limit section: the CPU tier without
+the sanitizer re-run about 3 min on 8 cores (the 65535-pixel frames take 15 .. 45 s each on the execution model, eight decoder paths twice), the
+sanitizer re-run 12 min 20 s of its 25 min limit with other work on the machine."""
 import ctypes as C
 import functools
 import os
@@ -536,6 +541,298 @@ def test_encoder_batch_at_the_extremes(O, G, dlib, size):
         assert g.size == want.size and np.array_equal(g, want), x
     got = enc.encode_batch_ptrs(p, pi, [np.array(r) for r in raws])
     assert all(np.array_equal(g, enc_expected(x, size[0], 100)[1]) for x, g in zip(patterns, got))
+    enc.close()
+
+
+# ================================================================================================ encoder: the output-buffer limit
+# The encoder's stream buffer holds 1000 + scan headers + 2 bytes per CODED sample (whole padded blocks; gj_encoder.c encoder_configure) + 4096 bytes.
+# The reference counts the image's own samples, which a thin image exceeds with ordinary content (65535x1 codes eight rows of blocks for one of
+# pixels): those frames are the first seven LIMIT_CASES. With the padded count a frame has about 2 bytes per coded sample of room and 0/255 noise at
+# quality 100 needs 1.6, so no image reaches the assembly kernels' guard (k_gather; k_scan_segments + k_assemble + k_segment_info) and the host
+# checks behind it through the public API any more: the developer setting GJ_ENC_OUT_CAP=<bytes> lowers the capacity they are told.
+# tests/MUTATIONS.md ("encoder output limit") records which of these tests fail for which deliberate defect.
+OUT_CAP = "GJ_ENC_OUT_CAP"
+S420 = ((2, 2), (1, 1), (1, 1))
+BYTES_PER_PIXEL = {0: 1, 1: 3, 3: 2}  # grey, packed RGB, packed 4:2:2
+# name, width, height, pixel format, quality, restart, interleaved, subsampling, content, the route of gj_tile_kernel (gj_encode.hip) it takes
+LIMIT_CASES = [
+    # streams beyond the reference's sizing rule (asserted below)
+    ("rgb_65535x1_q90_r8", 65535, 1, 1, 90, 8, 0, None, "ramp", "rgb444"),
+    ("rgb_il_1x65535_q90_r8", 1, 65535, 1, 90, 8, 1, None, "ramp", "blocks"),
+    ("rgb_65535x1_q100_r1", 65535, 1, 1, 100, 1, 0, None, "ramp", "planes"),
+    ("rgb_512x1_q100_r8", 512, 1, 1, 100, 8, 0, None, "noise", "rgb444"),
+    ("rgb_1025x9_q100", 1025, 9, 1, 100, -1, 0, None, "noise", "rgb444"),
+    ("rgb_9x1025_q100", 9, 1025, 1, 100, -1, 0, None, "noise", "rgb444"),
+    ("uyvy_il_1024x1_q100_r4", 1024, 1, 3, 100, 4, 1, None, "noise", "uyvy422"),
+    # the largest dimension a frame can have (the other suites stop at 15 360)
+    ("rgb_65535x8_auto", 65535, 8, 1, 90, -1, 0, None, "ramp", "rgb444"),
+    ("rgb_8x65535_auto", 8, 65535, 1, 90, -1, 0, None, "ramp", "rgb444"),
+    ("420_il_65535x9_r3", 65535, 9, 1, 90, 3, 1, S420, "ramp", "blocks"),
+    ("420_il_9x65535_r3", 9, 65535, 1, 90, 3, 1, S420, "ramp", "blocks"),
+    ("uyvy_il_65534x3_auto", 65534, 3, 3, 90, -1, 1, None, "ramp", "uyvy422"),
+    ("uyvy_2x65535_auto", 2, 65535, 3, 90, -1, 0, None, "ramp", "planes"),
+    ("grey_65535x5_r5", 65535, 5, 0, 90, 5, 0, None, "ramp", "blocks"),
+    ("grey_5x65535_r0", 5, 65535, 0, 90, 0, 0, None, "ramp", "planes"),
+]
+BEYOND_THE_REFERENCE_RULE = 7  # the first so many of LIMIT_CASES
+
+
+def limit_case(name, w, h, pf, q, ri, il, ss):
+    """the case tuple of conftest.oracle_image / api_params: enc_case's, with the pixel format (and YCbCr input for the formats that are not RGB)"""
+    c = enc_case("x", (name, w, h, ri, il, tuple(map(tuple, ss)) if ss else None), q)  # (tuples: the cases are keys of limit_expected's cache)
+    return (name,) + c[1:] if pf == 1 else (name,) + c[1:3] + (pf, 3) + c[5:]
+
+
+def limit_raw(content, w, h, pf, seed=0):
+    """0/255 noise (S.pattern), a ramp over the bytes with noise of 0 .. 23 on it, or one value -- in the byte count of the pixel format"""
+    n = w * h * BYTES_PER_PIXEL[pf]
+    if content == "noise":
+        raw = np.array(S.pattern("noise", w, h, seed)[:n])
+    elif content == "flat":
+        raw = np.full(n, 77, np.uint8)
+    else:
+        raw = ((np.arange(n, dtype=np.int64) * 3 // 11 + S.O.noise(n, seed=11 + seed) % 24) % 256).astype(np.uint8)  # (conftest.random_raw's ramp)
+    raw.setflags(write=False)
+    return raw
+
+
+@functools.lru_cache(maxsize=None)
+def limit_expected(case, content, segment_info=0, seed=0):
+    """(raw image, the oracle's stream, the oracle's Image) -- read-only"""
+    raw = limit_raw(content, case[1], case[2], case[3], seed)
+    img = oracle_image(S.O, case, segment_info=segment_info)
+    jpeg = S.O.encode(img, raw)
+    jpeg.setflags(write=False)
+    return raw, jpeg, img
+
+
+def segment_blocks(img):
+    """blocks per restart segment (0: no restart markers)"""
+    per_mcu = sum(img.samp_h[c] * img.samp_v[c] for c in range(img.comp_count)) if img.interleaved else 1
+    return img.restart_interval * per_mcu
+
+
+def expected_route(case, img):
+    """gj_tile_kernel (gj_encode.hip) restated for the configurations of these tests: a kernel from pixels to tile streams needs restart segments
+    of 4 .. 256 blocks; k_encode_rgb444 takes packed RGB 4:4:4 in one scan per component, k_encode_uyvy422 packed 4:2:2 in an interleaved scan,
+    k_encode_blocks the other RGB layouts and grey; everything else goes through the coefficient planes and k_huffman"""
+    pf, il = case[3], case[7]
+    if not 4 <= segment_blocks(img) <= 256 or (pf == 3 and not il):
+        return "planes"
+    if pf == 3:
+        return "uyvy422"
+    return "rgb444" if pf == 1 and not il and case[8] is None else "blocks"
+
+
+def assert_route(G, lib, enc, p, pi, raw, want, route):
+    """what the binding can tell: a batch call codes its frames by batched launches where a tile kernel takes the configuration, one by one otherwise"""
+    got = enc.encode_batch(p, pi, np.array(raw), 1, lib.image_size(pi))
+    assert got[0].size == want.size and np.array_equal(got[0], want), "batch of one"
+    assert enc.last_batch() == ((0, 1) if route == "planes" else (1, 0)), (route, enc.last_batch())
+
+
+def decode_paths(G, lib, monkeypatch, jpeg, want, fmt, paths=PATHS):
+    """the stream through the decoders of `paths`, two calls each (the second one runs on the cached header): the oracle's pixels"""
+    for path in paths:
+        dec = make_decoder(G, lib, monkeypatch, path)
+        if fmt:
+            dec.set_output_format(fmt[1], fmt[0])
+        for rep in range(2):
+            px = dec.decode(jpeg)[0]
+            assert px.size == want.size and np.array_equal(px, want), (path, rep, int(np.count_nonzero(px != want)))
+        dec.close()
+
+
+@pytest.mark.parametrize("tc", LIMIT_CASES, ids=[c[0] for c in LIMIT_CASES])
+def test_thin_and_extreme_geometries(O, G, dlib, tc, monkeypatch):
+    """Frames of one row or column of blocks and frames at the 65535 limit of a dimension, default settings: the fused kernels, the kernels that go
+    through the coefficient planes and the generic ones write the oracle's stream, every decoder path returns the oracle's pixels from it. The
+    first seven have streams that the reference's sizing rule (2 bytes per sample of the IMAGE) does not hold: refused before the buffer was
+    sized by the coded samples. Between them the cases take all four routes of gj_tile_kernel."""
+    name, w, h, pf, q, ri, il, ss, content, route = tc
+    case = limit_case(name, w, h, pf, q, ri, il, ss)
+    raw, want, img = limit_expected(case, content)
+    scan_headers = img.scan_count * 10 if not img.interleaved else 8 + 2 * img.comp_count  # SOS: marker, length, count, 2 per component, Ss Se AhAl
+    reference_rule = 1000 + scan_headers + w * h * img.comp_count * 2 + 4096
+    print(name, "oracle stream", want.size, "B; the reference's rule", reference_rule, "B; coded samples", int(img.data_size))
+    if LIMIT_CASES.index(tc) < BEYOND_THE_REFERENCE_RULE:
+        assert want.size > reference_rule, (want.size, reference_rule)
+    assert want.size <= 1000 + scan_headers + 2 * max(w * h * img.comp_count, int(img.data_size)) + 4096
+    assert expected_route(case, img) == route, (segment_blocks(img), route)
+    monkeypatch.delenv(OUT_CAP, raising=False)
+    p, pi = api_params(dlib, G, case)
+    enc = G.Encoder(dlib)
+    got = enc.encode(p, pi, raw)
+    assert got.size == want.size and np.array_equal(got, want), "fused"
+    assert_route(G, dlib, enc, p, pi, raw, want, route)
+    enc.keep_coefficients()
+    got = enc.encode(p, pi, raw)
+    assert got.size == want.size and np.array_equal(got, want), "coefficient planes"
+    enc.set_fused(False)
+    got = enc.encode(p, pi, raw)
+    assert got.size == want.size and np.array_equal(got, want), "generic"
+    enc.close()
+    fmt = (3, 3) if pf == 3 else None
+    want_px = O.decode(want, *(fmt or (-1, -1)))[0]
+    decode_paths(G, dlib, monkeypatch, want, want_px, fmt)
+    if name in ("rgb_65535x8_auto", "rgb_8x65535_auto"):  # a region that ends at the far edge, and the smallest reduced image
+        reg = (65000, 2, 535, 6) if w > h else (2, 65000, 6, 535)
+        dec = make_decoder(G, dlib, monkeypatch, "default")
+        for rep in range(2):
+            px = decode_at(G, dlib, dec, want, region=reg)
+            assert np.array_equal(px, crop(want_px, w, h, 1, reg)), (rep, reg)
+            px = decode_at(G, dlib, dec, want, scale=8)
+            small = SD.expected(O, want, -1, -1, 8)[0]
+            assert px.size == small.size and np.array_equal(px, small), (rep, "1/8")
+        dec.close()
+
+
+# ---- the guard: GJ_ENC_OUT_CAP on both sides of the boundary
+# route, size (ENC_SIZES' columns), pixel format, what the encoder is set to
+GUARD_SIZES = {"rgb444": (ENC_SIZES[0], 1), "blocks": (ENC_SIZES[1], 1), "uyvy422": (("uyvy_il_320x200_r4", 320, 200, 4, 1, None), 3),
+               "restart0": (("rgb_320x200_r0", 320, 200, 0, 0, None), 1), "keep": (ENC_SIZES[0], 1), "generic": (ENC_SIZES[1], 1)}
+# route, segment_info, enc_opt_huffman=optimal
+GUARD_ROUTES = [(r, 0, False) for r in GUARD_SIZES] + [(r, 1, False) for r in GUARD_SIZES if r != "restart0"] + [("rgb444", 0, True), ("generic", 0, True)]
+
+
+def guard_case(route):
+    size, pf = GUARD_SIZES[route]
+    return limit_case(size[0], size[1], size[2], pf, 100, size[3], size[4], size[5])
+
+
+def capped_encoder(G, lib, monkeypatch, cap, route="rgb444", optimal=False, out=None):
+    """an encoder created under GJ_ENC_OUT_CAP=<cap> (None: without the setting; the settings are taken when a coder is created), set to a route"""
+    with monkeypatch.context() as mp:
+        mp.delenv(OUT_CAP, raising=False)
+        if cap is not None:
+            mp.setenv(OUT_CAP, str(cap))
+        enc = G.Encoder(lib)
+    if route == "keep":
+        enc.keep_coefficients()
+    if route == "generic":
+        enc.set_fused(False)
+    if optimal:
+        assert enc.set_option(ENC_OPT, OPTIMAL) == 0
+    if out:
+        assert enc.set_option("enc_opt_out", out) == 0
+    return enc
+
+
+def encode_to_host(lib, enc, p, pi, raw, device_out):
+    """one encode call -> the stream as a numpy copy, whether the encoder leaves it in host or in device memory"""
+    ptr, n = enc.encode_noclone(p, pi, raw)
+    if not device_out:
+        return np.ctypeslib.as_array(ptr, shape=(n,)).copy()
+    L = lib.L
+    L.gj_hip_memcpy_d2h.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.gj_hip_stream_sync.argtypes = [C.c_void_p]
+    got = np.empty(n, np.uint8)
+    assert L.gj_hip_memcpy_d2h(got.ctypes.data, C.cast(ptr, C.c_void_p), n, None) == 0 and L.gj_hip_stream_sync(None) == 0
+    return got
+
+
+def refusal(size, cap):
+    return f"Compressed stream ({size} B) does not fit the output buffer ({cap} B)"
+
+
+@pytest.mark.parametrize("route,segment_info,optimal", GUARD_ROUTES, ids=[f"{r}{'-segment_info' * si}{'-optimal' * o}" for r, si, o in GUARD_ROUTES])
+def test_encoder_output_guard_both_sides(O, G, dlib, route, segment_info, optimal, monkeypatch, capfd):
+    """S = the oracle's size of a dense frame (0/255 noise, quality 100). An encoder told a capacity of S bytes returns the oracle's bytes (the
+    comparison is `total > capacity`), one told S - 1 returns -1 and its message names S bytes and the capacity in force -- through k_gather behind
+    each of the three tile kernels, through k_scan_segments + k_assemble (no restart markers, kept coefficients, generic kernels), with the
+    APP13 segment index (k_segment_info behind both), with the frame's own Huffman tables, into host and into device memory."""
+    case = guard_case(route)
+    raw, want, img = limit_expected(case, "noise", segment_info)
+    if optimal:
+        want = transcode(want)
+    S_ = int(want.size)
+    # (keep_coefficients() and set_fused(False) take a geometry of the tile kernels through the coefficient planes; without restart markers the geometry does)
+    assert expected_route(case, img) == {"restart0": "planes", "keep": "rgb444", "generic": "blocks"}.get(route, route)
+    tile_route = "planes" if route in ("restart0", "keep", "generic") else route
+    assert S_ - 1 < 2 * int(img.data_size), "both capacities are below the stream buffer's size: the setting is the capacity in force"
+    p, pi = api_params(dlib, G, case, segment_info=segment_info)
+    for device_out in (False, True):
+        out = "enc_out_val_device" if device_out else None
+        enc = capped_encoder(G, dlib, monkeypatch, S_, route, optimal, out)
+        if not optimal and not segment_info and not device_out:
+            assert_route(G, dlib, enc, p, pi, raw, want, tile_route)
+        for rep in range(2):
+            got = encode_to_host(dlib, enc, p, pi, raw, device_out)
+            assert got.size == S_ and np.array_equal(got, want), (device_out, rep, "capacity S")
+        enc.close()
+        enc = capped_encoder(G, dlib, monkeypatch, S_ - 1, route, optimal, out)
+        capfd.readouterr()
+        with pytest.raises(RuntimeError, match="gpujpeg_encoder_encode failed"):
+            enc.encode_noclone(p, pi, raw)
+        assert refusal(S_, S_ - 1) in capfd.readouterr().err, (device_out, "capacity S - 1")
+        enc.close()
+
+
+STATE_ROUTES = ["rgb444", "blocks", "keep"]
+
+
+@pytest.mark.parametrize("route", STATE_ROUTES)
+def test_encoder_state_after_a_refusal(O, G, dlib, route, monkeypatch, capfd):
+    """one encoder under a capacity between the sizes of a flat and a dense frame of one geometry: dense (refused), flat, dense (refused), flat --
+    the flat frames are the oracle's byte for byte. k_gather's two sets of group totals (the one a refused call leaves and the one it clears),
+    the set the host picks for the next call and the epoch of k_scan_segments' partial sums survive the early return."""
+    case = guard_case(route)
+    dense, dense_jpeg, _ = limit_expected(case, "noise")
+    flat, flat_jpeg, _ = limit_expected(case, "flat")
+    cap = (int(flat_jpeg.size) + int(dense_jpeg.size)) // 2
+    assert flat_jpeg.size < cap < dense_jpeg.size
+    p, pi = api_params(dlib, G, case)
+    enc = capped_encoder(G, dlib, monkeypatch, cap, route)
+    for step in range(2):
+        capfd.readouterr()
+        with pytest.raises(RuntimeError):
+            enc.encode(p, pi, dense)
+        assert refusal(int(dense_jpeg.size), cap) in capfd.readouterr().err, step
+        got = enc.encode(p, pi, flat)
+        assert got.size == flat_jpeg.size and np.array_equal(got, flat_jpeg), (step, got.size, int(flat_jpeg.size))
+    enc.close()
+
+
+BATCH_ROUTES = [("rgb444", (3, 0)), ("blocks", (3, 0)), ("restart0", (0, 3))]
+
+
+@pytest.mark.parametrize("route,how", BATCH_ROUTES, ids=[r for r, _ in BATCH_ROUTES])
+def test_encoder_batches_at_the_output_limit(O, G, dlib, route, how, monkeypatch, capfd):
+    """encode_batch and encode_batch_ptrs (the latter in chunks of two frames) on [flat, dense, flat] under a capacity between the two sizes return
+    -1 and name the frame; the next batch of three flat frames on the same encoder is the oracle's; under a capacity of the dense frame's size all
+    three frames are the oracle's. Batched launches (a result pair per frame) and a configuration the batch call codes frame by frame."""
+    case = guard_case(route)
+    dense, dense_jpeg, _ = limit_expected(case, "noise")
+    flat, flat_jpeg, _ = limit_expected(case, "flat")
+    other, other_jpeg, _ = limit_expected(case, "ramp")
+    cap = (int(max(flat_jpeg.size, other_jpeg.size)) + int(dense_jpeg.size)) // 2
+    assert max(flat_jpeg.size, other_jpeg.size) < cap < dense_jpeg.size
+    p, pi = api_params(dlib, G, case)
+    frame = dlib.image_size(pi)
+    mixed, calm = [flat, dense, other], [flat, other, flat]
+    calm_want = [flat_jpeg, other_jpeg, flat_jpeg]
+    enc = capped_encoder(G, dlib, monkeypatch, cap, route)
+    for ptrs in (False, True):
+        enc.set_batch_chunk(2 if ptrs else 0)
+        capfd.readouterr()
+        with pytest.raises(RuntimeError):
+            enc.encode_batch_ptrs(p, pi, [np.array(r) for r in mixed]) if ptrs else enc.encode_batch(p, pi, np.concatenate(mixed), 3, frame)
+        err = capfd.readouterr().err
+        assert f"({int(dense_jpeg.size)} B)" in err and f"does not fit the output buffer ({cap} B)" in err, ptrs
+        if how == (3, 0):
+            assert "of frame 1 " in err
+        got = enc.encode_batch_ptrs(p, pi, [np.array(r) for r in calm]) if ptrs else enc.encode_batch(p, pi, np.concatenate(calm), 3, frame)
+        assert enc.last_batch() == how
+        for f, (g, want) in enumerate(zip(got, calm_want)):
+            assert g.size == want.size and np.array_equal(g, want), (ptrs, f)
+    enc.close()
+    enc = capped_encoder(G, dlib, monkeypatch, int(dense_jpeg.size), route)
+    for ptrs in (False, True):
+        enc.set_batch_chunk(2 if ptrs else 0)
+        got = enc.encode_batch_ptrs(p, pi, [np.array(r) for r in mixed]) if ptrs else enc.encode_batch(p, pi, np.concatenate(mixed), 3, frame)
+        assert enc.last_batch() == how
+        for f, (g, want) in enumerate(zip(got, [flat_jpeg, dense_jpeg, other_jpeg])):
+            assert g.size == want.size and np.array_equal(g, want), (ptrs, f)
     enc.close()
 
 
