@@ -200,20 +200,27 @@ __device__ __forceinline__ void gj_slot_put(uint8_t* slot, const uint32_t swz /*
 // One block per lane: zeros, the DC term and the lane's tokens go into its tile slot. `fast`: the wave's tokens are in the stage
 // already (dense range starting at token S).
 // MULTI: several ranges are staged together when they fit (the kernels fed by the lane-per-segment decoders, where that is the normal case)
-template <bool MULTI>
+// CORNER (k_idct_tok_rgb444's corner path: the range is `fast`, no block of the wave is in the planes, every token of the wave lies in natural
+// rows 0 .. 3 x columns 0 .. 3): only the first 8 bytes of the slot's rows 0 .. 3 are cleared, written and later read
+template <bool MULTI, bool CORNER = false>
 __device__ __forceinline__ void gj_tok_to_slot(uint8_t* slot, uint16_t* stage, const int lane, const bool fast, const uint32_t S, const uint32_t start,
                                                const uint32_t cnt, const uint32_t dc, const bool in_plane, const uint4* __restrict__ plane_block,
                                                const uint16_t* __restrict__ d_tok)
 {
+    if (CORNER) {
 #pragma unroll
-    for (int r = 0; r < 8; r++) *gj_slot_row(slot, lane, r) = make_uint4(0, 0, 0, 0);
-    if (in_plane) { // block of a segment that was decoded piece by piece: it is in the coefficient plane
+        for (int r = 0; r < 4; r++) *reinterpret_cast<uint2*>(gj_slot_row(slot, lane, r)) = make_uint2(0, 0);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 8; r++) *gj_slot_row(slot, lane, r) = make_uint4(0, 0, 0, 0);
+    }
+    if (!CORNER && in_plane) { // block of a segment that was decoded piece by piece: it is in the coefficient plane
 #pragma unroll
         for (int r = 0; r < 8; r++) *gj_slot_row(slot, lane, r) = plane_block[r];
     }
     const uint32_t end = start + cnt;
     const uint32_t swz = ((uint32_t)lane & 7u) << 3;
-    if (fast) {
+    if (CORNER || fast) {
         gj_wave_sync();
         uint32_t a = start - S;
         const uint32_t b = end - S;
@@ -277,7 +284,7 @@ __device__ __forceinline__ void gj_tok_to_slot(uint8_t* slot, uint16_t* stage, c
     }
     // the DC term last: a token of a damaged stream that ran past its block's end sits on position 0 (the entropy decoders' zig-zag
     // tables say so) and disappears here, like in the plane kernels
-    if (!in_plane) *reinterpret_cast<uint16_t*>(slot + ((lane & 7) << 4)) = (uint16_t)dc;
+    if (CORNER || !in_plane) *reinterpret_cast<uint16_t*>(slot + ((lane & 7) << 4)) = (uint16_t)dc;
     gj_wave_sync(); // (the stage is rewritten by the next component)
 }
 
@@ -300,45 +307,143 @@ __device__ __forceinline__ void gj_tok_tables(GjTokLds& s, const gj_geom& g, con
     }
 }
 
-// The core of the 4:4:4 kernels: records (gj_tok_record) of the lane's block position lb -> the three components' samples, byte-packed. Per
+// a fetched range into the wave's stage
+__device__ __forceinline__ void gj_tok_stage(uint16_t* stage, const int lane, const GjTokRange& r)
+{
+    if (r.fast) {
+        *reinterpret_cast<uint4*>(stage + lane * 8) = r.t0;
+        if (lane * 8 + 512 < GJ_TOK_STAGE) *reinterpret_cast<uint4*>(stage + lane * 8 + 512) = r.t1;
+    }
+}
+
+// One component of the 4:4:4 cores: its staged range -> the lane's slot -> the block as rows -> dequantisation + IDCT. CORNER: see gj_tok_to_slot.
+template <bool CORNER>
+__device__ __forceinline__ void gj_tok_component(GjTokLds& s, const gj_geom& g, const int16_t* __restrict__ coefs, const uint16_t* __restrict__ d_tok,
+                                                 const unsigned lb, const int c, const bool fast, const uint32_t S, const uint32_t start, const uint32_t cd,
+                                                 uint32_t (&px)[16])
+{
+    const int lane = threadIdx.x & 63;
+    uint8_t* slot = s.blk + threadIdx.x * 128;
+    const bool in_plane = !CORNER && (int32_t)cd < 0;
+    gj_tok_to_slot<false, CORNER>(slot, s.stage[threadIdx.x >> 6], lane, fast, S, start, gj_rec_count(cd), cd & 0xFFFFu, in_plane,
+                                  reinterpret_cast<const uint4*>(coefs + g.comp[c].data_offset + (size_t)lb * 64), d_tok);
+    uint32_t wb[32];
+    if (CORNER) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const uint2 v = *reinterpret_cast<const uint2*>(gj_slot_row(slot, lane, r));
+            wb[r * 4] = v.x; wb[r * 4 + 1] = v.y;
+        }
+        gj_idct_pk_corner4(wb, s.q[0][c], px);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const uint4 v = *gj_slot_row(slot, lane, r);
+            wb[r * 4] = v.x; wb[r * 4 + 1] = v.y; wb[r * 4 + 2] = v.z; wb[r * 4 + 3] = v.w;
+        }
+        gj_idct_pk(wb, s.q[in_plane ? 1 : 0][c], px);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) GJ_KEEP(px[i]); // one transform at a time (see k_idct_fused_rgb444)
+}
+
+// The core of the region kernel: records (gj_tok_record) of the lane's block position lb -> the three components' samples, byte-packed. Per
 // component the tokens of the wave's 64 blocks go through the LDS stage (consecutive blocks of a scan have consecutive tokens); the loads of the
 // next component are in flight while this one is transformed. Everything is private to a wave.
 __device__ __forceinline__ void gj_tok_idct3(GjTokLds& s, const gj_geom& g, const int16_t* __restrict__ coefs, const uint16_t* __restrict__ d_tok,
                                              const unsigned lb, const uint32_t (&start)[3], const uint32_t (&cd)[3], uint32_t (&pk)[3][16])
 {
     const int lane = threadIdx.x & 63;
-    uint8_t* slot = s.blk + threadIdx.x * 128;
     uint16_t* stage = s.stage[threadIdx.x >> 6];
     GjTokRange cur = gj_tok_fetch(d_tok, start[0], gj_rec_count(cd[0]), lane);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         const bool fast = cur.fast;
         const uint32_t S = cur.S;
-        if (fast) {
-            *reinterpret_cast<uint4*>(stage + lane * 8) = cur.t0;
-            if (lane * 8 + 512 < GJ_TOK_STAGE) *reinterpret_cast<uint4*>(stage + lane * 8 + 512) = cur.t1;
-        }
+        gj_tok_stage(stage, lane, cur);
         if (c < 2) cur = gj_tok_fetch(d_tok, start[c + 1], gj_rec_count(cd[c + 1]), lane);
-        const bool in_plane = (int32_t)cd[c] < 0;
-        gj_tok_to_slot<false>(slot, stage, lane, fast, S, start[c], gj_rec_count(cd[c]), cd[c] & 0xFFFFu, in_plane,
-                       reinterpret_cast<const uint4*>(coefs + g.comp[c].data_offset + (size_t)lb * 64), d_tok);
-        // the block as rows; dequantisation + IDCT
-        uint32_t wb[32];
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const uint4 v = *gj_slot_row(slot, lane, r);
-            wb[r * 4] = v.x; wb[r * 4 + 1] = v.y; wb[r * 4 + 2] = v.z; wb[r * 4 + 3] = v.w;
-        }
-        gj_idct_pk(wb, s.q[in_plane ? 1 : 0][c], pk[c]);
-#pragma unroll
-        for (int i = 0; i < 16; i++) GJ_KEEP(pk[c][i]); // one transform at a time (see k_idct_fused_rgb444)
+        gj_tok_component<false>(s, g, coefs, d_tok, lb, c, fast, S, start[c], cd[c], pk[c]);
     }
+}
+
+#ifdef GJ_HIPEMU
+// CPU execution model only (tests/test_idct_corner.py): waves of k_idct_tok_rgb444 that took the dense [0] and the corner [1] body
+extern "C" GJ_HIP_API unsigned long long gj_emu_idct_tok_waves[2];
+unsigned long long gj_emu_idct_tok_waves[2] = {0, 0};
+#endif
+
+// does one of the wave's OWN tokens of this range -- token numbers first .. r.E - 1, `first` = the range's start in lane 0 -- lie outside the corner?
+// (the 16-byte pieces of a range also hold up to 7 tokens in front of it and behind it: other blocks', or whatever the memory held)
+__device__ __forceinline__ bool gj_tok_outside_corner(const GjTokRange& r, const uint32_t first, const int lane)
+{
+    const uint32_t t[8] = {r.t0.x, r.t0.y, r.t0.z, r.t0.w, r.t1.x, r.t1.y, r.t1.z, r.t1.w};
+    bool out = false;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const uint32_t at = r.S + (uint32_t)lane * 8u + (uint32_t)((k >> 3) * 512 + (k & 7));
+        out |= at >= first && at < r.E && ((t[k >> 1] >> (16 * (k & 1))) & 0x24u) != 0u;
+    }
+    return out;
+}
+
+// The core of k_idct_tok_rgb444: gj_tok_idct3 with the chrominance first and the kind of chrominance transform chosen per wave at its entry
+// (gj_tok_corner_entry), before anything but the records, the two chrominance ranges and the block position is live. Ordinary content has no
+// chrominance coefficient outside natural rows 0 .. 3 x columns 0 .. 3 (8K natural frame and camera frame at q75: every wave): a wave
+// whose Cb and Cr ranges are `fast`, none of whose Cb and Cr blocks is in the planes and none of whose Cb and Cr tokens lies outside that corner
+// (a token's low 6 bits are row << 3 | column: outside iff tok & 0x24) transforms Cb and Cr with gj_idct_pk_corner4 over half a slot; every other
+// wave, and every wave when `dense` (gj_tuning::idct_dense) is set, transforms them like gj_tok_idct3. The bytes are the same. Y comes last either
+// way, so the most registers are needed where they were: a dense transform with 32 result registers held.
+// The flag is wave-uniform and each chrominance component branches on it by itself: at Cb's branch no result is held, at Cr's 16 registers, and
+// the two sides meet in 16 results each. The other form, ONE branch into two whole bodies (Cb, Cr, Y and the stores twice), spills: 23 VGPRs, 96 B
+// of scratch per lane, whether the bodies meet in front of the stores or at the kernel's end, and still 24 with two copies of the dense body --
+// each body alone needs none (profiles/idct_side_resources.md). This form: 122 VGPRs, no scratch.
+__device__ __forceinline__ void gj_tok_idct3_body(GjTokLds& s, const gj_geom& g, const int16_t* __restrict__ coefs, const uint16_t* __restrict__ d_tok,
+                                                  const unsigned lb, const uint32_t (&start)[3], const uint32_t (&cd)[3], const bool corner,
+                                                  const GjTokRange& cb, const GjTokRange& cr, uint32_t (&pk)[3][16])
+{
+    const int lane = threadIdx.x & 63;
+    uint16_t* stage = s.stage[threadIdx.x >> 6];
+    gj_tok_stage(stage, lane, cb);
+    if (corner) gj_tok_component<true>(s, g, coefs, d_tok, lb, 1, cb.fast, cb.S, start[1], cd[1], pk[1]);
+    else gj_tok_component<false>(s, g, coefs, d_tok, lb, 1, cb.fast, cb.S, start[1], cd[1], pk[1]);
+    gj_tok_stage(stage, lane, cr);
+    const GjTokRange y = gj_tok_fetch(d_tok, start[0], gj_rec_count(cd[0]), lane); // (in flight while Cr is transformed)
+    if (corner) gj_tok_component<true>(s, g, coefs, d_tok, lb, 2, cr.fast, cr.S, start[2], cd[2], pk[2]);
+    else gj_tok_component<false>(s, g, coefs, d_tok, lb, 2, cr.fast, cr.S, start[2], cd[2], pk[2]);
+    gj_tok_stage(stage, lane, y);
+    gj_tok_component<false>(s, g, coefs, d_tok, lb, 0, y.fast, y.S, start[0], cd[0], pk[0]);
+}
+
+// which body for this wave? Fetches the two chrominance ranges and decides from the registers they arrive in.
+__device__ __forceinline__ bool gj_tok_corner_entry(const uint16_t* __restrict__ d_tok, const uint32_t (&start)[3], const uint32_t (&cd)[3], const int dense,
+                                                    GjTokRange& cb, GjTokRange& cr)
+{
+    const int lane = threadIdx.x & 63;
+    cb = gj_tok_fetch(d_tok, start[1], gj_rec_count(cd[1]), lane);
+    cr = gj_tok_fetch(d_tok, start[2], gj_rec_count(cd[2]), lane);
+    bool corner = !dense && cb.fast && cr.fast; // (wave-uniform, like everything this branches on)
+    if (corner) {
+        const bool planes = (int32_t)(cd[1] | cd[2]) < 0;
+        const uint32_t any = cb.t0.x | cb.t0.y | cb.t0.z | cb.t0.w | cb.t1.x | cb.t1.y | cb.t1.z | cb.t1.w |
+                             cr.t0.x | cr.t0.y | cr.t0.z | cr.t0.w | cr.t1.x | cr.t1.y | cr.t1.z | cr.t1.w;
+        corner = __ballot(planes || (any & 0x00240024u) != 0u) == 0ull;
+        // a hit may be a neighbour's token in one of the range's end pieces: look again, at the wave's own tokens only (rare, and it makes the
+        // choice a function of the wave's blocks alone)
+        if (!corner && __ballot(planes) == 0ull) {
+            const uint32_t first_cb = (uint32_t)__builtin_amdgcn_readlane((int)start[1], 0), first_cr = (uint32_t)__builtin_amdgcn_readlane((int)start[2], 0);
+            corner = __ballot(gj_tok_outside_corner(cb, first_cb, lane) || gj_tok_outside_corner(cr, first_cr, lane)) == 0ull;
+        }
+    }
+#ifdef GJ_HIPEMU
+    if (lane == 0) __atomic_fetch_add(&gj_emu_idct_tok_waves[corner ? 1 : 0], 1ull, __ATOMIC_RELAXED);
+#endif
+    return corner;
 }
 
 template <int CS_FROM, int CS_TO>
 __global__ __launch_bounds__(256, 4) void k_idct_tok_rgb444(const gj_geom g, const int16_t* __restrict__ coefs, const uint2* __restrict__ d_rec,
                                                             const uint16_t* __restrict__ d_tok, const uint32_t tok_cap,
-                                                            const float* __restrict__ qtab, uint8_t* __restrict__ raw)
+                                                            const float* __restrict__ qtab, uint8_t* __restrict__ raw, const int dense)
 {
     if (g.fb.sizes != nullptr) { // frame blockIdx.z of a batch
         const size_t z = blockIdx.z;
@@ -355,8 +460,10 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_rgb444(const gj_geom g, con
 #pragma unroll
     for (int c = 0; c < 3; c++) gj_tok_record(g, d_rec, tok_cap, lb < nb, lb, c, start[c], cd[c]);
     __syncthreads(); // (s.q; everything below is private to a wave)
+    GjTokRange cb, cr;
     uint32_t pk[3][16];
-    gj_tok_idct3(s, g, coefs, d_tok, lb, start, cd, pk);
+    const bool corner = gj_tok_corner_entry(d_tok, start, cd, dense, cb, cr);
+    gj_tok_idct3_body(s, g, coefs, d_tok, lb, start, cd, corner, cb, cr, pk);
     gj_store_rgb444<CS_FROM, CS_TO>(g, raw, pk, lb, nb, bx, by);
 }
 
@@ -449,7 +556,7 @@ __global__ __launch_bounds__(256, 4) void k_idct_tok_region_rgb444(const gj_geom
 // ================================================================================================
 __global__ __launch_bounds__(256, 4) void k_idct_tok_uyvy422(const gj_geom g, const int16_t* __restrict__ coefs, const uint2* __restrict__ d_rec,
                                                              const uint16_t* __restrict__ d_tok, const uint32_t tok_cap,
-                                                             const float* __restrict__ qtab, uint8_t* __restrict__ raw)
+                                                             const float* __restrict__ qtab, uint8_t* __restrict__ raw, const int /* (k_idct_tok_rgb444's `dense`) */)
 {
     if (g.fb.sizes != nullptr) { // frame blockIdx.z of a batch
         const size_t z = blockIdx.z;
@@ -751,7 +858,7 @@ void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_to
     } else if (tokens) {
         const unsigned nb = g.interleaved ? (unsigned)g.block_count : (unsigned)(g.comp[0].blocks_x * g.comp[0].blocks_y); // one lane per block (position)
         hipLaunchKernelGGL(idct_tok, dim3((nb + 255) / 256, 1, frames), dim3(256), 0, st, g, job->d_coefs, (const uint2*)job->d_blkrec, (const uint16_t*)job->d_tok, job->tok_cap,
-                           job->d_qtabf, job->d_raw);
+                           job->d_qtabf, job->d_raw, job->tune.idct_dense);
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
     } else if (job->use_fused && gj_is_uyvy422(g)) {
         const unsigned nm = (unsigned)(g.comp[1].blocks_x * g.comp[1].blocks_y);

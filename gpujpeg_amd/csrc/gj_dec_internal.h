@@ -277,7 +277,7 @@ __device__ __forceinline__ int gj_block_of(const gj_geom& g, const unsigned gb, 
     return c;
 }
 
-typedef void (*gj_idct_tok_t)(const gj_geom, const int16_t*, const uint2*, const uint16_t*, uint32_t, const float*, uint8_t*);
+typedef void (*gj_idct_tok_t)(const gj_geom, const int16_t*, const uint2*, const uint16_t*, uint32_t, const float*, uint8_t*, int /* gj_tuning::idct_dense */);
 gj_idct_tok_t gj_idct_tok_for(const gj_geom& g); // the token-fed IDCT kernel for this configuration, or nullptr
 bool gj_is_uyvy422(const gj_geom& g);
 // dequantisation + IDCT + postprocessing of the frame, whichever kind of call it is (full size, reduced size, region); channel remap; the one place

@@ -518,6 +518,93 @@ __device__ __forceinline__ void gj_idct_pk(const uint32_t (&w)[32], const float*
     }
 }
 
+// gj_idct8 with v1 = v2 = v4 = v5 = 0, by substitution only: a2, a4, a5 are zeros and t1 = v0 - 0 is v0, an fma whose product is a zero is its
+// addend (fma(0, k, x) = x), an fma whose addend is a zero is the single product (fma(x, k, -0) = x * k: one rounding either way). Every other
+// operation stands as it is in gj_idct8 -- nothing reassociated, no contraction -- so every result is the same fp32 number, except that a
+// zero may carry the other sign.
+template <typename T>
+__device__ __forceinline__ void gj_idct8_corner4(const T v0, const T v3, const T v6, const T v7, T (&o)[8])
+{
+    const float k0 = 0.4142135623f, k1 = 0.3535533905f, k2 = 0.4619397662f, k3 = 0.1989123673f, k4 = 0.7071067811f;
+    const T b1 = v0 * (T)k1;
+    const T b0 = gj_fma<T>(v0, (T)k4, -b1);
+    const T b3 = v3 * (T)k2;
+    const T b2 = b3 * (T)k0;
+    const T b6 = v6 * (T)k0;
+    const T b5 = b6 * (T)-0.6681786379f;
+    const T b7 = v7 * (T)0.49039264f;
+    const T b4 = b7 * (T)k3;
+    const T c1 = gj_fma<T>(v0, (T)k1, b2);
+    const T c2 = gj_fma<T>((T)-2.0f, b2, c1);
+    const T c4 = b5 + b4;
+    const T c5 = gj_fma<T>((T)2.0f, b5, -c4);
+    const T c7 = b6 + b7;
+    const T c6 = gj_fma<T>((T)-2.0f, b6, c7);
+    const T c0 = b3 + b0;
+    const T c3 = gj_fma<T>((T)-2.0f, b3, c0);
+    const T d5 = gj_fma<T>(c6, (T)k0, c5);
+    const T d6 = gj_fma<T>(d5, (T)-k4, c6);
+    const T e5 = gj_fma<T>(d6, (T)k0, d5);
+    const T d3 = c3 + c4;
+    const T e4 = gj_fma<T>((T)-2.0f, c4, d3);
+    const T d2 = c2 + e5;
+    const T f5 = gj_fma<T>((T)-2.0f, e5, d2);
+    const T e1 = d6 + c1;
+    const T e6 = gj_fma<T>((T)-2.0f, d6, e1);
+    const T e0 = c0 + c7;
+    const T e7 = gj_fma<T>((T)-2.0f, c7, e0);
+    o[0] = e0; o[1] = e1; o[2] = d2; o[3] = d3; o[4] = e4; o[5] = f5; o[6] = e6; o[7] = e7;
+}
+
+// gj_idct_pk for a block whose coefficients outside natural rows 0 .. 3 x columns 0 .. 3 are all zero (the chrominance blocks of ordinary
+// content): same w, qf and px, of which only the corner is read -- w[4r], w[4r + 1] and their table entries for r < 4. In the permuted operand
+// order {0,4,6,2,7,5,3,1} the operands 1, 2, 4 and 5 are rows (then columns) 4 .. 7, zero in both passes: the column pass runs on the column
+// pairs 0 and 1 only (the other two would transform zeros into zeros), the row pass on all four row pairs without E[4 .. 7], both through
+// gj_idct8_corner4. Against gj_idct_pk only the sign of a zero can differ, and no output sees it: a sum with a non-zero value does not depend
+// on the sign of the zero, a sum or product of zeros is a zero of either sign in both, and the last step adds 128 before v_cvt_pk_u8_f32
+// (the argument of profiles/r5_11_idct_zero_columns.txt). The bytes are gj_idct_pk's.
+__device__ __forceinline__ void gj_idct_pk_corner4(const uint32_t (&w)[32], const float* __restrict__ qf, uint32_t (&px)[16])
+{
+    const gj_f2* q2 = reinterpret_cast<const gj_f2*>(qf);
+    gj_f2 D[8][2];
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        gj_f2 x[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const uint32_t v = w[r * 4 + c];
+            x[r] = gj_f2{(float)(int)(int16_t)(v & 0xFFFF), (float)((int)v >> 16)} * q2[r * 4 + c];
+        }
+        gj_f2 o[8];
+        gj_idct8_corner4<gj_f2>(x[0], x[2], x[3], x[1], o);
+#pragma unroll
+        for (int r = 0; r < 8; r++) D[r][c] = o[r];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int rp = 0; rp < 4; rp++) {
+        gj_f2 E[4];
+#pragma unroll
+        for (int cp = 0; cp < 2; cp++) {
+            E[2 * cp] = gj_f2{D[2 * rp][cp].x, D[2 * rp + 1][cp].x};
+            E[2 * cp + 1] = gj_f2{D[2 * rp][cp].y, D[2 * rp + 1][cp].y};
+        }
+        gj_f2 X[8];
+        gj_idct8_corner4<gj_f2>(E[0], E[2], E[3], E[1], X);
+        uint32_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const gj_f2 lo = X[k] + (gj_f2)128.0f, hi = X[k + 4] + (gj_f2)128.0f;
+            a0 = __builtin_amdgcn_cvt_pk_u8_f32(lo.x, k, a0);
+            a1 = __builtin_amdgcn_cvt_pk_u8_f32(hi.x, k, a1);
+            b0 = __builtin_amdgcn_cvt_pk_u8_f32(lo.y, k, b0);
+            b1 = __builtin_amdgcn_cvt_pk_u8_f32(hi.y, k, b1);
+        }
+        px[4 * rp] = a0; px[4 * rp + 1] = a1; px[4 * rp + 2] = b0; px[4 * rp + 3] = b1;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Options that act on the planes / the raw image
 // ------------------------------------------------------------------------------------------------

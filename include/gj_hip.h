@@ -159,6 +159,8 @@ typedef struct gj_tuning {
                             a single frame within one generation of workgroups); A/B runs of the batch plan */
     int enc_out_cap;     /* GJ_ENC_OUT_CAP=<bytes>: the assembly kernels and the host's checks take min(the stream buffer's size, bytes) as the output
                             capacity (0: the buffer's size); tests of the overflow guard, which no image reaches through the public API */
+    int idct_dense;      /* GJ_IDCT_DENSE=1: every wave of k_idct_tok_rgb444 takes the dense body (full 8x8 transform of the chrominance blocks too); A/B
+                            runs on one build, tests of the corner path */
     int dec_careful;     /* set by the host for ONE call, never from the environment: a kernel that takes whole segments into LDS met one that
                             does not fit (overflow flag) -- this call uses the kernels without that limit */
 } gj_tuning;
