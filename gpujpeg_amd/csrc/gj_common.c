@@ -570,6 +570,7 @@ int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const st
     r->w = w; r->h = h;
     gj_region_frame* const rf = &r->frame;
     rf->x = x; rf->y = y;
+    rf->w = w; rf->h = h;
     const int px1 = x + gr->raw_width - 1, py1 = y + h - 1; /* the last pixel column / row whose samples are read */
     if (full->interleaved) {
         rf->mx0 = x / (8 * full->max_h);
@@ -604,6 +605,50 @@ int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const st
     gr->data_size = offset;
     gr->block_count = (int)(offset / 64);
     if (pi_region) *pi_region = rp;
+    return 0;
+}
+
+/* Crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize): a region whose rectangle is resampled to out_w x out_h. go becomes
+ * gj_geom_init of the out_w x out_h image -- what the resampling kernel stores -- over the component planes of `cover` (a geometry
+ * gj_geom_init_region made for the rectangle: the kernel reads them). `alignment` applies to the out_w line. -1 with a message: an output size
+ * outside 1 .. 16384, an output format whose pixels share samples. */
+int gj_geom_init_resized(gj_geom* go, const gj_geom* cover, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi, int out_w,
+                         int out_h, unsigned alignment, struct gpujpeg_image_parameters* pi_out)
+{
+    if (out_w < 1 || out_h < 1 || out_w > 16384 || out_h > 16384) {
+        GJ_ERROR("Crop-and-resize needs an output width and height of 1 to 16384 (given: %d x %d)!\n", out_w, out_h);
+        return -1;
+    }
+    const enum gpujpeg_pixel_format pf = pi->pixel_format;
+    if (pf != GPUJPEG_U8 && pf != GPUJPEG_444_U8_P012 && pf != GPUJPEG_444_U8_P0P1P2 && pf != GPUJPEG_4444_U8_P0123) {
+        GJ_ERROR("Crop-and-resize is implemented for pixel formats whose pixels do not share samples (u8, 444-u8-p012, 444-u8-p0p1p2, 4444-u8-p0123), not for %s!\n",
+                 gpujpeg_pixel_format_get_name(pf));
+        return -1;
+    }
+    struct gpujpeg_image_parameters rp = *pi;
+    rp.width = out_w;
+    rp.height = out_h;
+    rp.width_padding = 0;
+    if (alignment != 0) {
+        const unsigned linesize = (unsigned)gj_pixfmt_unit_size(rp.pixel_format) * (unsigned)rp.width;
+        rp.width_padding = (int)((linesize + alignment - 1) / alignment * alignment - linesize);
+    }
+    gj_comp_geom planes[GJ_MAX_COMP];
+    memcpy(planes, cover->comp, sizeof planes); /* (go may be the cover's geometry itself) */
+    const uint64_t data_size = cover->data_size;
+    const int block_count = cover->block_count;
+    if (gj_geom_init(go, param, &rp, false) != 0) return -1;
+    for (int c = 0; c < go->comp_count; c++) {
+        gj_comp_geom* k = &go->comp[c];
+        k->blocks_x = planes[c].blocks_x;
+        k->blocks_y = planes[c].blocks_y;
+        k->data_width = planes[c].data_width;
+        k->data_height = planes[c].data_height;
+        k->data_offset = planes[c].data_offset;
+    }
+    go->data_size = data_size;
+    go->block_count = block_count;
+    if (pi_out) *pi_out = rp;
     return 0;
 }
 

@@ -13,7 +13,8 @@
 //                               every kind of call and its one tail (debug stage, channel remap, gj_dec_job::idct_path)
 //   gj_dec_idct_scaled.hip      reduced-size output (dec_opt_scale): k_idct_scaled (from the planes), k_idct_tok_scaled_rgb444 (from tokens)
 //   gj_dec_region.hip           region decode (dec_opt_region): k_segment_select (table -> the entries that touch the region's cover), k_idct_region,
-//                               k_postprocess_region / k_copy_planes_region (cover blocks -> cover planes -> the region's pixels)
+//                               k_postprocess_region / k_copy_planes_region (cover blocks -> cover planes -> the region's pixels),
+//                               k_resize_region (crop-and-resize: the rectangle resampled to the call's output size instead of copied)
 //   this header                 what those share: the 4:4:4 configuration and its colour pairs (gj_is_rgb444, GJ_COLOR_PAIRS), gj_block_of, the block
 //                               records of the token-fed kernels (gj_rec_pack, gj_tok_record) and their token ranges (gj_tok_fetch)
 //   gj_bitreader.h              unstuffing of a restart segment into an LDS stage, two-level table look-up
@@ -290,14 +291,19 @@ bool gj_launch_idct_scaled(const gj_dec_job* job, hipStream_t st, bool tokens);
 
 // the generic pixel kernels' second half (k_postprocess, k_postprocess_region): the samples v of pixel (x, y) = number `pos` of a W x H image ->
 // colour transform -> the stores of the pixel format (src/gpujpeg_postprocessor.cu:193-217, src/gpujpeg_preprocessor_common.cuh:118-203)
-__device__ __forceinline__ void gj_store_pixel(const gj_geom& g, uint8_t* __restrict__ raw, const unsigned W, const unsigned H, const unsigned x,
-                                               const unsigned y, const unsigned pos, int (&v)[4])
+// (in two halves: k_resize_region blends the transformed values of four source pixels before the stores)
+__device__ __forceinline__ void gj_pixel_transform(const gj_geom& g, int (&v)[4])
 {
     if (g.comp_count == 1) { // single channel expanded for the colour transform (:127-170)
         if (g.color_space_internal == GJ_CS_RGB) v[1] = v[2] = v[0];
         else v[1] = v[2] = 128;
     }
     gj_color_transform(g.color_space_internal, g.color_space, v[0], v[1], v[2]);
+}
+
+__device__ __forceinline__ void gj_pixel_store(const gj_geom& g, uint8_t* __restrict__ raw, const unsigned W, const unsigned H, const unsigned x,
+                                               const unsigned y, const unsigned pos, const int (&v)[4])
+{
     switch (g.pixel_format) {
     case GJ_PF_U8: raw[(size_t)pos + (size_t)g.width_padding * y] = (uint8_t)v[0]; break;
     case GJ_PF_444_P012: {
@@ -332,6 +338,13 @@ __device__ __forceinline__ void gj_store_pixel(const gj_geom& g, uint8_t* __rest
         break;
     default: break;
     }
+}
+
+__device__ __forceinline__ void gj_store_pixel(const gj_geom& g, uint8_t* __restrict__ raw, const unsigned W, const unsigned H, const unsigned x,
+                                               const unsigned y, const unsigned pos, int (&v)[4])
+{
+    gj_pixel_transform(g, v);
+    gj_pixel_store(g, raw, W, H, x, y, pos, v);
 }
 
 // region decode (gj_dec_region.hip): the compacted segment table of job->region (from job's table, which has been written), and the IDCT side

@@ -8,12 +8,14 @@
 //                           (one lane per block like k_idct, the same arithmetic: gj_idct_pk)
 //   k_postprocess_region    the region's pixels from those planes: k_postprocess with the region's origin inside the cover
 //   k_copy_planes_region    the same for planar output whose layout equals the component layout (k_copy_planes_out)
+//   k_resize_region         crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize): in place of the two above, the rectangle resampled
+//                           bilinearly to the call's output size, with an optional horizontal mirror
 //
 // Every configuration can go this way; three-component 4:4:4 streams with non-interleaved scans and packed 3-byte output in token mode go
 // through k_idct_tok_region_rgb444 (gj_dec_idct.hip, beside k_idct_tok_rgb444 whose LDS helpers it shares) instead of the last three: same bytes.
 //
 // A BATCH of regions (gj_region::d_frames: one rectangle per frame, gpujpeg_amd_decoder_decode_batch_regions) runs the same code with blockIdx.z =
-// frame: k_segment_select_batch, k_idct_region_batch, k_postprocess_region_batch, k_copy_planes_region_batch and the batched instantiation of
+// frame: k_segment_select_batch, k_idct_region_batch, k_postprocess_region_batch, k_copy_planes_region_batch, k_resize_region_batch and the batched instantiation of
 // k_idct_tok_region_rgb444 read their frame's rectangle and cover from device memory and share the bodies of the single-frame kernels.
 // (part of the decoder's device code, see gj_dec_internal.h for the map of the files)
 #include "gj_dec_internal.h"
@@ -314,6 +316,51 @@ __global__ __launch_bounds__(256) void k_copy_planes_region_batch(const gj_geom 
     gj_copy_planes_region_body(gr, rb.d_frames[z], planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
 }
 
+// Crop-and-resize (gj_region::resize): the pixel stage of a call whose rectangle -- r.w x r.h, every frame's own -- is resampled to ONE output size,
+// gr.width x gr.height (gr: the geometry of the OUTPUT image over the cover's planes). One lane per output pixel: its four source pixels of the
+// rectangle (gj_resize_taps; a mirrored frame reads column OW - 1 - i), each made like k_postprocess_region makes a pixel -- the components' samples
+// inside the cover, the expansion of a single component, the colour transform --, blended per channel with 8-bit weights (gj_resize_blend) and
+// stored in the output format. The result is the resize of what the region call returns, which is why a no_transform configuration
+// (k_copy_planes_region: no colour stage) blends the samples as they are. Output formats whose pixels share no samples only (the host refuses the others).
+__device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const gj_region_frame& r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    const unsigned OW = (unsigned)gr.width, OH = (unsigned)gr.height;
+    const unsigned pos = blockIdx.x * 256u + threadIdx.x;
+    if (pos >= OW * OH) return;
+    const unsigned j = pos / OW, i = pos - j * OW;
+    int sx[2], sy[2], fx, fy;
+    gj_resize_taps(r.mirror ? (int)(OW - 1u - i) : (int)i, r.w, (int)OW, sx[0], sx[1], fx);
+    gj_resize_taps((int)j, r.h, (int)OH, sy[0], sy[1], fy);
+    int v[4][4]; // [source pixel: top left, top right, bottom left, bottom right][channel]
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        v[q][0] = v[q][1] = v[q][2] = 0;
+        v[q][3] = gr.pixel_format == GJ_PF_4444_P0123 ? 0xFF : 0;
+#pragma unroll
+        for (int c = 0; c < GJ_MAX_COMP; c++) {
+            if (c >= gr.comp_count) break;
+            v[q][c] = planes[gj_region_sample(gr.comp[c], r, c, (unsigned)sx[q & 1], (unsigned)sy[q >> 1])];
+        }
+        if (!gr.no_transform) gj_pixel_transform(gr, v[q]);
+    }
+    int o[4];
+#pragma unroll
+    for (int ch = 0; ch < 4; ch++) o[ch] = gj_resize_blend(v[0][ch], v[1][ch], v[2][ch], v[3][ch], fx, fy);
+    gj_pixel_store(gr, raw, OW, OH, i, j, pos, o);
+}
+
+__global__ __launch_bounds__(256) void k_resize_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    gj_resize_region_body(gr, r.frame, planes, raw);
+}
+
+// frame blockIdx.z of a batch: its rectangle and mirror flag, its cover planes (laid out for the largest cover: gr), its slot of the output
+__global__ __launch_bounds__(256) void k_resize_region_batch(const gj_geom gr, const gj_region rb, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    const size_t z = blockIdx.z;
+    gj_resize_region_body(gr, rb.d_frames[z], planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
+}
+
 // The IDCT side of a region call: cover blocks -> cover planes -> region pixels. A batch of regions (d_frames) runs the same stages through the
 // _batch kernels with blockIdx.z = frame and grids for the largest cover (gr).
 void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tokens, gj_event_t* ev)
@@ -330,7 +377,10 @@ void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tok
     hipLaunchKernelGGL(batch ? k_idct_region_batch : k_idct_region, dim3(((unsigned)gr.block_count + 255) / 256, 1, frames), dim3(256), 0, st, job->g, gr, r,
                        job->d_coefs, job->d_qtabf, job->d_planes);
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
-    if (gr.no_transform) {
+    if (r.resize) { // crop-and-resize: gr is the output image's geometry
+        const unsigned n = (unsigned)gr.width * (unsigned)gr.height;
+        hipLaunchKernelGGL(batch ? k_resize_region_batch : k_resize_region, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
+    } else if (gr.no_transform) {
         const size_t n = (size_t)gr.comp[0].width * gr.comp[0].height;
         hipLaunchKernelGGL(batch ? k_copy_planes_region_batch : k_copy_planes_region, dim3((unsigned)min((n + 255) / 256, (size_t)2048), 1, frames), dim3(256), 0, st,
                            gr, r, job->d_planes, job->d_raw);

@@ -51,6 +51,11 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     // (a region call: no scale, no flip; with a selection, room for the compacted table and its counts. A single frame -- or a batch of regions,
     // gj_region::d_frames: always with a selection, compacted tables at the frames' table stride, the found counts of every frame)
     const bool rg_batch = rg.on && rg.d_frames != nullptr;
+    // (crop-and-resize, gj_region::resize: the plane route only -- the host leaves gj_dec_job::tokens 0 --, an output size the taps' arithmetic takes,
+    // no channel remap)
+    if (rg.on && rg.resize && (job->tokens || job->channel_remap || job->gs.width < 1 || job->gs.height < 1 || job->gs.width > GJ_RESIZE_MAX_OUT ||
+                               job->gs.height > GJ_RESIZE_MAX_OUT || job->gs.raw_width != job->gs.width))
+        return -1;
     if (rg.on && (job->scale > 1 || job->flipped || (rg.select && (!rg.d_sel || !rg.h_sel_count || g.restart_interval <= 0)) ||
                   (rg_batch ? (g.fb.sizes == nullptr || !rg.select || job->channel_remap) : (g.fb.sizes != nullptr || job->batch.count > 1 || (rg.select && !rg.d_sel_count)))))
         return -1;

@@ -97,6 +97,10 @@ struct gpujpeg_decoder {
     gj_region_frame* b_rgn; size_t b_rgn_cap;      /* device: origin and covers of every frame of a call */
     gj_region_frame* bh_rgn; size_t bh_rgn_cap;    /* pinned staging of the same */
     uint32_t* bh_found; size_t bh_found_cap;       /* pinned: [frame][GJ_MAX_COMP] entries per scan the selection found */
+    /* crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize): a region call whose rectangle is resampled to resize_w x resize_h. Set by that
+     * call alone, for its own duration; its single-frame route is the region call with these on (dec_region_geometry) */
+    bool resize_on; int resize_w, resize_h, resize_mirror;
+    bool call_resize;                              /* what the decode call in progress (and, after it, the last one) used: geom_s / pi_s are the resampled image's */
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
@@ -128,6 +132,7 @@ static int dec_region_geometry(struct gpujpeg_decoder* d)
 {
     struct gj_coder* c = &d->coder;
     d->call_region = d->region_on;
+    d->call_resize = false;
     if (!d->call_region) return 0;
     d->call_region = false; /* (a refused call decodes nothing: what it leaves describes no region image) */
     if (d->call_scale > 1) {
@@ -140,12 +145,14 @@ static int dec_region_geometry(struct gpujpeg_decoder* d)
     }
     gj_region rg;
     if (gj_geom_init_region(&d->geom_s, &rg, &c->geom, &c->param, &c->param_image, d->region, d->req_alignment, &d->pi_s) != 0) return -1;
+    /* crop-and-resize: the image of the call is the resampled one, over the planes of this rectangle's cover */
+    if (d->resize_on && gj_geom_init_resized(&d->geom_s, &d->geom_s, &c->param, &c->param_image, d->resize_w, d->resize_h, d->req_alignment, &d->pi_s) != 0) return -1;
     /* the plan of a selection: one question per segment of the geometry, asked again only when the region or the stream's geometry changes */
     if (c->geom.restart_interval > 0) {
         /* (keyed on the cover itself -- the pixel rectangle alone does not fix it: packed 4:2:2 output widens it to the pixel pair --, so with the
          * origin taken out: it moves inside a cover without changing the selection; a new geometry drops the plan in decoder_configure) */
         gj_region_frame cover = rg.frame;
-        cover.x = cover.y = 0;
+        cover.x = cover.y = cover.w = cover.h = cover.mirror = 0;
         if (!d->plan_valid || memcmp(&d->plan_cover, &cover, sizeof cover) != 0) {
             memset(rg.sel_count, 0, sizeof rg.sel_count);
             for (int sc = 0, s = 0; sc < c->geom.scan_count && sc < GJ_MAX_COMP; sc++) {
@@ -157,6 +164,11 @@ static int dec_region_geometry(struct gpujpeg_decoder* d)
             d->plan_valid = true;
         }
         memcpy(rg.sel_count, d->plan_sel, sizeof rg.sel_count);
+    }
+    if (d->resize_on) {
+        rg.resize = 1;
+        rg.frame.mirror = d->resize_mirror;
+        d->call_resize = true;
     }
     d->rg = rg;
     d->call_region = true;
@@ -695,7 +707,8 @@ static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
         memset(d->h_sel_count, 0xFF, (1 + GJ_MAX_COMP) * sizeof(uint32_t));
     }
     /* token mode buffers (gj_hip.h): one record per block, 4 tokens per stream byte at most */
-    if (!d->keep_coefs && job.use_fused && k->tab2_ok && k->image_size < ((size_t)1 << 29) && gj_hip_decode_wants_tokens(&job.g, k->image_size, &d->tune)) {
+    /* (crop-and-resize resamples from the cover planes: no token mode) */
+    if (!d->keep_coefs && !d->call_resize && job.use_fused && k->tab2_ok && k->image_size < ((size_t)1 << 29) && gj_hip_decode_wants_tokens(&job.g, k->image_size, &d->tune)) {
         const size_t tok_need = (k->image_size * 4 + 64) * sizeof(uint16_t);
         if (tok_need > d->d_tok_cap) { /* (grown with headroom: frames of a sequence vary in size) */
             if (gj_ensure_device_buffer((void**)&d->d_tok, &d->d_tok_cap, tok_need + tok_need / 4) != 0) return -1;
@@ -960,16 +973,30 @@ struct dec_batch {
     bool host_io;                        /* copies from or into the caller's host memory have been queued */
     /* a batch of regions (gpujpeg_amd_decoder_decode_batch_regions; origins == NULL: the decoder's own options hold for every frame) */
     const int* origins; int rw, rh;      /* frame f: the rw x rh pixels at (origins[2f], origins[2f + 1]) */
+    /* crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize; origins == NULL): a batch of regions whose rectangles have their own sizes and
+     * are resampled to ONE ow x oh image per frame */
+    const int* rects; const uint8_t* mirror; int ow, oh; /* frame f: the rectangle rects[4f .. 4f + 3] = x, y, w, h; mirrored when mirror && mirror[f] */
     bool planned;                        /* the rectangles have been checked against the streams' geometry; what follows is valid then */
     int* plan;                           /* [count][GJ_MAX_COMP] restart segments of every scan that touch frame f's cover */
     int plan_max[GJ_MAX_COMP];           /* the largest of them per scan */
-    gj_geom gs_max;                      /* geometry of the rw x rh image with the planes of the largest cover (per component the widest and the highest) */
-    gj_geom gs_one; gj_region rg_one;    /* the same for one of the frames, and its region */
+    gj_geom gs_max;                      /* geometry of the rw x rh (crop-and-resize: ow x oh) image with the planes of the largest cover (per component the widest and the highest) */
+    gj_geom gs_one; gj_region rg_one;    /* the same for one of the frames, and its region (crop-and-resize: the ow x oh image over that frame's cover) */
     struct gpujpeg_image_parameters pi_r;
     int img_w, img_h;                    /* the streams' image, as the rectangles were checked against it */
     long stats[4];                       /* gpujpeg_amd_decoder_get_region_stats of the call: sums over the frames */
     bool unselected;                     /* a frame was entropy-decoded in full */
 };
+
+/* one rectangle per frame: a batch of regions, or crop-and-resize */
+static bool batch_has_regions(const struct dec_batch* b) { return b->origins != NULL || b->rects != NULL; }
+static void batch_rectangle(const struct dec_batch* b, int f, int region[4])
+{
+    if (b->rects) {
+        memcpy(region, b->rects + 4 * (size_t)f, 4 * sizeof(int));
+    } else {
+        region[0] = b->origins[2 * f]; region[1] = b->origins[2 * f + 1]; region[2] = b->rw; region[3] = b->rh;
+    }
+}
 
 /* restart segments of scan sc with a block / an MCU inside the cover: what counting gj_hip_segment_in_cover over the scan's segments gives, in closed
  * form -- a row of the cover is a run of cells, cell i belongs to segment i / restart_interval, and the rows' runs of segments follow each other
@@ -1003,11 +1030,17 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b)
     memset(b->plan_max, 0, sizeof b->plan_max);
     int wmax[GJ_MAX_COMP] = {0, 0, 0, 0}, hmax[GJ_MAX_COMP] = {0, 0, 0, 0};
     for (int f = 0; f < b->count; f++) {
-        const int region[4] = {b->origins[2 * f], b->origins[2 * f + 1], b->rw, b->rh};
+        int region[4];
+        batch_rectangle(b, f, region);
         gj_region rg;
         if (gj_geom_init_region(&b->gs_one, &rg, g, &c->param, &c->param_image, region, d->req_alignment, &b->pi_r) != 0) {
             GJ_ERROR("Frame %d of the batch: the region %d,%d,%d,%d was refused!\n", f, region[0], region[1], region[2], region[3]);
             return -1;
+        }
+        if (b->rects) { /* (the output image over this frame's cover; refuses the output formats whose pixels share samples) */
+            if (gj_geom_init_resized(&b->gs_one, &b->gs_one, &c->param, &c->param_image, b->ow, b->oh, d->req_alignment, &b->pi_r) != 0) return -1;
+            rg.resize = 1;
+            rg.frame.mirror = b->mirror && b->mirror[f] ? 1 : 0;
         }
         b->rg_one = rg;
         const gj_region_frame* rf = &rg.frame;
@@ -1050,12 +1083,17 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
     struct gj_coder* c = &d->coder;
     struct gpujpeg_decoder_output o;
     gpujpeg_decoder_output_set_cuda_buffer(&o);
-    if (b->origins) { /* (a batch of regions: the single-frame region call with this frame's rectangle -- the definition of the frame's result) */
+    if (batch_has_regions(b)) { /* (a batch of regions: the single-frame region call with this frame's rectangle -- the definition of the frame's result) */
         d->region_on = true;
-        d->region[0] = b->origins[2 * f]; d->region[1] = b->origins[2 * f + 1]; d->region[2] = b->rw; d->region[3] = b->rh;
+        batch_rectangle(b, f, d->region);
+        /* (crop-and-resize: the same call with the resampling kernel as its pixel stage -- resize_on, set by the public call for its duration) */
+        d->resize_mirror = b->mirror && b->mirror[f] ? 1 : 0;
     }
-    if (decoder_decode(d, (uint8_t*)(uintptr_t)(b->streams + (size_t)f * b->stream_stride), b->sizes[f], &o) != 0) return -1;
-    if (b->origins) {
+    if (decoder_decode(d, (uint8_t*)(uintptr_t)(b->streams + (size_t)f * b->stream_stride), b->sizes[f], &o) != 0) {
+        if (b->rects) GJ_ERROR("Frame %d of the batch: crop-and-resize of the rectangle %d,%d,%d,%d failed!\n", f, d->region[0], d->region[1], d->region[2], d->region[3]);
+        return -1;
+    }
+    if (batch_has_regions(b)) {
         if (d->region_stats[0] != 1) b->unselected = true;
         for (int i = 1; i < 4; i++) b->stats[i] += d->region_stats[i];
         /* (frame 0 ahead of everything: the streams' geometry is known now -- every rectangle is checked before a pixel goes to the caller's slots) */
@@ -1100,7 +1138,7 @@ static int batch_chunk_buffers(struct gpujpeg_decoder* d, gj_dec_job* job, gj_ba
     const size_t coefs_frame = ((size_t)g->data_size + 63) & ~(size_t)63;                                                   /* int16 */
     const int chunk_cap = d->b_chunk > 0 && d->b_chunk < GJ_DEC_BATCH_CHUNK_MAX ? d->b_chunk : GJ_DEC_BATCH_CHUNK_MAX;
     job->g.fb.frames = (uint32_t)(n_all < chunk_cap ? n_all : chunk_cap); /* (what the token / plane choice looks at) */
-    const bool tokens = gj_hip_decode_wants_tokens(&job->g, max_size, &d->tune) != 0;
+    const bool tokens = !d->call_resize && gj_hip_decode_wants_tokens(&job->g, max_size, &d->tune) != 0; /* (crop-and-resize: the cover planes) */
     const size_t tok_frame = tokens ? (max_size * 4 + 64 + 63) & ~(size_t)63 : 0;                                            /* tokens */
     const size_t rec_frame = tokens ? ((size_t)g->block_count + 8 + 7) & ~(size_t)7 : 0;                                    /* records */
     /* (a batch of regions: the cover planes of every configuration that does not take the token-fed region kernel, and a compacted table per frame;
@@ -1150,8 +1188,8 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     const int first = b->first, count = b->count, n_all = count - first;
     const size_t* sizes = b->sizes;
     /* (the region of the decoder's own option goes frame by frame: the single-frame region kernels do not know the frame dimension; a batch of
-     * regions -- b->origins -- has kernels that do, and so has a reduced-size decode, dec_opt_scale) */
-    const bool regions = b->origins != NULL;
+     * regions or crop-and-resize -- batch_has_regions -- has kernels that do, and so has a reduced-size decode, dec_opt_scale) */
+    const bool regions = batch_has_regions(b);
     bool batched = (regions || !d->region_on) && d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
                    (b->streams_on_device ? (b->stream_stride & 15u) == 0 : true) && d->tab2_ok;
     size_t max_size = 0;
@@ -1162,6 +1200,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     if (!batched || n_all < 1) return 0;
     d->call_scale = 1;
     d->call_region = false;
+    d->call_resize = false;
     const struct gj_reader_result* r = &d->hdr_cache_r;
     /* a scale the single call refuses for this header (a flip; packed 4:2:2 output of odd reduced width, gj_geom_init_scaled): nothing is launched,
      * the frames go the ordinary way and that call says why */
@@ -1181,6 +1220,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     geom_take_tables(&c->geom, r);
     if (regions) { /* (what a region call leaves for dec_raw_size / dec_out_param_image and what dec_job_base reads) */
         d->call_region = true;
+        d->call_resize = b->rects != NULL;
         d->geom_s = b->gs_one;
         d->pi_s = b->pi_r;
         d->rg = b->rg_one;
@@ -1308,19 +1348,24 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     return accepted == 0 && first == 0 && !force_first ? 1 : 0;
 }
 
-/* the batch call proper; origins (with width, height): a batch of regions */
-static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count, const int* origins,
-                        int width, int height, uint8_t* output, size_t output_stride, struct gpujpeg_image_parameters* param_image)
+/* the batch call proper; what: the rectangles of a batch of regions (origins, rw, rh) or of crop-and-resize (rects, mirror, ow, oh), or NULL */
+static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count, const struct dec_batch* what,
+                        uint8_t* output, size_t output_stride, struct gpujpeg_image_parameters* param_image)
 {
     struct gj_coder* c = &d->coder;
     struct dec_batch b = {.streams = streams, .stream_stride = stream_stride, .sizes = sizes, .count = count, .output_stride = output_stride,
-                          .d_out = output, .d_out_stride = output_stride, .origins = origins, .rw = width, .rh = height};
+                          .d_out = output, .d_out_stride = output_stride};
+    if (what) {
+        b.origins = what->origins; b.rw = what->rw; b.rh = what->rh;
+        b.rects = what->rects; b.mirror = what->mirror; b.ow = what->ow; b.oh = what->oh;
+    }
+    const bool regions = batch_has_regions(&b);
     b.streams_on_device = gj_hip_is_device_ptr(streams) != 0;
     b.out_on_device = gj_hip_is_device_ptr(output) != 0;
     int rc = -1;
     b.frame_done = calloc((size_t)count, 1);
-    if (origins) b.plan = calloc((size_t)count * GJ_MAX_COMP, sizeof(int));
-    if (!b.frame_done || (origins && !b.plan)) goto out;
+    if (regions) b.plan = calloc((size_t)count * GJ_MAX_COMP, sizeof(int));
+    if (!b.frame_done || (regions && !b.plan)) goto out;
     /* The header cache is what a batch launches on: frame 0 goes the ordinary way when there is none (or when it has to). A second pass, with
      * force_first, when the cached header turned out to be another sequence's: frame 0 replaces the cache, then the batch. */
     for (int pass = 0; pass < 2; pass++) {
@@ -1339,7 +1384,7 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
     /* a batch of regions none of whose rectangles has been looked at (nothing has been launched: no header to launch on that these streams share,
      * or a decoder state without batched launches): frame 0 the ordinary way tells the streams' geometry, and every rectangle is checked against it
      * before the first pixel goes to the caller's slots */
-    if (origins && !b.planned && b.first == 0) {
+    if (regions && !b.planned && b.first == 0) {
         if (batch_decode_one(d, &b, 0, true) != 0) goto out;
         b.frame_done[0] = 1;
         b.first = 1;
@@ -1362,7 +1407,7 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
         if (gj_hip_lane_end(down, c->stream, c->timers.lane_out) != 0 || copies != 0 || gj_hip_stream_sync(c->stream) != 0) goto out;
     }
     if (param_image) *param_image = dec_out_param_image(d);
-    if (origins) { /* (gpujpeg_amd_decoder_get_region_stats of the call: sums over its frames) */
+    if (regions) { /* (gpujpeg_amd_decoder_get_region_stats of the call: sums over its frames) */
         b.stats[0] = b.unselected ? 2 : 1;
         memcpy(d->region_stats, b.stats, sizeof d->region_stats);
     }
@@ -1378,7 +1423,7 @@ int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* d, const uint8_t* s
                                      uint8_t* output, size_t output_stride, struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output) return -1;
-    return decode_batch(d, streams, stream_stride, sizes, count, NULL, 0, 0, output, output_stride, param_image);
+    return decode_batch(d, streams, stream_stride, sizes, count, NULL, output, output_stride, param_image);
 }
 
 /* A batch of regions: one width x height rectangle per frame, each at its own origin. The decoder's own dec_opt_region is neither read nor changed
@@ -1403,7 +1448,58 @@ int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder* d, const ui
     const bool own_on = d->region_on;
     int own[4];
     memcpy(own, d->region, sizeof own);
-    const int rc = decode_batch(d, streams, stream_stride, sizes, count, origins, width, height, output, output_stride, param_image);
+    const struct dec_batch what = {.origins = origins, .rw = width, .rh = height};
+    const int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
+    d->region_on = own_on;
+    memcpy(d->region, own, sizeof own);
+    return rc;
+}
+
+/* Crop-and-resize: one rectangle per frame, each with its own size, resampled to ONE out_width x out_height image per frame (bilinear, gj_resize_taps),
+ * optionally mirrored. A batch of regions whose pixel stage resamples: the same plan, selection, entropy decoders and k_idct_region_batch -- always
+ * through the cover planes --, then k_resize_region_batch. As for the batch of regions, the decoder's own dec_opt_region is neither read nor changed. */
+int gpujpeg_amd_decoder_decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count,
+                                                 const int* rects, const uint8_t* mirror, int out_width, int out_height, uint8_t* output, size_t output_stride,
+                                                 struct gpujpeg_image_parameters* param_image)
+{
+    if (!d || !streams || !sizes || count < 1 || !output || !rects) return -1;
+    if (out_width < 1 || out_height < 1 || out_width > 16384 || out_height > 16384) {
+        GJ_ERROR("Crop-and-resize needs an output width and height of 1 to 16384 (given: %d x %d)!\n", out_width, out_height);
+        return -1;
+    }
+    for (int f = 0; f < count; f++)
+        if (rects[4 * f + 2] < 1 || rects[4 * f + 3] < 1) {
+            GJ_ERROR("Frame %d of the batch: the rectangle %d,%d,%d,%d needs a width and a height of at least 1!\n", f, rects[4 * f], rects[4 * f + 1],
+                     rects[4 * f + 2], rects[4 * f + 3]);
+            return -1;
+        }
+    if (d->scale > 1) {
+        GJ_ERROR("Crop-and-resize is not available together with " GPUJPEG_AMD_DEC_OPT_SCALE "=1/%d!\n", d->scale);
+        return -1;
+    }
+    if (d->flipped) {
+        GJ_ERROR("Crop-and-resize is not available together with " GPUJPEG_DEC_OPT_FLIPPED_BOOL "!\n");
+        return -1;
+    }
+    if (d->channel_remap) {
+        GJ_ERROR("Crop-and-resize is not available together with " GPUJPEG_DEC_OPT_CHANNEL_REMAP "!\n");
+        return -1;
+    }
+    const enum gpujpeg_pixel_format pf = d->req_pixel_format;
+    if (pf == GPUJPEG_422_U8_P1020 || pf == GPUJPEG_422_U8_P0P1P2 || pf == GPUJPEG_420_U8_P0P1P2) { /* (a format the stream decides: checked with its header) */
+        GJ_ERROR("Crop-and-resize is implemented for pixel formats whose pixels do not share samples, not for %s!\n", gpujpeg_pixel_format_get_name(pf));
+        return -1;
+    }
+    const bool own_on = d->region_on;
+    int own[4];
+    memcpy(own, d->region, sizeof own);
+    d->resize_on = true;
+    d->resize_w = out_width;
+    d->resize_h = out_height;
+    d->resize_mirror = 0;
+    const struct dec_batch what = {.rects = rects, .mirror = mirror, .ow = out_width, .oh = out_height};
+    const int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
+    d->resize_on = false;
     d->region_on = own_on;
     memcpy(d->region, own, sizeof own);
     return rc;

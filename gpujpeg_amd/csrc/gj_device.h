@@ -131,6 +131,28 @@ __host__ __device__ inline bool gj_segment_in_cover(const gj_geom& g, const gj_r
     return yb != ya && yb >= y0 && yb < y1 && xb >= x0;
 }
 
+// Crop-and-resize (gj_region::resize): output sample i of n_out along one axis of an n_src-sample crop reads source samples p0 and p1 with the
+// weights 256 - f and f (8 bits). Bilinear interpolation with half-pixel centres (align_corners = false, no antialiasing): the source position
+// is ((2i + 1) n_src - n_out) / (2 n_out), clamped at 0; p1 is clamped to the last sample. Integer arithmetic, division = floor; nothing
+// overflows 32 bits for n_src <= 65535 and n_out <= 16384 (2 * 16384 * 65535 < 2^31). The identity for n_src == n_out.
+// The ONE statement of the resampling positions: k_resize_region and host code ask here.
+#define GJ_RESIZE_MAX_OUT 16384
+__host__ __device__ inline void gj_resize_taps(const int i, const int n_src, const int n_out, int& p0, int& p1, int& f)
+{
+    const int d = 2 * n_out;
+    int n = (2 * i + 1) * n_src - n_out;
+    if (n < 0) n = 0;
+    p0 = (int)((unsigned)n / (unsigned)d);
+    f = (int)((unsigned)((n - p0 * d) * 256) / (unsigned)d);
+    p1 = p0 + 1 < n_src ? p0 + 1 : n_src - 1;
+}
+// ... and the blend of the four source values of one channel: (top (256 - fy) + bot fy + 32768) >> 16, top and bot blended with fx
+__host__ __device__ inline int gj_resize_blend(const int v00, const int v01, const int v10, const int v11, const int fx, const int fy)
+{
+    const int top = v00 * (256 - fx) + v01 * fx, bot = v10 * (256 - fx) + v11 * fx;
+    return (top * (256 - fy) + bot * fy + 32768) >> 16;
+}
+
 // LDS written by some lanes of a wave is read by other lanes of the SAME wave: the hardware keeps a wave's LDS operations in
 // order, the compiler only has to be told not to move them across this point (no instruction is emitted for the barrier).
 __device__ __forceinline__ void gj_wave_sync()

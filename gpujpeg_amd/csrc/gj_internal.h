@@ -47,6 +47,10 @@ int gj_geom_init_scaled(gj_geom* gs, const gj_geom* full, const struct gpujpeg_p
  * gr: the geometry of the w x h image whose component planes are the cover's; -1 (with a message) when the region is refused */
 int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
                         const int region[4], unsigned alignment, struct gpujpeg_image_parameters* pi_region);
+/* crop-and-resize: the geometry of the out_w x out_h image over the component planes of `cover` (from gj_geom_init_region; go may be cover itself);
+ * -1 (with a message) for an output size outside 1 .. 16384 or an output format whose pixels share samples */
+int gj_geom_init_resized(gj_geom* go, const gj_geom* cover, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
+                         int out_w, int out_h, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
 
 /* ---- tables ---- */
 extern const uint8_t gj_zigzag[64];

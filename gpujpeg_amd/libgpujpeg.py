@@ -160,6 +160,9 @@ class Library:
         if hasattr(L, "gpujpeg_amd_decoder_decode_batch_regions"):
             L.gpujpeg_amd_decoder_decode_batch_regions.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
                                                                    vp, C.c_size_t, C.POINTER(ImageParameters)]
+        if hasattr(L, "gpujpeg_amd_decoder_decode_batch_crop_resize"):
+            L.gpujpeg_amd_decoder_decode_batch_crop_resize.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int),
+                                                                       C.POINTER(C.c_uint8), C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(ImageParameters)]
 
     # ---- developer settings (include/gpujpeg_amd_ext.h: gpujpeg_amd_tuning) ----
     def tuning(self, setting):
@@ -460,6 +463,46 @@ class Decoder:
         raw = self.lib.image_size(pi)
         return [out[i * bound:i * bound + raw].copy() for i in range(n)], pi
 
+    def decode_batch_crop_resize(self, streams, rects, out_width, out_height, mirror=None, device_out=None, out_stride=None, device_in=None, in_stride=None,
+                                 sizes=None):
+        """gpujpeg_amd_decoder_decode_batch_crop_resize: decode_batch with one rectangle per frame, each of its own size -- frame f is the
+        rects[f] = (x, y, w, h) pixels of stream f's image resampled bilinearly to out_width x out_height and, where mirror[f] is set, mirrored
+        horizontally (the definition: include/gpujpeg_amd_ext.h). streams / device_in, in_stride, sizes and device_out, out_stride as for decode_batch;
+        without device_out the frames come back as a list of numpy arrays. Returns (pixels or None, ImageParameters)."""
+        if not hasattr(self.lib.L, "gpujpeg_amd_decoder_decode_batch_crop_resize"):
+            raise RuntimeError("this library has no gpujpeg_amd_decoder_decode_batch_crop_resize")
+        if device_in is None:
+            sizes = [int(x.size) for x in streams]
+            in_stride = (max(sizes) + 64 + 15) & ~15
+            buf = np.zeros(in_stride * len(sizes), np.uint8)
+            for i, x in enumerate(streams):
+                buf[i * in_stride:i * in_stride + x.size] = x
+            self._keep = buf
+            base = buf.ctypes.data
+        else:
+            base = int(device_in)
+        n = len(sizes)
+        if len(rects) != n or (mirror is not None and len(mirror) != n):
+            raise ValueError("decode_batch_crop_resize needs one rectangle (and, with mirror, one flag) per stream")
+        csz = (C.c_size_t * n)(*sizes)
+        rc4 = (C.c_int * (4 * n))(*[int(v) for r in rects for v in r])
+        mir = None if mirror is None else (C.c_uint8 * n)(*[1 if m else 0 for m in mirror])
+        pi = ImageParameters()
+        call = self.lib.L.gpujpeg_amd_decoder_decode_batch_crop_resize
+        if device_out is not None:
+            rc = call(self.h, base, in_stride, csz, n, rc4, mir, int(out_width), int(out_height), int(device_out), out_stride, C.byref(pi))
+            if rc != 0:
+                raise RuntimeError(f"gpujpeg_amd_decoder_decode_batch_crop_resize failed ({rc})")
+            return None, pi
+        ow, oh = min(max(int(out_width), 1), 16384), min(max(int(out_height), 1), 16384)
+        bound = ow * oh * 4 + 4096 * oh  # (room for any format and line alignment up to 4 KiB)
+        out = np.empty(bound * n, np.uint8)
+        rc = call(self.h, base, in_stride, csz, n, rc4, mir, int(out_width), int(out_height), out.ctypes.data, bound, C.byref(pi))
+        if rc != 0:
+            raise RuntimeError(f"gpujpeg_amd_decoder_decode_batch_crop_resize failed ({rc})")
+        raw = self.lib.image_size(pi)
+        return [out[i * bound:i * bound + raw].copy() for i in range(n)], pi
+
     def region_stats(self):
         """gpujpeg_amd_decoder_get_region_stats of the last decode call: (mode 0 none / 1 selected segments / 2 every segment, restart segments
         entropy-decoded, 8x8 blocks transformed, segments in the stream)"""
@@ -495,7 +538,7 @@ class Decoder:
 
     def idct_path(self):
         """IDCT side of the last perf_stats call: 0 full size, 1 reduced size from the coefficient planes, 2 reduced size from tokens,
-        3 region from the coefficient planes, 4 region from tokens"""
+        3 region from the coefficient planes, 4 region from tokens, 5 region resampled from the cover planes (crop-and-resize)"""
         ms = (C.c_float * 8)()
         if self.lib.L.gpujpeg_amd_decoder_get_kernel_times(self.h, ms) != 0:
             return None

@@ -270,6 +270,8 @@ typedef struct gj_region_frame {
     int x, y;                      /* pixels of the stream's image */
     int bx0[GJ_MAX_COMP], by0[GJ_MAX_COMP], bx1[GJ_MAX_COMP], by1[GJ_MAX_COMP]; /* cover: blocks [bx0, bx1) x [by0, by1) of the component's grid */
     int mx0, my0, mx1, my1;        /* interleaved scan: the cover in MCUs */
+    int w, h;                      /* pixels of the rectangle (a crop-and-resize call: every frame has its own; the other region calls read gj_region::w / h) */
+    int mirror;                    /* crop-and-resize: 1 = the resampled image is mirrored horizontally */
 } gj_region_frame;
 typedef struct gj_region {
     int on;                        /* 1: this call decodes a region */
@@ -287,6 +289,10 @@ typedef struct gj_region {
      * length 0: a segment without blocks for the entropy decoders) up to the next scan's, so that ONE batch plan serves every frame. d_sel_count is
      * not used (every compacted table has sum(sel_count) entries); h_sel_count holds GJ_MAX_COMP words per frame: the entries found per scan. */
     const gj_region_frame* d_frames; /* device memory, [gj_batch::count]; NULL: a single frame */
+    /* crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize): the rectangle -- gj_region_frame::w x h, per frame -- is resampled to the
+     * gs.width x gs.height image by the pixel stage (k_resize_region, bilinear: gj_resize_taps) instead of being copied. gs is then the geometry of
+     * the OUTPUT image over the cover's planes, w / h above are not used, and the call goes through the component planes (no token mode). */
+    int resize;
 } gj_region;
 /* the predicate of the selection (gj_device.h: gj_segment_in_cover) for host code: does restart segment s have a block / an MCU inside the cover? */
 GJ_HIP_API int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s);
@@ -337,7 +343,8 @@ typedef struct gj_dec_job {
      * d_raw, and gs.fb = g.fb. */
     int scale;
     gj_geom gs;
-    int* idct_path;                /* host, may be NULL: which IDCT side ran -- 0 full size, 1 k_idct_scaled, 2 k_idct_tok_scaled_rgb444, 3 k_idct_region, 4 k_idct_tok_region_rgb444 */
+    int* idct_path;                /* host, may be NULL: which IDCT side ran -- 0 full size, 1 k_idct_scaled, 2 k_idct_tok_scaled_rgb444, 3 k_idct_region, 4 k_idct_tok_region_rgb444,
+                                      5 k_idct_region + k_resize_region (crop-and-resize) */
     /* region decode (dec_opt_region, region.on): the entropy decoders work on g -- with region.select on the compacted table --, the IDCT side
      * transforms the cover's blocks -- from tokens straight into d_raw, or into cover-sized planes in d_planes from which the region's pixels go to d_raw --; gs is the geometry of the W x H image
      * with the cover's planes (gj_geom_init_region). No scale, no flip. A single frame, or (region.d_frames) a batch of frames with one

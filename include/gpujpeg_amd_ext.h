@@ -120,9 +120,10 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_optimal(const uint32_t freq[256], uint8
  *          k_scan_segments), [4] k_assemble (behind k_huffman only), [5] k_huffman_count (enc_opt_huffman=optimal; 0 otherwise)
  * decoder: [0] entropy decoder, [1] IDCT (fused path: postprocess included), [2] postprocess, [3] marker scan (k_markers; 0 when the host walked the stream),
  *          [4] not a duration: the IDCT side of that call -- 0 full size, 1 reduced size from the coefficient planes (k_idct_scaled), 2 reduced size from
- *          tokens (k_idct_tok_scaled_rgb444), 3 region from the coefficient planes (k_idct_region), 4 region from tokens (k_idct_tok_region_rgb444);
- *          gpujpeg_amd_decoder_decode_batch_regions leaves the side its batched launches took here (3 or 4) and no durations, and so does
- *          gpujpeg_amd_decoder_decode_batch with a dec_opt_scale (1 or 2) */
+ *          tokens (k_idct_tok_scaled_rgb444), 3 region from the coefficient planes (k_idct_region), 4 region from tokens (k_idct_tok_region_rgb444),
+ *          5 region resampled from the cover planes (k_idct_region + k_resize_region: gpujpeg_amd_decoder_decode_batch_crop_resize);
+ *          gpujpeg_amd_decoder_decode_batch_regions leaves the side its batched launches took here (3 or 4) and no durations, and so do
+ *          gpujpeg_amd_decoder_decode_batch with a dec_opt_scale (1 or 2) and gpujpeg_amd_decoder_decode_batch_crop_resize (5) */
 GPUJPEG_API int gpujpeg_amd_encoder_get_kernel_times(struct gpujpeg_encoder* encoder, float ms[8]);
 GPUJPEG_API int gpujpeg_amd_decoder_get_kernel_times(struct gpujpeg_decoder* decoder, float ms[8]);
 
@@ -186,6 +187,35 @@ GPUJPEG_API int gpujpeg_amd_decoder_get_region_stats(struct gpujpeg_decoder* dec
 GPUJPEG_API int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder* decoder, const uint8_t* streams, size_t stream_stride,
                                                          const size_t* sizes, int count, const int* origins, int width, int height, uint8_t* output,
                                                          size_t output_stride, struct gpujpeg_image_parameters* param_image);
+/* Crop-and-resize, one rectangle per frame: frame f is the rects[4f + 2] x rects[4f + 3] pixels at (rects[4f], rects[4f + 1]) of stream f's image,
+ * resampled to out_width x out_height and, where mirror != NULL and mirror[f] != 0, mirrored horizontally -- the random-resized crop (and flip) of a
+ * training pipeline in one call, every rectangle with its own size and aspect. streams, stream_stride, sizes, output (device or host memory) and
+ * output_stride as for gpujpeg_amd_decoder_decode_batch_regions; pixel format and colour space are the ones set with
+ * gpujpeg_decoder_set_output_format, dec_opt_alignment_bytes applies to the out_width line, param_image and the frame size are those of an
+ * out_width x out_height image. The decoder's own dec_opt_region is neither read nor changed.
+ * DEFINITION. Let C be the w x h image gpujpeg_decoder_decode of this decoder returns for stream f with dec_opt_region = "x,y,w,h", taken channel by
+ * channel, OW = out_width, OH = out_height; integers throughout, division = floor, arithmetic shifts:
+ *     nx = max((2 i + 1) w - OW, 0);  x0 = nx / (2 OW);  fx = ((nx - x0 2 OW) 256) / (2 OW);  x1 = min(x0 + 1, w - 1)          i < OW
+ *     ny, y0, fy, y1 likewise from j, h, OH                                                                                  j < OH
+ *     top = C[y0][x0] (256 - fx) + C[y0][x1] fx;   bot = C[y1][x0] (256 - fx) + C[y1][x1] fx
+ *     R[j][i] = (top (256 - fy) + bot fy + 32768) >> 16;    out[j][i] = mirror && mirror[f] ? R[j][OW - 1 - i] : R[j][i]
+ * Bilinear interpolation with half-pixel centres (align_corners = false, no antialiasing) with 8-bit weights, on output pixels -- after the colour
+ * transform --, the identity for w == OW and h == OH. The fourth byte of GPUJPEG_4444_U8_P0123 goes through the same formula (0xFF stays 0xFF).
+ * Output formats: those whose pixels share no samples (GPUJPEG_U8, GPUJPEG_444_U8_P012, GPUJPEG_444_U8_P0P1P2, GPUJPEG_4444_U8_P0123); they take any
+ * rectangle inside the image of a stream of any sampling.
+ * The frames go through the batched launches of the batch of regions on the coefficient-plane route (every frame's restart segments selected against
+ * its own cover, k_idct_region) with the resampling kernel k_resize_region as the pixel stage; a frame the batched launches do not cover (restart
+ * interval 0, another header, damaged markers, the first frame of a decoder's life, frame 0 of a call whose pixels go to host memory) goes through
+ * the single-frame region call with the same kernel as its pixel stage: the same bytes.
+ * Refused with a message, -1 returned, nothing of `output` written, the decoder usable as before: out_width or out_height outside 1 .. 16384; a
+ * rectangle with w or h < 1 or not inside the stream's image (the message names the frame); an output format whose pixels share samples (packed or
+ * planar 4:2:2, planar 4:2:0); a dec_opt_scale other than 1; dec_opt_flipped; a dec_opt_channel_remap.
+ * Afterwards gpujpeg_amd_decoder_last_batch and gpujpeg_amd_decoder_get_region_stats count as for gpujpeg_amd_decoder_decode_batch_regions, and slot
+ * [4] of gpujpeg_amd_decoder_get_kernel_times is 5. */
+GPUJPEG_API int gpujpeg_amd_decoder_decode_batch_crop_resize(struct gpujpeg_decoder* decoder, const uint8_t* streams, size_t stream_stride,
+                                                             const size_t* sizes, int count, const int* rects, const uint8_t* mirror, int out_width,
+                                                             int out_height, uint8_t* output, size_t output_stride,
+                                                             struct gpujpeg_image_parameters* param_image);
 
 #ifdef __cplusplus
 }
