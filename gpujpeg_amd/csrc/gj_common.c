@@ -571,6 +571,9 @@ int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const st
     gj_region_frame* const rf = &r->frame;
     rf->x = x; rf->y = y;
     rf->w = w; rf->h = h;
+    rf->scale = 1; /* (the covering rectangle of a prescaled crop-and-resize frame: gj_region_prescale) */
+    rf->src_w = w; rf->src_h = h;
+    r->scale_mask = 1u;
     const int px1 = x + gr->raw_width - 1, py1 = y + h - 1; /* the last pixel column / row whose samples are read */
     if (full->interleaved) {
         rf->mx0 = x / (8 * full->max_h);
@@ -649,6 +652,59 @@ int gj_geom_init_resized(gj_geom* go, const gj_geom* cover, const struct gpujpeg
     go->data_size = data_size;
     go->block_count = block_count;
     if (pi_out) *pi_out = rp;
+    return 0;
+}
+
+/* dec_opt_resize_prescale: what a crop-and-resize call puts in front of its resample for ONE frame. rect = x, y, w, h inside the
+ * image_w x image_h image, resampled to out_w x out_h; max_scale = S of the option (1, 2, 4, 8). out = s, x', y', w', h':
+ *     s   the largest of 1, 2, 4, 8 with s <= S, w >= s out_w and h >= s out_h -- the bilinear step then reduces by less than 2 per axis --; 1 for a
+ *         stream with a subsampled component (its chroma would be reduced by the same N as its luma: worse than no prescale)
+ *     x' = x / s, w' = ceil((x + w) / s) - x' (y', h' likewise): the rectangle's covering rectangle in the image reduced by s
+ * -1 where the call refuses (a rectangle that is not inside the image, an output size outside 1 .. 16384, another S). Host arithmetic only. */
+int gj_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const int rect[4], int out_w, int out_h, int max_scale, int out[5])
+{
+    const int x = rect[0], y = rect[1], w = rect[2], h = rect[3];
+    if (image_w < 1 || image_h < 1 || x < 0 || y < 0 || w < 1 || h < 1 || x >= image_w || y >= image_h || w > image_w - x || h > image_h - y) return -1;
+    if (out_w < 1 || out_h < 1 || out_w > 16384 || out_h > 16384) return -1;
+    if (max_scale != 1 && max_scale != 2 && max_scale != 4 && max_scale != 8) return -1;
+    int s = 1;
+    if (all_components_1x1)
+        for (int t = 2; t <= max_scale; t *= 2)
+            if ((long long)t * out_w <= w && (long long)t * out_h <= h) s = t;
+    const int xr = x / s, yr = y / s, wr = (x + w + s - 1) / s - xr, hr = (y + h + s - 1) / s - yr;
+    /* the last output sample's first tap lies inside the covering rectangle (gj_resize_taps: off + n_src <= s n_red); 64 bits here, whatever the sizes */
+    const long long nx = (2LL * out_w - 1) * w + 2LL * out_w * (x - s * xr) - (long long)out_w * s;
+    const long long ny = (2LL * out_h - 1) * h + 2LL * out_h * (y - s * yr) - (long long)out_h * s;
+    if ((nx > 0 && nx / (2LL * out_w * s) > wr - 1) || (ny > 0 && ny / (2LL * out_h * s) > hr - 1)) return -1; /* (cannot happen) */
+    out[0] = s; out[1] = xr; out[2] = yr; out[3] = wr; out[4] = hr;
+    return 0;
+}
+
+/* ... and that plan applied to a frame: go / r / pi_out as gj_geom_init_region + gj_geom_init_resized left them for the CALLER's rectangle `rect`
+ * (which has passed their checks). With s > 1 the frame's cover becomes the one gj_geom_init_region gives for the covering rectangle expanded to
+ * full size, (x' s, y' s, min(w' s, W - x' s), min(h' s, H - y' s)) -- reduced sample X of a component lies in block X / N, the block of full-size
+ * sample X s, so selection, batch plan and entropy decoders need nothing else --, go the out_w x out_h image over that cover's planes, and the
+ * frame's record what k_idct_region_scaled and k_resize_region read (gj_region_frame). */
+int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi,
+                       const int rect[4], int out_w, int out_h, int max_scale, unsigned alignment, struct gpujpeg_image_parameters* pi_out)
+{
+    int all_1x1 = 1, p[5];
+    for (int c = 0; c < full->comp_count; c++)
+        if (full->comp[c].sub_h != 1 || full->comp[c].sub_v != 1) all_1x1 = 0;
+    if (gj_crop_resize_plan(pi->width, pi->height, all_1x1, rect, out_w, out_h, max_scale > 1 ? max_scale : 1, p) != 0) return -1;
+    const int s = p[0];
+    if (s == 1) return 0;
+    int ex[4] = {p[1] * s, p[2] * s, p[3] * s, p[4] * s};
+    if (ex[2] > pi->width - ex[0]) ex[2] = pi->width - ex[0];
+    if (ex[3] > pi->height - ex[1]) ex[3] = pi->height - ex[1];
+    if (gj_geom_init_region(go, r, full, param, pi, ex, alignment, pi_out) != 0) return -1;
+    if (gj_geom_init_resized(go, go, param, pi, out_w, out_h, alignment, pi_out) != 0) return -1;
+    gj_region_frame* const rf = &r->frame;
+    rf->x = p[1]; rf->y = p[2]; rf->w = p[3]; rf->h = p[4];
+    rf->scale = s;
+    rf->src_w = rect[2]; rf->src_h = rect[3];
+    rf->off_x = rect[0] - s * p[1]; rf->off_y = rect[1] - s * p[2];
+    r->scale_mask = (unsigned)s;
     return 0;
 }
 

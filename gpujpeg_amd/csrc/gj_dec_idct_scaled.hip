@@ -21,65 +21,7 @@
 // (part of the decoder's device code, see gj_dec_internal.h for the map of the files)
 #include "gj_dec_internal.h"
 
-// M_N[x][u]
-template <int N>
-__device__ __forceinline__ constexpr int gj_mn(const int x, const int u)
-{
-    constexpr int M4[4][4] = {{2896, 3784, 2896, 1567}, {2896, 1567, -2896, -3784}, {2896, -1567, -2896, 3784}, {2896, -3784, 2896, -1567}};
-    return N == 1 ? 2896 : N == 2 ? ((x & u) ? -2896 : 2896) : M4[x & 3][u & 3];
-}
-
-__device__ __forceinline__ int gj_dequant_clamp(const int f, const int q) { return min(max(f * q, -32768), 32767); }
-
-// D[v * N + u] (dequantised, clamped) -> row y of the block's N x N samples in byte x of out[y]
-template <int N>
-__device__ __forceinline__ void gj_idct_corner(const int (&D)[N * N], uint32_t (&out)[N])
-{
-    int T[N * N];
-#pragma unroll
-    for (int y = 0; y < N; y++)
-#pragma unroll
-        for (int u = 0; u < N; u++) {
-            int s = 1024;
-#pragma unroll
-            for (int v = 0; v < N; v++) s += gj_mn<N>(y, v) * D[v * N + u];
-            T[y * N + u] = s >> 11;
-        }
-#pragma unroll
-    for (int y = 0; y < N; y++) {
-        uint32_t row = 0;
-#pragma unroll
-        for (int x = 0; x < N; x++) {
-            int s = 16384;
-#pragma unroll
-            for (int u = 0; u < N; u++) s += gj_mn<N>(x, u) * T[y * N + u];
-            row |= (uint32_t)min(max((s >> 15) + 128, 0), 255) << (8 * x);
-        }
-        out[y] = row;
-    }
-}
-
-// the N x N corner of a block of the coefficient planes (rows of 8 int16)
-template <int N>
-__device__ __forceinline__ void gj_corner_from_plane(const int16_t* __restrict__ blk, int (&F)[N * N])
-{
-    if constexpr (N == 4) {
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            const uint2 w = *reinterpret_cast<const uint2*>(blk + v * 8);
-            F[v * 4 + 0] = (int16_t)w.x; F[v * 4 + 1] = (int32_t)w.x >> 16;
-            F[v * 4 + 2] = (int16_t)w.y; F[v * 4 + 3] = (int32_t)w.y >> 16;
-        }
-    } else if constexpr (N == 2) {
-#pragma unroll
-        for (int v = 0; v < 2; v++) {
-            const uint32_t w = *reinterpret_cast<const uint32_t*>(blk + v * 8);
-            F[v * 2 + 0] = (int16_t)w; F[v * 2 + 1] = (int32_t)w >> 16;
-        }
-    } else {
-        F[0] = blk[0];
-    }
-}
+// (gj_mn, gj_dequant_clamp, gj_idct_corner, gj_corner_from_plane: gj_dec_internal.h -- k_idct_region_scaled shares them)
 
 // ================================================================================================
 // (a) generic: coefficient planes -> reduced component planes, one lane per block like k_idct

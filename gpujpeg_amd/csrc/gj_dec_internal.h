@@ -14,9 +14,11 @@
 //   gj_dec_idct_scaled.hip      reduced-size output (dec_opt_scale): k_idct_scaled (from the planes), k_idct_tok_scaled_rgb444 (from tokens)
 //   gj_dec_region.hip           region decode (dec_opt_region): k_segment_select (table -> the entries that touch the region's cover), k_idct_region,
 //                               k_postprocess_region / k_copy_planes_region (cover blocks -> cover planes -> the region's pixels),
-//                               k_resize_region (crop-and-resize: the rectangle resampled to the call's output size instead of copied)
+//                               k_resize_region (crop-and-resize: the rectangle resampled to the call's output size instead of copied),
+//                               k_idct_region_scaled (dec_opt_resize_prescale: the cover's blocks through the reduced-size IDCT ahead of it)
 //   this header                 what those share: the 4:4:4 configuration and its colour pairs (gj_is_rgb444, GJ_COLOR_PAIRS), gj_block_of, the block
-//                               records of the token-fed kernels (gj_rec_pack, gj_tok_record) and their token ranges (gj_tok_fetch)
+//                               records of the token-fed kernels (gj_rec_pack, gj_tok_record) and their token ranges (gj_tok_fetch), the N-point IDCT of a
+//                               block's corner (gj_idct_corner)
 //   gj_bitreader.h              unstuffing of a restart segment into an LDS stage, two-level table look-up
 //
 // Restates src/gpujpeg_huffman_gpu_decoder.cu:135-495 (entropy decoding semantics; identical results to
@@ -345,6 +347,67 @@ __device__ __forceinline__ void gj_store_pixel(const gj_geom& g, uint8_t* __rest
 {
     gj_pixel_transform(g, v);
     gj_pixel_store(g, raw, W, H, x, y, pos, v);
+}
+
+// ---- reduced-size IDCT (the definition: gj_dec_idct_scaled.hip), shared by k_idct_scaled, k_idct_tok_scaled_rgb444 and k_idct_region_scaled
+// M_N[x][u]
+template <int N>
+__device__ __forceinline__ constexpr int gj_mn(const int x, const int u)
+{
+    constexpr int M4[4][4] = {{2896, 3784, 2896, 1567}, {2896, 1567, -2896, -3784}, {2896, -1567, -2896, 3784}, {2896, -3784, 2896, -1567}};
+    return N == 1 ? 2896 : N == 2 ? ((x & u) ? -2896 : 2896) : M4[x & 3][u & 3];
+}
+
+__device__ __forceinline__ int gj_dequant_clamp(const int f, const int q) { return min(max(f * q, -32768), 32767); }
+
+// D[v * N + u] (dequantised, clamped) -> row y of the block's N x N samples in byte x of out[y]
+template <int N>
+__device__ __forceinline__ void gj_idct_corner(const int (&D)[N * N], uint32_t (&out)[N])
+{
+    int T[N * N];
+#pragma unroll
+    for (int y = 0; y < N; y++)
+#pragma unroll
+        for (int u = 0; u < N; u++) {
+            int s = 1024;
+#pragma unroll
+            for (int v = 0; v < N; v++) s += gj_mn<N>(y, v) * D[v * N + u];
+            T[y * N + u] = s >> 11;
+        }
+#pragma unroll
+    for (int y = 0; y < N; y++) {
+        uint32_t row = 0;
+#pragma unroll
+        for (int x = 0; x < N; x++) {
+            int s = 16384;
+#pragma unroll
+            for (int u = 0; u < N; u++) s += gj_mn<N>(x, u) * T[y * N + u];
+            row |= (uint32_t)min(max((s >> 15) + 128, 0), 255) << (8 * x);
+        }
+        out[y] = row;
+    }
+}
+
+// the N x N corner of a block of the coefficient planes (rows of 8 int16)
+template <int N>
+__device__ __forceinline__ void gj_corner_from_plane(const int16_t* __restrict__ blk, int (&F)[N * N])
+{
+    if constexpr (N == 4) {
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            const uint2 w = *reinterpret_cast<const uint2*>(blk + v * 8);
+            F[v * 4 + 0] = (int16_t)w.x; F[v * 4 + 1] = (int32_t)w.x >> 16;
+            F[v * 4 + 2] = (int16_t)w.y; F[v * 4 + 3] = (int32_t)w.y >> 16;
+        }
+    } else if constexpr (N == 2) {
+#pragma unroll
+        for (int v = 0; v < 2; v++) {
+            const uint32_t w = *reinterpret_cast<const uint32_t*>(blk + v * 8);
+            F[v * 2 + 0] = (int16_t)w; F[v * 2 + 1] = (int32_t)w >> 16;
+        }
+    } else {
+        F[0] = blk[0];
+    }
 }
 
 // region decode (gj_dec_region.hip): the compacted segment table of job->region (from job's table, which has been written), and the IDCT side

@@ -10,12 +10,15 @@
 //   k_copy_planes_region    the same for planar output whose layout equals the component layout (k_copy_planes_out)
 //   k_resize_region         crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize): in place of the two above, the rectangle resampled
 //                           bilinearly to the call's output size, with an optional horizontal mirror
+//   k_idct_region_scaled    in front of k_resize_region for the frames dec_opt_resize_prescale reduces (gj_region_frame::scale = s > 1): the
+//                           cover's blocks through the N-point IDCT of their N x N corner, N = 8 / s (k_idct_scaled's arithmetic: gj_idct_corner),
+//                           into REDUCED cover planes
 //
 // Every configuration can go this way; three-component 4:4:4 streams with non-interleaved scans and packed 3-byte output in token mode go
 // through k_idct_tok_region_rgb444 (gj_dec_idct.hip, beside k_idct_tok_rgb444 whose LDS helpers it shares) instead of the last three: same bytes.
 //
 // A BATCH of regions (gj_region::d_frames: one rectangle per frame, gpujpeg_amd_decoder_decode_batch_regions) runs the same code with blockIdx.z =
-// frame: k_segment_select_batch, k_idct_region_batch, k_postprocess_region_batch, k_copy_planes_region_batch, k_resize_region_batch and the batched instantiation of
+// frame: k_segment_select_batch, k_idct_region_batch, k_postprocess_region_batch, k_copy_planes_region_batch, k_resize_region_batch, k_idct_region_scaled_batch and the batched instantiation of
 // k_idct_tok_region_rgb444 read their frame's rectangle and cover from device memory and share the bodies of the single-frame kernels.
 // (part of the decoder's device code, see gj_dec_internal.h for the map of the files)
 #include "gj_dec_internal.h"
@@ -213,6 +216,7 @@ __device__ __forceinline__ void gj_idct_region_body(const gj_geom& g, const gj_g
 {
     const unsigned gb = blockIdx.x * 256u + threadIdx.x;
     if (gb >= (unsigned)gr.block_count) return;
+    if (BATCH && r.scale > 1) return; // (a prescaled frame of a crop-and-resize batch: k_idct_region_scaled_batch)
     unsigned bx, by;
     const int c = gj_block_of(gr, gb, bx, by);
     const gj_comp_geom& k = gr.comp[c];
@@ -250,14 +254,80 @@ __global__ __launch_bounds__(256) void k_idct_region_batch(const gj_geom g, cons
     gj_idct_region_body<true>(g, gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, planes + z * g.fb.coefs);
 }
 
-// sample of component c that pixel (x, y) of the REGION needs, in the cover-sized plane: pixel (r.x + x, r.y + y) of the stream's image
-__device__ __forceinline__ size_t gj_region_sample(const gj_comp_geom& k, const gj_region_frame& r, const int c, const unsigned x, const unsigned y)
+// The same for a frame dec_opt_resize_prescale reduces by s = 8 / N: block (bx, by) of the cover leaves the N x N samples of k_idct_scaled -- the
+// corner of the block, gj_dequant_clamp with the uint16 table, gj_idct_corner<N> -- at (bx N, by N) of the component's REDUCED cover plane, laid out
+// like k_idct_scaled's reduced planes inside the slot of the full-size ones: pitch data_width N / 8, offset data_offset N N / 64 (data_offset is a
+// multiple of 64, data_width of 8, the slot's base of 64: rows of N bytes are N-byte aligned). Reads and writes stay inside the frame's own cover.
+template <int N, bool BATCH>
+__device__ __forceinline__ void gj_idct_region_scaled_body(const gj_geom& g, const gj_geom& gr, const gj_region_frame& r, const int16_t* __restrict__ coefs,
+                                                           const uint16_t* __restrict__ qtab, uint8_t* __restrict__ planes)
 {
-    const unsigned sx = ((unsigned)r.x + x) / (unsigned)k.sub_h - (unsigned)r.bx0[c] * 8u;
-    const unsigned sy = ((unsigned)r.y + y) / (unsigned)k.sub_v - (unsigned)r.by0[c] * 8u;
+    const unsigned gb = blockIdx.x * 256u + threadIdx.x;
+    if (gb >= (unsigned)gr.block_count) return;
+    unsigned bx, by;
+    const int c = gj_block_of(gr, gb, bx, by);
+    const gj_comp_geom& k = gr.comp[c];
+    if (BATCH && (bx >= (unsigned)(r.bx1[c] - r.bx0[c]) || by >= (unsigned)(r.by1[c] - r.by0[c]))) return;
+    const gj_comp_geom& kf = g.comp[c];
+    const unsigned fbx = (unsigned)r.bx0[c] + bx, fby = (unsigned)r.by0[c] + by;
+    if (fbx >= (unsigned)kf.blocks_x || fby >= (unsigned)kf.blocks_y) return; // (cannot happen: the cover lies inside the component's grid)
+    int D[N * N];
+    gj_corner_from_plane<N>(coefs + kf.data_offset + ((size_t)fby * kf.blocks_x + fbx) * 64, D);
+    const uint16_t* q = qtab + kf.q_table * 64;
+#pragma unroll
+    for (int v = 0; v < N; v++)
+#pragma unroll
+        for (int u = 0; u < N; u++) D[v * N + u] = gj_dequant_clamp(D[v * N + u], (int)q[v * 8 + u]);
+    uint32_t px[N];
+    gj_idct_corner<N>(D, px);
+    const size_t pitch = (size_t)k.data_width * N / 8;
+    uint8_t* dst = planes + k.data_offset * (N * N) / 64 + (size_t)by * N * pitch + (size_t)bx * N;
+#pragma unroll
+    for (int y = 0; y < N; y++) {
+        if (N == 4) *reinterpret_cast<uint32_t*>(dst + y * pitch) = px[y];
+        else if (N == 2) *reinterpret_cast<uint16_t*>(dst + y * pitch) = (uint16_t)px[y];
+        else dst[0] = (uint8_t)px[0];
+    }
+}
+
+// ONE launch for every scale: the frame's scale is the same in all lanes of a workgroup (blockIdx.z = frame), so the switch does not diverge; a
+// frame of scale 1 leaves (k_idct_region_batch transforms it). The figures of this choice: profiles/idct_side_resources.md.
+template <bool BATCH>
+__device__ __forceinline__ void gj_idct_region_scaled_switch(const gj_geom& g, const gj_geom& gr, const gj_region_frame& r, const int16_t* __restrict__ coefs,
+                                                             const uint16_t* __restrict__ qtab, uint8_t* __restrict__ planes)
+{
+    switch (r.scale) {
+    case 2: gj_idct_region_scaled_body<4, BATCH>(g, gr, r, coefs, qtab, planes); break;
+    case 4: gj_idct_region_scaled_body<2, BATCH>(g, gr, r, coefs, qtab, planes); break;
+    case 8: gj_idct_region_scaled_body<1, BATCH>(g, gr, r, coefs, qtab, planes); break;
+    default: break;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_idct_region_scaled(const gj_geom g, const gj_geom gr, const gj_region r, const int16_t* __restrict__ coefs,
+                                                            const uint16_t* __restrict__ qtab, uint8_t* __restrict__ planes)
+{
+    gj_idct_region_scaled_switch<false>(g, gr, r.frame, coefs, qtab, planes);
+}
+
+__global__ __launch_bounds__(256) void k_idct_region_scaled_batch(const gj_geom g, const gj_geom gr, const gj_region rb, const int16_t* __restrict__ coefs,
+                                                                  const uint16_t* __restrict__ qtab, uint8_t* __restrict__ planes)
+{
+    const size_t z = blockIdx.z;
+    gj_idct_region_scaled_switch<true>(g, gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, planes + z * g.fb.coefs);
+}
+
+// sample of component c that pixel (x, y) of the REGION needs, in the cover-sized plane: pixel (r.x + x, r.y + y) of the stream's image
+// (N = 8, or with a prescale N = 8 / gj_region_frame::scale: the reduced cover plane of k_idct_region_scaled and pixel (x' + x, y' + y) of the reduced image)
+__device__ __forceinline__ size_t gj_region_sample(const gj_comp_geom& k, const gj_region_frame& r, const int c, const unsigned x, const unsigned y,
+                                                   const unsigned N = 8u)
+{
+    const unsigned sx = ((unsigned)r.x + x) / (unsigned)k.sub_h - (unsigned)r.bx0[c] * N;
+    const unsigned sy = ((unsigned)r.y + y) / (unsigned)k.sub_v - (unsigned)r.by0[c] * N;
     // (the cover holds them; its own size bounds them -- the planes of a frame of a batch are laid out for the largest cover, the frame's own may be smaller)
-    const unsigned cw = (unsigned)(r.bx1[c] - r.bx0[c]) * 8u, ch = (unsigned)(r.by1[c] - r.by0[c]) * 8u;
-    return k.data_offset + (size_t)min(sy, ch - 1u) * k.data_width + min(sx, cw - 1u);
+    const unsigned cw = (unsigned)(r.bx1[c] - r.bx0[c]) * N, ch = (unsigned)(r.by1[c] - r.by0[c]) * N;
+    const size_t offset = N == 8u ? (size_t)k.data_offset : (size_t)(k.data_offset * (N * N) / 64), pitch = N == 8u ? (size_t)k.data_width : (size_t)k.data_width * N / 8;
+    return offset + (size_t)min(sy, ch - 1u) * pitch + min(sx, cw - 1u);
 }
 
 // k_postprocess for a region: one lane per pixel of the W x H image (raw_width x height of gr)
@@ -320,7 +390,8 @@ __global__ __launch_bounds__(256) void k_copy_planes_region_batch(const gj_geom 
 // gr.width x gr.height (gr: the geometry of the OUTPUT image over the cover's planes). One lane per output pixel: its four source pixels of the
 // rectangle (gj_resize_taps; a mirrored frame reads column OW - 1 - i), each made like k_postprocess_region makes a pixel -- the components' samples
 // inside the cover, the expansion of a single component, the colour transform --, blended per channel with 8-bit weights (gj_resize_blend) and
-// stored in the output format. The result is the resize of what the region call returns, which is why a no_transform configuration
+// stored in the output format. A frame with a prescale (gj_region_frame::scale > 1) reads the reduced cover planes at the taps of the reduced image.
+// The result is the resize of what the region call returns, which is why a no_transform configuration
 // (k_copy_planes_region: no colour stage) blends the samples as they are. Output formats whose pixels share no samples only (the host refuses the others).
 __device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const gj_region_frame& r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
 {
@@ -329,8 +400,10 @@ __device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const g
     if (pos >= OW * OH) return;
     const unsigned j = pos / OW, i = pos - j * OW;
     int sx[2], sy[2], fx, fy;
-    gj_resize_taps(r.mirror ? (int)(OW - 1u - i) : (int)i, r.w, (int)OW, sx[0], sx[1], fx);
-    gj_resize_taps((int)j, r.h, (int)OH, sy[0], sy[1], fy);
+    const int s = r.scale > 1 ? r.scale : 1; // (a prescaled frame: the taps in the reduced image, the samples in the reduced cover planes)
+    const unsigned N = 8u / (unsigned)s;
+    gj_resize_taps(r.mirror ? (int)(OW - 1u - i) : (int)i, r.src_w, (int)OW, r.off_x, s, r.w, sx[0], sx[1], fx);
+    gj_resize_taps((int)j, r.src_h, (int)OH, r.off_y, s, r.h, sy[0], sy[1], fy);
     int v[4][4]; // [source pixel: top left, top right, bottom left, bottom right][channel]
 #pragma unroll
     for (int q = 0; q < 4; q++) {
@@ -339,7 +412,7 @@ __device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const g
 #pragma unroll
         for (int c = 0; c < GJ_MAX_COMP; c++) {
             if (c >= gr.comp_count) break;
-            v[q][c] = planes[gj_region_sample(gr.comp[c], r, c, (unsigned)sx[q & 1], (unsigned)sy[q >> 1])];
+            v[q][c] = planes[gj_region_sample(gr.comp[c], r, c, (unsigned)sx[q & 1], (unsigned)sy[q >> 1], N)];
         }
         if (!gr.no_transform) gj_pixel_transform(gr, v[q]);
     }
@@ -374,8 +447,13 @@ void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tok
         if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
         return;
     }
-    hipLaunchKernelGGL(batch ? k_idct_region_batch : k_idct_region, dim3(((unsigned)gr.block_count + 255) / 256, 1, frames), dim3(256), 0, st, job->g, gr, r,
-                       job->d_coefs, job->d_qtabf, job->d_planes);
+    // (crop-and-resize with a prescale: the frames of scale 1 through the full-size kernel, the others through the reduced-size one -- each launch
+    // only where the chunk has such frames, gj_region::scale_mask; every other region call: scale 1 alone)
+    const dim3 grid(((unsigned)gr.block_count + 255) / 256, 1, frames);
+    const unsigned scales = r.resize && r.scale_mask ? r.scale_mask : 1u;
+    if (scales & 1u) hipLaunchKernelGGL(batch ? k_idct_region_batch : k_idct_region, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtabf, job->d_planes);
+    if (scales & ~1u)
+        hipLaunchKernelGGL(batch ? k_idct_region_scaled_batch : k_idct_region_scaled, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtab, job->d_planes);
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
     if (r.resize) { // crop-and-resize: gr is the output image's geometry
         const unsigned n = (unsigned)gr.width * (unsigned)gr.height;

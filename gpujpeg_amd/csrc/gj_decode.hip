@@ -56,6 +56,8 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     if (rg.on && rg.resize && (job->tokens || job->channel_remap || job->gs.width < 1 || job->gs.height < 1 || job->gs.width > GJ_RESIZE_MAX_OUT ||
                                job->gs.height > GJ_RESIZE_MAX_OUT || job->gs.raw_width != job->gs.width))
         return -1;
+    // (a scale per frame, gj_region_frame::scale: inside a resize job alone -- dec_opt_resize_prescale --, one of 1, 2, 4, 8; gj_dec_job::scale stays 1)
+    if (rg.on && ((rg.scale_mask & ~(rg.resize ? 0xFu : 1u)) != 0 || (!rg_batch && rg.frame.scale > 1 && (!rg.resize || rg.scale_mask != (unsigned)rg.frame.scale)))) return -1;
     if (rg.on && (job->scale > 1 || job->flipped || (rg.select && (!rg.d_sel || !rg.h_sel_count || g.restart_interval <= 0)) ||
                   (rg_batch ? (g.fb.sizes == nullptr || !rg.select || job->channel_remap) : (g.fb.sizes != nullptr || job->batch.count > 1 || (rg.select && !rg.d_sel_count)))))
         return -1;

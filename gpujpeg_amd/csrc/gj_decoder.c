@@ -101,6 +101,10 @@ struct gpujpeg_decoder {
      * call alone, for its own duration; its single-frame route is the region call with these on (dec_region_geometry) */
     bool resize_on; int resize_w, resize_h, resize_mirror;
     bool call_resize;                              /* what the decode call in progress (and, after it, the last one) used: geom_s / pi_s are the resampled image's */
+    /* dec_opt_resize_prescale: the largest reduction crop-and-resize may put in front of its resample (0 / 1: none, else 2, 4, 8). Read by that call alone,
+     * per frame (gj_region_prescale); the scale every frame of its last call took: gpujpeg_amd_decoder_get_prescales */
+    int resize_prescale;
+    uint8_t* prescales; int prescales_n, prescales_cap;
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
@@ -147,12 +151,17 @@ static int dec_region_geometry(struct gpujpeg_decoder* d)
     if (gj_geom_init_region(&d->geom_s, &rg, &c->geom, &c->param, &c->param_image, d->region, d->req_alignment, &d->pi_s) != 0) return -1;
     /* crop-and-resize: the image of the call is the resampled one, over the planes of this rectangle's cover */
     if (d->resize_on && gj_geom_init_resized(&d->geom_s, &d->geom_s, &c->param, &c->param_image, d->resize_w, d->resize_h, d->req_alignment, &d->pi_s) != 0) return -1;
+    /* ... and with dec_opt_resize_prescale the planes are the reduced ones of the covering rectangle's cover */
+    if (d->resize_on && gj_region_prescale(&d->geom_s, &rg, &c->geom, &c->param, &c->param_image, d->region, d->resize_w, d->resize_h, d->resize_prescale,
+                                           d->req_alignment, &d->pi_s) != 0)
+        return -1;
     /* the plan of a selection: one question per segment of the geometry, asked again only when the region or the stream's geometry changes */
     if (c->geom.restart_interval > 0) {
         /* (keyed on the cover itself -- the pixel rectangle alone does not fix it: packed 4:2:2 output widens it to the pixel pair --, so with the
          * origin taken out: it moves inside a cover without changing the selection; a new geometry drops the plan in decoder_configure) */
         gj_region_frame cover = rg.frame;
         cover.x = cover.y = cover.w = cover.h = cover.mirror = 0;
+        cover.scale = cover.src_w = cover.src_h = cover.off_x = cover.off_y = 0;
         if (!d->plan_valid || memcmp(&d->plan_cover, &cover, sizeof cover) != 0) {
             memset(rg.sel_count, 0, sizeof rg.sel_count);
             for (int sc = 0, s = 0; sc < c->geom.scan_count && sc < GJ_MAX_COMP; sc++) {
@@ -250,7 +259,7 @@ int gpujpeg_decoder_destroy(struct gpujpeg_decoder* d)
     gj_hip_host_free(d->h_raw); gj_hip_host_free(d->h_seg); gj_hip_host_free(d->h_tabs);
     free(d->hdr_cache); gj_hip_free(d->d_hdr_cache);
     gj_hip_host_free(d->h_hdr); gj_hip_host_free(d->h_summary); gj_hip_host_free(d->h_maxlen); gj_hip_free(d->d_summary); gj_hip_free(d->d_scan_scratch);
-    free(d->segs.pos); free(d->segs.len); free(d->segs.index);
+    free(d->segs.pos); free(d->segs.len); free(d->segs.index); free(d->prescales);
     gj_hip_free(d->d_sel); gj_hip_free(d->d_sel_count); gj_hip_host_free(d->h_sel_count);
     gj_hip_free(d->b_dsum); gj_hip_free(d->b_sizes); gj_hip_free(d->b_seg); gj_hip_free(d->b_scratch); gj_hip_free(d->b_coefs); gj_hip_free(d->b_planes); gj_hip_free(d->b_tok);
     gj_hip_free(d->b_rec); gj_hip_free(d->b_jpeg); gj_hip_free(d->b_raw); gj_hip_free(d->b_gather); gj_hip_free(d->b_scatter);
@@ -1039,6 +1048,8 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b)
         }
         if (b->rects) { /* (the output image over this frame's cover; refuses the output formats whose pixels share samples) */
             if (gj_geom_init_resized(&b->gs_one, &b->gs_one, &c->param, &c->param_image, b->ow, b->oh, d->req_alignment, &b->pi_r) != 0) return -1;
+            if (gj_region_prescale(&b->gs_one, &rg, g, &c->param, &c->param_image, region, b->ow, b->oh, d->resize_prescale, d->req_alignment, &b->pi_r) != 0) return -1;
+            if (f < d->prescales_n) d->prescales[f] = (uint8_t)rg.frame.scale;
             rg.resize = 1;
             rg.frame.mirror = b->mirror && b->mirror[f] ? 1 : 0;
         }
@@ -1093,6 +1104,7 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
         if (b->rects) GJ_ERROR("Frame %d of the batch: crop-and-resize of the rectangle %d,%d,%d,%d failed!\n", f, d->region[0], d->region[1], d->region[2], d->region[3]);
         return -1;
     }
+    if (b->rects && f < d->prescales_n) d->prescales[f] = (uint8_t)d->rg.frame.scale;
     if (batch_has_regions(b)) {
         if (d->region_stats[0] != 1) b->unselected = true;
         for (int i = 1; i < 4; i++) b->stats[i] += d->region_stats[i];
@@ -1305,6 +1317,8 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         if (regions || job.scale > 1) job.gs.fb.sizes = B.d_sizes;
         if (regions) {
             job.region.d_frames = d->b_rgn + first + a;
+            job.region.scale_mask = 0; /* (which of the two IDCT kernels this chunk's frames need) */
+            for (uint32_t i = 0; i < B.count; i++) job.region.scale_mask |= (unsigned)d->bh_rgn[first + a + (int)i].scale;
             job.region.h_sel_count = d->bh_found + (size_t)(first + a) * GJ_MAX_COMP;
         }
         job.d_jpeg = d_streams + (size_t)a * d_stride;
@@ -1463,6 +1477,7 @@ int gpujpeg_amd_decoder_decode_batch_crop_resize(struct gpujpeg_decoder* d, cons
                                                  struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !rects) return -1;
+    d->prescales_n = 0;
     if (out_width < 1 || out_height < 1 || out_width > 16384 || out_height > 16384) {
         GJ_ERROR("Crop-and-resize needs an output width and height of 1 to 16384 (given: %d x %d)!\n", out_width, out_height);
         return -1;
@@ -1497,8 +1512,24 @@ int gpujpeg_amd_decoder_decode_batch_crop_resize(struct gpujpeg_decoder* d, cons
     d->resize_w = out_width;
     d->resize_h = out_height;
     d->resize_mirror = 0;
+    /* (the scale every frame takes, as launched: written by the plan of the batched launches and by the frames that go the ordinary way) */
+    d->prescales_n = 0;
+    if (count > d->prescales_cap) {
+        uint8_t* p = realloc(d->prescales, (size_t)count);
+        if (!p) return -1;
+        d->prescales = p;
+        d->prescales_cap = count;
+    }
+    memset(d->prescales, 1, (size_t)count);
+    d->prescales_n = count;
     const struct dec_batch what = {.rects = rects, .mirror = mirror, .ow = out_width, .oh = out_height};
-    const int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
+    int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
+    if (rc == 0) { /* (slot [4] of the kernel times, gpujpeg_amd_ext.h: 6 when any frame of the call was prescaled, whichever launch came last) */
+        for (int f = 0; f < count; f++)
+            if (d->prescales[f] > 1) { d->coder.kernel_ms[4] = 6.0f; break; }
+    } else {
+        d->prescales_n = 0;
+    }
     d->resize_on = false;
     d->region_on = own_on;
     memcpy(d->region, own, sizeof own);
@@ -1625,6 +1656,13 @@ int gpujpeg_decoder_set_option(struct gpujpeg_decoder* d, const char* opt, const
         GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_SCALE " (1, 1/2, 1/4 or 1/8)\n", val);
         return GPUJPEG_ERROR;
     }
+    if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE) == 0) { /* read by gpujpeg_amd_decoder_decode_batch_crop_resize alone */
+        static const char* const names[4] = {"1", "1/2", "1/4", "1/8"};
+        for (int i = 0; i < 4; i++)
+            if (strcmp(val, names[i]) == 0) { d->resize_prescale = 1 << i; return GPUJPEG_NOERR; }
+        GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE " (1, 1/2, 1/4 or 1/8)\n", val);
+        return GPUJPEG_ERROR;
+    }
     if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_REGION) == 0) { /* syntax only: the decode call checks the region against its stream */
         if (strcmp(val, "full") == 0) { d->region_on = false; return GPUJPEG_NOERR; }
         long v[4];
@@ -1655,6 +1693,7 @@ void gpujpeg_decoder_print_options(void)
     printf("\t" GPUJPEG_DEC_OPT_FLIPPED_BOOL "=[" GPUJPEG_VAL_TRUE "|" GPUJPEG_VAL_FALSE "] - whether the output image should be vertically flipped\n");
     printf("\t" GPUJPEG_DEC_OPT_CHANNEL_REMAP "=XYZ[W] - output channel remapping, 'help' for details\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_SCALE "=[1|1/2|1/4|1/8] - decode to a reduced-size image (MI355X extension)\n");
+    printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE "=[1|1/2|1/4|1/8] - largest reduced-size IDCT crop-and-resize may put ahead of its resample (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_REGION "=[X,Y,W,H|full] - decode the W x H pixels at (X, Y) only (MI355X extension)\n");
 }
 
@@ -1693,6 +1732,19 @@ size_t gpujpeg_amd_decoder_read_planes(struct gpujpeg_decoder* d, uint8_t* dst, 
     if (!d->coder.configured || capacity < n) return 0;
     if (gj_hip_memcpy_d2h(dst, d->coder.d_planes, n, d->coder.stream) != 0 || gj_hip_stream_sync(d->coder.stream) != 0) return 0;
     return n;
+}
+
+int gpujpeg_amd_host_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const int rect[4], int out_w, int out_h, int max_scale, int out[5])
+{
+    if (!rect || !out) return -1;
+    return gj_crop_resize_plan(image_w, image_h, all_components_1x1, rect, out_w, out_h, max_scale, out);
+}
+
+int gpujpeg_amd_decoder_get_prescales(struct gpujpeg_decoder* d, uint8_t* dst, int capacity)
+{
+    if (!d || !dst || d->prescales_n < 1 || capacity < d->prescales_n) return 0;
+    memcpy(dst, d->prescales, (size_t)d->prescales_n);
+    return d->prescales_n;
 }
 
 int gpujpeg_amd_decoder_get_region_stats(struct gpujpeg_decoder* d, long out[4])

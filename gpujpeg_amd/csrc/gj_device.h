@@ -133,18 +133,27 @@ __host__ __device__ inline bool gj_segment_in_cover(const gj_geom& g, const gj_r
 
 // Crop-and-resize (gj_region::resize): output sample i of n_out along one axis of an n_src-sample crop reads source samples p0 and p1 with the
 // weights 256 - f and f (8 bits). Bilinear interpolation with half-pixel centres (align_corners = false, no antialiasing): the source position
-// is ((2i + 1) n_src - n_out) / (2 n_out), clamped at 0; p1 is clamped to the last sample. Integer arithmetic, division = floor; nothing
-// overflows 32 bits for n_src <= 65535 and n_out <= 16384 (2 * 16384 * 65535 < 2^31). The identity for n_src == n_out.
+// is ((2i + 1) n_src - n_out) / (2 n_out), clamped at 0; p1 is clamped to the last sample. Integer arithmetic, division = floor. The identity
+// for n_src == n_out.
+// With a prescale (dec_opt_resize_prescale, gj_region_frame::scale = s > 1) the samples are those of the image reduced by s: the crop starts `off`
+// full-size samples (0 .. s - 1) behind the first of its n_red reduced samples, and the source position is ((off + (i + 1/2) n_src / n_out) / s) - 1/2
+// in reduced samples -- exactly: n = (2i + 1) n_src + 2 n_out off - n_out s over d = 2 n_out s. For s = 1, off = 0, n_red = n_src these are the
+// lines above term for term.
+// Range: off + n_src <= s n_red (the reduced samples cover the crop), so n < d n_red and p0 <= n_red - 1. s n_red < 65535 + 2 s for the images
+// a JPEG header can describe, n_out <= 16384: d n_red < 2^15 * 65551 < 2^32, and (n - p0 d) 256 < d 256 <= 2^26 -- 32-bit UNSIGNED throughout
+// (the sum of the two positive terms first, then the clamped subtraction).
 // The ONE statement of the resampling positions: k_resize_region and host code ask here.
 #define GJ_RESIZE_MAX_OUT 16384
-__host__ __device__ inline void gj_resize_taps(const int i, const int n_src, const int n_out, int& p0, int& p1, int& f)
+__host__ __device__ inline void gj_resize_taps(const int i, const int n_src, const int n_out, const int off, const int s, const int n_red, int& p0, int& p1,
+                                               int& f)
 {
-    const int d = 2 * n_out;
-    int n = (2 * i + 1) * n_src - n_out;
-    if (n < 0) n = 0;
-    p0 = (int)((unsigned)n / (unsigned)d);
-    f = (int)((unsigned)((n - p0 * d) * 256) / (unsigned)d);
-    p1 = p0 + 1 < n_src ? p0 + 1 : n_src - 1;
+    const unsigned d = 2u * (unsigned)n_out * (unsigned)s;
+    const unsigned a = (2u * (unsigned)i + 1u) * (unsigned)n_src + 2u * (unsigned)n_out * (unsigned)off, b = (unsigned)n_out * (unsigned)s;
+    const unsigned n = a > b ? a - b : 0u;
+    const unsigned q = n / d;
+    p0 = (int)q;
+    f = (int)(((n - q * d) * 256u) / d);
+    p1 = p0 + 1 < n_red ? p0 + 1 : n_red - 1;
 }
 // ... and the blend of the four source values of one channel: (top (256 - fy) + bot fy + 32768) >> 16, top and bot blended with fx
 __host__ __device__ inline int gj_resize_blend(const int v00, const int v01, const int v10, const int v11, const int fx, const int fy)

@@ -51,6 +51,11 @@ int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const st
  * -1 (with a message) for an output size outside 1 .. 16384 or an output format whose pixels share samples */
 int gj_geom_init_resized(gj_geom* go, const gj_geom* cover, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
                          int out_w, int out_h, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
+/* dec_opt_resize_prescale: the scale and covering rectangle of one crop-and-resize frame (out = s, x', y', w', h'; -1 where the call refuses), and
+ * that plan applied to what gj_geom_init_region + gj_geom_init_resized made for the caller's rectangle `rect` (s > 1: the expanded cover, the frame's record) */
+int gj_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const int rect[4], int out_w, int out_h, int max_scale, int out[5]);
+int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
+                       const int rect[4], int out_w, int out_h, int max_scale, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
 
 /* ---- tables ---- */
 extern const uint8_t gj_zigzag[64];

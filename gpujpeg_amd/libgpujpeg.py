@@ -163,6 +163,9 @@ class Library:
         if hasattr(L, "gpujpeg_amd_decoder_decode_batch_crop_resize"):
             L.gpujpeg_amd_decoder_decode_batch_crop_resize.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int),
                                                                        C.POINTER(C.c_uint8), C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(ImageParameters)]
+        if hasattr(L, "gpujpeg_amd_host_crop_resize_plan"):
+            L.gpujpeg_amd_host_crop_resize_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+            L.gpujpeg_amd_decoder_get_prescales.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int]
 
     # ---- developer settings (include/gpujpeg_amd_ext.h: gpujpeg_amd_tuning) ----
     def tuning(self, setting):
@@ -196,6 +199,15 @@ class Library:
 
     def image_size(self, param_image):
         return self.L.gpujpeg_image_calculate_size(C.byref(param_image))
+
+
+def crop_resize_plan(lib, image_w, image_h, all_components_1x1, rect, out_w, out_h, max_scale):
+    """gpujpeg_amd_host_crop_resize_plan (host only, lib: a Library): what dec_opt_resize_prescale = 1/max_scale gives one frame of a crop-and-resize
+    call -- rect = (x, y, w, h) of an image_w x image_h image resampled to out_w x out_h -> (s, x', y', w', h'), or None where the call would refuse"""
+    out = (C.c_int * 5)()
+    r4 = (C.c_int * 4)(*[int(v) for v in rect])
+    rc = lib.L.gpujpeg_amd_host_crop_resize_plan(int(image_w), int(image_h), int(bool(all_components_1x1)), r4, int(out_w), int(out_h), int(max_scale), out)
+    return tuple(out) if rc == 0 else None
 
 
 def apply_environment_settings(lib, environ=None):
@@ -503,6 +515,14 @@ class Decoder:
         raw = self.lib.image_size(pi)
         return [out[i * bound:i * bound + raw].copy() for i in range(n)], pi
 
+    def prescales(self):
+        """gpujpeg_amd_decoder_get_prescales: the scale s_f (1, 2, 4, 8) every frame of the last decode_batch_crop_resize call took ahead of its resample
+        (set_option("dec_opt_resize_prescale", "1/8") allows up to 8); [] when there was no such call or it failed"""
+        cap = 65536
+        a = (C.c_uint8 * cap)()
+        n = self.lib.L.gpujpeg_amd_decoder_get_prescales(self.h, a, cap)
+        return [int(a[i]) for i in range(n)]
+
     def region_stats(self):
         """gpujpeg_amd_decoder_get_region_stats of the last decode call: (mode 0 none / 1 selected segments / 2 every segment, restart segments
         entropy-decoded, 8x8 blocks transformed, segments in the stream)"""
@@ -538,7 +558,8 @@ class Decoder:
 
     def idct_path(self):
         """IDCT side of the last perf_stats call: 0 full size, 1 reduced size from the coefficient planes, 2 reduced size from tokens,
-        3 region from the coefficient planes, 4 region from tokens, 5 region resampled from the cover planes (crop-and-resize)"""
+        3 region from the coefficient planes, 4 region from tokens, 5 region resampled from the cover planes (crop-and-resize), 6 the same with a frame
+        reduced ahead of the resample (dec_opt_resize_prescale)"""
         ms = (C.c_float * 8)()
         if self.lib.L.gpujpeg_amd_decoder_get_kernel_times(self.h, ms) != 0:
             return None

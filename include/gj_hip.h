@@ -272,6 +272,12 @@ typedef struct gj_region_frame {
     int mx0, my0, mx1, my1;        /* interleaved scan: the cover in MCUs */
     int w, h;                      /* pixels of the rectangle (a crop-and-resize call: every frame has its own; the other region calls read gj_region::w / h) */
     int mirror;                    /* crop-and-resize: 1 = the resampled image is mirrored horizontally */
+    /* crop-and-resize with dec_opt_resize_prescale: the cover's blocks leave N x N samples, N = 8 / scale, and the resample reads the
+     * REDUCED cover planes. x, y, w, h above are then x', y', w', h' -- the rectangle's covering rectangle in the image reduced by `scale` --,
+     * src_w / src_h the caller's w and h, off_x / off_y = x - scale x', y - scale y': what gj_resize_taps needs. Every other region call: scale 1,
+     * src_w = w, src_h = h, offsets 0 (gj_geom_init_region). */
+    int scale;                     /* 1, 2, 4 or 8 */
+    int src_w, src_h, off_x, off_y;
 } gj_region_frame;
 typedef struct gj_region {
     int on;                        /* 1: this call decodes a region */
@@ -293,6 +299,9 @@ typedef struct gj_region {
      * gs.width x gs.height image by the pixel stage (k_resize_region, bilinear: gj_resize_taps) instead of being copied. gs is then the geometry of
      * the OUTPUT image over the cover's planes, w / h above are not used, and the call goes through the component planes (no token mode). */
     int resize;
+    /* ... and the scales (gj_region_frame::scale) among the frames of this launch, bit log2(scale): k_idct_region serves the frames of scale 1,
+     * k_idct_region_scaled the others; a launch without frames for one of them is left out. Anything but 1 outside a resize job is refused. */
+    unsigned scale_mask;
 } gj_region;
 /* the predicate of the selection (gj_device.h: gj_segment_in_cover) for host code: does restart segment s have a block / an MCU inside the cover? */
 GJ_HIP_API int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s);
@@ -344,7 +353,7 @@ typedef struct gj_dec_job {
     int scale;
     gj_geom gs;
     int* idct_path;                /* host, may be NULL: which IDCT side ran -- 0 full size, 1 k_idct_scaled, 2 k_idct_tok_scaled_rgb444, 3 k_idct_region, 4 k_idct_tok_region_rgb444,
-                                      5 k_idct_region + k_resize_region (crop-and-resize) */
+                                      5 k_idct_region + k_resize_region (crop-and-resize), 6 the same with a frame through k_idct_region_scaled (dec_opt_resize_prescale) */
     /* region decode (dec_opt_region, region.on): the entropy decoders work on g -- with region.select on the compacted table --, the IDCT side
      * transforms the cover's blocks -- from tokens straight into d_raw, or into cover-sized planes in d_planes from which the region's pixels go to d_raw --; gs is the geometry of the W x H image
      * with the cover's planes (gj_geom_init_region). No scale, no flip. A single frame, or (region.d_frames) a batch of frames with one

@@ -110,6 +110,12 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
  * of component c: see DESIGN 4.2) and gpujpeg_amd_decoder_read_coefficients the full planes, of which only the blocks of the entropy-decoded
  * segments are this frame's. */
 #define GPUJPEG_AMD_DEC_OPT_REGION "dec_opt_region"
+/* Decoder option "dec_opt_resize_prescale" = "1" (default), "1/2", "1/4" or "1/8": the largest reduction S that
+ * gpujpeg_amd_decoder_decode_batch_crop_resize may put in front of its resample -- the reduced-size IDCT of dec_opt_scale over the rectangle's cover,
+ * a low-pass filter that costs less than the transform it replaces, where the bilinear resample alone would point-sample a rectangle much larger
+ * than the output. Read by that call alone (its definition with a prescale: below); every other call, and that call with "1", is what it is without
+ * the option. Another value is refused by gpujpeg_decoder_set_option and leaves the setting as it was. dec_opt_scale itself stays refused by the call. */
+#define GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE "dec_opt_resize_prescale"
 /* Host-only: the table enc_opt_huffman=optimal builds for one class from symbol counts freq[256] (ITU T.81 Annex K.2: Figures K.1, K.3, K.4;
  * reserved code point, ties to the larger symbol value), code lengths limited to the largest L of 16 .. 10 whose table the library's
  * two-level decode tables take. Writes BITS (bits[1..16]) and HUFFVAL; returns L, or -1 when no count is non-zero. */
@@ -121,9 +127,10 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_optimal(const uint32_t freq[256], uint8
  * decoder: [0] entropy decoder, [1] IDCT (fused path: postprocess included), [2] postprocess, [3] marker scan (k_markers; 0 when the host walked the stream),
  *          [4] not a duration: the IDCT side of that call -- 0 full size, 1 reduced size from the coefficient planes (k_idct_scaled), 2 reduced size from
  *          tokens (k_idct_tok_scaled_rgb444), 3 region from the coefficient planes (k_idct_region), 4 region from tokens (k_idct_tok_region_rgb444),
- *          5 region resampled from the cover planes (k_idct_region + k_resize_region: gpujpeg_amd_decoder_decode_batch_crop_resize);
+ *          5 region resampled from the cover planes (k_idct_region + k_resize_region: gpujpeg_amd_decoder_decode_batch_crop_resize),
  *          gpujpeg_amd_decoder_decode_batch_regions leaves the side its batched launches took here (3 or 4) and no durations, and so do
- *          gpujpeg_amd_decoder_decode_batch with a dec_opt_scale (1 or 2) and gpujpeg_amd_decoder_decode_batch_crop_resize (5) */
+ *          6 the same with at least one frame of the call reduced ahead of the resample (k_idct_region_scaled: dec_opt_resize_prescale);
+ *          gpujpeg_amd_decoder_decode_batch with a dec_opt_scale (1 or 2) and gpujpeg_amd_decoder_decode_batch_crop_resize (5 or 6) */
 GPUJPEG_API int gpujpeg_amd_encoder_get_kernel_times(struct gpujpeg_encoder* encoder, float ms[8]);
 GPUJPEG_API int gpujpeg_amd_decoder_get_kernel_times(struct gpujpeg_decoder* decoder, float ms[8]);
 
@@ -211,11 +218,35 @@ GPUJPEG_API int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder*
  * rectangle with w or h < 1 or not inside the stream's image (the message names the frame); an output format whose pixels share samples (packed or
  * planar 4:2:2, planar 4:2:0); a dec_opt_scale other than 1; dec_opt_flipped; a dec_opt_channel_remap.
  * Afterwards gpujpeg_amd_decoder_last_batch and gpujpeg_amd_decoder_get_region_stats count as for gpujpeg_amd_decoder_decode_batch_regions, and slot
- * [4] of gpujpeg_amd_decoder_get_kernel_times is 5. */
+ * [4] of gpujpeg_amd_decoder_get_kernel_times is 5.
+ * WITH dec_opt_resize_prescale = 1/S. Frame f with rectangle (x, y, w, h) takes the scale s_f = the largest s of 1, 2, 4, 8 with s <= S, w >= s OW and
+ * h >= s OH (the bilinear step then reduces by less than 2 per axis); s_f = 1 for a stream with a component whose sampling is not 1 x 1 (dec_opt_scale
+ * reduces subsampled chroma by the same N as luma: at 1/8 one sample per 16 x 16 pixels, worse than no prescale). With s_f = 1 the frame is as above.
+ * With s = s_f > 1 let Rs be the image gpujpeg_decoder_decode of this decoder returns for stream f with dec_opt_scale = 1/s, and
+ *     x' = x / s;  w' = ceil((x + w) / s) - x';  y', h' likewise;  C' = the w' x h' crop of Rs at (x', y')  (inside Rs because x + w <= W)
+ *     d  = 2 OW s;  nx = max((2 i + 1) w + 2 OW (x - s x') - OW s, 0);  x0 = nx / d;  fx = ((nx - x0 d) 256) / d;  x1 = min(x0 + 1, w' - 1)
+ *     ny, y0, fy, y1 likewise from j, h, y, y', h', OH;  top, bot, R and the mirror as above with C' for C.
+ * The source position is ((x + (i + 1/2) w / OW) / s) - 1/2 in reduced pixels, exactly: the rectangle does not move (resizing the covering rectangle
+ * with the taps above would move it by up to s - 1 pixels); x0 <= w' - 1 always; for s = 1 the lines are the ones above term for term.
+ * The cover of such a frame is the one the region call has for (x' s, y' s, min(w' s, W - x' s), min(h' s, H - y' s)): selection and entropy decoding
+ * as before, k_idct_region_scaled for its blocks (N = 8 / s samples per block edge), k_resize_region over the reduced cover planes; a batch mixes
+ * scales freely, and the single-frame route takes the same kernels: the same bytes. Refusals are the same and are made on the caller's rectangle.
+ * Afterwards gpujpeg_amd_decoder_get_prescales gives s_f of every frame, slot [4] of the kernel times is 6 when any s_f > 1 (else 5),
+ * gpujpeg_amd_decoder_get_region_stats counts the covers as launched (out[2]: their 8x8 blocks), and gpujpeg_amd_decoder_read_planes returns the last
+ * frame's cover-sized buffer whose first bytes are its REDUCED cover planes (component c: offset N N / 64 of the cover plane's, pitch N / 8 of its). */
 GPUJPEG_API int gpujpeg_amd_decoder_decode_batch_crop_resize(struct gpujpeg_decoder* decoder, const uint8_t* streams, size_t stream_stride,
                                                              const size_t* sizes, int count, const int* rects, const uint8_t* mirror, int out_width,
                                                              int out_height, uint8_t* output, size_t output_stride,
                                                              struct gpujpeg_image_parameters* param_image);
+/* Host-only: scale and covering rectangle dec_opt_resize_prescale gives ONE frame of a crop-and-resize call -- rect = x, y, w, h in an
+ * image_w x image_h image whose components are (all_components_1x1 != 0) or are not all sampled 1 x 1, output out_w x out_h, max_scale = S (1, 2, 4, 8).
+ * Writes out = s, x', y', w', h' (the definition above; the code the call itself runs) and returns 0, or -1 where the call would refuse: a rectangle
+ * with w or h < 1 or not inside the image, an output size outside 1 .. 16384, another max_scale. */
+GPUJPEG_API int gpujpeg_amd_host_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const int rect[4], int out_w, int out_h, int max_scale,
+                                                  int out[5]);
+/* s_f of every frame of the decoder's last gpujpeg_amd_decoder_decode_batch_crop_resize call, as launched: dst[f], one byte per frame. Returns the
+ * frame count, or 0 on error (no such call yet, the last one failed, capacity too small). */
+GPUJPEG_API int gpujpeg_amd_decoder_get_prescales(struct gpujpeg_decoder* decoder, uint8_t* dst, int capacity);
 
 #ifdef __cplusplus
 }
