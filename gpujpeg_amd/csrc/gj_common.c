@@ -5,6 +5,7 @@
  */
 #define _GNU_SOURCE
 #include <assert.h>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -614,9 +615,12 @@ int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const st
 /* Crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize): a region whose rectangle is resampled to out_w x out_h. go becomes
  * gj_geom_init of the out_w x out_h image -- what the resampling kernel stores -- over the component planes of `cover` (a geometry
  * gj_geom_init_region made for the rectangle: the kernel reads them). `alignment` applies to the out_w line. -1 with a message: an output size
- * outside 1 .. 16384, an output format whose pixels share samples. */
+ * outside 1 .. 16384, an output format whose pixels share samples.
+ * tensor (may be NULL; on = 0: none): the call stores a tensor instead of the format's bytes (gpujpeg_amd_decoder_decode_batch_crop_resize_tensor).
+ * Its channel count is set here -- 1 for u8, 3 for packed or planar 4:4:4, any other format is refused -- and go->raw_size, the ONE statement of a
+ * frame's byte size for everything behind it (stride check, staging, download), becomes channels x out_w x out_h x the element size. */
 int gj_geom_init_resized(gj_geom* go, const gj_geom* cover, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi, int out_w,
-                         int out_h, unsigned alignment, struct gpujpeg_image_parameters* pi_out)
+                         int out_h, unsigned alignment, gj_tensor* tensor, struct gpujpeg_image_parameters* pi_out)
 {
     if (out_w < 1 || out_h < 1 || out_w > 16384 || out_h > 16384) {
         GJ_ERROR("Crop-and-resize needs an output width and height of 1 to 16384 (given: %d x %d)!\n", out_w, out_h);
@@ -651,6 +655,23 @@ int gj_geom_init_resized(gj_geom* go, const gj_geom* cover, const struct gpujpeg
     }
     go->data_size = data_size;
     go->block_count = block_count;
+    if (tensor && tensor->on) {
+        if (pf != GPUJPEG_U8 && pf != GPUJPEG_444_U8_P012 && pf != GPUJPEG_444_U8_P0P1P2) {
+            GJ_ERROR("Tensor output is implemented for the pixel formats u8, 444-u8-p012 and 444-u8-p0p1p2, not for %s!\n", gpujpeg_pixel_format_get_name(pf));
+            return -1;
+        }
+        if (rp.width_padding != 0) { /* (cannot happen: the call refuses a line alignment) */
+            GJ_ERROR("Tensor output has no line padding!\n");
+            return -1;
+        }
+        tensor->channels = pf == GPUJPEG_U8 ? 1 : 3;
+        for (int c = 0; c < tensor->channels; c++)
+            if (!isfinite(tensor->scale[c]) || !isfinite(tensor->bias[c])) {
+                GJ_ERROR("Tensor output: scale and bias of channel %d must be finite (given: %g, %g)!\n", c, (double)tensor->scale[c], (double)tensor->bias[c]);
+                return -1;
+            }
+        go->raw_size = (uint64_t)tensor->channels * (uint64_t)out_w * (uint64_t)out_h * GJ_TENSOR_ELSIZE(tensor->dtype);
+    }
     if (pi_out) *pi_out = rp;
     return 0;
 }
@@ -697,8 +718,10 @@ int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const str
     int ex[4] = {p[1] * s, p[2] * s, p[3] * s, p[4] * s};
     if (ex[2] > pi->width - ex[0]) ex[2] = pi->width - ex[0];
     if (ex[3] > pi->height - ex[1]) ex[3] = pi->height - ex[1];
+    const gj_tensor tensor = r->tensor; /* (what the frame stores: the caller's, kept across the new region) */
     if (gj_geom_init_region(go, r, full, param, pi, ex, alignment, pi_out) != 0) return -1;
-    if (gj_geom_init_resized(go, go, param, pi, out_w, out_h, alignment, pi_out) != 0) return -1;
+    r->tensor = tensor;
+    if (gj_geom_init_resized(go, go, param, pi, out_w, out_h, alignment, &r->tensor, pi_out) != 0) return -1;
     gj_region_frame* const rf = &r->frame;
     rf->x = p[1]; rf->y = p[2]; rf->w = p[3]; rf->h = p[4];
     rf->scale = s;

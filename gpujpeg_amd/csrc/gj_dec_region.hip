@@ -10,6 +10,8 @@
 //   k_copy_planes_region    the same for planar output whose layout equals the component layout (k_copy_planes_out)
 //   k_resize_region         crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize): in place of the two above, the rectangle resampled
 //                           bilinearly to the call's output size, with an optional horizontal mirror
+//   k_resize_region_tensor  the same pixels stored as a normalised float tensor (gpujpeg_amd_decoder_decode_batch_crop_resize_tensor: f32 / f16 / bf16,
+//                           CHW / HWC, element = byte * scale[c] + bias[c]) -- k_resize_region up to and including the blend, another store
 //   k_idct_region_scaled    in front of k_resize_region for the frames dec_opt_resize_prescale reduces (gj_region_frame::scale = s > 1): the
 //                           cover's blocks through the N-point IDCT of their N x N corner, N = 8 / s (k_idct_scaled's arithmetic: gj_idct_corner),
 //                           into REDUCED cover planes
@@ -18,12 +20,13 @@
 // through k_idct_tok_region_rgb444 (gj_dec_idct.hip, beside k_idct_tok_rgb444 whose LDS helpers it shares) instead of the last three: same bytes.
 //
 // A BATCH of regions (gj_region::d_frames: one rectangle per frame, gpujpeg_amd_decoder_decode_batch_regions) runs the same code with blockIdx.z =
-// frame: k_segment_select_batch, k_idct_region_batch, k_postprocess_region_batch, k_copy_planes_region_batch, k_resize_region_batch, k_idct_region_scaled_batch and the batched instantiation of
+// frame: k_segment_select_batch, k_idct_region_batch, k_postprocess_region_batch, k_copy_planes_region_batch, k_resize_region_batch, k_resize_region_tensor_batch, k_idct_region_scaled_batch and the batched instantiation of
 // k_idct_tok_region_rgb444 read their frame's rectangle and cover from device memory and share the bodies of the single-frame kernels.
 // (part of the decoder's device code, see gj_dec_internal.h for the map of the files)
 #include "gj_dec_internal.h"
 
 extern "C" int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s) { return gj_segment_in_cover(*g, r->frame, s) ? 1 : 0; }
+extern "C" uint32_t gj_hip_tensor_element(const gj_tensor* t, int c, int v) { return gj_tensor_element(*t, c, v); }
 
 // ================================================================================================
 // Selection
@@ -386,6 +389,21 @@ __global__ __launch_bounds__(256) void k_copy_planes_region_batch(const gj_geom 
     gj_copy_planes_region_body(gr, rb.d_frames[z], planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
 }
 
+// The store of a tensor call's pixel stage: channel c of output pixel `pos` (of `plane` = OW x OH) -> element pos of plane c (CHW) or element
+// pos x channels + c (HWC) of the frame's tensor `out`, as gj_tensor_element makes it. One lane per pixel: a wave's stores to a plane of a CHW frame are
+// 64 consecutive elements, to an HWC frame 64 x channels consecutive elements. dtype and layout are the same in every lane (kernel arguments).
+__device__ __forceinline__ void gj_tensor_store(const gj_tensor& t, uint8_t* __restrict__ out, const unsigned plane, const unsigned pos, const int (&v)[4])
+{
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        if (c >= t.channels) break;
+        const size_t at = t.layout == GJ_TENSOR_HWC ? (size_t)pos * (unsigned)t.channels + c : (size_t)c * plane + pos;
+        const uint32_t e = gj_tensor_element(t, c, v[c]);
+        if (t.dtype == GJ_TENSOR_F32) reinterpret_cast<uint32_t*>(out)[at] = e;
+        else reinterpret_cast<uint16_t*>(out)[at] = (uint16_t)e;
+    }
+}
+
 // Crop-and-resize (gj_region::resize): the pixel stage of a call whose rectangle -- r.w x r.h, every frame's own -- is resampled to ONE output size,
 // gr.width x gr.height (gr: the geometry of the OUTPUT image over the cover's planes). One lane per output pixel: its four source pixels of the
 // rectangle (gj_resize_taps; a mirrored frame reads column OW - 1 - i), each made like k_postprocess_region makes a pixel -- the components' samples
@@ -393,7 +411,11 @@ __global__ __launch_bounds__(256) void k_copy_planes_region_batch(const gj_geom 
 // stored in the output format. A frame with a prescale (gj_region_frame::scale > 1) reads the reduced cover planes at the taps of the reduced image.
 // The result is the resize of what the region call returns, which is why a no_transform configuration
 // (k_copy_planes_region: no colour stage) blends the samples as they are. Output formats whose pixels share no samples only (the host refuses the others).
-__device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const gj_region_frame& r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+// TENSOR (gj_region::tensor, gpujpeg_amd_decoder_decode_batch_crop_resize_tensor): the same up to and including the blend; the channels of the blended pixel
+// then go to the frame's tensor as float(byte) * scale + bias in the call's element type and layout (gj_tensor_store) instead of to the pixel format's bytes.
+template <bool TENSOR>
+__device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const gj_region_frame& r, const gj_tensor& t, const uint8_t* __restrict__ planes,
+                                                      uint8_t* __restrict__ raw)
 {
     const unsigned OW = (unsigned)gr.width, OH = (unsigned)gr.height;
     const unsigned pos = blockIdx.x * 256u + threadIdx.x;
@@ -419,19 +441,32 @@ __device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const g
     int o[4];
 #pragma unroll
     for (int ch = 0; ch < 4; ch++) o[ch] = gj_resize_blend(v[0][ch], v[1][ch], v[2][ch], v[3][ch], fx, fy);
-    gj_pixel_store(gr, raw, OW, OH, i, j, pos, o);
+    if (TENSOR) gj_tensor_store(t, raw, OW * OH, pos, o);
+    else gj_pixel_store(gr, raw, OW, OH, i, j, pos, o);
 }
 
 __global__ __launch_bounds__(256) void k_resize_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
 {
-    gj_resize_region_body(gr, r.frame, planes, raw);
+    gj_resize_region_body<false>(gr, r.frame, r.tensor, planes, raw);
+}
+
+__global__ __launch_bounds__(256) void k_resize_region_tensor(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    gj_resize_region_body<true>(gr, r.frame, r.tensor, planes, raw);
 }
 
 // frame blockIdx.z of a batch: its rectangle and mirror flag, its cover planes (laid out for the largest cover: gr), its slot of the output
 __global__ __launch_bounds__(256) void k_resize_region_batch(const gj_geom gr, const gj_region rb, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
 {
     const size_t z = blockIdx.z;
-    gj_resize_region_body(gr, rb.d_frames[z], planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
+    gj_resize_region_body<false>(gr, rb.d_frames[z], rb.tensor, planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
+}
+
+// ... and its slot of the output as a tensor (gr.fb.raw: bytes between two frames, a multiple of the element size)
+__global__ __launch_bounds__(256) void k_resize_region_tensor_batch(const gj_geom gr, const gj_region rb, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    const size_t z = blockIdx.z;
+    gj_resize_region_body<true>(gr, rb.d_frames[z], rb.tensor, planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
 }
 
 // The IDCT side of a region call: cover blocks -> cover planes -> region pixels. A batch of regions (d_frames) runs the same stages through the
@@ -457,7 +492,10 @@ void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tok
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
     if (r.resize) { // crop-and-resize: gr is the output image's geometry
         const unsigned n = (unsigned)gr.width * (unsigned)gr.height;
-        hipLaunchKernelGGL(batch ? k_resize_region_batch : k_resize_region, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
+        if (r.tensor.on) // (gpujpeg_amd_decoder_decode_batch_crop_resize_tensor: the same pixels, stored as the call's tensor)
+            hipLaunchKernelGGL(batch ? k_resize_region_tensor_batch : k_resize_region_tensor, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
+        else
+            hipLaunchKernelGGL(batch ? k_resize_region_batch : k_resize_region, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
     } else if (gr.no_transform) {
         const size_t n = (size_t)gr.comp[0].width * gr.comp[0].height;
         hipLaunchKernelGGL(batch ? k_copy_planes_region_batch : k_copy_planes_region, dim3((unsigned)min((n + 255) / 256, (size_t)2048), 1, frames), dim3(256), 0, st,

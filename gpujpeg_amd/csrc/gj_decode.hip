@@ -56,6 +56,14 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     if (rg.on && rg.resize && (job->tokens || job->channel_remap || job->gs.width < 1 || job->gs.height < 1 || job->gs.width > GJ_RESIZE_MAX_OUT ||
                                job->gs.height > GJ_RESIZE_MAX_OUT || job->gs.raw_width != job->gs.width))
         return -1;
+    // (a tensor, gj_region::tensor: the store of a resize job alone; an element type and a layout the store knows; one channel for single-channel
+    // output, three for packed or planar 4:4:4; gs.raw_size is the tensor's, and in a batch the frames lie whole elements apart)
+    if (rg.on && rg.tensor.on &&
+        (!rg.resize || rg.tensor.dtype < GJ_TENSOR_F32 || rg.tensor.dtype > GJ_TENSOR_BF16 || (rg.tensor.layout != GJ_TENSOR_CHW && rg.tensor.layout != GJ_TENSOR_HWC) ||
+         rg.tensor.channels != (job->gs.pixel_format == GJ_PF_U8 ? 1 : 3) || (job->gs.pixel_format != GJ_PF_U8 && job->gs.pixel_format != GJ_PF_444_P012 && job->gs.pixel_format != GJ_PF_444_P0P1P2) ||
+         job->gs.raw_size != (uint64_t)rg.tensor.channels * job->gs.width * job->gs.height * GJ_TENSOR_ELSIZE(rg.tensor.dtype) ||
+         ((uintptr_t)job->d_raw | (g.fb.sizes != nullptr ? (uintptr_t)job->gs.fb.raw : 0)) % GJ_TENSOR_ELSIZE(rg.tensor.dtype) != 0))
+        return -1;
     // (a scale per frame, gj_region_frame::scale: inside a resize job alone -- dec_opt_resize_prescale --, one of 1, 2, 4, 8; gj_dec_job::scale stays 1)
     if (rg.on && ((rg.scale_mask & ~(rg.resize ? 0xFu : 1u)) != 0 || (!rg_batch && rg.frame.scale > 1 && (!rg.resize || rg.scale_mask != (unsigned)rg.frame.scale)))) return -1;
     if (rg.on && (job->scale > 1 || job->flipped || (rg.select && (!rg.d_sel || !rg.h_sel_count || g.restart_interval <= 0)) ||

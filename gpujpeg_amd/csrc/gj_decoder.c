@@ -100,6 +100,9 @@ struct gpujpeg_decoder {
     /* crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize): a region call whose rectangle is resampled to resize_w x resize_h. Set by that
      * call alone, for its own duration; its single-frame route is the region call with these on (dec_region_geometry) */
     bool resize_on; int resize_w, resize_h, resize_mirror;
+    /* ... and what its pixel stage stores: on = 0 the bytes of the pixel format, 1 the tensor of gpujpeg_amd_decoder_decode_batch_crop_resize_tensor.
+     * Set by that call alone, for its own duration, like the fields above */
+    gj_tensor resize_tensor;
     bool call_resize;                              /* what the decode call in progress (and, after it, the last one) used: geom_s / pi_s are the resampled image's */
     /* dec_opt_resize_prescale: the largest reduction crop-and-resize may put in front of its resample (0 / 1: none, else 2, 4, 8). Read by that call alone,
      * per frame (gj_region_prescale); the scale every frame of its last call took: gpujpeg_amd_decoder_get_prescales */
@@ -150,7 +153,8 @@ static int dec_region_geometry(struct gpujpeg_decoder* d)
     gj_region rg;
     if (gj_geom_init_region(&d->geom_s, &rg, &c->geom, &c->param, &c->param_image, d->region, d->req_alignment, &d->pi_s) != 0) return -1;
     /* crop-and-resize: the image of the call is the resampled one, over the planes of this rectangle's cover */
-    if (d->resize_on && gj_geom_init_resized(&d->geom_s, &d->geom_s, &c->param, &c->param_image, d->resize_w, d->resize_h, d->req_alignment, &d->pi_s) != 0) return -1;
+    if (d->resize_on) rg.tensor = d->resize_tensor; /* (a tensor call: geom_s.raw_size is the tensor's) */
+    if (d->resize_on && gj_geom_init_resized(&d->geom_s, &d->geom_s, &c->param, &c->param_image, d->resize_w, d->resize_h, d->req_alignment, &rg.tensor, &d->pi_s) != 0) return -1;
     /* ... and with dec_opt_resize_prescale the planes are the reduced ones of the covering rectangle's cover */
     if (d->resize_on && gj_region_prescale(&d->geom_s, &rg, &c->geom, &c->param, &c->param_image, d->region, d->resize_w, d->resize_h, d->resize_prescale,
                                            d->req_alignment, &d->pi_s) != 0)
@@ -985,6 +989,7 @@ struct dec_batch {
     /* crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize; origins == NULL): a batch of regions whose rectangles have their own sizes and
      * are resampled to ONE ow x oh image per frame */
     const int* rects; const uint8_t* mirror; int ow, oh; /* frame f: the rectangle rects[4f .. 4f + 3] = x, y, w, h; mirrored when mirror && mirror[f] */
+    gj_tensor tensor;                    /* ... stored as this tensor (on = 0: as the bytes of the pixel format) */
     bool planned;                        /* the rectangles have been checked against the streams' geometry; what follows is valid then */
     int* plan;                           /* [count][GJ_MAX_COMP] restart segments of every scan that touch frame f's cover */
     int plan_max[GJ_MAX_COMP];           /* the largest of them per scan */
@@ -1047,7 +1052,8 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b)
             return -1;
         }
         if (b->rects) { /* (the output image over this frame's cover; refuses the output formats whose pixels share samples) */
-            if (gj_geom_init_resized(&b->gs_one, &b->gs_one, &c->param, &c->param_image, b->ow, b->oh, d->req_alignment, &b->pi_r) != 0) return -1;
+            rg.tensor = b->tensor; /* (a tensor call: gs_one.raw_size is the tensor's) */
+            if (gj_geom_init_resized(&b->gs_one, &b->gs_one, &c->param, &c->param_image, b->ow, b->oh, d->req_alignment, &rg.tensor, &b->pi_r) != 0) return -1;
             if (gj_region_prescale(&b->gs_one, &rg, g, &c->param, &c->param_image, region, b->ow, b->oh, d->resize_prescale, d->req_alignment, &b->pi_r) != 0) return -1;
             if (f < d->prescales_n) d->prescales[f] = (uint8_t)rg.frame.scale;
             rg.resize = 1;
@@ -1099,6 +1105,7 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
         batch_rectangle(b, f, d->region);
         /* (crop-and-resize: the same call with the resampling kernel as its pixel stage -- resize_on, set by the public call for its duration) */
         d->resize_mirror = b->mirror && b->mirror[f] ? 1 : 0;
+        d->resize_tensor = b->tensor;
     }
     if (decoder_decode(d, (uint8_t*)(uintptr_t)(b->streams + (size_t)f * b->stream_stride), b->sizes[f], &o) != 0) {
         if (b->rects) GJ_ERROR("Frame %d of the batch: crop-and-resize of the rectangle %d,%d,%d,%d failed!\n", f, d->region[0], d->region[1], d->region[2], d->region[3]);
@@ -1372,6 +1379,7 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
     if (what) {
         b.origins = what->origins; b.rw = what->rw; b.rh = what->rh;
         b.rects = what->rects; b.mirror = what->mirror; b.ow = what->ow; b.oh = what->oh;
+        b.tensor = what->tensor;
     }
     const bool regions = batch_has_regions(&b);
     b.streams_on_device = gj_hip_is_device_ptr(streams) != 0;
@@ -1472,9 +1480,10 @@ int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder* d, const ui
 /* Crop-and-resize: one rectangle per frame, each with its own size, resampled to ONE out_width x out_height image per frame (bilinear, gj_resize_taps),
  * optionally mirrored. A batch of regions whose pixel stage resamples: the same plan, selection, entropy decoders and k_idct_region_batch -- always
  * through the cover planes --, then k_resize_region_batch. As for the batch of regions, the decoder's own dec_opt_region is neither read nor changed. */
-int gpujpeg_amd_decoder_decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count,
-                                                 const int* rects, const uint8_t* mirror, int out_width, int out_height, uint8_t* output, size_t output_stride,
-                                                 struct gpujpeg_image_parameters* param_image)
+/* (tensor: NULL, or what gpujpeg_amd_decoder_decode_batch_crop_resize_tensor checked -- the same call with another store in its pixel stage) */
+static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count, const int* rects,
+                                    const uint8_t* mirror, int out_width, int out_height, const gj_tensor* tensor, uint8_t* output, size_t output_stride,
+                                    struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !rects) return -1;
     d->prescales_n = 0;
@@ -1522,7 +1531,8 @@ int gpujpeg_amd_decoder_decode_batch_crop_resize(struct gpujpeg_decoder* d, cons
     }
     memset(d->prescales, 1, (size_t)count);
     d->prescales_n = count;
-    const struct dec_batch what = {.rects = rects, .mirror = mirror, .ow = out_width, .oh = out_height};
+    struct dec_batch what = {.rects = rects, .mirror = mirror, .ow = out_width, .oh = out_height};
+    if (tensor) what.tensor = *tensor;
     int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
     if (rc == 0) { /* (slot [4] of the kernel times, gpujpeg_amd_ext.h: 6 when any frame of the call was prescaled, whichever launch came last) */
         for (int f = 0; f < count; f++)
@@ -1531,9 +1541,62 @@ int gpujpeg_amd_decoder_decode_batch_crop_resize(struct gpujpeg_decoder* d, cons
         d->prescales_n = 0;
     }
     d->resize_on = false;
+    memset(&d->resize_tensor, 0, sizeof d->resize_tensor); /* (no later call sees a tensor) */
     d->region_on = own_on;
     memcpy(d->region, own, sizeof own);
     return rc;
+}
+
+int gpujpeg_amd_decoder_decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count,
+                                                 const int* rects, const uint8_t* mirror, int out_width, int out_height, uint8_t* output, size_t output_stride,
+                                                 struct gpujpeg_image_parameters* param_image)
+{
+    return decode_batch_crop_resize(d, streams, stream_stride, sizes, count, rects, mirror, out_width, out_height, NULL, output, output_stride, param_image);
+}
+
+/* The same call with a normalised float tensor as its result: what is checked here is the format and what it asks of the output; everything else --
+ * refusals, routing, fallbacks, statistics -- is the call above. The frame's byte size is the tensor's from gj_geom_init_resized on. */
+int gpujpeg_amd_decoder_decode_batch_crop_resize_tensor(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count,
+                                                        const int* rects, const uint8_t* mirror, int out_width, int out_height,
+                                                        const struct gpujpeg_amd_tensor_format* format, void* output, size_t output_stride,
+                                                        struct gpujpeg_image_parameters* param_image)
+{
+    if (!d || !streams || !sizes || count < 1 || !output || !rects) return -1;
+    d->prescales_n = 0;
+    if (!format) {
+        GJ_ERROR("Tensor output needs a format!\n");
+        return -1;
+    }
+    if (format->dtype < GPUJPEG_AMD_TENSOR_F32 || format->dtype > GPUJPEG_AMD_TENSOR_BF16 || (format->layout != GPUJPEG_AMD_TENSOR_CHW && format->layout != GPUJPEG_AMD_TENSOR_HWC)) {
+        GJ_ERROR("Tensor output: unknown element type %d or layout %d!\n", format->dtype, format->layout);
+        return -1;
+    }
+    /* (the pixel format -- and with it the channel count -- and the scales and biases of those channels are checked where the frame's geometry is made,
+     * gj_geom_init_resized: for a cold and a warm decoder alike before anything is written) */
+    if (d->req_alignment > 1) {
+        GJ_ERROR("Tensor output is not available together with " GPUJPEG_DEC_OPT_ALIGNMENT_BYTES_INT "=%u: its frames are dense!\n", d->req_alignment);
+        return -1;
+    }
+    const size_t elsize = (size_t)GJ_TENSOR_ELSIZE(format->dtype);
+    if ((uintptr_t)output % elsize != 0 || output_stride % elsize != 0) {
+        GJ_ERROR("Tensor output: the buffer and the output stride (%zu) must be multiples of the element size (%zu B)!\n", output_stride, elsize);
+        return -1;
+    }
+    /* (a stride smaller than a frame: the call above refuses it once the channel count is known, before anything is written) */
+    gj_tensor t = {.on = 1, .dtype = format->dtype, .layout = format->layout};
+    memcpy(t.scale, format->scale, sizeof t.scale);
+    memcpy(t.bias, format->bias, sizeof t.bias);
+    return decode_batch_crop_resize(d, streams, stream_stride, sizes, count, rects, mirror, out_width, out_height, &t, (uint8_t*)output, output_stride, param_image);
+}
+
+/* host-only: the element the tensor call stores for byte v of channel c (the code its kernels run: gj_device.h, gj_tensor_element) */
+uint32_t gpujpeg_amd_host_tensor_element(const struct gpujpeg_amd_tensor_format* format, int channel, int v)
+{
+    if (!format || format->dtype < GPUJPEG_AMD_TENSOR_F32 || format->dtype > GPUJPEG_AMD_TENSOR_BF16 || channel < 0 || channel > 2 || v < 0 || v > 255) return 0;
+    gj_tensor t = {.on = 1, .dtype = format->dtype, .layout = format->layout};
+    memcpy(t.scale, format->scale, sizeof t.scale);
+    memcpy(t.bias, format->bias, sizeof t.bias);
+    return gj_hip_tensor_element(&t, channel, v);
 }
 
 /* The same for streams and destinations that are separate buffers (device or host memory). The streams are gathered 16 bytes aligned in a staging

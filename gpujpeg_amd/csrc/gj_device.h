@@ -162,6 +162,57 @@ __host__ __device__ inline int gj_resize_blend(const int v00, const int v01, con
     return (top * (256 - fy) + bot * fy + 32768) >> 16;
 }
 
+// Tensor output of crop-and-resize (gj_tensor): binary32 -> the bits of binary16 / bfloat16, round to nearest even. binary16: subnormals are produced
+// (not flushed), what rounds to 65520 or more is infinity; bfloat16: the upper half of the word after the rounding increment. Integer arithmetic on
+// the float's bits -- the portable form, which host code and the CPU tier run --; device code takes the hardware's conversion (v_cvt_f16_f32,
+// v_cvt_pk_bf16_f32: the same rounding, the binary16 denormal mode of a HIP kernel keeps subnormals).
+__host__ __device__ inline uint32_t gj_f32_to_f16_bits(const float f)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(GJ_HIPEMU)
+    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+#else
+    const uint32_t b = __builtin_bit_cast(uint32_t, f), sign = (b >> 16) & 0x8000u, a = b & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) return sign | 0x7E00u;  // NaN
+    if (a >= 0x47800000u) return sign | 0x7C00u; // 65536 and more, infinity
+    const uint32_t e = a >> 23;
+    uint32_t h, rem, half;
+    if (e >= 113u) { // normal: exponent rebiased by 112, 13 bits of the mantissa dropped (a carry out of the mantissa raises the exponent, up to infinity)
+        h = (a - 0x38000000u) >> 13;
+        rem = a & 0x1FFFu;
+        half = 0x1000u;
+    } else { // subnormal: units of 2^-24
+        if (e < 102u) return sign; // less than 2^-25
+        const uint32_t m = (a & 0x7FFFFFu) | 0x800000u, shift = 126u - e; // 14 .. 24
+        h = m >> shift;
+        rem = m & ((1u << shift) - 1u);
+        half = 1u << (shift - 1u);
+    }
+    if (rem > half || (rem == half && (h & 1u))) h++;
+    return sign | h;
+#endif
+}
+
+__host__ __device__ inline uint32_t gj_f32_to_bf16_bits(const float f)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(GJ_HIPEMU)
+    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f);
+#else
+    const uint32_t b = __builtin_bit_cast(uint32_t, f);
+    if ((b & 0x7FFFFFFFu) > 0x7F800000u) return (b >> 16) | 0x40u; // NaN
+    return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;
+#endif
+}
+
+// ... and the element itself: the bits stored for byte v of channel c -- float(v) * scale[c], then + bias[c], each rounded to nearest even in binary32
+// and never fused into one operation, then the conversion. The ONE statement of it: k_resize_region_tensor and gpujpeg_amd_host_tensor_element ask here.
+__host__ __device__ inline uint32_t gj_tensor_element(const gj_tensor& t, const int c, const int v)
+{
+#pragma clang fp contract(off)
+    const float p = (float)v * t.scale[c];
+    const float f = p + t.bias[c];
+    return t.dtype == GJ_TENSOR_F32 ? __builtin_bit_cast(uint32_t, f) : t.dtype == GJ_TENSOR_F16 ? gj_f32_to_f16_bits(f) : gj_f32_to_bf16_bits(f);
+}
+
 // LDS written by some lanes of a wave is read by other lanes of the SAME wave: the hardware keeps a wave's LDS operations in
 // order, the compiler only has to be told not to move them across this point (no instruction is emitted for the barrier).
 __device__ __forceinline__ void gj_wave_sync()

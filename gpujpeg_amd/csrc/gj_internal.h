@@ -48,11 +48,13 @@ int gj_geom_init_scaled(gj_geom* gs, const gj_geom* full, const struct gpujpeg_p
 int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
                         const int region[4], unsigned alignment, struct gpujpeg_image_parameters* pi_region);
 /* crop-and-resize: the geometry of the out_w x out_h image over the component planes of `cover` (from gj_geom_init_region; go may be cover itself);
- * -1 (with a message) for an output size outside 1 .. 16384 or an output format whose pixels share samples */
+ * -1 (with a message) for an output size outside 1 .. 16384 or an output format whose pixels share samples. tensor (NULL or on = 0: none): the call
+ * stores a tensor -- its channel count is set, go->raw_size becomes the tensor's byte size, a format other than u8 / packed / planar 4:4:4 is refused */
 int gj_geom_init_resized(gj_geom* go, const gj_geom* cover, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
-                         int out_w, int out_h, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
+                         int out_w, int out_h, unsigned alignment, gj_tensor* tensor, struct gpujpeg_image_parameters* pi_out);
 /* dec_opt_resize_prescale: the scale and covering rectangle of one crop-and-resize frame (out = s, x', y', w', h'; -1 where the call refuses), and
- * that plan applied to what gj_geom_init_region + gj_geom_init_resized made for the caller's rectangle `rect` (s > 1: the expanded cover, the frame's record) */
+ * that plan applied to what gj_geom_init_region + gj_geom_init_resized made for the caller's rectangle `rect` (s > 1: the expanded cover, the frame's record;
+ * r->tensor is kept and the new geometry sized with it) */
 int gj_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const int rect[4], int out_w, int out_h, int max_scale, int out[5]);
 int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
                        const int rect[4], int out_w, int out_h, int max_scale, unsigned alignment, struct gpujpeg_image_parameters* pi_out);

@@ -89,6 +89,34 @@ class ImageInfo(C.Union):  # gpujpeg_decoder.h:270-283 (512-byte union)
     _fields_ = [("f", _ImageInfoFields), ("reserved", C.c_char * 512)]
 
 
+TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2  # gpujpeg_amd_ext.h: GPUJPEG_AMD_TENSOR_*
+TENSOR_CHW, TENSOR_HWC = 0, 1
+TENSOR_ELSIZE = {TENSOR_F32: 4, TENSOR_F16: 2, TENSOR_BF16: 2}
+TENSOR_NUMPY = {TENSOR_F32: np.float32, TENSOR_F16: np.float16, TENSOR_BF16: np.uint16}  # (bfloat16: the bit patterns)
+
+
+class TensorFormat(C.Structure):  # gpujpeg_amd_ext.h: struct gpujpeg_amd_tensor_format (40 bytes; scale / bias [3] reserved)
+    _fields_ = [("dtype", C.c_int), ("layout", C.c_int), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
+def tensor_format(dtype, layout, scale, bias):
+    """a TensorFormat from an element type, a layout and up to three scales and biases (a scalar: the same for every channel)"""
+    fmt = TensorFormat()
+    fmt.dtype, fmt.layout = int(dtype), int(layout)
+    for name, values in (("scale", scale), ("bias", bias)):
+        values = [float(values)] * 3 if np.isscalar(values) else [float(v) for v in values]
+        if not 1 <= len(values) <= 4:
+            raise ValueError(f"{name}: one value per channel")
+        for c, v in enumerate(values):
+            getattr(fmt, name)[c] = v
+    return fmt
+
+
+def tensor_element(lib, fmt, c, v):
+    """gpujpeg_amd_host_tensor_element (host only, lib: a Library): the bits decode_batch_crop_resize_tensor stores for byte v of channel c"""
+    return int(lib.L.gpujpeg_amd_host_tensor_element(C.byref(fmt), int(c), int(v)))
+
+
 PRODUCT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libgpujpeg.so")
 
 
@@ -163,6 +191,12 @@ class Library:
         if hasattr(L, "gpujpeg_amd_decoder_decode_batch_crop_resize"):
             L.gpujpeg_amd_decoder_decode_batch_crop_resize.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int),
                                                                        C.POINTER(C.c_uint8), C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(ImageParameters)]
+        if hasattr(L, "gpujpeg_amd_decoder_decode_batch_crop_resize_tensor"):
+            L.gpujpeg_amd_decoder_decode_batch_crop_resize_tensor.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int),
+                                                                              C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(TensorFormat), vp, C.c_size_t,
+                                                                              C.POINTER(ImageParameters)]
+            L.gpujpeg_amd_host_tensor_element.restype = C.c_uint32
+            L.gpujpeg_amd_host_tensor_element.argtypes = [C.POINTER(TensorFormat), C.c_int, C.c_int]
         if hasattr(L, "gpujpeg_amd_host_crop_resize_plan"):
             L.gpujpeg_amd_host_crop_resize_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
             L.gpujpeg_amd_decoder_get_prescales.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int]
@@ -514,6 +548,66 @@ class Decoder:
             raise RuntimeError(f"gpujpeg_amd_decoder_decode_batch_crop_resize failed ({rc})")
         raw = self.lib.image_size(pi)
         return [out[i * bound:i * bound + raw].copy() for i in range(n)], pi
+
+    def decode_batch_crop_resize_tensor(self, streams, rects, out_width, out_height, dtype, layout, scale, bias, mirror=None, out=None, out_stride=None,
+                                        device_in=None, in_stride=None, sizes=None):
+        """gpujpeg_amd_decoder_decode_batch_crop_resize_tensor: decode_batch_crop_resize whose frames come as normalised float tensors -- element
+        (c, j, i) = byte * scale[c] + bias[c] in dtype (TENSOR_F32 / _F16 / _BF16), laid out as layout says (TENSOR_CHW / _HWC); the definition:
+        include/gpujpeg_amd_ext.h. The usual recipe: scale = 1 / (255 std), bias = -mean / std. streams / device_in, in_stride, sizes, rects and mirror as
+        for decode_batch_crop_resize. out: an integer pointer (device or host memory) with out_stride = bytes between two frames, or an object with
+        data_ptr(), element_size() and is_contiguous() -- a torch tensor on the GPU or the CPU, contiguous, of the dtype's element size and with room for
+        the frames; its first dimension is the frame. Returns (None, ImageParameters) then. Without out the frames come back as one numpy array of shape
+        (n, C, OH, OW) or (n, OH, OW, C), float32, float16, or uint16 holding the bit patterns of bfloat16."""
+        if not hasattr(self.lib.L, "gpujpeg_amd_decoder_decode_batch_crop_resize_tensor"):
+            raise RuntimeError("this library has no gpujpeg_amd_decoder_decode_batch_crop_resize_tensor")
+        if device_in is None:
+            sizes = [int(x.size) for x in streams]
+            in_stride = (max(sizes) + 64 + 15) & ~15
+            buf = np.zeros(in_stride * len(sizes), np.uint8)
+            for i, x in enumerate(streams):
+                buf[i * in_stride:i * in_stride + x.size] = x
+            self._keep = buf
+            base = buf.ctypes.data
+        else:
+            base = int(device_in)
+        n = len(sizes)
+        if len(rects) != n or (mirror is not None and len(mirror) != n):
+            raise ValueError("decode_batch_crop_resize_tensor needs one rectangle (and, with mirror, one flag) per stream")
+        fmt = tensor_format(dtype, layout, scale, bias)
+        if fmt.dtype not in TENSOR_ELSIZE:
+            raise ValueError(f"decode_batch_crop_resize_tensor: unknown dtype {dtype}")
+        elsize = TENSOR_ELSIZE[fmt.dtype]
+        csz = (C.c_size_t * n)(*sizes)
+        rc4 = (C.c_int * (4 * n))(*[int(v) for r in rects for v in r])
+        mir = None if mirror is None else (C.c_uint8 * n)(*[1 if m else 0 for m in mirror])
+        pi = ImageParameters()
+        call = self.lib.L.gpujpeg_amd_decoder_decode_batch_crop_resize_tensor
+        if out is not None:
+            if hasattr(out, "data_ptr"):  # (a torch tensor, without importing torch: frames along its first dimension)
+                if not out.is_contiguous():
+                    raise ValueError("decode_batch_crop_resize_tensor: out must be contiguous")
+                if out.element_size() != elsize:
+                    raise ValueError(f"decode_batch_crop_resize_tensor: out has elements of {out.element_size()} B, the dtype asks for {elsize} B")
+                if out.shape[0] != n:
+                    raise ValueError(f"decode_batch_crop_resize_tensor: out holds {out.shape[0]} frames, the call has {n}")
+                ptr, out_stride = int(out.data_ptr()), int(out.numel() // n) * elsize
+            else:
+                if out_stride is None:
+                    raise ValueError("decode_batch_crop_resize_tensor: an integer out needs out_stride")
+                ptr = int(out)
+            rc = call(self.h, base, in_stride, csz, n, rc4, mir, int(out_width), int(out_height), C.byref(fmt), ptr, int(out_stride), C.byref(pi))
+            if rc != 0:
+                raise RuntimeError(f"gpujpeg_amd_decoder_decode_batch_crop_resize_tensor failed ({rc})")
+            return None, pi
+        ow, oh = min(max(int(out_width), 1), 16384), min(max(int(out_height), 1), 16384)
+        bound = ow * oh * 3 * elsize  # (room for three channels; a single-channel result uses a third of every slot)
+        host = np.empty(bound * n, np.uint8)
+        rc = call(self.h, base, in_stride, csz, n, rc4, mir, int(out_width), int(out_height), C.byref(fmt), host.ctypes.data, bound, C.byref(pi))
+        if rc != 0:
+            raise RuntimeError(f"gpujpeg_amd_decoder_decode_batch_crop_resize_tensor failed ({rc})")
+        ch = 1 if pi.pixel_format == 0 else 3
+        frames = host.reshape(n, bound)[:, :ch * ow * oh * elsize].copy().view(TENSOR_NUMPY[fmt.dtype])
+        return frames.reshape((n, ch, oh, ow) if fmt.layout == TENSOR_CHW else (n, oh, ow, ch)), pi
 
     def prescales(self):
         """gpujpeg_amd_decoder_get_prescales: the scale s_f (1, 2, 4, 8) every frame of the last decode_batch_crop_resize call took ahead of its resample

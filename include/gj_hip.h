@@ -279,6 +279,18 @@ typedef struct gj_region_frame {
     int scale;                     /* 1, 2, 4 or 8 */
     int src_w, src_h, off_x, off_y;
 } gj_region_frame;
+/* Tensor output of crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize_tensor): the pixel stage stores, in place of the bytes of the pixel
+ * format, element (c, j, i) = convert(float(byte) * scale[c] + bias[c]) -- two binary32 operations, each rounded to nearest even, never fused; the
+ * conversion to binary16 / bfloat16 rounds to nearest even (gj_device.h: gj_tensor_element, the ONE statement of it) -- at (c OH + j) OW + i (CHW) or
+ * (j OW + i) channels + c (HWC) of the frame. channels: 1 for single-channel output, 3 for packed or planar 4:4:4 (gj_geom_init_resized sets it). */
+enum { GJ_TENSOR_F32 = 0, GJ_TENSOR_F16 = 1, GJ_TENSOR_BF16 = 2 };
+enum { GJ_TENSOR_CHW = 0, GJ_TENSOR_HWC = 1 };
+typedef struct gj_tensor {
+    int on;                        /* 1: the call stores a tensor */
+    int dtype, layout, channels;
+    float scale[4], bias[4];       /* [3]: not used */
+} gj_tensor;
+#define GJ_TENSOR_ELSIZE(dtype) ((dtype) == GJ_TENSOR_F32 ? 4 : 2)
 typedef struct gj_region {
     int on;                        /* 1: this call decodes a region */
     int select;                    /* 1: only the restart segments that touch the cover are entropy-decoded (k_segment_select compacts the table) */
@@ -302,9 +314,14 @@ typedef struct gj_region {
     /* ... and the scales (gj_region_frame::scale) among the frames of this launch, bit log2(scale): k_idct_region serves the frames of scale 1,
      * k_idct_region_scaled the others; a launch without frames for one of them is left out. Anything but 1 outside a resize job is refused. */
     unsigned scale_mask;
+    /* ... and what the pixel stage of a resize job stores: tensor.on = 0 the bytes of gs's pixel format (k_resize_region), 1 the tensor
+     * (k_resize_region_tensor; gs.raw_size is then the tensor's size) */
+    gj_tensor tensor;
 } gj_region;
 /* the predicate of the selection (gj_device.h: gj_segment_in_cover) for host code: does restart segment s have a block / an MCU inside the cover? */
 GJ_HIP_API int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s);
+/* the bits k_resize_region_tensor stores for byte v (0 .. 255) of channel c (gj_device.h: gj_tensor_element) for host code */
+GJ_HIP_API uint32_t gj_hip_tensor_element(const gj_tensor* t, int c, int v);
 
 typedef struct gj_dec_job {
     gj_geom g;                     /* pixel_format / color_space describe the requested output */

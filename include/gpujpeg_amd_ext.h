@@ -238,6 +238,35 @@ GPUJPEG_API int gpujpeg_amd_decoder_decode_batch_crop_resize(struct gpujpeg_deco
                                                              const size_t* sizes, int count, const int* rects, const uint8_t* mirror, int out_width,
                                                              int out_height, uint8_t* output, size_t output_stride,
                                                              struct gpujpeg_image_parameters* param_image);
+/* Crop-and-resize with a normalised float tensor as its result: the call above with one more pixel stage -- what a training pipeline otherwise does in
+ * a pass of its own over the batch (uint8 -> float, HWC -> CHW, (x / 255 - mean) / std, cast), done where the pixel is still in registers.
+ * DEFINITION. Let R_f be the bytes gpujpeg_amd_decoder_decode_batch_crop_resize of this decoder returns for frame f with every other argument the same
+ * (mirror, dec_opt_resize_prescale, output colour space), taken as R_f[j][i][c]; C = 1 where that call's pixel format is GPUJPEG_U8, 3 where it is
+ * GPUJPEG_444_U8_P012 or GPUJPEG_444_U8_P0P1P2 (the two give the same tensor: the layout is format->layout); OW = out_width, OH = out_height. Then
+ *     T_f(c, j, i) = cvt(fadd(fmul((float)R_f[j][i][c], format->scale[c]), format->bias[c]))                                  c < C, j < OH, i < OW
+ * fmul and fadd each round to nearest-even in binary32 and are never fused into one operation; cvt is the identity for GPUJPEG_AMD_TENSOR_F32 and
+ * round-to-nearest-even for GPUJPEG_AMD_TENSOR_F16 (subnormals are produced, not flushed; overflow gives infinity) and GPUJPEG_AMD_TENSOR_BF16.
+ * The usual recipe is scale[c] = 1 / (255 std[c]), bias[c] = -mean[c] / std[c]; it differs from (x / 255 - mean) / std in the last place of some elements.
+ * LAYOUT. GPUJPEG_AMD_TENSOR_CHW: element (c, j, i) at index (c OH + j) OW + i; GPUJPEG_AMD_TENSOR_HWC: at (j OW + i) C + c. Frames are dense; frame f
+ * starts output_stride BYTES behind frame f - 1; output_stride is a multiple of the element size (4, 2, 2) and at least C OW OH times it. `output` is
+ * device or host memory, as above. param_image is what the call above reports.
+ * Routing, fallbacks, gpujpeg_amd_decoder_last_batch, _get_region_stats, _get_prescales and slot [4] of the kernel times are exactly those of the call above
+ * on the same arguments: the batched launches end in k_resize_region_tensor_batch in place of k_resize_region_batch, the single-frame route in
+ * k_resize_region_tensor. The decoder's own dec_opt_region is neither read nor changed, and no later call of the decoder sees anything of the format.
+ * Refused with a message, -1 returned, nothing of `output` written, the decoder usable as before: everything the call above refuses, and format == NULL;
+ * a dtype or layout outside the enums; a scale or bias among the first C that is not finite; a pixel format other than the three above
+ * (GPUJPEG_4444_U8_P0123 included); a dec_opt_alignment_bytes greater than 1; an `output` or output_stride that is not a multiple of the element size; an
+ * output_stride smaller than a frame. */
+enum { GPUJPEG_AMD_TENSOR_F32 = 0, GPUJPEG_AMD_TENSOR_F16 = 1, GPUJPEG_AMD_TENSOR_BF16 = 2 };
+enum { GPUJPEG_AMD_TENSOR_CHW = 0, GPUJPEG_AMD_TENSOR_HWC = 1 };
+struct gpujpeg_amd_tensor_format { int dtype, layout; float scale[4], bias[4]; }; /* 40 bytes; scale / bias [3] reserved */
+GPUJPEG_API int gpujpeg_amd_decoder_decode_batch_crop_resize_tensor(struct gpujpeg_decoder* decoder, const uint8_t* streams, size_t stream_stride,
+                                                                    const size_t* sizes, int count, const int* rects, const uint8_t* mirror, int out_width,
+                                                                    int out_height, const struct gpujpeg_amd_tensor_format* format, void* output,
+                                                                    size_t output_stride, struct gpujpeg_image_parameters* param_image);
+/* Host-only: the bits that call stores for the 8-bit value v (0 .. 255) of channel c (0 .. 2) -- a float's 32 bits, or the 16 bits of a binary16 /
+ * bfloat16 in the low half; the code the call itself runs. 0 for arguments outside those ranges, a NULL format or a dtype outside the enum. */
+GPUJPEG_API uint32_t gpujpeg_amd_host_tensor_element(const struct gpujpeg_amd_tensor_format* format, int channel, int v);
 /* Host-only: scale and covering rectangle dec_opt_resize_prescale gives ONE frame of a crop-and-resize call -- rect = x, y, w, h in an
  * image_w x image_h image whose components are (all_components_1x1 != 0) or are not all sampled 1 x 1, output out_w x out_h, max_scale = S (1, 2, 4, 8).
  * Writes out = s, x', y', w', h' (the definition above; the code the call itself runs) and returns 0, or -1 where the call would refuse: a rectangle
