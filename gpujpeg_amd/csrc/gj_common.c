@@ -565,6 +565,10 @@ int gj_geom_init_region(gj_geom* gr, gj_region* r, const gj_geom* full, const st
         const unsigned linesize = (unsigned)gj_pixfmt_unit_size(rp.pixel_format) * (unsigned)rp.width;
         rp.width_padding = (int)((linesize + alignment - 1) / alignment * alignment - linesize);
     }
+    if (rp.pixel_format == GPUJPEG_422_U8_P1020 && (rp.width & 1)) { /* (w is odd only where the region ends at the edge of an image of odd width) */
+        GJ_ERROR("Packed 4:2:2 output needs an even width: the region %d,%d,%d,%d of the %dx%d image is %dx%d!\n", x, y, w, h, pi->width, pi->height, w, h);
+        return -1;
+    }
     if (gj_geom_init(gr, param, &rp, false) != 0) return -1;
     memset(r, 0, sizeof *r);
     r->on = 1;

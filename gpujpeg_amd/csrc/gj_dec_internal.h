@@ -321,9 +321,10 @@ __device__ __forceinline__ void gj_pixel_store(const gj_geom& g, uint8_t* __rest
         break;
     case GJ_PF_422_P0P1P2:
         raw[pos] = (uint8_t)v[0];
-        if ((x & 1) == 0) {
-            raw[(size_t)W * H + pos / 2] = (uint8_t)v[1];
-            raw[(size_t)W * H + (size_t)H * ((W + 1) / 2) + pos / 2] = (uint8_t)v[2];
+        if ((x & 1) == 0) { // chroma by row, the layout of raw_size and k_copy_planes_out (the reference's pos / 2 makes rows of odd W share a byte: DESIGN 1)
+            const size_t cpos = (size_t)y * ((W + 1) / 2) + x / 2;
+            raw[(size_t)W * H + cpos] = (uint8_t)v[1];
+            raw[(size_t)W * H + (size_t)H * ((W + 1) / 2) + cpos] = (uint8_t)v[2];
         }
         break;
     case GJ_PF_422_P1020: {

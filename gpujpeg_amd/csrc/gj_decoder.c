@@ -120,6 +120,17 @@ static struct gpujpeg_image_parameters dec_out_param_image(const struct gpujpeg_
     return pi;
 }
 
+/* a full-size call, once the coder is configured for the stream: packed 4:2:2 of odd width has no image -- the pixel kernels would store the whole
+ * last pixel pair, past the raw_size bytes of the output. 0 or -1 with a message. Not for a call that cuts rectangles out of the image
+ * (the decoder's region option, a batch of regions) or reduces it: those images have their own width checked (gj_geom_init_region, gj_geom_init_scaled) */
+static int dec_full_size_geometry(const struct gpujpeg_decoder* d)
+{
+    const gj_geom* g = &d->coder.geom;
+    if (g->raw_width == g->width) return 0;
+    GJ_ERROR("Packed 4:2:2 output needs an even width: the image is %dx%d!\n", g->width, g->height);
+    return -1;
+}
+
 /* the scale of this call and the geometry of the reduced image, once the coder is configured for the stream; 0 or -1 (no such image / option clash) */
 static int dec_scale_geometry(struct gpujpeg_decoder* d)
 {
@@ -900,7 +911,9 @@ static int dec_attempt(struct gpujpeg_decoder* d, struct dec_call* k)
     int rc = dec_headers(d, k);
     if (rc != 0) return rc;
     for (int i = 0; i < GPUJPEG_METADATA_COUNT; i++) d->metadata.vals[i] = k->r.metadata.vals[i];
-    if (decoder_configure(d, &k->r.param, &k->r.param_image) != 0 || dec_scale_geometry(d) != 0 || dec_region_geometry(d) != 0) return DEC_FAILED;
+    if (decoder_configure(d, &k->r.param, &k->r.param_image) != 0 || dec_scale_geometry(d) != 0 || dec_region_geometry(d) != 0 ||
+        (!dec_reduced_or_region(d) && dec_full_size_geometry(d) != 0))
+        return DEC_FAILED;
     c->init_end_time = k->stats ? gpujpeg_get_time() : 0;
     if (dec_upload(d, k) != 0) return DEC_FAILED;
     if ((rc = dec_segment_table(d, k)) != 0) return rc;
@@ -1225,6 +1238,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
      * the frames go the ordinary way and that call says why */
     if (d->scale > 1 && (d->flipped || (r->param_image.pixel_format == GPUJPEG_422_U8_P1020 && (GPUJPEG_AMD_SCALED_DIM(r->param_image.width, d->scale) & 1)))) return 0;
     if (decoder_configure(d, &r->param, &r->param_image) != 0) return -1; /* (the geometry of the cached header, whatever the coder was last set up for) */
+    if (d->scale <= 1 && !regions && dec_full_size_geometry(d) != 0) return -1;
     if (dec_scale_geometry(d) != 0) return -1; /* (call_scale, and with a scale geom_s / pi_s: the reduced image of the cached header's geometry) */
     /* a batch of regions: the rectangles against the cached header's geometry, unless frame 0 went ahead and they have been checked against its own.
      * A rectangle the CACHED header refuses may be one the streams' own header takes (an older sequence's cache): frame 0 goes ahead and decides. */

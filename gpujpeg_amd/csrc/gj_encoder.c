@@ -175,6 +175,11 @@ static int encoder_configure(struct gpujpeg_encoder* e, const struct gpujpeg_par
     }
     GJ_DEBUG(p->verbose, "coder image reconfiguration\n");
     c->configured = false;
+    /* the pixel kernels would run over the width rounded up to a whole pixel pair, past the raw_size bytes the caller holds */
+    if (pi->pixel_format == GPUJPEG_422_U8_P1020 && (pi->width & 1)) {
+        GJ_ERROR("Packed 4:2:2 input needs an even width: the image is %dx%d!\n", pi->width, pi->height);
+        return -1;
+    }
     c->param = *p;
     c->param_image = *pi;
     gj_geom* g = &c->geom;

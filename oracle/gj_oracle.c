@@ -97,6 +97,8 @@ static int round_up_div(int a, int b) { return (a + b - 1) / b; }
 int gjo_image_init(gjo_image* img)
 {
     if (img->comp_count < 1 || img->comp_count > GJO_MAX_COMP || img->width <= 0 || img->height <= 0) return -1;
+    /* packed 4:2:2 of odd width: the pixel loops run over the width rounded up to a pixel pair, past raw_size */
+    if (img->pixel_format == GJO_PF_422_P1020 && (img->width & 1)) return -1;
     img->raw_size = gjo_raw_size(img->width, img->height, img->width_padding, img->pixel_format);
     img->max_h = img->max_v = 0;
     for (int c = 0; c < img->comp_count; c++) {
@@ -1209,7 +1211,8 @@ void gjo_postprocess(const gjo_image* img, const uint8_t* planes, uint8_t* raw)
             case GJO_PF_444_P0P1P2: raw[pos] = r[0]; raw[W * H + pos] = r[1]; raw[2 * W * H + pos] = r[2]; break;
             case GJO_PF_422_P0P1P2:
                 raw[pos] = r[0];
-                if ((x % 2) == 0) { raw[W * H + pos / 2] = r[1]; raw[W * H + H * ((W + 1) / 2) + pos / 2] = r[2]; }
+                /* chroma by row, the layout raw_size has (the reference's pos / 2 makes two pixels of an odd W share a byte: DESIGN 1) */
+                if ((x % 2) == 0) { int cpos = y * ((W + 1) / 2) + x / 2; raw[W * H + cpos] = r[1]; raw[W * H + H * ((W + 1) / 2) + cpos] = r[2]; }
                 break;
             case GJO_PF_422_P1020: {
                 size_t off = (size_t)pos * 2 + (size_t)img->width_padding * y;

@@ -219,6 +219,65 @@ def test_output_format_requests(O, G, ref, pf, w, h):
         assert np.array_equal(px, opx), (opf, ocs)
 
 
+# ---- the format-conversion matrix (tests/test_format_matrix.py): the restatement pinned to the reference for every cell the product is compared on
+def test_format_matrix_encode_cells(O, G, ref):
+    """Every cell of the encode matrix: the reference's bytes are the restatement's. This includes the generic load of an odd-width planar 4:2:2
+    image (W*H + pos/2, src/gpujpeg_preprocessor.cu:88-159), which is deterministic and stays as the reference has it. The matrix holds packed
+    4:2:2 input at even widths only.
+    One kind of cell cannot be run: three components in a sampling the reference has no specialised kernel for (4:1:1, 4:1:0, mixed) take its
+    dynamic-sampling kernel, which divides by the zero factor of the unused fourth component (src/gpujpeg_preprocessor.cu:53-63) -- a trap on the
+    CPU, a fault when compiled for gfx950 (tests/test_gpu_refhip.py), so the reference shows no behaviour for them anywhere. The same kernel and the
+    same three samplings ARE pinned here by the matrix's four-component cells (SAMPLINGS4: every factor set), and what the reference's decoder makes
+    of the restatement's 4:1:1, 4:1:0 and mixed streams by test_format_matrix_decode_cells."""
+    import test_format_matrix as M
+    dynamic3 = (M.SAMPLINGS["411"], M.SAMPLINGS["410"], M.SAMPLINGS["mixed"])
+    not_run, dynamic4 = set(), set()
+    for case, pad in M.ENCODE_CELLS:
+        assert not (case[3] == 3 and case[1] % 2)  # odd-width packed 4:2:2: the reference reads past the caller's buffer -- never run
+        if case[8] in dynamic3:
+            not_run.add(case[8])  # the dynamic-sampling kernel with three components divides by zero: see above
+            continue
+        raw, img, want = M.make_cell(O, case, pad)
+        p, pi = api_params(ref, G, case)
+        pi.width_padding = pad
+        enc = G.Encoder(ref)  # (a fresh one per cell, as the tests above have it)
+        got = enc.encode(p, pi, raw)
+        enc.close()
+        assert got.size == want.size and np.array_equal(got, want), (case[0], pad)
+        if img.comp_count == 4:
+            dynamic4.add(case[8])
+    assert not_run == set(dynamic3)
+    assert dynamic4 == set(M.SAMPLINGS4.values())  # (plain 4:4:4:4, and 4:1:1, 4:1:0 and mixed with a fourth component)
+
+
+@pytest.mark.parametrize("kind,il", [(k, i) for k in ("444", "422", "420", "440", "411", "410", "mixed") for i in (0, 1)] + [("grey", 0), ("4444", 1), ("4444", 0)])
+def test_format_matrix_decode_cells(O, G, ref, kind, il):
+    """Every cell of the decode matrix: the reference's pixels, size and reported parameters are the restatement's -- but for the two kinds of cell
+    the restatement leaves the reference on purpose, which are not run."""
+    import test_format_matrix as M
+    skipped = set()
+    for w, h in M.SIZES:
+        jpeg = M.make_stream(O, kind, il, w, h)
+        for pf, cs in M.OUTPUTS:
+            want = M.oracle_decode(O, jpeg, pf, cs, kind, il)
+            if want is None:
+                assert pf == 3 and w % 2
+                skipped.add("packed")  # odd-width packed 4:2:2: the reference stores past the end of its output buffer -- no behaviour to match
+                continue
+            raw, img = want
+            if img.pixel_format == 4 and w % 2 and h > 1 and M.decode_route(img, False) == "postprocess":
+                skipped.add("planar")  # odd-width planar 4:2:2 through the per-pixel store: two pixels of the reference share a byte -- a race
+                continue  # (1x1 has no second row to collide with and is run)
+            dec = G.Decoder(ref)
+            dec.set_output_format(cs, pf)
+            px, info = dec.decode(jpeg)
+            dec.close()
+            assert (info.width, info.height, info.pixel_format, info.color_space) == (img.width, img.height, img.pixel_format, img.color_space), (w, h, pf, cs)
+            assert px.size == raw.size and np.array_equal(px, raw), (w, h, pf, cs, int(np.count_nonzero(px != raw)))
+    # (a 4:2:2 stream's planar 4:2:2 output is its own layout: k_copy_planes_out's side, the reference's memcpy -- pinned above at odd widths too)
+    assert skipped == ({"packed"} if kind == "422" else {"packed", "planar"})
+
+
 @pytest.mark.parametrize("pf,mapping,flip", [(1, "210", False), (1, "F0Z", True), (6, "1230", True), (1, "012", True)])
 def test_channel_remap_and_flip_options(O, G, ref, pf, mapping, flip):
     """The reference's own option parsing, call order (src/gpujpeg_encoder.c:661-699,767-771, src/gpujpeg_decoder.c:499-503) and
