@@ -735,6 +735,50 @@ int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const str
     return 0;
 }
 
+/* restart segments of scan sc with a block / an MCU inside the cover: what counting gj_segment_in_cover (gj_device.h) over the scan's segments gives,
+ * in closed form -- a row of the cover is a run of cells, cell i belongs to segment i / restart_interval, and the rows' runs of segments follow each
+ * other (a segment that wraps from one row's end to the next row's start is counted once). The host's only count (DESIGN 4.2 says what holds it to
+ * the predicate) */
+static int region_scan_segments(const gj_geom* g, const gj_region_frame* r, int sc)
+{
+    const int gridx = g->interleaved ? g->mcu_count_x : g->comp[sc].blocks_x, ri = g->restart_interval;
+    const int x0 = g->interleaved ? r->mx0 : r->bx0[sc], x1 = g->interleaved ? r->mx1 : r->bx1[sc];
+    const int y0 = g->interleaved ? r->my0 : r->by0[sc], y1 = g->interleaved ? r->my1 : r->by1[sc];
+    if (ri <= 0 || gridx <= 0 || x0 >= x1) return 0;
+    /* row y's run is the segments lo .. hi of its first and last cell, y gridx + x0 and y gridx + x1 - 1; both move on by gridx cells per row, so
+     * quotient and remainder are carried from row to row (this runs in every region call: four divisions per scan, none per row) */
+    const long first = (long)y0 * gridx + x0, last = (long)y0 * gridx + x1 - 1, step_q = gridx / ri, step_r = gridx % ri;
+    long lo = first / ri, lo_r = first % ri, hi = last / ri, hi_r = last % ri;
+    long n = 0, prev_hi = -1;
+    for (int y = y0; y < y1; y++) {
+        const long from = lo <= prev_hi ? prev_hi + 1 : lo;
+        if (hi >= from) n += hi - from + 1;
+        if (hi > prev_hi) prev_hi = hi;
+        lo += step_q; lo_r += step_r;
+        if (lo_r >= ri) { lo++; lo_r -= ri; }
+        hi += step_q; hi_r += step_r;
+        if (hi_r >= ri) { hi++; hi_r -= ri; }
+    }
+    return (int)n;
+}
+
+int gj_region_plan(gj_geom* gr, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi,
+                   const int rect[4], const struct gj_resize* resize, unsigned alignment, struct gpujpeg_image_parameters* pi_out)
+{
+    if (gj_geom_init_region(gr, r, full, param, pi, rect, alignment, pi_out) != 0) return -1;
+    if (resize) {
+        /* crop-and-resize: the image of the call is the resampled one, over the planes of this rectangle's cover (a tensor call: gr->raw_size is the
+         * tensor's) -- and with a prescale the planes are the reduced ones of the covering rectangle's cover */
+        r->tensor = resize->tensor;
+        if (gj_geom_init_resized(gr, gr, param, pi, resize->out_w, resize->out_h, alignment, &r->tensor, pi_out) != 0) return -2;
+        if (gj_region_prescale(gr, r, full, param, pi, rect, resize->out_w, resize->out_h, resize->prescale, alignment, pi_out) != 0) return -2;
+        r->resize = 1;
+        r->frame.mirror = resize->mirror ? 1 : 0;
+    }
+    for (int sc = 0; sc < full->scan_count && sc < GJ_MAX_COMP; sc++) r->sel_count[sc] = region_scan_segments(full, &r->frame, sc);
+    return 0;
+}
+
 /* ------------------------------------------------------------------ buffers / timers / statistics */
 int gj_ensure_device_buffer(void** p, size_t* cap, size_t need)
 {

@@ -13,6 +13,25 @@
 #include "gj_internal.h"
 #include "gpujpeg_amd_ext.h"
 
+/* What ONE call was asked for: made by its entry point -- gpujpeg_decoder_decode from the options, a batch call's single-frame route from the batch's
+ * rectangle of that frame --, handed to decoder_decode and constant from there on, the same for every attempt. Never stored in the decoder. */
+struct dec_request {
+    int scale;                 /* 1, 2, 4, 8 */
+    bool region; int rect[4];  /* the x, y, w, h pixels only */
+    bool resize;               /* crop-and-resize: a region call whose rectangle is resampled ... */
+    struct gj_resize rs;       /* ... like this */
+};
+
+/* The image a call decodes to: the stream's own (scale 1, no region), the reduced one, or the W x H one over a region's cover planes (crop-and-resize:
+ * the resampled one). Written by dec_image_set alone. */
+struct dec_image {
+    int scale;                           /* 1, 2, 4, 8 */
+    bool region, resize;                 /* (the scale and a region exclude each other; resize: a region whose image is the resampled one) */
+    gj_geom geom;                        /* scale > 1 or region: geometry and parameters of that image */
+    struct gpujpeg_image_parameters pi;
+    gj_region rg;                        /* region: pixel rectangle, cover, planned selection */
+};
+
 struct gpujpeg_decoder {
     struct gj_coder coder;
     enum gpujpeg_pixel_format req_pixel_format;
@@ -76,85 +95,85 @@ struct gpujpeg_decoder {
     int last_folded;                               /* the last decode call did without the k_marker_table launch (gj_scan_deferred) */
     long n_spec, n_folded, n_again;                /* calls launched on the cached header / of those without the table launch / decoded again the careful way */
     int b_chunk;                                   /* gpujpeg_amd_decoder_set_batch_chunk: frames per launch at most, 0 = the default */
-    /* reduced-size decode (dec_opt_scale). The option is read once per attempt (dec_scale_geometry); the header cache and the speculative launch
-     * hold nothing that depends on it: the parse result and the entropy side are the full-size ones at every scale. */
-    int scale;                                     /* the option: 0 / 1 = full size, else 2, 4, 8 */
-    int call_scale;                                /* what the decode call in progress (and, after it, the last one) used */
-    gj_geom geom_s;                                /* call_scale > 1: geometry and parameters of the reduced image */
-    struct gpujpeg_image_parameters pi_s;
+    /* reduced-size decode (dec_opt_scale) and region decode (dec_opt_region): the options. A call reads them once, into its request (struct
+     * dec_request); the header cache and the speculative launch hold nothing that depends on them: the parse result and the entropy side are the
+     * full-size ones at every scale and for every region. */
+    int scale;                                     /* 0 / 1 = full size, else 2, 4, 8 */
+    bool region_on; int region[4];                 /* x, y, w, h: written by gpujpeg_decoder_set_option alone */
+    struct dec_image img;                          /* what the decode call in progress (and, after it, the last one) decodes to */
     int last_idct_path;                            /* gj_dec_job::idct_path of the last call */
-    /* region decode (dec_opt_region). Like the scale, the option is read once per attempt (dec_region_geometry) and nothing cached depends on it.
-     * A region call shares geom_s / pi_s with the reduced-size decode (the two exclude each other): the W x H image over the cover's planes. */
-    bool region_on; int region[4];                 /* the option: x, y, w, h */
-    bool call_region;                              /* what the decode call in progress (and, after it, the last one) used */
-    gj_region rg;                                  /* call_region: pixel rectangle, cover, planned selection */
-    uint32_t* d_sel; size_t d_sel_cap;             /* the compacted segment table of a selection */
+    uint32_t* d_sel; size_t d_sel_cap;             /* the compacted segment table of a region's selection */
     uint32_t* d_sel_count; uint32_t* h_sel_count;  /* its entry count on the device; pinned: [0] the same, [1 + c] entries of scan c */
-    gj_region_frame plan_cover; int plan_sel[GJ_MAX_COMP]; bool plan_valid; /* the cover whose selection plan_sel counts (a loop over the geometry's segments) */
     long region_stats[4];                          /* gpujpeg_amd_decoder_get_region_stats */
     /* batches of regions (gpujpeg_amd_decoder_decode_batch_regions): one rectangle per frame */
     uint32_t* b_sel; size_t b_sel_cap;             /* device: the compacted segment tables of one chunk of frames, laid out like b_seg */
     gj_region_frame* b_rgn; size_t b_rgn_cap;      /* device: origin and covers of every frame of a call */
     gj_region_frame* bh_rgn; size_t bh_rgn_cap;    /* pinned staging of the same */
     uint32_t* bh_found; size_t bh_found_cap;       /* pinned: [frame][GJ_MAX_COMP] entries per scan the selection found */
-    /* crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize): a region call whose rectangle is resampled to resize_w x resize_h. Set by that
-     * call alone, for its own duration; its single-frame route is the region call with these on (dec_region_geometry) */
-    bool resize_on; int resize_w, resize_h, resize_mirror;
-    /* ... and what its pixel stage stores: on = 0 the bytes of the pixel format, 1 the tensor of gpujpeg_amd_decoder_decode_batch_crop_resize_tensor.
-     * Set by that call alone, for its own duration, like the fields above */
-    gj_tensor resize_tensor;
-    bool call_resize;                              /* what the decode call in progress (and, after it, the last one) used: geom_s / pi_s are the resampled image's */
     /* dec_opt_resize_prescale: the largest reduction crop-and-resize may put in front of its resample (0 / 1: none, else 2, 4, 8). Read by that call alone,
-     * per frame (gj_region_prescale); the scale every frame of its last call took: gpujpeg_amd_decoder_get_prescales */
+     * into its rectangles' description (struct dec_rects); the scale every frame of its last call took: gpujpeg_amd_decoder_get_prescales */
     int resize_prescale;
     uint8_t* prescales; int prescales_n, prescales_cap;
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
-static bool dec_reduced_or_region(const struct gpujpeg_decoder* d) { return d->call_scale > 1 || d->call_region; }
-static size_t dec_raw_size(const struct gpujpeg_decoder* d) { return dec_reduced_or_region(d) ? d->geom_s.raw_size : d->coder.geom.raw_size; }
+static bool dec_reduced_or_region(const struct gpujpeg_decoder* d) { return d->img.scale > 1 || d->img.region; }
+static size_t dec_raw_size(const struct gpujpeg_decoder* d) { return dec_reduced_or_region(d) ? d->img.geom.raw_size : d->coder.geom.raw_size; }
 static struct gpujpeg_image_parameters dec_out_param_image(const struct gpujpeg_decoder* d)
 {
-    struct gpujpeg_image_parameters pi = dec_reduced_or_region(d) ? d->pi_s : d->coder.param_image;
+    struct gpujpeg_image_parameters pi = dec_reduced_or_region(d) ? d->img.pi : d->coder.param_image;
     if (pi.color_space == GPUJPEG_NONE) pi.color_space = d->coder.param.color_space_internal;
     return pi;
 }
 
-/* a full-size call, once the coder is configured for the stream: packed 4:2:2 of odd width has no image -- the pixel kernels would store the whole
- * last pixel pair, past the raw_size bytes of the output. 0 or -1 with a message. Not for a call that cuts rectangles out of the image
- * (the decoder's region option, a batch of regions) or reduces it: those images have their own width checked (gj_geom_init_region, gj_geom_init_scaled) */
-static int dec_full_size_geometry(const struct gpujpeg_decoder* d)
+/* the one writer of d->img. geom / pi: the reduced or the region image, NULL where there is none (the stream's own image, or a refusal: what a
+ * refused call leaves describes no region image); rg: NULL unless the image is a region's */
+static void dec_image_set(struct gpujpeg_decoder* d, int scale, const gj_geom* geom, const struct gpujpeg_image_parameters* pi, const gj_region* rg)
 {
-    const gj_geom* g = &d->coder.geom;
-    if (g->raw_width == g->width) return 0;
-    GJ_ERROR("Packed 4:2:2 output needs an even width: the image is %dx%d!\n", g->width, g->height);
-    return -1;
+    struct dec_image* m = &d->img;
+    m->scale = scale;
+    m->region = rg != NULL;
+    m->resize = rg != NULL && rg->resize != 0;
+    if (geom) m->geom = *geom;
+    if (pi) m->pi = *pi;
+    if (rg) m->rg = *rg;
 }
 
-/* the scale of this call and the geometry of the reduced image, once the coder is configured for the stream; 0 or -1 (no such image / option clash) */
-static int dec_scale_geometry(struct gpujpeg_decoder* d)
+static struct dec_request dec_request_options(const struct gpujpeg_decoder* d)
 {
-    struct gj_coder* c = &d->coder;
-    d->call_scale = d->scale > 1 ? d->scale : 1;
-    if (d->call_scale == 1) return 0;
-    if (d->flipped) {
-        GJ_ERROR(GPUJPEG_DEC_OPT_FLIPPED_BOOL " is not available together with " GPUJPEG_AMD_DEC_OPT_SCALE "=1/%d!\n", d->call_scale);
+    struct dec_request q = {.scale = d->scale > 1 ? d->scale : 1, .region = d->region_on};
+    memcpy(q.rect, d->region, sizeof q.rect);
+    return q;
+}
+
+/* The image of the call, once the coder is configured for the stream: the request checked against the stream and the decoder's other options, geometry
+ * and parameters of the reduced image (gj_geom_init_scaled) or of the region's (gj_region_plan: cover, selection per scan) derived. 0 or -1 (refused,
+ * with a message). */
+static int dec_call_geometry(struct gpujpeg_decoder* d, const struct dec_request* q)
+{
+    const struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    gj_geom gs;
+    struct gpujpeg_image_parameters ps;
+    dec_image_set(d, q->scale, NULL, NULL, NULL);
+    if (q->scale > 1) {
+        if (d->flipped) {
+            GJ_ERROR(GPUJPEG_DEC_OPT_FLIPPED_BOOL " is not available together with " GPUJPEG_AMD_DEC_OPT_SCALE "=1/%d!\n", q->scale);
+            return -1;
+        }
+        if (gj_geom_init_scaled(&gs, g, &c->param, &c->param_image, q->scale, d->req_alignment, &ps) != 0) return -1;
+        dec_image_set(d, q->scale, &gs, &ps, NULL);
+    }
+    if (!q->region) {
+        if (q->scale > 1 || g->raw_width == g->width) return 0;
+        /* a full-size call: packed 4:2:2 of odd width has no image -- the pixel kernels would store the whole last pixel pair, past the raw_size bytes of
+         * the output. Not for a call that cuts rectangles out of the image or reduces it: those images have their own width checked
+         * (gj_geom_init_region, gj_geom_init_scaled) */
+        GJ_ERROR("Packed 4:2:2 output needs an even width: the image is %dx%d!\n", g->width, g->height);
         return -1;
     }
-    return gj_geom_init_scaled(&d->geom_s, &c->geom, &c->param, &c->param_image, d->call_scale, d->req_alignment, &d->pi_s);
-}
-
-/* the region of this call, once the coder is configured for the stream and the scale is known: validated against the stream, cover and geometry
- * of the W x H image derived (gj_geom_init_region), segments per scan that touch the cover counted; 0 or -1 (refused, with a message) */
-static int dec_region_geometry(struct gpujpeg_decoder* d)
-{
-    struct gj_coder* c = &d->coder;
-    d->call_region = d->region_on;
-    d->call_resize = false;
-    if (!d->call_region) return 0;
-    d->call_region = false; /* (a refused call decodes nothing: what it leaves describes no region image) */
-    if (d->call_scale > 1) {
-        GJ_ERROR(GPUJPEG_AMD_DEC_OPT_REGION " is not available together with " GPUJPEG_AMD_DEC_OPT_SCALE "=1/%d!\n", d->call_scale);
+    if (q->scale > 1) {
+        GJ_ERROR(GPUJPEG_AMD_DEC_OPT_REGION " is not available together with " GPUJPEG_AMD_DEC_OPT_SCALE "=1/%d!\n", q->scale);
         return -1;
     }
     if (d->flipped) {
@@ -162,40 +181,8 @@ static int dec_region_geometry(struct gpujpeg_decoder* d)
         return -1;
     }
     gj_region rg;
-    if (gj_geom_init_region(&d->geom_s, &rg, &c->geom, &c->param, &c->param_image, d->region, d->req_alignment, &d->pi_s) != 0) return -1;
-    /* crop-and-resize: the image of the call is the resampled one, over the planes of this rectangle's cover */
-    if (d->resize_on) rg.tensor = d->resize_tensor; /* (a tensor call: geom_s.raw_size is the tensor's) */
-    if (d->resize_on && gj_geom_init_resized(&d->geom_s, &d->geom_s, &c->param, &c->param_image, d->resize_w, d->resize_h, d->req_alignment, &rg.tensor, &d->pi_s) != 0) return -1;
-    /* ... and with dec_opt_resize_prescale the planes are the reduced ones of the covering rectangle's cover */
-    if (d->resize_on && gj_region_prescale(&d->geom_s, &rg, &c->geom, &c->param, &c->param_image, d->region, d->resize_w, d->resize_h, d->resize_prescale,
-                                           d->req_alignment, &d->pi_s) != 0)
-        return -1;
-    /* the plan of a selection: one question per segment of the geometry, asked again only when the region or the stream's geometry changes */
-    if (c->geom.restart_interval > 0) {
-        /* (keyed on the cover itself -- the pixel rectangle alone does not fix it: packed 4:2:2 output widens it to the pixel pair --, so with the
-         * origin taken out: it moves inside a cover without changing the selection; a new geometry drops the plan in decoder_configure) */
-        gj_region_frame cover = rg.frame;
-        cover.x = cover.y = cover.w = cover.h = cover.mirror = 0;
-        cover.scale = cover.src_w = cover.src_h = cover.off_x = cover.off_y = 0;
-        if (!d->plan_valid || memcmp(&d->plan_cover, &cover, sizeof cover) != 0) {
-            memset(rg.sel_count, 0, sizeof rg.sel_count);
-            for (int sc = 0, s = 0; sc < c->geom.scan_count && sc < GJ_MAX_COMP; sc++) {
-                const int n = c->geom.interleaved ? c->geom.segment_count : c->geom.comp[sc].segment_count;
-                for (int i = 0; i < n; i++, s++) rg.sel_count[sc] += gj_hip_segment_in_cover(&c->geom, &rg, s);
-            }
-            d->plan_cover = cover;
-            memcpy(d->plan_sel, rg.sel_count, sizeof d->plan_sel);
-            d->plan_valid = true;
-        }
-        memcpy(rg.sel_count, d->plan_sel, sizeof rg.sel_count);
-    }
-    if (d->resize_on) {
-        rg.resize = 1;
-        rg.frame.mirror = d->resize_mirror;
-        d->call_resize = true;
-    }
-    d->rg = rg;
-    d->call_region = true;
+    if (gj_region_plan(&gs, &rg, g, &c->param, &c->param_image, q->rect, q->resize ? &q->rs : NULL, d->req_alignment, &ps) != 0) return -1;
+    dec_image_set(d, 1, &gs, &ps, &rg);
     return 0;
 }
 
@@ -299,7 +286,6 @@ static int decoder_configure(struct gpujpeg_decoder* d, const struct gpujpeg_par
     if (c->configured && gj_parameters_equal(&c->param, p) && gj_image_parameters_equal(&c->param_image, pi)) return 0;
     if (c->configured && verbose >= GPUJPEG_LL_INFO) fprintf(stderr, "[GPUJPEG] [Info] Reinitializing decoder.\n");
     c->configured = false;
-    d->plan_valid = false;
     c->param = *p;
     c->param.verbose = verbose;
     c->param.perf_stats = perf;
@@ -433,19 +419,20 @@ static void dec_job_base(struct gpujpeg_decoder* d, bool tab2_ok, gj_dec_job* jo
     job->flipped = d->flipped;
     job->channel_remap = d->channel_remap;
     job->tune = d->tune;
-    if (d->call_scale > 1) {
-        job->scale = d->call_scale;
-        job->gs = d->geom_s;
+    if (d->img.scale > 1) {
+        job->scale = d->img.scale;
+        job->gs = d->img.geom;
     }
-    if (d->call_region) {
-        job->region = d->rg;
+    if (d->img.region) {
+        job->region = d->img.rg;
         job->region.on = 1;
-        job->gs = d->geom_s;
+        job->gs = d->img.geom;
     }
 }
 
 /* One call = up to three attempts (decoder_decode). What the stages of an attempt share: */
 struct dec_call {
+    const struct dec_request* req;           /* what the call was asked for: the same for every attempt */
     uint8_t* image; size_t image_size;       /* the stream as the caller gave it */
     struct gpujpeg_decoder_output* output;
     bool jpeg_on_device;                     /* device-resident stream (MI355X extension) */
@@ -721,7 +708,7 @@ static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
     /* region call: where the stream is (or, on the cached header, is assumed to be) the regular one of the geometry, only the segments that touch
      * the cover are entropy-decoded. The selected table has fewer entries than the geometry by design; no clear is needed for it -- every block of
      * the cover belongs to a selected segment, and the decoders zero-fill the blocks of the segments they decode. */
-    k->select = d->call_region && !k->no_select && g->restart_interval > 0 && (k->spec || k->seg_count == g->segment_count);
+    k->select = d->img.region && !k->no_select && g->restart_interval > 0 && (k->spec || k->seg_count == g->segment_count);
     if (k->select) {
         if (gj_ensure_device_buffer((void**)&d->d_sel, &d->d_sel_cap, 3 * S * sizeof(uint32_t)) != 0) return -1;
         job.region.select = 1;
@@ -732,7 +719,7 @@ static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
     }
     /* token mode buffers (gj_hip.h): one record per block, 4 tokens per stream byte at most */
     /* (crop-and-resize resamples from the cover planes: no token mode) */
-    if (!d->keep_coefs && !d->call_resize && job.use_fused && k->tab2_ok && k->image_size < ((size_t)1 << 29) && gj_hip_decode_wants_tokens(&job.g, k->image_size, &d->tune)) {
+    if (!d->keep_coefs && !d->img.resize && job.use_fused && k->tab2_ok && k->image_size < ((size_t)1 << 29) && gj_hip_decode_wants_tokens(&job.g, k->image_size, &d->tune)) {
         const size_t tok_need = (k->image_size * 4 + 64) * sizeof(uint16_t);
         if (tok_need > d->d_tok_cap) { /* (grown with headroom: frames of a sequence vary in size) */
             if (gj_ensure_device_buffer((void**)&d->d_tok, &d->d_tok_cap, tok_need + tok_need / 4) != 0) return -1;
@@ -766,7 +753,7 @@ static int dec_launch(struct gpujpeg_decoder* d, struct dec_call* k)
         }
     }
     if (!k->spec && k->seg_count != g->segment_count) memset(job.scan_bytes, 0, sizeof job.scan_bytes); /* (table and geometry out of step: one batch size) */
-    if (k->select) selected_scan_bytes(g, d->rg.sel_count, job.scan_bytes);
+    if (k->select) selected_scan_bytes(g, d->img.rg.sel_count, job.scan_bytes);
     if (gj_hip_decode(&job, c->stream, k->stats ? c->timers.ev : NULL) != 0) {
         GJ_ERROR("Decoder kernels failed: %s\n", gj_hip_last_error());
         return -1;
@@ -806,8 +793,8 @@ static bool dec_selection_ok(const struct gpujpeg_decoder* d, const struct dec_c
     if (!k->select) return true;
     uint32_t sum = 0;
     for (int sc = 0; sc < GJ_MAX_COMP; sc++) {
-        if (d->h_sel_count[1 + sc] != (uint32_t)d->rg.sel_count[sc]) return false;
-        sum += (uint32_t)d->rg.sel_count[sc];
+        if (d->h_sel_count[1 + sc] != (uint32_t)d->img.rg.sel_count[sc]) return false;
+        sum += (uint32_t)d->img.rg.sel_count[sc];
     }
     return d->h_sel_count[0] == sum;
 }
@@ -911,9 +898,7 @@ static int dec_attempt(struct gpujpeg_decoder* d, struct dec_call* k)
     int rc = dec_headers(d, k);
     if (rc != 0) return rc;
     for (int i = 0; i < GPUJPEG_METADATA_COUNT; i++) d->metadata.vals[i] = k->r.metadata.vals[i];
-    if (decoder_configure(d, &k->r.param, &k->r.param_image) != 0 || dec_scale_geometry(d) != 0 || dec_region_geometry(d) != 0 ||
-        (!dec_reduced_or_region(d) && dec_full_size_geometry(d) != 0))
-        return DEC_FAILED;
+    if (decoder_configure(d, &k->r.param, &k->r.param_image) != 0 || dec_call_geometry(d, k->req) != 0) return DEC_FAILED;
     c->init_end_time = k->stats ? gpujpeg_get_time() : 0;
     if (dec_upload(d, k) != 0) return DEC_FAILED;
     if ((rc = dec_segment_table(d, k)) != 0) return rc;
@@ -930,9 +915,9 @@ static int dec_attempt(struct gpujpeg_decoder* d, struct dec_call* k)
     if (dec_after(d, k) == DEC_AGAIN) return DEC_AGAIN;
     /* what this call did (gpujpeg_amd_decoder_get_region_stats): from what was launched and what the selection found */
     const long stream_segs = k->spec ? (long)d->h_summary->segment_count : (long)k->seg_count;
-    d->region_stats[0] = !d->call_region ? 0 : k->select ? 1 : 2;
+    d->region_stats[0] = !d->img.region ? 0 : k->select ? 1 : 2;
     d->region_stats[1] = k->select ? (long)d->h_sel_count[0] : stream_segs;
-    d->region_stats[2] = d->call_region ? (long)d->geom_s.block_count : (long)c->geom.block_count;
+    d->region_stats[2] = d->img.region ? (long)d->img.geom.block_count : (long)c->geom.block_count;
     d->region_stats[3] = stream_segs;
     dec_stats(d, k);
     k->output->metadata = &d->metadata;
@@ -943,9 +928,10 @@ static int dec_attempt(struct gpujpeg_decoder* d, struct dec_call* k)
 
 /* At most three attempts: on the cached header; rejected for its header or scan structure, the plain way; and when that meets a segment too
  * long for the LDS stage, the careful way (an attempt that is careful already never asks for another). */
-static int decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t image_size, struct gpujpeg_decoder_output* output)
+static int decoder_decode(struct gpujpeg_decoder* d, const struct dec_request* req, uint8_t* image, size_t image_size, struct gpujpeg_decoder_output* output)
 {
     struct dec_call k; /* (not cleared as a whole: it holds a parse result of several KiB) */
+    k.req = req;
     k.image = image;
     k.image_size = image_size;
     k.output = output;
@@ -968,7 +954,8 @@ static int decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t imag
 
 int gpujpeg_decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t image_size, struct gpujpeg_decoder_output* output)
 {
-    return decoder_decode(d, image, image_size, output);
+    const struct dec_request q = dec_request_options(d);
+    return decoder_decode(d, &q, image, image_size, output);
 }
 
 int gpujpeg_decoder_get_stats(struct gpujpeg_decoder* d, struct gpujpeg_duration_stats* stats)
@@ -987,6 +974,14 @@ int gpujpeg_decoder_get_stats(struct gpujpeg_decoder* d, struct gpujpeg_duration
 #define GJ_DEC_BATCH_CHUNK_MAX 256
 #define GJ_DEC_BATCH_BYTES ((size_t)8 << 30) /* work buffers of one chunk */
 
+/* one rectangle per frame of a batch call: a batch of regions (gpujpeg_amd_decoder_decode_batch_regions) or crop-and-resize
+ * (gpujpeg_amd_decoder_decode_batch_crop_resize); neither (all NULL / 0): the decoder's own options hold for every frame */
+struct dec_rects {
+    const int* origins; int rw, rh;          /* a batch of regions, frame f: the rw x rh pixels at (origins[2f], origins[2f + 1]) */
+    const int* rects; const uint8_t* mirror; /* crop-and-resize, frame f: the rectangle rects[4f .. 4f + 3] = x, y, w, h, each with its own size ... */
+    struct gj_resize resize;                 /* ... resampled to ONE out_w x out_h image per frame (mirror: per frame, when mirror && mirror[f]) */
+};
+
 /* what the parts of a batch call share */
 struct dec_batch {
     const uint8_t* streams; size_t stream_stride; const size_t* sizes; int count;
@@ -997,17 +992,12 @@ struct dec_batch {
     int first;                           /* 1: frame 0 went the ordinary way ahead of the batched launches */
     uint8_t* frame_done;
     bool host_io;                        /* copies from or into the caller's host memory have been queued */
-    /* a batch of regions (gpujpeg_amd_decoder_decode_batch_regions; origins == NULL: the decoder's own options hold for every frame) */
-    const int* origins; int rw, rh;      /* frame f: the rw x rh pixels at (origins[2f], origins[2f + 1]) */
-    /* crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize; origins == NULL): a batch of regions whose rectangles have their own sizes and
-     * are resampled to ONE ow x oh image per frame */
-    const int* rects; const uint8_t* mirror; int ow, oh; /* frame f: the rectangle rects[4f .. 4f + 3] = x, y, w, h; mirrored when mirror && mirror[f] */
-    gj_tensor tensor;                    /* ... stored as this tensor (on = 0: as the bytes of the pixel format) */
+    struct dec_rects what;               /* the rectangles, if the call has its own */
     bool planned;                        /* the rectangles have been checked against the streams' geometry; what follows is valid then */
     int* plan;                           /* [count][GJ_MAX_COMP] restart segments of every scan that touch frame f's cover */
     int plan_max[GJ_MAX_COMP];           /* the largest of them per scan */
-    gj_geom gs_max;                      /* geometry of the rw x rh (crop-and-resize: ow x oh) image with the planes of the largest cover (per component the widest and the highest) */
-    gj_geom gs_one; gj_region rg_one;    /* the same for one of the frames, and its region (crop-and-resize: the ow x oh image over that frame's cover) */
+    gj_geom gs_max;                      /* geometry of the rw x rh (crop-and-resize: out_w x out_h) image with the planes of the largest cover (per component the widest and the highest) */
+    gj_geom gs_one; gj_region rg_one;    /* the same for one of the frames, and its region (crop-and-resize: the out_w x out_h image over that frame's cover) */
     struct gpujpeg_image_parameters pi_r;
     int img_w, img_h;                    /* the streams' image, as the rectangles were checked against it */
     long stats[4];                       /* gpujpeg_amd_decoder_get_region_stats of the call: sums over the frames */
@@ -1015,38 +1005,26 @@ struct dec_batch {
 };
 
 /* one rectangle per frame: a batch of regions, or crop-and-resize */
-static bool batch_has_regions(const struct dec_batch* b) { return b->origins != NULL || b->rects != NULL; }
-static void batch_rectangle(const struct dec_batch* b, int f, int region[4])
+static bool batch_has_regions(const struct dec_batch* b) { return b->what.origins != NULL || b->what.rects != NULL; }
+/* ... as the request of frame f's own call: what the single-frame route decodes and what the plan of the batched launches checks */
+static struct dec_request batch_request(const struct gpujpeg_decoder* d, const struct dec_batch* b, int f)
 {
-    if (b->rects) {
-        memcpy(region, b->rects + 4 * (size_t)f, 4 * sizeof(int));
-    } else {
-        region[0] = b->origins[2 * f]; region[1] = b->origins[2 * f + 1]; region[2] = b->rw; region[3] = b->rh;
+    const struct dec_rects* w = &b->what;
+    struct dec_request q = dec_request_options(d);
+    if (w->rects) {
+        q.region = q.resize = true;
+        memcpy(q.rect, w->rects + 4 * (size_t)f, sizeof q.rect);
+        q.rs = w->resize;
+        q.rs.mirror = w->mirror && w->mirror[f] ? 1 : 0;
+    } else if (w->origins) {
+        q.region = true;
+        q.rect[0] = w->origins[2 * f]; q.rect[1] = w->origins[2 * f + 1]; q.rect[2] = w->rw; q.rect[3] = w->rh;
     }
+    return q;
 }
 
-/* restart segments of scan sc with a block / an MCU inside the cover: what counting gj_hip_segment_in_cover over the scan's segments gives, in closed
- * form -- a row of the cover is a run of cells, cell i belongs to segment i / restart_interval, and the rows' runs of segments follow each other
- * (a segment that wraps from one row's end to the next row's start is counted once) */
-static int region_scan_segments(const gj_geom* g, const gj_region_frame* r, int sc)
-{
-    const int gridx = g->interleaved ? g->mcu_count_x : g->comp[sc].blocks_x, ri = g->restart_interval;
-    const int x0 = g->interleaved ? r->mx0 : r->bx0[sc], x1 = g->interleaved ? r->mx1 : r->bx1[sc];
-    const int y0 = g->interleaved ? r->my0 : r->by0[sc], y1 = g->interleaved ? r->my1 : r->by1[sc];
-    if (ri <= 0 || gridx <= 0 || x0 >= x1) return 0;
-    long n = 0, prev_hi = -1;
-    for (int y = y0; y < y1; y++) {
-        long lo = ((long)y * gridx + x0) / ri;
-        const long hi = ((long)y * gridx + x1 - 1) / ri;
-        if (lo <= prev_hi) lo = prev_hi + 1;
-        if (hi >= lo) n += hi - lo + 1;
-        if (hi > prev_hi) prev_hi = hi;
-    }
-    return (int)n;
-}
-
-/* A batch of regions, once the coder is configured for the streams' geometry: every frame's rectangle checked against it (gj_geom_init_region; a
- * refusal names the frame), its origin and covers into the pinned records, its selection counted; the largest cover and the largest selection
+/* A batch of regions, once the coder is configured for the streams' geometry: every frame's rectangle checked against it (gj_region_plan; a
+ * refusal names the frame), its origin and covers into the pinned records, its selection per scan; the largest cover and the largest selection
  * per scan of the call. 0 or -1. Nothing has been launched and nothing of the caller's output has been written when this runs. */
 static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b)
 {
@@ -1057,30 +1035,19 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b)
     memset(b->plan_max, 0, sizeof b->plan_max);
     int wmax[GJ_MAX_COMP] = {0, 0, 0, 0}, hmax[GJ_MAX_COMP] = {0, 0, 0, 0};
     for (int f = 0; f < b->count; f++) {
-        int region[4];
-        batch_rectangle(b, f, region);
-        gj_region rg;
-        if (gj_geom_init_region(&b->gs_one, &rg, g, &c->param, &c->param_image, region, d->req_alignment, &b->pi_r) != 0) {
-            GJ_ERROR("Frame %d of the batch: the region %d,%d,%d,%d was refused!\n", f, region[0], region[1], region[2], region[3]);
-            return -1;
-        }
-        if (b->rects) { /* (the output image over this frame's cover; refuses the output formats whose pixels share samples) */
-            rg.tensor = b->tensor; /* (a tensor call: gs_one.raw_size is the tensor's) */
-            if (gj_geom_init_resized(&b->gs_one, &b->gs_one, &c->param, &c->param_image, b->ow, b->oh, d->req_alignment, &rg.tensor, &b->pi_r) != 0) return -1;
-            if (gj_region_prescale(&b->gs_one, &rg, g, &c->param, &c->param_image, region, b->ow, b->oh, d->resize_prescale, d->req_alignment, &b->pi_r) != 0) return -1;
-            if (f < d->prescales_n) d->prescales[f] = (uint8_t)rg.frame.scale;
-            rg.resize = 1;
-            rg.frame.mirror = b->mirror && b->mirror[f] ? 1 : 0;
-        }
-        b->rg_one = rg;
-        const gj_region_frame* rf = &rg.frame;
+        const struct dec_request q = batch_request(d, b, f);
+        const int refused = gj_region_plan(&b->gs_one, &b->rg_one, g, &c->param, &c->param_image, q.rect, q.resize ? &q.rs : NULL, d->req_alignment, &b->pi_r);
+        if (refused == -1) GJ_ERROR("Frame %d of the batch: the region %d,%d,%d,%d was refused!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3]);
+        if (refused != 0) return -1;
+        if (q.resize && f < d->prescales_n) d->prescales[f] = (uint8_t)b->rg_one.frame.scale;
+        const gj_region_frame* rf = &b->rg_one.frame;
         d->bh_rgn[f] = *rf;
         for (int i = 0; i < g->comp_count && i < GJ_MAX_COMP; i++) {
             if (rf->bx1[i] - rf->bx0[i] > wmax[i]) wmax[i] = rf->bx1[i] - rf->bx0[i];
             if (rf->by1[i] - rf->by0[i] > hmax[i]) hmax[i] = rf->by1[i] - rf->by0[i];
         }
         for (int sc = 0; sc < GJ_MAX_COMP; sc++) {
-            const int n = sc < g->scan_count && g->restart_interval > 0 ? region_scan_segments(g, rf, sc) : 0;
+            const int n = b->rg_one.sel_count[sc];
             b->plan[f * GJ_MAX_COMP + sc] = n;
             if (n > b->plan_max[sc]) b->plan_max[sc] = n;
         }
@@ -1113,18 +1080,14 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
     struct gj_coder* c = &d->coder;
     struct gpujpeg_decoder_output o;
     gpujpeg_decoder_output_set_cuda_buffer(&o);
-    if (batch_has_regions(b)) { /* (a batch of regions: the single-frame region call with this frame's rectangle -- the definition of the frame's result) */
-        d->region_on = true;
-        batch_rectangle(b, f, d->region);
-        /* (crop-and-resize: the same call with the resampling kernel as its pixel stage -- resize_on, set by the public call for its duration) */
-        d->resize_mirror = b->mirror && b->mirror[f] ? 1 : 0;
-        d->resize_tensor = b->tensor;
-    }
-    if (decoder_decode(d, (uint8_t*)(uintptr_t)(b->streams + (size_t)f * b->stream_stride), b->sizes[f], &o) != 0) {
-        if (b->rects) GJ_ERROR("Frame %d of the batch: crop-and-resize of the rectangle %d,%d,%d,%d failed!\n", f, d->region[0], d->region[1], d->region[2], d->region[3]);
+    /* (a batch of regions: the single-frame region call with this frame's rectangle -- the definition of the frame's result; crop-and-resize: the same
+     * call with the resampling kernel as its pixel stage) */
+    const struct dec_request q = batch_request(d, b, f);
+    if (decoder_decode(d, &q, (uint8_t*)(uintptr_t)(b->streams + (size_t)f * b->stream_stride), b->sizes[f], &o) != 0) {
+        if (q.resize) GJ_ERROR("Frame %d of the batch: crop-and-resize of the rectangle %d,%d,%d,%d failed!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3]);
         return -1;
     }
-    if (b->rects && f < d->prescales_n) d->prescales[f] = (uint8_t)d->rg.frame.scale;
+    if (q.resize && f < d->prescales_n) d->prescales[f] = (uint8_t)d->img.rg.frame.scale;
     if (batch_has_regions(b)) {
         if (d->region_stats[0] != 1) b->unselected = true;
         for (int i = 1; i < 4; i++) b->stats[i] += d->region_stats[i];
@@ -1170,7 +1133,7 @@ static int batch_chunk_buffers(struct gpujpeg_decoder* d, gj_dec_job* job, gj_ba
     const size_t coefs_frame = ((size_t)g->data_size + 63) & ~(size_t)63;                                                   /* int16 */
     const int chunk_cap = d->b_chunk > 0 && d->b_chunk < GJ_DEC_BATCH_CHUNK_MAX ? d->b_chunk : GJ_DEC_BATCH_CHUNK_MAX;
     job->g.fb.frames = (uint32_t)(n_all < chunk_cap ? n_all : chunk_cap); /* (what the token / plane choice looks at) */
-    const bool tokens = !d->call_resize && gj_hip_decode_wants_tokens(&job->g, max_size, &d->tune) != 0; /* (crop-and-resize: the cover planes) */
+    const bool tokens = !d->img.resize && gj_hip_decode_wants_tokens(&job->g, max_size, &d->tune) != 0; /* (crop-and-resize: the cover planes) */
     const size_t tok_frame = tokens ? (max_size * 4 + 64 + 63) & ~(size_t)63 : 0;                                            /* tokens */
     const size_t rec_frame = tokens ? ((size_t)g->block_count + 8 + 7) & ~(size_t)7 : 0;                                    /* records */
     /* (a batch of regions: the cover planes of every configuration that does not take the token-fed region kernel, and a compacted table per frame;
@@ -1230,20 +1193,20 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         if (sizes[f] <= d->hdr_cache_len + 2 || sizes[f] > 0x1FFFFFF0u) batched = false;
     }
     if (!batched || n_all < 1) return 0;
-    d->call_scale = 1;
-    d->call_region = false;
-    d->call_resize = false;
+    dec_image_set(d, 1, NULL, NULL, NULL);
     const struct gj_reader_result* r = &d->hdr_cache_r;
     /* a scale the single call refuses for this header (a flip; packed 4:2:2 output of odd reduced width, gj_geom_init_scaled): nothing is launched,
      * the frames go the ordinary way and that call says why */
     if (d->scale > 1 && (d->flipped || (r->param_image.pixel_format == GPUJPEG_422_U8_P1020 && (GPUJPEG_AMD_SCALED_DIM(r->param_image.width, d->scale) & 1)))) return 0;
     if (decoder_configure(d, &r->param, &r->param_image) != 0) return -1; /* (the geometry of the cached header, whatever the coder was last set up for) */
-    if (d->scale <= 1 && !regions && dec_full_size_geometry(d) != 0) return -1;
-    if (dec_scale_geometry(d) != 0) return -1; /* (call_scale, and with a scale geom_s / pi_s: the reduced image of the cached header's geometry) */
+    if (!regions) { /* (the image of the decoder's options -- no region among them here -- over the cached header's geometry) */
+        const struct dec_request q = dec_request_options(d);
+        if (dec_call_geometry(d, &q) != 0) return -1;
+    }
     /* a batch of regions: the rectangles against the cached header's geometry, unless frame 0 went ahead and they have been checked against its own.
      * A rectangle the CACHED header refuses may be one the streams' own header takes (an older sequence's cache): frame 0 goes ahead and decides. */
     if (regions && !b->planned && batch_regions_plan(d, b) != 0) return first == 0 && !force_first ? 1 : -1;
-    const size_t frame_raw = regions ? (size_t)b->gs_one.raw_size : d->call_scale > 1 ? (size_t)d->geom_s.raw_size : (size_t)g->raw_size;
+    const size_t frame_raw = regions ? (size_t)b->gs_one.raw_size : dec_raw_size(d);
     if (b->output_stride < frame_raw || (b->frame_raw != 0 && b->frame_raw != frame_raw)) {
         /* the cached header is an OLDER sequence's (a larger image than the caller's slots, ADVICE r4: this used to fail the call): these
          * streams are strangers to it */
@@ -1251,13 +1214,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     }
     b->frame_raw = frame_raw;
     geom_take_tables(&c->geom, r);
-    if (regions) { /* (what a region call leaves for dec_raw_size / dec_out_param_image and what dec_job_base reads) */
-        d->call_region = true;
-        d->call_resize = b->rects != NULL;
-        d->geom_s = b->gs_one;
-        d->pi_s = b->pi_r;
-        d->rg = b->rg_one;
-    }
+    if (regions) dec_image_set(d, 1, &b->gs_one, &b->pi_r, &b->rg_one); /* (what a region call leaves: the image of one of the frames) */
     gj_dec_job job;
     dec_job_base(d, true, &job);
     job.seg_count = g->segment_count;
@@ -1383,18 +1340,14 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     return accepted == 0 && first == 0 && !force_first ? 1 : 0;
 }
 
-/* the batch call proper; what: the rectangles of a batch of regions (origins, rw, rh) or of crop-and-resize (rects, mirror, ow, oh), or NULL */
-static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count, const struct dec_batch* what,
+/* the batch call proper; what: the rectangles of a batch of regions or of crop-and-resize, or NULL */
+static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count, const struct dec_rects* what,
                         uint8_t* output, size_t output_stride, struct gpujpeg_image_parameters* param_image)
 {
     struct gj_coder* c = &d->coder;
     struct dec_batch b = {.streams = streams, .stream_stride = stream_stride, .sizes = sizes, .count = count, .output_stride = output_stride,
                           .d_out = output, .d_out_stride = output_stride};
-    if (what) {
-        b.origins = what->origins; b.rw = what->rw; b.rh = what->rh;
-        b.rects = what->rects; b.mirror = what->mirror; b.ow = what->ow; b.oh = what->oh;
-        b.tensor = what->tensor;
-    }
+    if (what) b.what = *what;
     const bool regions = batch_has_regions(&b);
     b.streams_on_device = gj_hip_is_device_ptr(streams) != 0;
     b.out_on_device = gj_hip_is_device_ptr(output) != 0;
@@ -1463,7 +1416,7 @@ int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* d, const uint8_t* s
 }
 
 /* A batch of regions: one width x height rectangle per frame, each at its own origin. The decoder's own dec_opt_region is neither read nor changed
- * (frames that go the ordinary way borrow the option's fields for their call). */
+ * (frames that go the ordinary way have their rectangle in their call's request). */
 int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count,
                                              const int* origins, int width, int height, uint8_t* output, size_t output_stride,
                                              struct gpujpeg_image_parameters* param_image)
@@ -1481,14 +1434,8 @@ int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder* d, const ui
         GJ_ERROR("A batch of regions is not available together with " GPUJPEG_DEC_OPT_FLIPPED_BOOL "!\n");
         return -1;
     }
-    const bool own_on = d->region_on;
-    int own[4];
-    memcpy(own, d->region, sizeof own);
-    const struct dec_batch what = {.origins = origins, .rw = width, .rh = height};
-    const int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
-    d->region_on = own_on;
-    memcpy(d->region, own, sizeof own);
-    return rc;
+    const struct dec_rects what = {.origins = origins, .rw = width, .rh = height};
+    return decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
 }
 
 /* Crop-and-resize: one rectangle per frame, each with its own size, resampled to ONE out_width x out_height image per frame (bilinear, gj_resize_taps),
@@ -1528,13 +1475,6 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
         GJ_ERROR("Crop-and-resize is implemented for pixel formats whose pixels do not share samples, not for %s!\n", gpujpeg_pixel_format_get_name(pf));
         return -1;
     }
-    const bool own_on = d->region_on;
-    int own[4];
-    memcpy(own, d->region, sizeof own);
-    d->resize_on = true;
-    d->resize_w = out_width;
-    d->resize_h = out_height;
-    d->resize_mirror = 0;
     /* (the scale every frame takes, as launched: written by the plan of the batched launches and by the frames that go the ordinary way) */
     d->prescales_n = 0;
     if (count > d->prescales_cap) {
@@ -1545,8 +1485,8 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
     }
     memset(d->prescales, 1, (size_t)count);
     d->prescales_n = count;
-    struct dec_batch what = {.rects = rects, .mirror = mirror, .ow = out_width, .oh = out_height};
-    if (tensor) what.tensor = *tensor;
+    struct dec_rects what = {.rects = rects, .mirror = mirror, .resize = {.out_w = out_width, .out_h = out_height, .prescale = d->resize_prescale}};
+    if (tensor) what.resize.tensor = *tensor;
     int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
     if (rc == 0) { /* (slot [4] of the kernel times, gpujpeg_amd_ext.h: 6 when any frame of the call was prescaled, whichever launch came last) */
         for (int f = 0; f < count; f++)
@@ -1554,10 +1494,6 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
     } else {
         d->prescales_n = 0;
     }
-    d->resize_on = false;
-    memset(&d->resize_tensor, 0, sizeof d->resize_tensor); /* (no later call sees a tensor) */
-    d->region_on = own_on;
-    memcpy(d->region, own, sizeof own);
     return rc;
 }
 
@@ -1805,7 +1741,7 @@ size_t gpujpeg_amd_decoder_read_coefficients(struct gpujpeg_decoder* d, int16_t*
 
 size_t gpujpeg_amd_decoder_read_planes(struct gpujpeg_decoder* d, uint8_t* dst, size_t capacity)
 {
-    const size_t n = dec_reduced_or_region(d) ? d->geom_s.data_size : d->coder.geom.data_size; /* (the reduced planes of a reduced-size decode, the cover's of a region decode) */
+    const size_t n = dec_reduced_or_region(d) ? d->img.geom.data_size : d->coder.geom.data_size; /* (the reduced planes of a reduced-size decode, the cover's of a region decode) */
     if (!d->coder.configured || capacity < n) return 0;
     if (gj_hip_memcpy_d2h(dst, d->coder.d_planes, n, d->coder.stream) != 0 || gj_hip_stream_sync(d->coder.stream) != 0) return 0;
     return n;

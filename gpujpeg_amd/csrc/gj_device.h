@@ -101,8 +101,8 @@ __device__ __forceinline__ uint64_t gj_segment_block(const gj_geom& g, const GjS
 // Region decode (gj_region): does restart segment s have a block (non-interleaved scan: of its component's grid) or an MCU (interleaved scan)
 // inside the region's cover? A segment is a run of consecutive cells [first, last] of a raster whose rows are `gridx` cells long; it meets the
 // rectangle [x0, x1) x [y0, y1) in its first row (cells xa .. end of the row), in its last row (0 .. xb) or in any whole row between them.
-// The ONE statement of the selection: k_segment_select (for every kind of table, a host-walked one included) and -- through gj_hip_segment_in_cover -- the host's count of the
-// batch plan ask here.
+// The ONE statement of the selection for the kernels: k_segment_select (for every kind of table, a host-walked one included) asks here. The host's plan
+// counts the same segments in closed form from the cover (gj_region_plan, gj_common.c); host code that wants the predicate itself: gj_hip_segment_in_cover.
 // (r: gj_region::frame, or one frame's record of a batch of regions, read where it lies in device memory)
 __host__ __device__ inline bool gj_segment_in_cover(const gj_geom& g, const gj_region_frame& r, const int s)
 {

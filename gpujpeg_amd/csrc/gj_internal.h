@@ -58,6 +58,12 @@ int gj_geom_init_resized(gj_geom* go, const gj_geom* cover, const struct gpujpeg
 int gj_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const int rect[4], int out_w, int out_h, int max_scale, int out[5]);
 int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
                        const int rect[4], int out_w, int out_h, int max_scale, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
+/* the ONE plan of a region call, single frame or frame f of a batch: the three steps above in that order (resize == NULL: a plain region, the first
+ * step alone), r->resize / frame.mirror / tensor set, and r->sel_count[sc] = restart segments of scan sc that touch the cover (0 without a restart
+ * interval). -1: the rectangle was refused, -2: the resize was; either with the step's own message */
+struct gj_resize { int out_w, out_h, mirror, prescale; gj_tensor tensor; }; /* prescale: dec_opt_resize_prescale; tensor.on = 0: the bytes of the pixel format */
+int gj_region_plan(gj_geom* gr, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
+                   const int rect[4], const struct gj_resize* resize, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
 
 /* ---- tables ---- */
 extern const uint8_t gj_zigzag[64];

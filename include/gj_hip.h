@@ -318,7 +318,8 @@ typedef struct gj_region {
      * (k_resize_region_tensor; gs.raw_size is then the tensor's size) */
     gj_tensor tensor;
 } gj_region;
-/* the predicate of the selection (gj_device.h: gj_segment_in_cover) for host code: does restart segment s have a block / an MCU inside the cover? */
+/* the predicate of the selection (gj_device.h: gj_segment_in_cover) for host code: does restart segment s have a block / an MCU inside the cover?
+ * (the decoder's own plan does not call it: gj_region_plan counts in closed form) */
 GJ_HIP_API int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s);
 /* the bits k_resize_region_tensor stores for byte v (0 .. 255) of channel c (gj_device.h: gj_tensor_element) for host code */
 GJ_HIP_API uint32_t gj_hip_tensor_element(const gj_tensor* t, int c, int v);

@@ -312,6 +312,18 @@ def test_a_stream_of_another_size_fails_the_call(O, G, dlib):
             dec.decode_batch_crop_resize([streams[0], other, streams[2]], rects, 16, 16)
         got, _ = dec.decode_batch_crop_resize(streams, rects, 16, 16)  # (and with a header to launch on the second time)
         assert same(got, expected(O, streams, rects, 16, 16))
+    # the decoder's own region option across a call that fails part-way: the batch's rectangles travel in its calls' requests, never in the option
+    own, full0 = (5, 7, 50, 40), O.decode(streams[0])[0]
+    assert dec.set_option(OPT, opt_value(own)) == 0
+    with pytest.raises(RuntimeError):
+        dec.decode_batch_crop_resize([streams[0], other, streams[2]], rects, 16, 16)
+    px, pi = dec.decode(streams[0])
+    assert (pi.width, pi.height) == (50, 40) and np.array_equal(px, crop(full0, 480, 272, 1, own))
+    got, _ = dec.decode_batch_crop_resize(streams, rects, 16, 16)
+    assert same(got, expected(O, streams, rects, 16, 16))
+    assert dec.set_option(OPT, "full") == 0
+    px, pi = dec.decode(streams[0])
+    assert (pi.width, pi.height) == (480, 272) and np.array_equal(px, full0) and dec.region_stats()[0] == 0
     dec.close()
 
 

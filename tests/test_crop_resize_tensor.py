@@ -14,7 +14,7 @@ import pytest
 
 from test_crop_resize import HD_CASE, HD_RECTS, expected, resize_image
 from test_region_batch import dlib, emu, frames_of, new_decoder  # noqa: F401  (emu, dlib: the fixtures of the two tiers)
-from test_region_decode import OPT, case_named, crop, damaged_restart_markers, opt_value
+from test_region_decode import OPT, case_named, case_stream, crop, damaged_restart_markers, opt_value
 
 F32, F16, BF16 = 0, 1, 2
 CHW, HWC = 0, 1
@@ -334,6 +334,29 @@ def test_state_between_calls(O, G, dlib, hd):
         px, pi = dec.decode(streams[3])
         assert (pi.width, pi.height) == (50, 40) and np.array_equal(px, crop(full, 480, 272, 1, (5, 7, 50, 40))), rep
         assert dec.set_option(OPT, "full") == 0
+    dec.close()
+
+
+def test_a_stream_of_another_size_fails_the_call(O, G, dlib):
+    """a tensor call that fails part-way leaves nothing of itself in the decoder: its own region option holds for the single decode that follows, the
+    next tensor call is correct, and a plain decode returns the u8 pixels of the full frame -- no tensor, no resize, no rectangle seen"""
+    streams = frames_of(O, case_named(HD_CASE), 3)
+    other = case_stream(O, case_named("rgb_natural_auto"))  # 640 x 368: the rectangles below lie inside it as well
+    rects = [(0, 0, 64, 40), (8, 8, 30, 50), (16, 16, 100, 20)]
+    want = expected(O, streams, rects, 16, 16)
+    own, full0 = (5, 7, 50, 40), O.decode(streams[0])[0]
+    dec = new_decoder(G, dlib)
+    assert dec.set_option(OPT, opt_value(own)) == 0
+    for rep in range(2):
+        with pytest.raises(RuntimeError):
+            dec.decode_batch_crop_resize_tensor([streams[0], other, streams[2]], rects, 16, 16, F16, CHW, *IMAGENET)
+        px, pi = dec.decode(streams[0])
+        assert (pi.width, pi.height) == (50, 40) and px.dtype == np.uint8 and np.array_equal(px, crop(full0, 480, 272, 1, own)), rep
+        got, _ = dec.decode_batch_crop_resize_tensor(streams, rects, 16, 16, F16, CHW, *IMAGENET)  # (and with a header to launch on the second time)
+        assert tensors_equal(got, want, 1, 16, 16, F16, CHW, *IMAGENET) == [0] * 3, rep
+    assert dec.set_option(OPT, "full") == 0
+    px, pi = dec.decode(streams[0])
+    assert (pi.width, pi.height) == (480, 272) and px.dtype == np.uint8 and np.array_equal(px, full0) and dec.region_stats()[0] == 0
     dec.close()
 
 

@@ -410,6 +410,28 @@ def test_restart_interval_0_decodes_every_segment(O, G, dlib):
     dec.close()
 
 
+@pytest.mark.parametrize("name", ["rgb_big_restart", "rgb_hdlike_r24"])
+def test_alternating_regions_are_counted_per_call(O, G, dlib, name):
+    """one decoder, two regions in turn (A, B, A, B): every call's statistics are its own region's brute-force count -- nothing of the call before
+    is kept. rgb_big_restart: 512 x 256, interval 300, a segment spans more than four block rows; rgb_hdlike_r24: segments wrap row ends.
+    A: an interior rectangle, all four numbers odd; B: a full-height strip narrower than a block -- their selections differ in every scan"""
+    case = case_named(name)
+    jpeg = case_stream(O, case)
+    full = O.decode(jpeg)
+    w, h = case[1], case[2]
+    a, b = ((w // 3) | 1, (h // 3) | 1, (w // 4) | 1, (h // 4) | 1), ((w // 2) | 1, 0, 5, h)
+    assert all(v % 2 == 1 for v in a) and b[2] < 8 and b[3] == h
+    geo = stream_geometry(G, dlib, jpeg)
+    scans_a, scans_b = expected_work(geo, a, 1)[0], expected_work(geo, b, 1)[0]
+    assert geo["ri"] > 0 and len(scans_a) == 3 and all(x != y for x, y in zip(scans_a, scans_b)), (scans_a, scans_b)
+    dec = G.Decoder(dlib)
+    for reg in (a, b, a, b):
+        check(O, G, dlib, jpeg, None, None, reg, dec, full)
+        per_scan, _ = check_stats(G, dlib, dec, jpeg, reg, 1)  # (mode 1, the sum of the brute-force count, the cover's blocks)
+        assert per_scan == (scans_a if reg == a else scans_b)
+    dec.close()
+
+
 def test_cover_planes_after_a_region_call(O, G, dlib):
     """gpujpeg_amd_decoder_read_planes after a region call: the cover-sized component planes = the crop of the oracle's planes at the cover"""
     jpeg = case_stream(O, case_named("rgb_to_422_nonil"))
