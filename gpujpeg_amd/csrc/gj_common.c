@@ -774,6 +774,21 @@ int gj_region_plan(gj_geom* gr, gj_region* r, const gj_geom* full, const struct 
         if (gj_region_prescale(gr, r, full, param, pi, rect, resize->out_w, resize->out_h, resize->prescale, alignment, pi_out) != 0) return -2;
         r->resize = 1;
         r->frame.mirror = resize->mirror ? 1 : 0;
+        if (resize->filter == GJ_RESIZE_FILTER_ANTIALIAS) {
+            /* the antialiased filter: the rectangle itself at full size, at most 256 times the output along either axis (what keeps its sums in 64 bits) */
+            if (r->frame.scale > 1) {
+                GJ_ERROR("The antialiased resize filter is not available together with a prescale!\n");
+                return -3;
+            }
+            if (rect[2] > 256LL * resize->out_w || rect[3] > 256LL * resize->out_h) {
+                GJ_ERROR("The antialiased resize filter takes a rectangle of at most 256 times the output's width and height: %dx%d to %dx%d is refused!\n", rect[2],
+                         rect[3], resize->out_w, resize->out_h);
+                return -3;
+            }
+            r->filter = GJ_RESIZE_FILTER_ANTIALIAS;
+        } else if (resize->filter != GJ_RESIZE_FILTER_BILINEAR) {
+            return -3;
+        }
     }
     for (int sc = 0; sc < full->scan_count && sc < GJ_MAX_COMP; sc++) r->sel_count[sc] = region_scan_segments(full, &r->frame, sc);
     return 0;

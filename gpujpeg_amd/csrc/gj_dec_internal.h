@@ -15,7 +15,8 @@
 //   gj_dec_region.hip           region decode (dec_opt_region): k_segment_select (table -> the entries that touch the region's cover), k_idct_region,
 //                               k_postprocess_region / k_copy_planes_region (cover blocks -> cover planes -> the region's pixels),
 //                               k_resize_region (crop-and-resize: the rectangle resampled to the call's output size instead of copied),
-//                               k_idct_region_scaled (dec_opt_resize_prescale: the cover's blocks through the reduced-size IDCT ahead of it)
+//                               k_idct_region_scaled (dec_opt_resize_prescale: the cover's blocks through the reduced-size IDCT ahead of it),
+//                               k_resize_region_aa (dec_opt_resize_filter = antialias: the resample with the triangle filter, tiled through LDS)
 //   this header                 what those share: the 4:4:4 configuration and its colour pairs (gj_is_rgb444, GJ_COLOR_PAIRS), gj_block_of, the block
 //                               records of the token-fed kernels (gj_rec_pack, gj_tok_record) and their token ranges (gj_tok_fetch), the N-point IDCT of a
 //                               block's corner (gj_idct_corner)

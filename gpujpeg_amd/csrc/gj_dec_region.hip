@@ -12,6 +12,8 @@
 //                           bilinearly to the call's output size, with an optional horizontal mirror
 //   k_resize_region_tensor  the same pixels stored as a normalised float tensor (gpujpeg_amd_decoder_decode_batch_crop_resize_tensor: f32 / f16 / bf16,
 //                           CHW / HWC, element = byte * scale[c] + bias[c]) -- k_resize_region up to and including the blend, another store
+//   k_resize_region_aa      both of them with the antialiased triangle filter in place of the four-tap blend (dec_opt_resize_filter = antialias:
+//   (.._aa_tensor)          gj_resize_aa_taps, exact rational weights over a footprint that grows with the reduction, one rounding)
 //   k_idct_region_scaled    in front of k_resize_region for the frames dec_opt_resize_prescale reduces (gj_region_frame::scale = s > 1): the
 //                           cover's blocks through the N-point IDCT of their N x N corner, N = 8 / s (k_idct_scaled's arithmetic: gj_idct_corner),
 //                           into REDUCED cover planes
@@ -27,6 +29,21 @@
 
 extern "C" int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s) { return gj_segment_in_cover(*g, r->frame, s) ? 1 : 0; }
 extern "C" uint32_t gj_hip_tensor_element(const gj_tensor* t, int c, int v) { return gj_tensor_element(*t, c, v); }
+extern "C" int gj_hip_resize_aa_weights(int n_src, int n_out, int i, int* first, int* count, uint32_t* weights, int capacity, uint64_t* sum)
+{
+    if (n_src < 1 || n_out < 1 || n_src > 65535 || n_out > GJ_RESIZE_MAX_OUT || i < 0 || i >= n_out || n_src > GJ_RESIZE_AA_MAX_RATIO * n_out) return -1;
+    int k0, n;
+    uint32_t U;
+    gj_resize_aa_taps(n_src, n_out, i, k0, n, U);
+    if (first) *first = k0;
+    if (count) *count = n;
+    if (sum) *sum = U;
+    if (weights) {
+        if (capacity < n) return -2;
+        for (int k = 0; k < n; k++) weights[k] = gj_resize_aa_weight(n_src, n_out, i, k0 + k);
+    }
+    return 0;
+}
 
 // ================================================================================================
 // Selection
@@ -469,6 +486,145 @@ __global__ __launch_bounds__(256) void k_resize_region_tensor_batch(const gj_geo
     gj_resize_region_body<true>(gr, rb.d_frames[z], rb.tensor, planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
 }
 
+// Crop-and-resize with the antialiased filter (gj_region::filter, dec_opt_resize_filter = antialias): the pixel stage above with the triangle filter
+// of gj_resize_aa_taps in place of the four-tap blend, separably -- along the rows with u_i(k), down the columns with v_j(l) -- and exactly: one 64-bit
+// multiply-add per row and channel, one 64-bit division per channel (gj_resize_aa_round). No prescale under this filter: N = 8 throughout.
+// WIDE: the row's sums in 64 bits, for a frame whose rectangle is so wide that 255 U_i may pass 2^32 (gj_resize_aa_row_fits_32: w above ~32 900);
+// every other frame keeps them in 32. The choice is the frame's, the same in every lane of a workgroup.
+// The fourth channel of GJ_PF_4444_P0123 is 0xFF in every source pixel and a constant stays a constant under the filter: it is stored as that.
+template <bool WIDE> struct gj_aa_row_sum { typedef uint32_t type; };
+template <> struct gj_aa_row_sum<true> { typedef uint64_t type; };
+
+// acc[ch] = sum over the taps k = kx .. kx + nx - 1 of output column ii of u_ii(k) P[y][k][ch], P[y][k] = pixel (k, y) of the rectangle made as
+// gj_resize_region_body makes it: the components' samples (gj_region_sample), gj_pixel_transform unless no_transform.
+// gj_region_sample -- two divisions per component -- is asked for the row's FIRST tap only. Along a row the sample of component c moves on by one
+// where (r.x + k) reaches a multiple of sub_h, and stays at the last column of the frame's cover (the clamp of gj_region_sample, which no tap of
+// a rectangle inside the image meets): `rem` counts the pixels into the sample, `room` the columns left.
+template <bool WIDE>
+__device__ __forceinline__ void gj_resize_aa_row(const gj_geom& gr, const gj_region_frame& r, const uint8_t* __restrict__ planes, const int ii, const int kx,
+                                                 const int nx, const unsigned y, typename gj_aa_row_sum<WIDE>::type (&acc)[3])
+{
+    typedef typename gj_aa_row_sum<WIDE>::type row_t;
+    const uint8_t* at[GJ_MAX_COMP] = {planes, planes, planes, planes};
+    unsigned rem[GJ_MAX_COMP] = {0, 0, 0, 0}, room[GJ_MAX_COMP] = {0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < GJ_MAX_COMP; c++) {
+        if (c >= gr.comp_count) break;
+        const gj_comp_geom& k = gr.comp[c];
+        const unsigned X = (unsigned)r.x + (unsigned)kx, q = X / (unsigned)k.sub_h;
+        const unsigned sx = q - (unsigned)r.bx0[c] * 8u, last = (unsigned)(r.bx1[c] - r.bx0[c]) * 8u - 1u;
+        at[c] = planes + gj_region_sample(k, r, c, (unsigned)kx, y);
+        rem[c] = X - q * (unsigned)k.sub_h;
+        room[c] = sx < last ? last - sx : 0u;
+    }
+    acc[0] = acc[1] = acc[2] = 0;
+    for (int k = 0; k < nx; k++) {
+        const uint32_t u = gj_resize_aa_weight(r.w, gr.width, ii, kx + k);
+        int v[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < GJ_MAX_COMP; c++) {
+            if (c >= gr.comp_count) break;
+            v[c] = *at[c];
+            if (++rem[c] == (unsigned)gr.comp[c].sub_h) {
+                rem[c] = 0;
+                if (room[c]) { room[c]--; at[c]++; }
+            }
+        }
+        if (!gr.no_transform) gj_pixel_transform(gr, v);
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) acc[ch] += (row_t)u * (uint32_t)v[ch];
+    }
+}
+
+// A workgroup per tile of GJ_AA_TX x GJ_AA_TY output pixels (blockIdx.x, blockIdx.y; 256 lanes), one lane per pixel of the tile. The rows of the
+// rectangle the tile's pixels weigh -- from the first tap of its first row to the last tap of its last -- are taken GJ_AA_TY at a time: lane
+// (ti, tj) leaves the sums of row base + tj for ITS column in LDS (gj_resize_aa_row), and after the barrier adds, of those GJ_AA_TY rows, the ones
+// inside its own pixel's taps, each times v_j(l). Neighbouring output rows share half of their source rows when reducing: a source pixel is made
+// and weighted along its row about once per output column that holds it (twice when reducing) instead of once per output PIXEL (four times) --
+// the figures of this shape and of the two it was measured against: profiles/crop_resize_antialias.md. Every lane reaches every barrier (lanes outside the image carry no work).
+#define GJ_AA_TX 32
+#define GJ_AA_TY 8
+template <bool TENSOR, bool WIDE>
+__device__ __forceinline__ void gj_resize_region_aa_tile(const gj_geom& gr, const gj_region_frame& r, const gj_tensor& t, const uint8_t* __restrict__ planes,
+                                                         uint8_t* __restrict__ raw)
+{
+    typedef typename gj_aa_row_sum<WIDE>::type row_t;
+    __shared__ row_t H[GJ_AA_TY][GJ_AA_TX][3];
+    const unsigned OW = (unsigned)gr.width, OH = (unsigned)gr.height;
+    const unsigned ti = threadIdx.x % GJ_AA_TX, tj = threadIdx.x / GJ_AA_TX;
+    const unsigned i = blockIdx.x * GJ_AA_TX + ti, j0 = blockIdx.y * GJ_AA_TY, j = j0 + tj;
+    const bool col = i < OW, pix = col && j < OH;
+    const int ii = r.mirror ? (int)(OW - 1u - (col ? i : 0u)) : (int)(col ? i : 0u);
+    int kx, nx, ky = 0, ny = 0;
+    uint32_t U, V = 1;
+    gj_resize_aa_taps(r.w, (int)OW, ii, kx, nx, U);
+    if (pix) gj_resize_aa_taps(r.h, (int)OH, (int)j, ky, ny, V);
+    // the tile's rows of the rectangle (j0 < OH: the grid has no tile below the image)
+    int row_lo, row_hi, n;
+    gj_resize_aa_range(r.h, (int)OH, (int)j0, row_lo, n);
+    gj_resize_aa_range(r.h, (int)OH, (int)min(j0 + GJ_AA_TY - 1u, OH - 1u), row_hi, n);
+    row_hi += n - 1;
+    uint64_t S[3] = {0, 0, 0};
+    for (int base = row_lo; base <= row_hi; base += GJ_AA_TY) {
+        if (col && base + (int)tj <= row_hi) {
+            row_t acc[3];
+            gj_resize_aa_row<WIDE>(gr, r, planes, ii, kx, nx, (unsigned)(base + (int)tj), acc);
+            H[tj][ti][0] = acc[0]; H[tj][ti][1] = acc[1]; H[tj][ti][2] = acc[2];
+        }
+        __syncthreads();
+        const int from = max(base, ky), to = min(base + GJ_AA_TY, ky + ny); // (a pixel outside the image: ny = 0, no row)
+        for (int l = from; l < to; l++) {
+            const uint32_t vw = gj_resize_aa_weight(r.h, (int)OH, (int)j, l);
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) S[ch] += (uint64_t)vw * H[l - base][ti][ch];
+        }
+        __syncthreads(); // (H is rewritten by the next trip)
+    }
+    if (!pix) return;
+    int o[4];
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) o[ch] = gj_resize_aa_round(S[ch], U, V);
+    o[3] = gr.pixel_format == GJ_PF_4444_P0123 ? 0xFF : 0;
+    const unsigned pos = j * OW + i;
+    if (TENSOR) gj_tensor_store(t, raw, OW * OH, pos, o);
+    else gj_pixel_store(gr, raw, OW, OH, i, j, pos, o);
+}
+static dim3 gj_resize_aa_grid(const gj_geom& gr, const unsigned frames)
+{
+    return dim3(((unsigned)gr.width + GJ_AA_TX - 1) / GJ_AA_TX, ((unsigned)gr.height + GJ_AA_TY - 1) / GJ_AA_TY, frames);
+}
+
+template <bool TENSOR>
+__device__ __forceinline__ void gj_resize_region_aa_body(const gj_geom& gr, const gj_region_frame& r, const gj_tensor& t, const uint8_t* __restrict__ planes,
+                                                         uint8_t* __restrict__ raw)
+{
+    if (gj_resize_aa_row_fits_32(r.w, gr.width)) gj_resize_region_aa_tile<TENSOR, false>(gr, r, t, planes, raw);
+    else gj_resize_region_aa_tile<TENSOR, true>(gr, r, t, planes, raw);
+}
+
+__global__ __launch_bounds__(256) void k_resize_region_aa(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    gj_resize_region_aa_body<false>(gr, r.frame, r.tensor, planes, raw);
+}
+
+__global__ __launch_bounds__(256) void k_resize_region_aa_tensor(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    gj_resize_region_aa_body<true>(gr, r.frame, r.tensor, planes, raw);
+}
+
+// frame blockIdx.z of a batch, as for k_resize_region_batch
+__global__ __launch_bounds__(256) void k_resize_region_aa_batch(const gj_geom gr, const gj_region rb, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    const size_t z = blockIdx.z;
+    gj_resize_region_aa_body<false>(gr, rb.d_frames[z], rb.tensor, planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
+}
+
+__global__ __launch_bounds__(256) void k_resize_region_aa_tensor_batch(const gj_geom gr, const gj_region rb, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
+{
+    const size_t z = blockIdx.z;
+    gj_resize_region_aa_body<true>(gr, rb.d_frames[z], rb.tensor, planes + z * gr.fb.coefs, raw + z * gr.fb.raw);
+}
+
 // The IDCT side of a region call: cover blocks -> cover planes -> region pixels. A batch of regions (d_frames) runs the same stages through the
 // _batch kernels with blockIdx.z = frame and grids for the largest cover (gr).
 void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tokens, gj_event_t* ev)
@@ -492,7 +648,12 @@ void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tok
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
     if (r.resize) { // crop-and-resize: gr is the output image's geometry
         const unsigned n = (unsigned)gr.width * (unsigned)gr.height;
-        if (r.tensor.on) // (gpujpeg_amd_decoder_decode_batch_crop_resize_tensor: the same pixels, stored as the call's tensor)
+        if (r.filter == GJ_RESIZE_FILTER_ANTIALIAS) { // (dec_opt_resize_filter = antialias: the triangle filter's kernels on their own grid)
+            if (r.tensor.on)
+                hipLaunchKernelGGL(batch ? k_resize_region_aa_tensor_batch : k_resize_region_aa_tensor, gj_resize_aa_grid(gr, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
+            else
+                hipLaunchKernelGGL(batch ? k_resize_region_aa_batch : k_resize_region_aa, gj_resize_aa_grid(gr, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
+        } else if (r.tensor.on) // (gpujpeg_amd_decoder_decode_batch_crop_resize_tensor: the same pixels, stored as the call's tensor)
             hipLaunchKernelGGL(batch ? k_resize_region_tensor_batch : k_resize_region_tensor, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);
         else
             hipLaunchKernelGGL(batch ? k_resize_region_batch : k_resize_region, dim3((n + 255) / 256, 1, frames), dim3(256), 0, st, gr, r, job->d_planes, job->d_raw);

@@ -66,6 +66,11 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
         return -1;
     // (a scale per frame, gj_region_frame::scale: inside a resize job alone -- dec_opt_resize_prescale --, one of 1, 2, 4, 8; gj_dec_job::scale stays 1)
     if (rg.on && ((rg.scale_mask & ~(rg.resize ? 0xFu : 1u)) != 0 || (!rg_batch && rg.frame.scale > 1 && (!rg.resize || rg.scale_mask != (unsigned)rg.frame.scale)))) return -1;
+    // (a filter, gj_region::filter: one the pixel stage knows; the antialiased one inside a resize job alone and over frames of scale 1 alone)
+    if (rg.on && rg.filter != GJ_RESIZE_FILTER_BILINEAR &&
+        (rg.filter != GJ_RESIZE_FILTER_ANTIALIAS || !rg.resize || (rg.scale_mask & ~1u) != 0 ||
+         (!rg_batch && (rg.frame.scale > 1 || rg.frame.w > GJ_RESIZE_AA_MAX_RATIO * job->gs.width || rg.frame.h > GJ_RESIZE_AA_MAX_RATIO * job->gs.height))))
+        return -1;
     if (rg.on && (job->scale > 1 || job->flipped || (rg.select && (!rg.d_sel || !rg.h_sel_count || g.restart_interval <= 0)) ||
                   (rg_batch ? (g.fb.sizes == nullptr || !rg.select || job->channel_remap) : (g.fb.sizes != nullptr || job->batch.count > 1 || (rg.select && !rg.d_sel_count)))))
         return -1;

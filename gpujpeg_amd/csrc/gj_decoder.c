@@ -114,6 +114,9 @@ struct gpujpeg_decoder {
      * into its rectangles' description (struct dec_rects); the scale every frame of its last call took: gpujpeg_amd_decoder_get_prescales */
     int resize_prescale;
     uint8_t* prescales; int prescales_n, prescales_cap;
+    /* dec_opt_resize_filter: the filter of crop-and-resize's resample (GJ_RESIZE_FILTER_BILINEAR, the default, or _ANTIALIAS). Read by that call alone,
+     * into its rectangles' description like the prescale */
+    int resize_filter;
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
@@ -1038,6 +1041,7 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b)
         const struct dec_request q = batch_request(d, b, f);
         const int refused = gj_region_plan(&b->gs_one, &b->rg_one, g, &c->param, &c->param_image, q.rect, q.resize ? &q.rs : NULL, d->req_alignment, &b->pi_r);
         if (refused == -1) GJ_ERROR("Frame %d of the batch: the region %d,%d,%d,%d was refused!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3]);
+        if (refused == -3) GJ_ERROR("Frame %d of the batch: the rectangle %d,%d,%d,%d was refused by the resize filter!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3]);
         if (refused != 0) return -1;
         if (q.resize && f < d->prescales_n) d->prescales[f] = (uint8_t)b->rg_one.frame.scale;
         const gj_region_frame* rf = &b->rg_one.frame;
@@ -1470,6 +1474,11 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
         GJ_ERROR("Crop-and-resize is not available together with " GPUJPEG_DEC_OPT_CHANNEL_REMAP "!\n");
         return -1;
     }
+    if (d->resize_filter == GJ_RESIZE_FILTER_ANTIALIAS && d->resize_prescale > 1) { /* (the filter over the reduced cover: not built) */
+        GJ_ERROR(GPUJPEG_AMD_DEC_OPT_RESIZE_FILTER "=" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_ANTIALIAS " is not available together with " GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE "=1/%d!\n",
+                 d->resize_prescale);
+        return -1;
+    }
     const enum gpujpeg_pixel_format pf = d->req_pixel_format;
     if (pf == GPUJPEG_422_U8_P1020 || pf == GPUJPEG_422_U8_P0P1P2 || pf == GPUJPEG_420_U8_P0P1P2) { /* (a format the stream decides: checked with its header) */
         GJ_ERROR("Crop-and-resize is implemented for pixel formats whose pixels do not share samples, not for %s!\n", gpujpeg_pixel_format_get_name(pf));
@@ -1485,7 +1494,7 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
     }
     memset(d->prescales, 1, (size_t)count);
     d->prescales_n = count;
-    struct dec_rects what = {.rects = rects, .mirror = mirror, .resize = {.out_w = out_width, .out_h = out_height, .prescale = d->resize_prescale}};
+    struct dec_rects what = {.rects = rects, .mirror = mirror, .resize = {.out_w = out_width, .out_h = out_height, .prescale = d->resize_prescale, .filter = d->resize_filter}};
     if (tensor) what.resize.tensor = *tensor;
     int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
     if (rc == 0) { /* (slot [4] of the kernel times, gpujpeg_amd_ext.h: 6 when any frame of the call was prescaled, whichever launch came last) */
@@ -1676,6 +1685,12 @@ int gpujpeg_decoder_set_option(struct gpujpeg_decoder* d, const char* opt, const
         GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE " (1, 1/2, 1/4 or 1/8)\n", val);
         return GPUJPEG_ERROR;
     }
+    if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_RESIZE_FILTER) == 0) { /* read by gpujpeg_amd_decoder_decode_batch_crop_resize (and _tensor) alone */
+        if (strcmp(val, GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_BILINEAR) == 0) { d->resize_filter = GJ_RESIZE_FILTER_BILINEAR; return GPUJPEG_NOERR; }
+        if (strcmp(val, GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_ANTIALIAS) == 0) { d->resize_filter = GJ_RESIZE_FILTER_ANTIALIAS; return GPUJPEG_NOERR; }
+        GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_RESIZE_FILTER " (" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_BILINEAR " or " GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_ANTIALIAS ")\n", val);
+        return GPUJPEG_ERROR;
+    }
     if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_REGION) == 0) { /* syntax only: the decode call checks the region against its stream */
         if (strcmp(val, "full") == 0) { d->region_on = false; return GPUJPEG_NOERR; }
         long v[4];
@@ -1707,6 +1722,7 @@ void gpujpeg_decoder_print_options(void)
     printf("\t" GPUJPEG_DEC_OPT_CHANNEL_REMAP "=XYZ[W] - output channel remapping, 'help' for details\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_SCALE "=[1|1/2|1/4|1/8] - decode to a reduced-size image (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE "=[1|1/2|1/4|1/8] - largest reduced-size IDCT crop-and-resize may put ahead of its resample (MI355X extension)\n");
+    printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_FILTER "=[" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_BILINEAR "|" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_ANTIALIAS "] - filter of crop-and-resize's resample: four taps, or a footprint that grows with the reduction (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_REGION "=[X,Y,W,H|full] - decode the W x H pixels at (X, Y) only (MI355X extension)\n");
 }
 
@@ -1751,6 +1767,11 @@ int gpujpeg_amd_host_crop_resize_plan(int image_w, int image_h, int all_componen
 {
     if (!rect || !out) return -1;
     return gj_crop_resize_plan(image_w, image_h, all_components_1x1, rect, out_w, out_h, max_scale, out);
+}
+
+int gpujpeg_amd_host_resize_weights(int n_src, int n_out, int i, int* first, int* count, uint32_t* weights, int capacity, uint64_t* sum)
+{
+    return gj_hip_resize_aa_weights(n_src, n_out, i, first, count, weights, weights ? capacity : 0, sum);
 }
 
 int gpujpeg_amd_decoder_get_prescales(struct gpujpeg_decoder* d, uint8_t* dst, int capacity)

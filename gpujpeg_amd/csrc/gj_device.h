@@ -162,6 +162,58 @@ __host__ __device__ inline int gj_resize_blend(const int v00, const int v01, con
     return (top * (256 - fy) + bot * fy + 32768) >> 16;
 }
 
+// The antialiased resample (dec_opt_resize_filter = antialias, gj_region::filter): the triangle filter with half-pixel centres whose support is
+// stretched by n_src / n_out when reducing and is one sample when enlarging. Along one axis, with D = max(n_src, n_out) and c = (2i + 1) n_src,
+// source sample k weighs u_i(k) = max(0, 2D - |(2k + 1) n_out - c|) in output sample i; taps outside the crop are dropped and the rest
+// renormalised by their exact sum U_i. Exact rational weights, ONE rounding at the end (gj_resize_aa_round).
+// The taps with a positive weight are those with c - 2D < (2k + 1) n_out < c + 2D, a run of k in closed form:
+//     first = max(0, floor((c - 2D - n_out) / (2 n_out)) + 1),  last = min(n_src - 1, floor((c + 2D - n_out - 1) / (2 n_out)))
+// The tap nearest to the centre always lies inside the crop with a weight of at least D, so first <= last and U_i >= D > 0.
+// Range: n_src <= 65535, n_out <= 16384: c + 2D < 2^32 and (2k + 1) n_out < 2^31 -- 32-bit UNSIGNED; a weight is at most 2D < 2^18. The call
+// refuses n_src > 256 n_out (GJ_RESIZE_AA_MAX_RATIO): at most 2 * 256 + 1 taps, U_i < 2^26.
+// The ONE statement of the filter: k_resize_region_aa and host code (gpujpeg_amd_host_resize_weights) ask here.
+#define GJ_RESIZE_AA_MAX_RATIO 256
+// weight of tap k (first <= k <= last)
+__host__ __device__ inline uint32_t gj_resize_aa_weight(const int n_src, const int n_out, const int i, const int k)
+{
+    const unsigned D = (unsigned)(n_src > n_out ? n_src : n_out);
+    const int t = (int)((2u * (unsigned)k + 1u) * (unsigned)n_out - (2u * (unsigned)i + 1u) * (unsigned)n_src); // (|t| < 2D: the difference of two 32-bit values, taken modulo 2^32)
+    return 2u * D - (unsigned)(t < 0 ? -t : t);
+}
+// first tap and tap count of output sample i
+__host__ __device__ inline void gj_resize_aa_range(const int n_src, const int n_out, const int i, int& first, int& count)
+{
+    const unsigned D = (unsigned)(n_src > n_out ? n_src : n_out), O = (unsigned)n_out;
+    const unsigned c = (2u * (unsigned)i + 1u) * (unsigned)n_src;
+    const unsigned lo = c >= 2u * D + O ? (c - 2u * D - O) / (2u * O) + 1u : 0u; // (a negative numerator: every k >= 0 lies above it)
+    unsigned hi = (c + 2u * D - O - 1u) / (2u * O);
+    if (hi > (unsigned)n_src - 1u) hi = (unsigned)n_src - 1u;
+    first = (int)lo;
+    count = (int)(hi - lo + 1u);
+}
+// ... and U_i with them (a loop over the taps of the run, never over the crop)
+__host__ __device__ inline void gj_resize_aa_taps(const int n_src, const int n_out, const int i, int& first, int& count, uint32_t& sum)
+{
+    gj_resize_aa_range(n_src, n_out, i, first, count);
+    uint32_t s = 0;
+    for (int k = first; k < first + count; k++) s += gj_resize_aa_weight(n_src, n_out, i, k);
+    sum = s;
+}
+// Do 32 bits hold the weighted sum of a row, sum_k u_i(k) C[k] <= 255 U_i, for EVERY i of this axis? U_i is a sum of samples of a triangle of
+// height 2D and half-width 2D taken 2 n_out apart: at most area / spacing + height = 2 D D / n_out + 2D. The kernels ask once per frame.
+__host__ __device__ inline bool gj_resize_aa_row_fits_32(const int n_src, const int n_out)
+{
+    const uint64_t D = (uint64_t)(n_src > n_out ? n_src : n_out);
+    return 255ull * (2ull * D * D / (uint64_t)n_out + 2ull * D) < (1ull << 32);
+}
+// ... and the value of a channel from S = sum_l v_j(l) sum_k u_i(k) C[l][k]: (2S + U V) / (2 U V), floor -- S / (U V) rounded half up, the one
+// rounding of the filter. U, V < 2^26 and S <= 255 U V: 2S + UV < 2^62.
+__host__ __device__ inline int gj_resize_aa_round(const uint64_t S, const uint32_t U, const uint32_t V)
+{
+    const uint64_t uv = (uint64_t)U * V;
+    return (int)((2ull * S + uv) / (2ull * uv));
+}
+
 // Tensor output of crop-and-resize (gj_tensor): binary32 -> the bits of binary16 / bfloat16, round to nearest even. binary16: subnormals are produced
 // (not flushed), what rounds to 65520 or more is infinity; bfloat16: the upper half of the word after the rounding increment. Integer arithmetic on
 // the float's bits -- the portable form, which host code and the CPU tier run --; device code takes the hardware's conversion (v_cvt_f16_f32,

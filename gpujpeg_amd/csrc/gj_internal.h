@@ -61,7 +61,9 @@ int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const str
 /* the ONE plan of a region call, single frame or frame f of a batch: the three steps above in that order (resize == NULL: a plain region, the first
  * step alone), r->resize / frame.mirror / tensor set, and r->sel_count[sc] = restart segments of scan sc that touch the cover (0 without a restart
  * interval). -1: the rectangle was refused, -2: the resize was; either with the step's own message */
-struct gj_resize { int out_w, out_h, mirror, prescale; gj_tensor tensor; }; /* prescale: dec_opt_resize_prescale; tensor.on = 0: the bytes of the pixel format */
+struct gj_resize { int out_w, out_h, mirror, prescale; gj_tensor tensor; int filter; }; /* prescale: dec_opt_resize_prescale; tensor.on = 0: the bytes of the pixel format;
+                                                                                           filter: dec_opt_resize_filter (GJ_RESIZE_FILTER_*; antialias: -3 with a message
+                                                                                           for a rectangle more than 256 times the output along an axis, or with a prescale) */
 int gj_region_plan(gj_geom* gr, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
                    const int rect[4], const struct gj_resize* resize, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
 

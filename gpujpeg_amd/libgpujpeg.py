@@ -200,6 +200,9 @@ class Library:
         if hasattr(L, "gpujpeg_amd_host_crop_resize_plan"):
             L.gpujpeg_amd_host_crop_resize_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
             L.gpujpeg_amd_decoder_get_prescales.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int]
+        if hasattr(L, "gpujpeg_amd_host_resize_weights"):
+            L.gpujpeg_amd_host_resize_weights.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.c_int,
+                                                          C.POINTER(C.c_uint64)]
 
     # ---- developer settings (include/gpujpeg_amd_ext.h: gpujpeg_amd_tuning) ----
     def tuning(self, setting):
@@ -242,6 +245,21 @@ def crop_resize_plan(lib, image_w, image_h, all_components_1x1, rect, out_w, out
     r4 = (C.c_int * 4)(*[int(v) for v in rect])
     rc = lib.L.gpujpeg_amd_host_crop_resize_plan(int(image_w), int(image_h), int(bool(all_components_1x1)), r4, int(out_w), int(out_h), int(max_scale), out)
     return tuple(out) if rc == 0 else None
+
+
+def resize_weights(lib, n_src, n_out, i, capacity=None):
+    """gpujpeg_amd_host_resize_weights (host only, lib: a Library): the taps dec_opt_resize_filter = antialias gives output sample i along an axis of
+    n_src source samples resampled to n_out -> (first, [weights], sum); None where the call would refuse. capacity: room offered for the weights
+    (default: enough); too little raises ValueError with the count needed"""
+    first, count, total = C.c_int(), C.c_int(), C.c_uint64()
+    if lib.L.gpujpeg_amd_host_resize_weights(int(n_src), int(n_out), int(i), C.byref(first), C.byref(count), None, 0, C.byref(total)) != 0:
+        return None
+    cap = count.value if capacity is None else int(capacity)
+    w = (C.c_uint32 * max(cap, 1))()
+    rc = lib.L.gpujpeg_amd_host_resize_weights(int(n_src), int(n_out), int(i), C.byref(first), C.byref(count), w, cap, C.byref(total))
+    if rc == -2:
+        raise ValueError(f"capacity {cap} < {count.value} taps")
+    return (first.value, [int(v) for v in w[:count.value]], int(total.value)) if rc == 0 else None
 
 
 def apply_environment_settings(lib, environ=None):
@@ -513,7 +531,8 @@ class Decoder:
                                  sizes=None):
         """gpujpeg_amd_decoder_decode_batch_crop_resize: decode_batch with one rectangle per frame, each of its own size -- frame f is the
         rects[f] = (x, y, w, h) pixels of stream f's image resampled bilinearly to out_width x out_height and, where mirror[f] is set, mirrored
-        horizontally (the definition: include/gpujpeg_amd_ext.h). streams / device_in, in_stride, sizes and device_out, out_stride as for decode_batch;
+        horizontally (the definition: include/gpujpeg_amd_ext.h; set_option("dec_opt_resize_filter", "antialias") makes the resample the antialiased
+        triangle filter, whose taps resize_weights() returns). streams / device_in, in_stride, sizes and device_out, out_stride as for decode_batch;
         without device_out the frames come back as a list of numpy arrays. Returns (pixels or None, ImageParameters)."""
         if not hasattr(self.lib.L, "gpujpeg_amd_decoder_decode_batch_crop_resize"):
             raise RuntimeError("this library has no gpujpeg_amd_decoder_decode_batch_crop_resize")
@@ -653,7 +672,7 @@ class Decoder:
     def idct_path(self):
         """IDCT side of the last perf_stats call: 0 full size, 1 reduced size from the coefficient planes, 2 reduced size from tokens,
         3 region from the coefficient planes, 4 region from tokens, 5 region resampled from the cover planes (crop-and-resize), 6 the same with a frame
-        reduced ahead of the resample (dec_opt_resize_prescale)"""
+        reduced ahead of the resample (dec_opt_resize_prescale), 7 region resampled with the antialiased filter (dec_opt_resize_filter=antialias)"""
         ms = (C.c_float * 8)()
         if self.lib.L.gpujpeg_amd_decoder_get_kernel_times(self.h, ms) != 0:
             return None

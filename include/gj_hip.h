@@ -317,12 +317,20 @@ typedef struct gj_region {
     /* ... and what the pixel stage of a resize job stores: tensor.on = 0 the bytes of gs's pixel format (k_resize_region), 1 the tensor
      * (k_resize_region_tensor; gs.raw_size is then the tensor's size) */
     gj_tensor tensor;
+    /* ... and the filter of the resample (dec_opt_resize_filter): GJ_RESIZE_FILTER_BILINEAR the four taps of k_resize_region, GJ_RESIZE_FILTER_ANTIALIAS
+     * the triangle filter of k_resize_region_aa (gj_device.h: gj_resize_aa_taps) over frames of scale 1 -- with a prescaled frame, or outside a
+     * resize job, anything but BILINEAR is refused */
+    int filter;
 } gj_region;
+enum { GJ_RESIZE_FILTER_BILINEAR = 0, GJ_RESIZE_FILTER_ANTIALIAS = 1 };
 /* the predicate of the selection (gj_device.h: gj_segment_in_cover) for host code: does restart segment s have a block / an MCU inside the cover?
  * (the decoder's own plan does not call it: gj_region_plan counts in closed form) */
 GJ_HIP_API int gj_hip_segment_in_cover(const gj_geom* g, const gj_region* r, int s);
 /* the bits k_resize_region_tensor stores for byte v (0 .. 255) of channel c (gj_device.h: gj_tensor_element) for host code */
 GJ_HIP_API uint32_t gj_hip_tensor_element(const gj_tensor* t, int c, int v);
+/* the taps k_resize_region_aa gives output sample i of n_out along an axis of n_src source samples (gj_device.h: gj_resize_aa_taps, _weight) for host
+ * code: first tap, tap count, the weights (NULL: not wanted) and their sum. -1: arguments the call refuses (sizes, i, n_src > 256 n_out), -2: capacity < count */
+GJ_HIP_API int gj_hip_resize_aa_weights(int n_src, int n_out, int i, int* first, int* count, uint32_t* weights, int capacity, uint64_t* sum);
 
 typedef struct gj_dec_job {
     gj_geom g;                     /* pixel_format / color_space describe the requested output */
@@ -371,7 +379,8 @@ typedef struct gj_dec_job {
     int scale;
     gj_geom gs;
     int* idct_path;                /* host, may be NULL: which IDCT side ran -- 0 full size, 1 k_idct_scaled, 2 k_idct_tok_scaled_rgb444, 3 k_idct_region, 4 k_idct_tok_region_rgb444,
-                                      5 k_idct_region + k_resize_region (crop-and-resize), 6 the same with a frame through k_idct_region_scaled (dec_opt_resize_prescale) */
+                                      5 k_idct_region + k_resize_region (crop-and-resize), 6 the same with a frame through k_idct_region_scaled (dec_opt_resize_prescale),
+                                      7 k_idct_region + k_resize_region_aa (dec_opt_resize_filter = antialias) */
     /* region decode (dec_opt_region, region.on): the entropy decoders work on g -- with region.select on the compacted table --, the IDCT side
      * transforms the cover's blocks -- from tokens straight into d_raw, or into cover-sized planes in d_planes from which the region's pixels go to d_raw --; gs is the geometry of the W x H image
      * with the cover's planes (gj_geom_init_region). No scale, no flip. A single frame, or (region.d_frames) a batch of frames with one

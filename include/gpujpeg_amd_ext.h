@@ -116,6 +116,31 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
  * than the output. Read by that call alone (its definition with a prescale: below); every other call, and that call with "1", is what it is without
  * the option. Another value is refused by gpujpeg_decoder_set_option and leaves the setting as it was. dec_opt_scale itself stays refused by the call. */
 #define GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE "dec_opt_resize_prescale"
+/* Decoder option "dec_opt_resize_filter" = "bilinear" (default) or "antialias": the filter of the resample of
+ * gpujpeg_amd_decoder_decode_batch_crop_resize and gpujpeg_amd_decoder_decode_batch_crop_resize_tensor. Read by those two calls alone; it holds from the
+ * next call on and may be changed between two calls of a decoder. Another value is refused by gpujpeg_decoder_set_option (GPUJPEG_ERROR) and leaves the
+ * setting as it was. With "bilinear" every byte, counter and kernel of every call is what it is without the option.
+ * WITH "antialias" everything in the DEFINITION of the crop-and-resize call (below) stands -- C, the mirror, the output formats, param_image, the strides,
+ * the fourth byte of GPUJPEG_4444_U8_P0123 going through the same formula -- except the lines that make R. For a frame with rectangle w x h and output
+ * OW x OH, channel by channel on output pixels; integers throughout, division = floor:
+ *     Dx = max(w, OW);  u_i(k) = max(0, 2 Dx - |(2k + 1) OW - (2i + 1) w|)   k in [0, w),  U_i = sum_k u_i(k)        i < OW
+ *     Dy = max(h, OH);  v_j(l) = max(0, 2 Dy - |(2l + 1) OH - (2j + 1) h|)   l in [0, h),  V_j = sum_l v_j(l)        j < OH
+ *     S       = sum_l v_j(l) sum_k u_i(k) C[l][k]
+ *     R[j][i] = (2 S + U_i V_j) / (2 U_i V_j);      out[j][i] = mirror && mirror[f] ? R[j][OW - 1 - i] : R[j][i]
+ * The triangle filter with half-pixel centres whose support is stretched by w / OW when reducing and is one pixel when enlarging; taps outside the
+ * rectangle are dropped and the rest renormalised by their exact sum: the antialias = True bilinear filter of torch and PIL with exact rational weights
+ * and ONE rounding (half up) -- at most half a level from that filter evaluated in float64. The identity for w == OW and h == OH; a constant stays
+ * that constant (0xFF stays 0xFF); U_i >= Dx > 0. Where w <= OW and h <= OH it is bilinear interpolation with exact weights, which may differ from the
+ * 8-bit weights of "bilinear" by a level.
+ * Refused by the call with a message, -1 returned, nothing of `output` written, the decoder usable as before: a frame with w > 256 OW or h > 256 OH (the
+ * message names the frame; with image sides <= 65535 this keeps U_i, V_j < 2^26 and 2 S + U V < 2^62: every accepted frame comes out exact); the
+ * filter together with a dec_opt_resize_prescale other than 1. Every other refusal, the routing, the fallbacks, gpujpeg_amd_decoder_last_batch,
+ * _get_region_stats and _get_prescales (all 1) are those of the call with "bilinear"; the batched launches end in k_resize_region_aa_batch
+ * (k_resize_region_aa_tensor_batch), the single-frame route in k_resize_region_aa (_tensor): the same bytes. Slot [4] of
+ * gpujpeg_amd_decoder_get_kernel_times is 7 after a call that resampled with this filter. */
+#define GPUJPEG_AMD_DEC_OPT_RESIZE_FILTER "dec_opt_resize_filter"
+#define GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_BILINEAR "bilinear"
+#define GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_ANTIALIAS "antialias"
 /* Host-only: the table enc_opt_huffman=optimal builds for one class from symbol counts freq[256] (ITU T.81 Annex K.2: Figures K.1, K.3, K.4;
  * reserved code point, ties to the larger symbol value), code lengths limited to the largest L of 16 .. 10 whose table the library's
  * two-level decode tables take. Writes BITS (bits[1..16]) and HUFFVAL; returns L, or -1 when no count is non-zero. */
@@ -130,7 +155,8 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_optimal(const uint32_t freq[256], uint8
  *          5 region resampled from the cover planes (k_idct_region + k_resize_region: gpujpeg_amd_decoder_decode_batch_crop_resize),
  *          gpujpeg_amd_decoder_decode_batch_regions leaves the side its batched launches took here (3 or 4) and no durations, and so do
  *          6 the same with at least one frame of the call reduced ahead of the resample (k_idct_region_scaled: dec_opt_resize_prescale);
- *          gpujpeg_amd_decoder_decode_batch with a dec_opt_scale (1 or 2) and gpujpeg_amd_decoder_decode_batch_crop_resize (5 or 6) */
+ *          gpujpeg_amd_decoder_decode_batch with a dec_opt_scale (1 or 2) and gpujpeg_amd_decoder_decode_batch_crop_resize (5, 6 or 7);
+ *          7 region resampled from the cover planes with the antialiased filter (k_idct_region + k_resize_region_aa: dec_opt_resize_filter = antialias) */
 GPUJPEG_API int gpujpeg_amd_encoder_get_kernel_times(struct gpujpeg_encoder* encoder, float ms[8]);
 GPUJPEG_API int gpujpeg_amd_decoder_get_kernel_times(struct gpujpeg_decoder* decoder, float ms[8]);
 
@@ -273,6 +299,12 @@ GPUJPEG_API uint32_t gpujpeg_amd_host_tensor_element(const struct gpujpeg_amd_te
  * with w or h < 1 or not inside the image, an output size outside 1 .. 16384, another max_scale. */
 GPUJPEG_API int gpujpeg_amd_host_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const int rect[4], int out_w, int out_h, int max_scale,
                                                   int out[5]);
+/* Host-only: the taps dec_opt_resize_filter = antialias gives output sample i (0 .. n_out - 1) along one axis of n_src source samples resampled to
+ * n_out, by the code the call itself runs: *first = the first source sample with a positive weight, *count = how many follow each other from there,
+ * weights[0 .. count) = u_i(first + t) of the definition above, *sum = their sum U_i. Every pointer may be NULL (not wanted); `capacity` = room in
+ * `weights`. Returns 0; -1 where the call would refuse (n_src outside 1 .. 65535, n_out outside 1 .. 16384, i outside the output, n_src > 256 n_out);
+ * -2 when capacity < count (first, count and sum are written, weights is not). */
+GPUJPEG_API int gpujpeg_amd_host_resize_weights(int n_src, int n_out, int i, int* first, int* count, uint32_t* weights, int capacity, uint64_t* sum);
 /* s_f of every frame of the decoder's last gpujpeg_amd_decoder_decode_batch_crop_resize call, as launched: dst[f], one byte per frame. Returns the
  * frame count, or 0 on error (no such call yet, the last one failed, capacity too small). */
 GPUJPEG_API int gpujpeg_amd_decoder_get_prescales(struct gpujpeg_decoder* decoder, uint8_t* dst, int capacity);
