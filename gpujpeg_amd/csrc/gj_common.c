@@ -683,7 +683,8 @@ int gj_geom_init_resized(gj_geom* go, const gj_geom* cover, const struct gpujpeg
 /* dec_opt_resize_prescale: what a crop-and-resize call puts in front of its resample for ONE frame. rect = x, y, w, h inside the
  * image_w x image_h image, resampled to out_w x out_h; max_scale = S of the option (1, 2, 4, 8). out = s, x', y', w', h':
  *     s   the largest of 1, 2, 4, 8 with s <= S, w >= s out_w and h >= s out_h -- the bilinear step then reduces by less than 2 per axis --; 1 for a
- *         stream with a subsampled component (its chroma would be reduced by the same N as its luma: worse than no prescale)
+ *         stream with a subsampled component (its chroma would be reduced by the same N as its luma: worse than no prescale) -- all_components_1x1 = 0;
+ *         callers pass non-zero as well for a stream that dec_opt_resize_prescale_subsampled reduces per component (gj_region_prescale)
  *     x' = x / s, w' = ceil((x + w) / s) - x' (y', h' likewise): the rectangle's covering rectangle in the image reduced by s
  * -1 where the call refuses (a rectangle that is not inside the image, an output size outside 1 .. 16384, another S). Host arithmetic only. */
 int gj_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const int rect[4], int out_w, int out_h, int max_scale, int out[5])
@@ -709,14 +710,31 @@ int gj_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const 
  * (which has passed their checks). With s > 1 the frame's cover becomes the one gj_geom_init_region gives for the covering rectangle expanded to
  * full size, (x' s, y' s, min(w' s, W - x' s), min(h' s, H - y' s)) -- reduced sample X of a component lies in block X / N, the block of full-size
  * sample X s, so selection, batch plan and entropy decoders need nothing else --, go the out_w x out_h image over that cover's planes, and the
- * frame's record what k_idct_region_scaled and k_resize_region read (gj_region_frame). */
+ * frame's record what k_idct_region_scaled and k_resize_region read (gj_region_frame).
+ * subsampled (dec_opt_resize_prescale_subsampled): a stream that is reduced per component (gj_geom_prescale_per_component) takes its scale by the
+ * same rule -- the plan's all_components_1x1 argument is non-zero for it -- and its frame is marked per_comp: component c is reduced by s / sub_h
+ * (N_c = 8 sub_h / s), so reduced pixel X of the image covers full-size pixels [sX, sX + s), the samples of block X / N_c of EVERY component: the
+ * cover is the same one. */
+int gj_geom_prescale_per_component(const gj_geom* full)
+{
+    int any = 0;
+    for (int c = 0; c < full->comp_count; c++) {
+        const gj_comp_geom* k = &full->comp[c];
+        if (k->sub_h != k->sub_v || (k->sub_h != 1 && k->sub_h != 2)) return 0;
+        if (c > 0 && k->sub_h < full->comp[c - 1].sub_h) return 0;
+        if (k->sub_h == 2) any = 1;
+    }
+    return any;
+}
+
 int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi,
-                       const int rect[4], int out_w, int out_h, int max_scale, unsigned alignment, struct gpujpeg_image_parameters* pi_out)
+                       const int rect[4], int out_w, int out_h, int max_scale, int subsampled, unsigned alignment, struct gpujpeg_image_parameters* pi_out)
 {
     int all_1x1 = 1, p[5];
     for (int c = 0; c < full->comp_count; c++)
         if (full->comp[c].sub_h != 1 || full->comp[c].sub_v != 1) all_1x1 = 0;
-    if (gj_crop_resize_plan(pi->width, pi->height, all_1x1, rect, out_w, out_h, max_scale > 1 ? max_scale : 1, p) != 0) return -1;
+    const int per_comp = subsampled && gj_geom_prescale_per_component(full);
+    if (gj_crop_resize_plan(pi->width, pi->height, all_1x1 || per_comp, rect, out_w, out_h, max_scale > 1 ? max_scale : 1, p) != 0) return -1;
     const int s = p[0];
     if (s == 1) return 0;
     int ex[4] = {p[1] * s, p[2] * s, p[3] * s, p[4] * s};
@@ -732,6 +750,11 @@ int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const str
     rf->src_w = rect[2]; rf->src_h = rect[3];
     rf->off_x = rect[0] - s * p[1]; rf->off_y = rect[1] - s * p[2];
     r->scale_mask = (unsigned)s;
+    if (per_comp) { /* (its IDCT kernel is k_idct_region_scaled_comp alone) */
+        rf->per_comp = 1;
+        r->scale_mask = 0;
+        r->comp_mask = (unsigned)s;
+    }
     return 0;
 }
 
@@ -771,7 +794,7 @@ int gj_region_plan(gj_geom* gr, gj_region* r, const gj_geom* full, const struct 
          * tensor's) -- and with a prescale the planes are the reduced ones of the covering rectangle's cover */
         r->tensor = resize->tensor;
         if (gj_geom_init_resized(gr, gr, param, pi, resize->out_w, resize->out_h, alignment, &r->tensor, pi_out) != 0) return -2;
-        if (gj_region_prescale(gr, r, full, param, pi, rect, resize->out_w, resize->out_h, resize->prescale, alignment, pi_out) != 0) return -2;
+        if (gj_region_prescale(gr, r, full, param, pi, rect, resize->out_w, resize->out_h, resize->prescale, resize->subsampled, alignment, pi_out) != 0) return -2;
         r->resize = 1;
         r->frame.mirror = resize->mirror ? 1 : 0;
         if (resize->filter == GJ_RESIZE_FILTER_ANTIALIAS) {

@@ -847,7 +847,7 @@ void gj_launch_idct(const gj_dec_job* job, hipStream_t st, gj_idct_tok_t idct_to
     const char* what = "idct / postprocess";
     if (job->region.on) { // region decode (gj_dec_region.hip): the cover's blocks, the region's pixels
         gj_launch_idct_region(job, st, tokens, ev);
-        path = job->region.resize ? (job->region.filter == GJ_RESIZE_FILTER_ANTIALIAS ? 7 : (job->region.scale_mask & ~1u) ? 6 : 5) : tokens ? 4 : 3;
+        path = job->region.resize ? (job->region.filter == GJ_RESIZE_FILTER_ANTIALIAS ? 7 : job->region.comp_mask ? 8 : (job->region.scale_mask & ~1u) ? 6 : 5) : tokens ? 4 : 3;
         what = job->region.d_frames ? "idct / postprocess (batch of regions)" : "idct / postprocess (region)";
     } else if (job->scale > 1) { // reduced-size decode (gj_dec_idct_scaled.hip): the pixel kernels work on the reduced image's geometry
         const bool done = gj_launch_idct_scaled(job, st, tokens);

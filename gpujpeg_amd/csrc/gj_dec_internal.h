@@ -16,6 +16,7 @@
 //                               k_postprocess_region / k_copy_planes_region (cover blocks -> cover planes -> the region's pixels),
 //                               k_resize_region (crop-and-resize: the rectangle resampled to the call's output size instead of copied),
 //                               k_idct_region_scaled (dec_opt_resize_prescale: the cover's blocks through the reduced-size IDCT ahead of it),
+//                               k_idct_region_scaled_comp (dec_opt_resize_prescale_subsampled: the same on 4:2:0 streams, N per component),
 //                               k_resize_region_aa (dec_opt_resize_filter = antialias: the resample with the triangle filter, tiled through LDS)
 //   this header                 what those share: the 4:4:4 configuration and its colour pairs (gj_is_rgb444, GJ_COLOR_PAIRS), gj_block_of, the block
 //                               records of the token-fed kernels (gj_rec_pack, gj_tok_record) and their token ranges (gj_tok_fetch), the N-point IDCT of a

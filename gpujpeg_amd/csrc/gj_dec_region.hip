@@ -17,12 +17,14 @@
 //   k_idct_region_scaled    in front of k_resize_region for the frames dec_opt_resize_prescale reduces (gj_region_frame::scale = s > 1): the
 //                           cover's blocks through the N-point IDCT of their N x N corner, N = 8 / s (k_idct_scaled's arithmetic: gj_idct_corner),
 //                           into REDUCED cover planes
+//   k_idct_region_scaled_comp  the same for the frames dec_opt_resize_prescale_subsampled reduces PER COMPONENT (gj_region_frame::per_comp: 4:2:0):
+//                           component c's blocks through N_c = 8 sub_h / s -- N_c = 8 is k_idct_region's transform --, one sample per reduced pixel in every plane
 //
 // Every configuration can go this way; three-component 4:4:4 streams with non-interleaved scans and packed 3-byte output in token mode go
 // through k_idct_tok_region_rgb444 (gj_dec_idct.hip, beside k_idct_tok_rgb444 whose LDS helpers it shares) instead of the last three: same bytes.
 //
 // A BATCH of regions (gj_region::d_frames: one rectangle per frame, gpujpeg_amd_decoder_decode_batch_regions) runs the same code with blockIdx.z =
-// frame: k_segment_select_batch, k_idct_region_batch, k_postprocess_region_batch, k_copy_planes_region_batch, k_resize_region_batch, k_resize_region_tensor_batch, k_idct_region_scaled_batch and the batched instantiation of
+// frame: k_segment_select_batch, k_idct_region_batch, k_postprocess_region_batch, k_copy_planes_region_batch, k_resize_region_batch, k_resize_region_tensor_batch, k_idct_region_scaled_batch, k_idct_region_scaled_comp_batch and the batched instantiation of
 // k_idct_tok_region_rgb444 read their frame's rectangle and cover from device memory and share the bodies of the single-frame kernels.
 // (part of the decoder's device code, see gj_dec_internal.h for the map of the files)
 #include "gj_dec_internal.h"
@@ -230,23 +232,12 @@ void gj_launch_segment_select_batch(const gj_dec_job* job, hipStream_t st)
 // (bx0 + bx, by0 + by) of the component's coefficient plane, which holds its blocks in raster order for every kind of scan.
 // (BATCH: gr holds the planes of the largest cover of the batch, r is the frame's: lanes beyond the frame's own cover leave)
 // (r: gj_region::frame, or the frame's record where it lies in device memory)
-template <bool BATCH>
-__device__ __forceinline__ void gj_idct_region_body(const gj_geom& g, const gj_geom& gr, const gj_region_frame& r, const int16_t* __restrict__ coefs,
-                                                    const float* __restrict__ qtab, uint8_t* __restrict__ planes)
+// one block: its 64 coefficients at blk (float table qf of its component) -> its 8 x 8 samples at dst, rows `pitch` bytes apart
+__device__ __forceinline__ void gj_idct_region_block(const int16_t* __restrict__ blk, const float* __restrict__ qf, uint8_t* __restrict__ dst, const size_t pitch)
 {
-    const unsigned gb = blockIdx.x * 256u + threadIdx.x;
-    if (gb >= (unsigned)gr.block_count) return;
-    if (BATCH && r.scale > 1) return; // (a prescaled frame of a crop-and-resize batch: k_idct_region_scaled_batch)
-    unsigned bx, by;
-    const int c = gj_block_of(gr, gb, bx, by);
-    const gj_comp_geom& k = gr.comp[c];
-    if (BATCH && (bx >= (unsigned)(r.bx1[c] - r.bx0[c]) || by >= (unsigned)(r.by1[c] - r.by0[c]))) return;
-    const gj_comp_geom& kf = g.comp[c];
-    const unsigned fbx = (unsigned)r.bx0[c] + bx, fby = (unsigned)r.by0[c] + by;
-    if (fbx >= (unsigned)kf.blocks_x || fby >= (unsigned)kf.blocks_y) return; // (cannot happen: the cover lies inside the component's grid)
     uint32_t w[32];
     {
-        const uint4* p = reinterpret_cast<const uint4*>(coefs + kf.data_offset + ((size_t)fby * kf.blocks_x + fbx) * 64);
+        const uint4* p = reinterpret_cast<const uint4*>(blk);
 #pragma unroll
         for (int q = 0; q < 8; q++) {
             const uint4 v = p[q];
@@ -254,10 +245,27 @@ __device__ __forceinline__ void gj_idct_region_body(const gj_geom& g, const gj_g
         }
     }
     uint32_t px[16];
-    gj_idct_pk(w, qtab + kf.q_table * 64, px);
-    uint8_t* dst = planes + k.data_offset + (size_t)by * 8 * k.data_width + bx * 8;
+    gj_idct_pk(w, qf, px);
 #pragma unroll
-    for (int q = 0; q < 8; q++) *reinterpret_cast<uint2*>(dst + (size_t)q * k.data_width) = make_uint2(px[2 * q], px[2 * q + 1]);
+    for (int q = 0; q < 8; q++) *reinterpret_cast<uint2*>(dst + (size_t)q * pitch) = make_uint2(px[2 * q], px[2 * q + 1]);
+}
+
+template <bool BATCH>
+__device__ __forceinline__ void gj_idct_region_body(const gj_geom& g, const gj_geom& gr, const gj_region_frame& r, const int16_t* __restrict__ coefs,
+                                                    const float* __restrict__ qtab, uint8_t* __restrict__ planes)
+{
+    const unsigned gb = blockIdx.x * 256u + threadIdx.x;
+    if (gb >= (unsigned)gr.block_count) return;
+    if (r.scale > 1) return; // (a prescaled frame of a crop-and-resize call: k_idct_region_scaled, k_idct_region_scaled_comp -- whole or per component)
+    unsigned bx, by;
+    const int c = gj_block_of(gr, gb, bx, by);
+    const gj_comp_geom& k = gr.comp[c];
+    if (BATCH && (bx >= (unsigned)(r.bx1[c] - r.bx0[c]) || by >= (unsigned)(r.by1[c] - r.by0[c]))) return;
+    const gj_comp_geom& kf = g.comp[c];
+    const unsigned fbx = (unsigned)r.bx0[c] + bx, fby = (unsigned)r.by0[c] + by;
+    if (fbx >= (unsigned)kf.blocks_x || fby >= (unsigned)kf.blocks_y) return; // (cannot happen: the cover lies inside the component's grid)
+    gj_idct_region_block(coefs + kf.data_offset + ((size_t)fby * kf.blocks_x + fbx) * 64, qtab + kf.q_table * 64,
+                         planes + k.data_offset + (size_t)by * 8 * k.data_width + bx * 8, (size_t)k.data_width);
 }
 
 __global__ __launch_bounds__(256) void k_idct_region(const gj_geom g, const gj_geom gr, const gj_region r, const int16_t* __restrict__ coefs,
@@ -278,22 +286,13 @@ __global__ __launch_bounds__(256) void k_idct_region_batch(const gj_geom g, cons
 // corner of the block, gj_dequant_clamp with the uint16 table, gj_idct_corner<N> -- at (bx N, by N) of the component's REDUCED cover plane, laid out
 // like k_idct_scaled's reduced planes inside the slot of the full-size ones: pitch data_width N / 8, offset data_offset N N / 64 (data_offset is a
 // multiple of 64, data_width of 8, the slot's base of 64: rows of N bytes are N-byte aligned). Reads and writes stay inside the frame's own cover.
-template <int N, bool BATCH>
-__device__ __forceinline__ void gj_idct_region_scaled_body(const gj_geom& g, const gj_geom& gr, const gj_region_frame& r, const int16_t* __restrict__ coefs,
-                                                           const uint16_t* __restrict__ qtab, uint8_t* __restrict__ planes)
+// one block: the N x N corner of its coefficients at blk (uint16 table q of its component) -> block (bx, by) of component k's reduced cover plane
+template <int N>
+__device__ __forceinline__ void gj_idct_region_scaled_block(const gj_comp_geom& k, const unsigned bx, const unsigned by, const int16_t* __restrict__ blk,
+                                                            const uint16_t* __restrict__ q, uint8_t* __restrict__ planes)
 {
-    const unsigned gb = blockIdx.x * 256u + threadIdx.x;
-    if (gb >= (unsigned)gr.block_count) return;
-    unsigned bx, by;
-    const int c = gj_block_of(gr, gb, bx, by);
-    const gj_comp_geom& k = gr.comp[c];
-    if (BATCH && (bx >= (unsigned)(r.bx1[c] - r.bx0[c]) || by >= (unsigned)(r.by1[c] - r.by0[c]))) return;
-    const gj_comp_geom& kf = g.comp[c];
-    const unsigned fbx = (unsigned)r.bx0[c] + bx, fby = (unsigned)r.by0[c] + by;
-    if (fbx >= (unsigned)kf.blocks_x || fby >= (unsigned)kf.blocks_y) return; // (cannot happen: the cover lies inside the component's grid)
     int D[N * N];
-    gj_corner_from_plane<N>(coefs + kf.data_offset + ((size_t)fby * kf.blocks_x + fbx) * 64, D);
-    const uint16_t* q = qtab + kf.q_table * 64;
+    gj_corner_from_plane<N>(blk, D);
 #pragma unroll
     for (int v = 0; v < N; v++)
 #pragma unroll
@@ -310,12 +309,29 @@ __device__ __forceinline__ void gj_idct_region_scaled_body(const gj_geom& g, con
     }
 }
 
+template <int N, bool BATCH>
+__device__ __forceinline__ void gj_idct_region_scaled_body(const gj_geom& g, const gj_geom& gr, const gj_region_frame& r, const int16_t* __restrict__ coefs,
+                                                           const uint16_t* __restrict__ qtab, uint8_t* __restrict__ planes)
+{
+    const unsigned gb = blockIdx.x * 256u + threadIdx.x;
+    if (gb >= (unsigned)gr.block_count) return;
+    unsigned bx, by;
+    const int c = gj_block_of(gr, gb, bx, by);
+    const gj_comp_geom& k = gr.comp[c];
+    if (BATCH && (bx >= (unsigned)(r.bx1[c] - r.bx0[c]) || by >= (unsigned)(r.by1[c] - r.by0[c]))) return;
+    const gj_comp_geom& kf = g.comp[c];
+    const unsigned fbx = (unsigned)r.bx0[c] + bx, fby = (unsigned)r.by0[c] + by;
+    if (fbx >= (unsigned)kf.blocks_x || fby >= (unsigned)kf.blocks_y) return; // (cannot happen: the cover lies inside the component's grid)
+    gj_idct_region_scaled_block<N>(k, bx, by, coefs + kf.data_offset + ((size_t)fby * kf.blocks_x + fbx) * 64, qtab + kf.q_table * 64, planes);
+}
+
 // ONE launch for every scale: the frame's scale is the same in all lanes of a workgroup (blockIdx.z = frame), so the switch does not diverge; a
 // frame of scale 1 leaves (k_idct_region_batch transforms it). The figures of this choice: profiles/idct_side_resources.md.
 template <bool BATCH>
 __device__ __forceinline__ void gj_idct_region_scaled_switch(const gj_geom& g, const gj_geom& gr, const gj_region_frame& r, const int16_t* __restrict__ coefs,
                                                              const uint16_t* __restrict__ qtab, uint8_t* __restrict__ planes)
 {
+    if (r.per_comp) return; // (reduced per component: k_idct_region_scaled_comp)
     switch (r.scale) {
     case 2: gj_idct_region_scaled_body<4, BATCH>(g, gr, r, coefs, qtab, planes); break;
     case 4: gj_idct_region_scaled_body<2, BATCH>(g, gr, r, coefs, qtab, planes); break;
@@ -337,13 +353,62 @@ __global__ __launch_bounds__(256) void k_idct_region_scaled_batch(const gj_geom 
     gj_idct_region_scaled_switch<true>(g, gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, planes + z * g.fb.coefs);
 }
 
+// The same for a frame that is reduced PER COMPONENT (gj_region_frame::per_comp, dec_opt_resize_prescale_subsampled: a 4:2:0-like stream, sub_h == sub_v
+// in {1, 2}): component c's blocks leave N_c x N_c samples, N_c = 8 sub_h / scale -- at scale 2 luma 4 and chroma 8, at 4 luma 2 and chroma 4, at 8
+// luma 1 and chroma 2 --, so that every reduced plane has one sample per reduced pixel. N_c <= 4: the arithmetic above; N_c = 8: k_idct_region's
+// (gj_idct_pk with the float table), into the same place the full-size kernel writes. The planes lie where the formulas above put them with N_c for N;
+// the host admits only streams whose sub_h does not fall from one component to the next, for which those ranges do not overlap.
+// One lane per block of the cover, the blocks of a component one after the other (gj_block_of): N_c is the same in all lanes of a wave except in the
+// waves that hold the last blocks of one component and the first of the next -- at most comp_count - 1 = 2 waves per frame, which run two arms.
+// Every other frame leaves at entry (the same decision in all lanes of a workgroup: blockIdx.z = frame).
+template <bool BATCH>
+__device__ __forceinline__ void gj_idct_region_scaled_comp_body(const gj_geom& g, const gj_geom& gr, const gj_region_frame& r, const int16_t* __restrict__ coefs,
+                                                                const uint16_t* __restrict__ qtab, const float* __restrict__ qtabf, uint8_t* __restrict__ planes)
+{
+    if (!r.per_comp || r.scale < 2) return;
+    const unsigned gb = blockIdx.x * 256u + threadIdx.x;
+    if (gb >= (unsigned)gr.block_count) return;
+    unsigned bx, by;
+    const int c = gj_block_of(gr, gb, bx, by);
+    const gj_comp_geom& k = gr.comp[c];
+    if (BATCH && (bx >= (unsigned)(r.bx1[c] - r.bx0[c]) || by >= (unsigned)(r.by1[c] - r.by0[c]))) return;
+    const gj_comp_geom& kf = g.comp[c];
+    const unsigned fbx = (unsigned)r.bx0[c] + bx, fby = (unsigned)r.by0[c] + by;
+    if (fbx >= (unsigned)kf.blocks_x || fby >= (unsigned)kf.blocks_y) return; // (cannot happen: the cover lies inside the component's grid)
+    const int16_t* blk = coefs + kf.data_offset + ((size_t)fby * kf.blocks_x + fbx) * 64;
+    const uint16_t* q = qtab + kf.q_table * 64;
+    switch (8u * (unsigned)kf.sub_h / (unsigned)r.scale) { // N_c
+    case 8: gj_idct_region_block(blk, qtabf + kf.q_table * 64, planes + k.data_offset + (size_t)by * 8 * k.data_width + bx * 8, (size_t)k.data_width); break;
+    case 4: gj_idct_region_scaled_block<4>(k, bx, by, blk, q, planes); break;
+    case 2: gj_idct_region_scaled_block<2>(k, bx, by, blk, q, planes); break;
+    case 1: gj_idct_region_scaled_block<1>(k, bx, by, blk, q, planes); break;
+    default: break; // (cannot happen: sub_h is 1 or 2, scale 2, 4 or 8, and sub_h 2 comes with every scale)
+    }
+}
+
+__global__ __launch_bounds__(256) void k_idct_region_scaled_comp(const gj_geom g, const gj_geom gr, const gj_region r, const int16_t* __restrict__ coefs,
+                                                                 const uint16_t* __restrict__ qtab, const float* __restrict__ qtabf, uint8_t* __restrict__ planes)
+{
+    gj_idct_region_scaled_comp_body<false>(g, gr, r.frame, coefs, qtab, qtabf, planes);
+}
+
+__global__ __launch_bounds__(256) void k_idct_region_scaled_comp_batch(const gj_geom g, const gj_geom gr, const gj_region rb, const int16_t* __restrict__ coefs,
+                                                                       const uint16_t* __restrict__ qtab, const float* __restrict__ qtabf, uint8_t* __restrict__ planes)
+{
+    const size_t z = blockIdx.z;
+    gj_idct_region_scaled_comp_body<true>(g, gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, qtabf, planes + z * g.fb.coefs);
+}
+
 // sample of component c that pixel (x, y) of the REGION needs, in the cover-sized plane: pixel (r.x + x, r.y + y) of the stream's image
 // (N = 8, or with a prescale N = 8 / gj_region_frame::scale: the reduced cover plane of k_idct_region_scaled and pixel (x' + x, y' + y) of the reduced image)
+// (PER_COMP, a frame reduced per component: N = N_c, and the component's reduced plane has ONE sample per reduced pixel -- sample (x' + x, y' + y), no
+// division by sub_h / sub_v)
+template <bool PER_COMP = false>
 __device__ __forceinline__ size_t gj_region_sample(const gj_comp_geom& k, const gj_region_frame& r, const int c, const unsigned x, const unsigned y,
                                                    const unsigned N = 8u)
 {
-    const unsigned sx = ((unsigned)r.x + x) / (unsigned)k.sub_h - (unsigned)r.bx0[c] * N;
-    const unsigned sy = ((unsigned)r.y + y) / (unsigned)k.sub_v - (unsigned)r.by0[c] * N;
+    const unsigned sx = (PER_COMP ? (unsigned)r.x + x : ((unsigned)r.x + x) / (unsigned)k.sub_h) - (unsigned)r.bx0[c] * N;
+    const unsigned sy = (PER_COMP ? (unsigned)r.y + y : ((unsigned)r.y + y) / (unsigned)k.sub_v) - (unsigned)r.by0[c] * N;
     // (the cover holds them; its own size bounds them -- the planes of a frame of a batch are laid out for the largest cover, the frame's own may be smaller)
     const unsigned cw = (unsigned)(r.bx1[c] - r.bx0[c]) * N, ch = (unsigned)(r.by1[c] - r.by0[c]) * N;
     const size_t offset = N == 8u ? (size_t)k.data_offset : (size_t)(k.data_offset * (N * N) / 64), pitch = N == 8u ? (size_t)k.data_width : (size_t)k.data_width * N / 8;
@@ -430,9 +495,12 @@ __device__ __forceinline__ void gj_tensor_store(const gj_tensor& t, uint8_t* __r
 // (k_copy_planes_region: no colour stage) blends the samples as they are. Output formats whose pixels share no samples only (the host refuses the others).
 // TENSOR (gj_region::tensor, gpujpeg_amd_decoder_decode_batch_crop_resize_tensor): the same up to and including the blend; the channels of the blended pixel
 // then go to the frame's tensor as float(byte) * scale + bias in the call's element type and layout (gj_tensor_store) instead of to the pixel format's bytes.
-template <bool TENSOR>
-__device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const gj_region_frame& r, const gj_tensor& t, const uint8_t* __restrict__ planes,
-                                                      uint8_t* __restrict__ raw)
+// PER_COMP: a frame that is reduced per component (gj_region_frame::per_comp) -- the taps are the prescaled frame's, in reduced pixels with s; the sample
+// of component c comes from ITS reduced plane, N_c = N sub_h (gj_region_sample<true>). Behind a template parameter so that every other frame runs the
+// instructions it ran without it; the choice is the frame's, the same in every lane of a workgroup (gj_resize_region_body).
+template <bool TENSOR, bool PER_COMP>
+__device__ __forceinline__ void gj_resize_region_pixel(const gj_geom& gr, const gj_region_frame& r, const gj_tensor& t, const uint8_t* __restrict__ planes,
+                                                       uint8_t* __restrict__ raw)
 {
     const unsigned OW = (unsigned)gr.width, OH = (unsigned)gr.height;
     const unsigned pos = blockIdx.x * 256u + threadIdx.x;
@@ -451,7 +519,8 @@ __device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const g
 #pragma unroll
         for (int c = 0; c < GJ_MAX_COMP; c++) {
             if (c >= gr.comp_count) break;
-            v[q][c] = planes[gj_region_sample(gr.comp[c], r, c, (unsigned)sx[q & 1], (unsigned)sy[q >> 1], N)];
+            if (PER_COMP) v[q][c] = planes[gj_region_sample<true>(gr.comp[c], r, c, (unsigned)sx[q & 1], (unsigned)sy[q >> 1], N * (unsigned)gr.comp[c].sub_h)];
+            else v[q][c] = planes[gj_region_sample(gr.comp[c], r, c, (unsigned)sx[q & 1], (unsigned)sy[q >> 1], N)];
         }
         if (!gr.no_transform) gj_pixel_transform(gr, v[q]);
     }
@@ -460,6 +529,14 @@ __device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const g
     for (int ch = 0; ch < 4; ch++) o[ch] = gj_resize_blend(v[0][ch], v[1][ch], v[2][ch], v[3][ch], fx, fy);
     if (TENSOR) gj_tensor_store(t, raw, OW * OH, pos, o);
     else gj_pixel_store(gr, raw, OW, OH, i, j, pos, o);
+}
+
+template <bool TENSOR>
+__device__ __forceinline__ void gj_resize_region_body(const gj_geom& gr, const gj_region_frame& r, const gj_tensor& t, const uint8_t* __restrict__ planes,
+                                                      uint8_t* __restrict__ raw)
+{
+    if (r.per_comp) gj_resize_region_pixel<TENSOR, true>(gr, r, t, planes, raw);
+    else gj_resize_region_pixel<TENSOR, false>(gr, r, t, planes, raw);
 }
 
 __global__ __launch_bounds__(256) void k_resize_region(const gj_geom gr, const gj_region r, const uint8_t* __restrict__ planes, uint8_t* __restrict__ raw)
@@ -639,12 +716,17 @@ void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tok
         return;
     }
     // (crop-and-resize with a prescale: the frames of scale 1 through the full-size kernel, the others through the reduced-size one -- each launch
-    // only where the chunk has such frames, gj_region::scale_mask; every other region call: scale 1 alone)
+    // only where the chunk has such frames, gj_region::scale_mask; the frames that are reduced per component through the kernel of their own,
+    // gj_region::comp_mask; every other region call: scale 1 alone)
     const dim3 grid(((unsigned)gr.block_count + 255) / 256, 1, frames);
-    const unsigned scales = r.resize && r.scale_mask ? r.scale_mask : 1u;
+    const unsigned comp = r.resize ? r.comp_mask : 0u;
+    const unsigned scales = r.resize && (r.scale_mask || comp) ? r.scale_mask : 1u;
     if (scales & 1u) hipLaunchKernelGGL(batch ? k_idct_region_batch : k_idct_region, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtabf, job->d_planes);
     if (scales & ~1u)
         hipLaunchKernelGGL(batch ? k_idct_region_scaled_batch : k_idct_region_scaled, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtab, job->d_planes);
+    if (comp)
+        hipLaunchKernelGGL(batch ? k_idct_region_scaled_comp_batch : k_idct_region_scaled_comp, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtab,
+                           job->d_qtabf, job->d_planes);
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
     if (r.resize) { // crop-and-resize: gr is the output image's geometry
         const unsigned n = (unsigned)gr.width * (unsigned)gr.height;

@@ -65,10 +65,16 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
          ((uintptr_t)job->d_raw | (g.fb.sizes != nullptr ? (uintptr_t)job->gs.fb.raw : 0)) % GJ_TENSOR_ELSIZE(rg.tensor.dtype) != 0))
         return -1;
     // (a scale per frame, gj_region_frame::scale: inside a resize job alone -- dec_opt_resize_prescale --, one of 1, 2, 4, 8; gj_dec_job::scale stays 1)
-    if (rg.on && ((rg.scale_mask & ~(rg.resize ? 0xFu : 1u)) != 0 || (!rg_batch && rg.frame.scale > 1 && (!rg.resize || rg.scale_mask != (unsigned)rg.frame.scale)))) return -1;
+    // (... and the frames reduced per component, gj_region_frame::per_comp, in comp_mask instead: scales 2, 4, 8, inside a resize job alone; a single
+    // frame is in the mask of its kind alone)
+    if (rg.on && ((rg.scale_mask & ~(rg.resize ? 0xFu : 1u)) != 0 || (rg.comp_mask & ~(rg.resize ? 0xEu : 0u)) != 0 ||
+                  (!rg_batch && rg.frame.scale > 1 &&
+                   (!rg.resize || (rg.frame.per_comp ? rg.comp_mask : rg.scale_mask) != (unsigned)rg.frame.scale || (rg.frame.per_comp ? rg.scale_mask : rg.comp_mask) != 0u)) ||
+                  (!rg_batch && rg.frame.scale <= 1 && (rg.frame.per_comp || rg.comp_mask))))
+        return -1;
     // (a filter, gj_region::filter: one the pixel stage knows; the antialiased one inside a resize job alone and over frames of scale 1 alone)
     if (rg.on && rg.filter != GJ_RESIZE_FILTER_BILINEAR &&
-        (rg.filter != GJ_RESIZE_FILTER_ANTIALIAS || !rg.resize || (rg.scale_mask & ~1u) != 0 ||
+        (rg.filter != GJ_RESIZE_FILTER_ANTIALIAS || !rg.resize || (rg.scale_mask & ~1u) != 0 || rg.comp_mask != 0 ||
          (!rg_batch && (rg.frame.scale > 1 || rg.frame.w > GJ_RESIZE_AA_MAX_RATIO * job->gs.width || rg.frame.h > GJ_RESIZE_AA_MAX_RATIO * job->gs.height))))
         return -1;
     if (rg.on && (job->scale > 1 || job->flipped || (rg.select && (!rg.d_sel || !rg.h_sel_count || g.restart_interval <= 0)) ||

@@ -117,6 +117,9 @@ struct gpujpeg_decoder {
     /* dec_opt_resize_filter: the filter of crop-and-resize's resample (GJ_RESIZE_FILTER_BILINEAR, the default, or _ANTIALIAS). Read by that call alone,
      * into its rectangles' description like the prescale */
     int resize_filter;
+    /* dec_opt_resize_prescale_subsampled: 1 = the prescale reduces 4:2:0-like streams too, each component at its own N (gj_region_prescale). Read by that
+     * call alone, into its rectangles' description like the two above; no effect without a prescale */
+    int resize_prescale_subsampled;
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
@@ -1299,8 +1302,12 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         if (regions || job.scale > 1) job.gs.fb.sizes = B.d_sizes;
         if (regions) {
             job.region.d_frames = d->b_rgn + first + a;
-            job.region.scale_mask = 0; /* (which of the two IDCT kernels this chunk's frames need) */
-            for (uint32_t i = 0; i < B.count; i++) job.region.scale_mask |= (unsigned)d->bh_rgn[first + a + (int)i].scale;
+            job.region.scale_mask = job.region.comp_mask = 0; /* (which of the three IDCT kernels this chunk's frames need) */
+            for (uint32_t i = 0; i < B.count; i++) {
+                const gj_region_frame* rf = d->bh_rgn + first + a + (int)i;
+                if (rf->per_comp) job.region.comp_mask |= (unsigned)rf->scale;
+                else job.region.scale_mask |= (unsigned)rf->scale;
+            }
             job.region.h_sel_count = d->bh_found + (size_t)(first + a) * GJ_MAX_COMP;
         }
         job.d_jpeg = d_streams + (size_t)a * d_stride;
@@ -1494,12 +1501,15 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
     }
     memset(d->prescales, 1, (size_t)count);
     d->prescales_n = count;
-    struct dec_rects what = {.rects = rects, .mirror = mirror, .resize = {.out_w = out_width, .out_h = out_height, .prescale = d->resize_prescale, .filter = d->resize_filter}};
+    struct dec_rects what = {.rects = rects, .mirror = mirror, .resize = {.out_w = out_width, .out_h = out_height, .prescale = d->resize_prescale, .filter = d->resize_filter,
+                                                                                   .subsampled = d->resize_prescale_subsampled}};
     if (tensor) what.resize.tensor = *tensor;
     int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
-    if (rc == 0) { /* (slot [4] of the kernel times, gpujpeg_amd_ext.h: 6 when any frame of the call was prescaled, whichever launch came last) */
+    if (rc == 0) { /* (slot [4] of the kernel times, gpujpeg_amd_ext.h: 6 when any frame of the call was prescaled -- 8 when per component: the call's
+                      streams share one header, the coder's geometry --, whichever launch came last) */
+        const float path = what.resize.subsampled && gj_geom_prescale_per_component(&d->coder.geom) ? 8.0f : 6.0f;
         for (int f = 0; f < count; f++)
-            if (d->prescales[f] > 1) { d->coder.kernel_ms[4] = 6.0f; break; }
+            if (d->prescales[f] > 1) { d->coder.kernel_ms[4] = path; break; }
     } else {
         d->prescales_n = 0;
     }
@@ -1691,6 +1701,12 @@ int gpujpeg_decoder_set_option(struct gpujpeg_decoder* d, const char* opt, const
         GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_RESIZE_FILTER " (" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_BILINEAR " or " GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_ANTIALIAS ")\n", val);
         return GPUJPEG_ERROR;
     }
+    if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE_SUBSAMPLED) == 0) { /* read by gpujpeg_amd_decoder_decode_batch_crop_resize (and _tensor) alone */
+        if (strcmp(val, GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_OFF) == 0) { d->resize_prescale_subsampled = 0; return GPUJPEG_NOERR; }
+        if (strcmp(val, GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_ON) == 0) { d->resize_prescale_subsampled = 1; return GPUJPEG_NOERR; }
+        GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE_SUBSAMPLED " (" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_OFF " or " GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_ON ")\n", val);
+        return GPUJPEG_ERROR;
+    }
     if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_REGION) == 0) { /* syntax only: the decode call checks the region against its stream */
         if (strcmp(val, "full") == 0) { d->region_on = false; return GPUJPEG_NOERR; }
         long v[4];
@@ -1723,6 +1739,7 @@ void gpujpeg_decoder_print_options(void)
     printf("\t" GPUJPEG_AMD_DEC_OPT_SCALE "=[1|1/2|1/4|1/8] - decode to a reduced-size image (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE "=[1|1/2|1/4|1/8] - largest reduced-size IDCT crop-and-resize may put ahead of its resample (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_FILTER "=[" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_BILINEAR "|" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_ANTIALIAS "] - filter of crop-and-resize's resample: four taps, or a footprint that grows with the reduction (MI355X extension)\n");
+    printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE_SUBSAMPLED "=[" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_OFF "|" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_ON "] - let that prescale reduce 4:2:0 streams too, each component at its own N (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_REGION "=[X,Y,W,H|full] - decode the W x H pixels at (X, Y) only (MI355X extension)\n");
 }
 

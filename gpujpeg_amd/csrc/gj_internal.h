@@ -56,14 +56,20 @@ int gj_geom_init_resized(gj_geom* go, const gj_geom* cover, const struct gpujpeg
  * that plan applied to what gj_geom_init_region + gj_geom_init_resized made for the caller's rectangle `rect` (s > 1: the expanded cover, the frame's record;
  * r->tensor is kept and the new geometry sized with it) */
 int gj_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const int rect[4], int out_w, int out_h, int max_scale, int out[5]);
+/* (subsampled: dec_opt_resize_prescale_subsampled -- non-zero: a stream gj_geom_prescale_per_component accepts is planned like an all-1x1 one and its
+ * frames of s > 1 are reduced per component, gj_region_frame::per_comp) */
 int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
-                       const int rect[4], int out_w, int out_h, int max_scale, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
+                       const int rect[4], int out_w, int out_h, int max_scale, int subsampled, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
+/* 1 for a stream dec_opt_resize_prescale_subsampled reduces per component: every component sub_h == sub_v in {1, 2}, at least one 2, and no
+ * component less subsampled than the one ahead of it (the reduced planes lie at data_offset N_c^2 / 64: they would overlap otherwise) */
+int gj_geom_prescale_per_component(const gj_geom* full);
 /* the ONE plan of a region call, single frame or frame f of a batch: the three steps above in that order (resize == NULL: a plain region, the first
  * step alone), r->resize / frame.mirror / tensor set, and r->sel_count[sc] = restart segments of scan sc that touch the cover (0 without a restart
  * interval). -1: the rectangle was refused, -2: the resize was; either with the step's own message */
-struct gj_resize { int out_w, out_h, mirror, prescale; gj_tensor tensor; int filter; }; /* prescale: dec_opt_resize_prescale; tensor.on = 0: the bytes of the pixel format;
+struct gj_resize { int out_w, out_h, mirror, prescale; gj_tensor tensor; int filter; int subsampled; }; /* prescale: dec_opt_resize_prescale; tensor.on = 0: the bytes of the pixel format;
                                                                                            filter: dec_opt_resize_filter (GJ_RESIZE_FILTER_*; antialias: -3 with a message
-                                                                                           for a rectangle more than 256 times the output along an axis, or with a prescale) */
+                                                                                           for a rectangle more than 256 times the output along an axis, or with a prescale);
+                                                                                           subsampled: dec_opt_resize_prescale_subsampled (0 / 1) */
 int gj_region_plan(gj_geom* gr, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
                    const int rect[4], const struct gj_resize* resize, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
 

@@ -630,7 +630,8 @@ class Decoder:
 
     def prescales(self):
         """gpujpeg_amd_decoder_get_prescales: the scale s_f (1, 2, 4, 8) every frame of the last decode_batch_crop_resize call took ahead of its resample
-        (set_option("dec_opt_resize_prescale", "1/8") allows up to 8); [] when there was no such call or it failed"""
+        (set_option("dec_opt_resize_prescale", "1/8") allows up to 8; 4:2:0 streams take one only with set_option("dec_opt_resize_prescale_subsampled",
+        "on")); [] when there was no such call or it failed"""
         cap = 65536
         a = (C.c_uint8 * cap)()
         n = self.lib.L.gpujpeg_amd_decoder_get_prescales(self.h, a, cap)
@@ -672,7 +673,8 @@ class Decoder:
     def idct_path(self):
         """IDCT side of the last perf_stats call: 0 full size, 1 reduced size from the coefficient planes, 2 reduced size from tokens,
         3 region from the coefficient planes, 4 region from tokens, 5 region resampled from the cover planes (crop-and-resize), 6 the same with a frame
-        reduced ahead of the resample (dec_opt_resize_prescale), 7 region resampled with the antialiased filter (dec_opt_resize_filter=antialias)"""
+        reduced ahead of the resample (dec_opt_resize_prescale), 7 region resampled with the antialiased filter (dec_opt_resize_filter=antialias),
+        8 as 6 with a frame of a 4:2:0 stream reduced per component (dec_opt_resize_prescale_subsampled=on)"""
         ms = (C.c_float * 8)()
         if self.lib.L.gpujpeg_amd_decoder_get_kernel_times(self.h, ms) != 0:
             return None

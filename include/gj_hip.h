@@ -278,6 +278,10 @@ typedef struct gj_region_frame {
      * src_w = w, src_h = h, offsets 0 (gj_geom_init_region). */
     int scale;                     /* 1, 2, 4 or 8 */
     int src_w, src_h, off_x, off_y;
+    /* ... with dec_opt_resize_prescale_subsampled on a stream gj_geom_prescale_per_component accepts (4:2:0): 1 = the frame is reduced PER COMPONENT --
+     * component c's blocks leave N_c x N_c samples, N_c = 8 sub_h / scale (1, 2, 4 or 8: the full-size IDCT), so that every reduced plane has one
+     * sample per reduced pixel (k_idct_region_scaled_comp; k_resize_region reads sample x' + x, no division by sub_h). 0: every other frame */
+    int per_comp;
 } gj_region_frame;
 /* Tensor output of crop-and-resize (gpujpeg_amd_decoder_decode_batch_crop_resize_tensor): the pixel stage stores, in place of the bytes of the pixel
  * format, element (c, j, i) = convert(float(byte) * scale[c] + bias[c]) -- two binary32 operations, each rounded to nearest even, never fused; the
@@ -314,6 +318,9 @@ typedef struct gj_region {
     /* ... and the scales (gj_region_frame::scale) among the frames of this launch, bit log2(scale): k_idct_region serves the frames of scale 1,
      * k_idct_region_scaled the others; a launch without frames for one of them is left out. Anything but 1 outside a resize job is refused. */
     unsigned scale_mask;
+    /* ... and the scales among the frames of this launch that are reduced per component (gj_region_frame::per_comp; they are NOT in scale_mask):
+     * k_idct_region_scaled_comp serves them, and is left out where there are none. Anything but 0 outside a resize job is refused. */
+    unsigned comp_mask;
     /* ... and what the pixel stage of a resize job stores: tensor.on = 0 the bytes of gs's pixel format (k_resize_region), 1 the tensor
      * (k_resize_region_tensor; gs.raw_size is then the tensor's size) */
     gj_tensor tensor;
@@ -380,7 +387,8 @@ typedef struct gj_dec_job {
     gj_geom gs;
     int* idct_path;                /* host, may be NULL: which IDCT side ran -- 0 full size, 1 k_idct_scaled, 2 k_idct_tok_scaled_rgb444, 3 k_idct_region, 4 k_idct_tok_region_rgb444,
                                       5 k_idct_region + k_resize_region (crop-and-resize), 6 the same with a frame through k_idct_region_scaled (dec_opt_resize_prescale),
-                                      7 k_idct_region + k_resize_region_aa (dec_opt_resize_filter = antialias) */
+                                      7 k_idct_region + k_resize_region_aa (dec_opt_resize_filter = antialias),
+                                      8 5 with a frame through k_idct_region_scaled_comp (dec_opt_resize_prescale_subsampled) */
     /* region decode (dec_opt_region, region.on): the entropy decoders work on g -- with region.select on the compacted table --, the IDCT side
      * transforms the cover's blocks -- from tokens straight into d_raw, or into cover-sized planes in d_planes from which the region's pixels go to d_raw --; gs is the geometry of the W x H image
      * with the cover's planes (gj_geom_init_region). No scale, no flip. A single frame, or (region.d_frames) a batch of frames with one

@@ -116,6 +116,37 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
  * than the output. Read by that call alone (its definition with a prescale: below); every other call, and that call with "1", is what it is without
  * the option. Another value is refused by gpujpeg_decoder_set_option and leaves the setting as it was. dec_opt_scale itself stays refused by the call. */
 #define GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE "dec_opt_resize_prescale"
+/* Decoder option "dec_opt_resize_prescale_subsampled" = "off" (default) or "on": lets that prescale reduce 4:2:0 streams too -- the streams of
+ * photographs --, each component at its own N, the way libjpeg's scaled decode does. Read by gpujpeg_amd_decoder_decode_batch_crop_resize and
+ * gpujpeg_amd_decoder_decode_batch_crop_resize_tensor alone; it holds from the next call on and may be changed between two calls of a decoder. Another
+ * value is refused by gpujpeg_decoder_set_option (GPUJPEG_ERROR) and leaves the setting as it was. It has an effect only together with a
+ * dec_opt_resize_prescale other than 1; with "off" every byte, counter, launch and kernel-times slot of every call is what it is without the option.
+ * WITH "on". Take sub_h, sub_v of a component as the largest horizontal (vertical) sampling factor of the stream divided by the component's. A stream is
+ * ELIGIBLE when every component has sub_h == sub_v in {1, 2}, at least one has 2, and no component has a smaller sub_h than the component ahead of
+ * it: 4:2:0, and Y sampled 2 x 2 followed by further 2 x 2 components and then by 1 x 1 ones, in the stream's order (sub_h 1 ... 1 2 ... 2). [The last condition
+ * is this library's: the reduced planes below lie inside the slots of the full-size ones and would overlap in another order.] A frame of an eligible
+ * stream takes s_f by the rule of the streams whose components are all 1 x 1 (below; gpujpeg_amd_host_crop_resize_plan with all_components_1x1 != 0). Every
+ * other subsampled stream keeps s_f = 1: 4:2:2, 4:4:0, 4:1:1, anything with a factor of 4 or sub_h != sub_v (no rectangular reduced IDCT).
+ * For s = s_f > 1, Rs of the definition below is the ceil(W / s) x ceil(H / s) image built like this. Component c has t_c = sub_h and N_c = 8 t_c / s, one of
+ * 1, 2, 4, 8; sample (X, Y) of its reduced plane is
+ *     N_c <= 4:  sample (X mod N_c, Y mod N_c) of block (X / N_c, Y / N_c) under the transform of dec_opt_scale with N = N_c (gj_dequant_clamp with the
+ *                uint16 table, then the N_c-point IDCT of the block's N_c x N_c corner: DESIGN "Reduced-size decode")
+ *     N_c = 8:   sample (X, Y) of the component's plane of the full-size decode (the float IDCT of k_idct_region, with the FMA-parity caveat it carries)
+ * and pixel (X, Y) of Rs is made from the components' samples at (X, Y) exactly as a pixel of a stream whose components are all 1 x 1: the same colour
+ * transform, the same expansion of a single component, the same no_transform rule. Every plane has one sample per reduced pixel: at s = 2 a 4:2:0
+ * stream's chroma goes through the full-size IDCT and its luma through N = 4, at s = 8 luma takes N = 1 and chroma N = 2. Blocks line up: reduced pixel
+ * X covers the full-size pixels [sX, sX + s), the samples of block X / N_c of every component.
+ * From there x', w', C', the taps, the blend, the mirror, the output formats and the tensor store are the text below, word for word, and so is the
+ * cover: the region call's for the covering rectangle expanded to full size; reduced sample X of component c lies in block X / N_c of it.
+ *   Refusals:  all unchanged.    Antialias:  dec_opt_resize_filter = antialias together with a prescale stays refused.
+ *   Prescales: gpujpeg_amd_decoder_get_prescales reports s_f.
+ *   Planes:    gpujpeg_amd_decoder_read_planes returns the reduced cover planes with N_c per component: component c at offset data_offset N_c^2 / 64 with
+ *              pitch data_width N_c / 8 of the cover plane's.
+ *   Slot [4] of gpujpeg_amd_decoder_get_kernel_times is 8 after a call in which at least one frame was reduced per component (k_idct_region_scaled_comp);
+ *              it stays 6 when only frames of all-1 x 1 streams were reduced, and 5 when none was. */
+#define GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE_SUBSAMPLED "dec_opt_resize_prescale_subsampled"
+#define GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_OFF "off"
+#define GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_ON "on"
 /* Decoder option "dec_opt_resize_filter" = "bilinear" (default) or "antialias": the filter of the resample of
  * gpujpeg_amd_decoder_decode_batch_crop_resize and gpujpeg_amd_decoder_decode_batch_crop_resize_tensor. Read by those two calls alone; it holds from the
  * next call on and may be changed between two calls of a decoder. Another value is refused by gpujpeg_decoder_set_option (GPUJPEG_ERROR) and leaves the
@@ -156,7 +187,8 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_optimal(const uint32_t freq[256], uint8
  *          gpujpeg_amd_decoder_decode_batch_regions leaves the side its batched launches took here (3 or 4) and no durations, and so do
  *          6 the same with at least one frame of the call reduced ahead of the resample (k_idct_region_scaled: dec_opt_resize_prescale);
  *          gpujpeg_amd_decoder_decode_batch with a dec_opt_scale (1 or 2) and gpujpeg_amd_decoder_decode_batch_crop_resize (5, 6 or 7);
- *          7 region resampled from the cover planes with the antialiased filter (k_idct_region + k_resize_region_aa: dec_opt_resize_filter = antialias) */
+ *          7 region resampled from the cover planes with the antialiased filter (k_idct_region + k_resize_region_aa: dec_opt_resize_filter = antialias);
+ *          8 as 6 with at least one frame reduced per component (k_idct_region_scaled_comp: dec_opt_resize_prescale_subsampled) */
 GPUJPEG_API int gpujpeg_amd_encoder_get_kernel_times(struct gpujpeg_encoder* encoder, float ms[8]);
 GPUJPEG_API int gpujpeg_amd_decoder_get_kernel_times(struct gpujpeg_decoder* decoder, float ms[8]);
 
@@ -247,7 +279,8 @@ GPUJPEG_API int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder*
  * [4] of gpujpeg_amd_decoder_get_kernel_times is 5.
  * WITH dec_opt_resize_prescale = 1/S. Frame f with rectangle (x, y, w, h) takes the scale s_f = the largest s of 1, 2, 4, 8 with s <= S, w >= s OW and
  * h >= s OH (the bilinear step then reduces by less than 2 per axis); s_f = 1 for a stream with a component whose sampling is not 1 x 1 (dec_opt_scale
- * reduces subsampled chroma by the same N as luma: at 1/8 one sample per 16 x 16 pixels, worse than no prescale). With s_f = 1 the frame is as above.
+ * reduces subsampled chroma by the same N as luma: at 1/8 one sample per 16 x 16 pixels, worse than no prescale; dec_opt_resize_prescale_subsampled = on reduces 4:2:0 per component instead: see the
+ * option). With s_f = 1 the frame is as above.
  * With s = s_f > 1 let Rs be the image gpujpeg_decoder_decode of this decoder returns for stream f with dec_opt_scale = 1/s, and
  *     x' = x / s;  w' = ceil((x + w) / s) - x';  y', h' likewise;  C' = the w' x h' crop of Rs at (x', y')  (inside Rs because x + w <= W)
  *     d  = 2 OW s;  nx = max((2 i + 1) w + 2 OW (x - s x') - OW s, 0);  x0 = nx / d;  fx = ((nx - x0 d) 256) / d;  x1 = min(x0 + 1, w' - 1)
@@ -296,7 +329,8 @@ GPUJPEG_API uint32_t gpujpeg_amd_host_tensor_element(const struct gpujpeg_amd_te
 /* Host-only: scale and covering rectangle dec_opt_resize_prescale gives ONE frame of a crop-and-resize call -- rect = x, y, w, h in an
  * image_w x image_h image whose components are (all_components_1x1 != 0) or are not all sampled 1 x 1, output out_w x out_h, max_scale = S (1, 2, 4, 8).
  * Writes out = s, x', y', w', h' (the definition above; the code the call itself runs) and returns 0, or -1 where the call would refuse: a rectangle
- * with w or h < 1 or not inside the image, an output size outside 1 .. 16384, another max_scale. */
+ * with w or h < 1 or not inside the image, an output size outside 1 .. 16384, another max_scale. Callers pass all_components_1x1 != 0 as well for a
+ * stream that is eligible under dec_opt_resize_prescale_subsampled = on (above): its frames take the same plan. */
 GPUJPEG_API int gpujpeg_amd_host_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const int rect[4], int out_w, int out_h, int max_scale,
                                                   int out[5]);
 /* Host-only: the taps dec_opt_resize_filter = antialias gives output sample i (0 .. n_out - 1) along one axis of n_src source samples resampled to

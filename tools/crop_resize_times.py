@@ -14,10 +14,14 @@ synchronise; the figure of a point is the MEDIAN of its rounds:
     d        the crop-and-resize call with every rectangle 224 x 224 (c's rectangles): against c, the resample stage, the plane route and per-frame covers
     e        a with dec_opt_resize_prescale=1/8: the reduced-size IDCT ahead of the resample wherever the rectangle is at least twice the output
              (the share of frames per scale that the seed draws is in the report: scale_share)
+    f        e with dec_opt_resize_prescale_subsampled=on: on 4:2:0 streams (--sampling 420) the prescale per component; on 4:4:4 streams it is e
+    g        a with dec_opt_resize_filter=antialias, for reference
     a2       a once more: the difference to a is the spread every other difference has to beat
+             (--sampling 420: e is a as well -- the prescale leaves 4:2:0 streams alone without f's option --, so a, e and a2 are three repeats of today's call)
 
     python tools/crop_resize_times.py --out profiles/crop_resize.json [--calls 20]
     rocprofv3 --kernel-trace --stats -d DIR -o NAME -- python tools/crop_resize_times.py --trace a      (kernel durations of ONE point; 256 x HD, a few calls)
+    python tools/crop_resize_times.py --sampling 420 --points a,e,f,g,a2 --out profiles/crop_resize_420.json      (interleaved 4:2:0 streams)
     python tools/crop_resize_times.py --lib OTHER/libgpujpeg.so --points a,a2 --workloads hd          (another build of the library, some points: A/B runs
                                                                                                      alternate two such processes)
 
@@ -66,11 +70,13 @@ def random_resized_crops(w, h, n, seed, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0
 class Point:
     """one decoder and one way to get the frames; run(n) times n passes over the frames as one round"""
 
-    def __init__(self, name, kind, lib, d_in, stride, sizes, rects, mirror, prescale=None):
+    def __init__(self, name, kind, lib, d_in, stride, sizes, rects, mirror, prescale=None, options=()):
         self.name, self.kind, self.lib = name, kind, lib
         self.dec = G.Decoder(lib)
         if prescale:
             assert self.dec.set_option("dec_opt_resize_prescale", prescale) == 0
+        for opt, val in options:
+            assert self.dec.set_option(opt, val) == 0, (opt, val)
         self.d_in, self.stride, self.sizes = d_in, stride, sizes
         self.rects, self.mirror = rects, mirror
         self.raw = OUT * OUT * 3
@@ -109,8 +115,9 @@ class Point:
         if self.kind != "b":
             r["last_batch"] = list(self.dec.last_batch())
             r["region_stats"] = list(self.dec.region_stats())
-        if self.kind == "e":
+        if self.kind in ("e", "f"):
             r["idct_side"] = self.dec.idct_path()
+            r["prescaled_frames"] = sum(1 for s in self.dec.prescales() if s > 1)
         return r
 
 
@@ -119,11 +126,13 @@ def points_for(lib, d_in, stride, sizes, w, h, seed, which):
     rng = np.random.default_rng(seed + 1)
     fixed = [(int(rng.integers(0, w - OUT + 1)), int(rng.integers(0, h - OUT + 1)), OUT, OUT) for _ in range(FRAMES)]
     mirror = [f & 1 for f in range(FRAMES)]
-    mk = lambda name, kind, rc, mir, pre=None: Point(name, kind, lib, d_in, stride, sizes, rc, mir, pre)  # noqa: E731
+    mk = lambda name, kind, rc, mir, pre=None, opts=(): Point(name, kind, lib, d_in, stride, sizes, rc, mir, pre, opts)  # noqa: E731
     makers = {"a": lambda: mk("a_crop_resize", "a", rects, mirror), "b": lambda: mk("b_single_region_calls", "b", rects, None),
               "c": lambda: mk("c_batch_regions_224", "c", fixed, None), "d": lambda: mk("d_crop_resize_224_rectangles", "d", fixed, None),
-              "e": lambda: mk("e_crop_resize_prescale_8", "e", rects, mirror, "1/8"), "a2": lambda: mk("a2_crop_resize_again", "a", rects, mirror)}
-    return [makers[k]() for k in ("a", "b", "c", "d", "e", "a2") if k in which], rects
+              "e": lambda: mk("e_crop_resize_prescale_8", "e", rects, mirror, "1/8"), "a2": lambda: mk("a2_crop_resize_again", "a", rects, mirror),
+              "f": lambda: mk("f_crop_resize_prescale_8_subsampled", "f", rects, mirror, "1/8", (("dec_opt_resize_prescale_subsampled", "on"),)),
+              "g": lambda: mk("g_crop_resize_antialias", "g", rects, mirror, None, (("dec_opt_resize_filter", "antialias"),))}
+    return [makers[k]() for k in ("a", "b", "c", "d", "e", "f", "g", "a2") if k in which], rects
 
 
 def main():
@@ -133,20 +142,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--workloads", default="hd,4k")
-    ap.add_argument("--trace", default=None, metavar="POINT", help="a, b, c, d or e: 256 x HD, a few calls of that point alone and no report -- for a kernel trace")
+    ap.add_argument("--trace", default=None, metavar="POINT", help="a, b, c, d, e, f or g: 256 x HD, a few calls of that point alone and no report -- for a kernel trace")
     ap.add_argument("--points", default="a,b,c,d,e,a2", help="the points to measure (a library without dec_opt_resize_prescale: leave e out)")
+    ap.add_argument("--sampling", default="444", choices=["444", "420"], help="the streams: non-interleaved 4:4:4, or interleaved 4:2:0")
     ap.add_argument("--lib", default=None, help="another build of the library (A/B runs)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
     device = torch.device("cuda:0")
     lib = G.Library(args.lib)
     assert lib.L.gpujpeg_init_device(0, 0) == 0
-    report = {"frames": FRAMES, "streams": "RGB 4:4:4 q75 non-interleaved, restart auto", "output": [OUT, OUT], "calls_per_point": args.calls,
+    report = {"frames": FRAMES, "streams": "RGB 4:4:4 q75 non-interleaved, restart auto" if args.sampling == "444" else "RGB 4:2:0 q75 interleaved, restart auto", "output": [OUT, OUT], "calls_per_point": args.calls,
               "rounds": args.rounds, "workloads": {}}
     for wname, w, h in WORKLOADS:
         if wname not in args.workloads.split(",") or (args.trace and wname != "hd"):
             continue
-        d_in, stride, sizes = encode_frames(lib, w, h, device)
+        d_in, stride, sizes = encode_frames(lib, w, h, device, args.sampling)
         pts, rects = points_for(lib, d_in, stride, sizes, w, h, w + OUT, [args.trace] if args.trace else args.points.split(","))
         out = {"size": [w, h], "stream_bytes_mean": int(np.mean(sizes)), "rectangle_area_share_mean": round(float(np.mean([r[2] * r[3] for r in rects])) / (w * h), 4)}
         if hasattr(lib.L, "gpujpeg_amd_host_crop_resize_plan"):  # (frames per scale that dec_opt_resize_prescale=1/8 gives these rectangles)

@@ -50,12 +50,15 @@ def natural_frame(w, h, seed, device):
     return torch.stack(chans, -1).contiguous()
 
 
-def encode_frames(lib, w, h, device):
-    """FRAMES streams with one header in one device buffer -> (tensor, stride, sizes)"""
+def encode_frames(lib, w, h, device, sampling="444"):
+    """FRAMES streams with one header in one device buffer -> (tensor, stride, sizes); sampling "420": interleaved 4:2:0 streams, what photographs are"""
     base = natural_frame(w, h, 1, device)
     frames = torch.stack([torch.roll(base, (37 * f, 101 * f), (0, 1)) for f in range(FRAMES)]).contiguous()
     p = lib.default_parameters()
     p.quality, p.restart_interval, p.verbose = 75, G.RESTART_AUTO, -1
+    if sampling == "420":
+        p.interleaved = 1
+        lib.L.gpujpeg_parameters_chroma_subsampling(C.byref(p), G.SUBSAMPLING_420)
     pi = lib.default_image_parameters()
     pi.width, pi.height = w, h
     enc = G.Encoder(lib)
