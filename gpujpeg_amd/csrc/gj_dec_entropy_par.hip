@@ -118,8 +118,10 @@ __device__ __forceinline__ uint32_t gj_decode_sub(const uint32_t* __restrict__ U
     return (bitpos - end_bit) | ((uint32_t)z << 5) | ((uint32_t)p << 11);
 }
 
-template <bool INTERLEAVED, int SUB_BYTES>
-__global__ __launch_bounds__(256) void k_huffman_decode_par(const gj_geom g, const uint8_t* __restrict__ jpeg, uint64_t jpeg_size,
+// (MIXED: a batch of frames of different image sizes -- segments, blocks and planes are frame blockIdx.z's own, gj_frame_geom; the strides between the
+// frames' buffers are the launch's)
+template <bool INTERLEAVED, int SUB_BYTES, bool MIXED = false>
+__global__ __launch_bounds__(256) void k_huffman_decode_par(const gj_geom g_launch, const uint8_t* __restrict__ jpeg, uint64_t jpeg_size,
                                                             const uint32_t* __restrict__ seg_pos, const uint32_t* __restrict__ seg_len,
                                                             const uint32_t* __restrict__ seg_index, const int seg_count_max,
                                                             const uint32_t* __restrict__ seg_count_ptr, const GjBatchPlan plan,
@@ -130,13 +132,14 @@ __global__ __launch_bounds__(256) void k_huffman_decode_par(const gj_geom g, con
     // hold only for short sub-sequences; nsub is clamped below all the same, so that a fault in this arithmetic cannot become a write
     // behind the per-sub-sequence arrays)
     constexpr int MAX_SUBS = GJ_PAR_CAP_U / SUB_BYTES + GJ_PAR_GMAX;
-    if (g.fb.sizes != nullptr) { // frame blockIdx.z of a batch: its stream, its table, its summary word, its coefficient planes
+    const gj_geom& g = gj_frame_geom<MIXED>(g_launch);
+    if (g_launch.fb.sizes != nullptr) { // frame blockIdx.z of a batch: its stream, its table, its summary word, its coefficient planes
         const size_t z = blockIdx.z;
-        jpeg += z * g.fb.jpeg;
-        jpeg_size = g.fb.sizes[z];
-        seg_pos += z * g.fb.seg; seg_len += z * g.fb.seg; seg_index += z * g.fb.seg;
+        jpeg += z * g_launch.fb.jpeg;
+        jpeg_size = g_launch.fb.sizes[z];
+        seg_pos += z * g_launch.fb.seg; seg_len += z * g_launch.fb.seg; seg_index += z * g_launch.fb.seg;
         if (seg_count_ptr) seg_count_ptr += z * (sizeof(gj_scan_summary) / 4);
-        coefs += z * g.fb.coefs;
+        coefs += z * g_launch.fb.coefs;
     }
     static_assert(MAX_SUBS <= GJ_PAR_MAX_BLOCKS, "the work list lives in the DC array");
     constexpr uint32_t SUB_BITS = SUB_BYTES * 8;
@@ -735,6 +738,12 @@ void gj_launch_huffman_par(const gj_dec_job* job, hipStream_t st)
                                 : (sub == 256 ? k_huffman_decode_par<false, 256> : sub == 128 ? k_huffman_decode_par<false, 128>
                                    : sub == 64 ? k_huffman_decode_par<false, 64> : sub == 32 ? k_huffman_decode_par<false, 32>
                                    : sub == 8 ? k_huffman_decode_par<false, 8> : k_huffman_decode_par<false, 16>);
+    // (frames of different image sizes, gj_frame_strides::geoms: the instantiations of the default sub-sequence sizes -- the host launches no such
+    // batch with the tuning aid's)
+    if (g.fb.geoms != nullptr) {
+        if (es) { gj_hip_note((int)hipErrorInvalidValue); return; }
+        kernel = g.interleaved ? k_huffman_decode_par<true, 32, true> : k_huffman_decode_par<false, GJ_PAR_SUB, true>;
+    }
     GjFold F = {nullptr, nullptr, 0, 0, 0, nullptr, nullptr};
     const bool fold = gj_par_folds_table(job);
     if (fold) {

@@ -2,6 +2,7 @@
 //
 //   gj_decode.hip               gj_hip_decode: picks the kernels of a frame and launches them
 //   gj_dec_markers.hip          k_marker_scan, k_marker_segments: segment table built on the device, summary for the host in pinned memory
+//                               k_gather_headers: the headers of a batch's streams to the host in one launch (dec_opt_batch_sizes = mixed)
 //   gj_dec_entropy_tok.hip      k_huffman_decode_tok: sub-sequence parallel entropy decoding into 16-bit TOKENS + one record per block
 //                               (the default for large non-interleaved frames)
 //   gj_dec_entropy_par.hip      k_huffman_decode_par: sub-sequence parallel entropy decoding into the coefficient planes (segments of any length)

@@ -45,6 +45,7 @@ struct GjScanBatch {
     const uint32_t* sizes;         // [frames] bytes of every stream
     uint64_t jpeg;                 // bytes between two streams
     uint32_t seg, scratch, maxlen; // words between the frames' tables, scratch areas (records, then lists) and longest-segment words
+    const gj_geom* geoms;          // frames of different image sizes (gj_frame_strides::geoms): every frame's geometry, else nullptr
 };
 
 // ITERS pieces of 4 KB per round (16 bytes per lane and piece), `rounds` rounds per workgroup
@@ -203,12 +204,17 @@ __global__ __launch_bounds__(256) void k_marker_scan(const uint8_t* __restrict__
     GJ_TRACE_M(2);
 }
 
-__global__ __launch_bounds__(256) void k_marker_table(const gj_geom g, const uint8_t* __restrict__ jpeg, const uint64_t begin, uint64_t size, const uint32_t part_bytes,
+// (MIXED: a batch of frames of different image sizes -- the scans' first segments and segment counts, and the bound of the table, are frame
+// blockIdx.z's own, gj_frame_geom)
+template <bool MIXED>
+__global__ __launch_bounds__(256) void k_marker_table(const gj_geom g_launch, const uint8_t* __restrict__ jpeg, const uint64_t begin, uint64_t size, const uint32_t part_bytes,
                                                       const uint32_t* __restrict__ recs, const uint32_t* __restrict__ lists, uint32_t* __restrict__ wg_maxlen /* host memory */,
                                                       gj_scan_summary* __restrict__ sum, gj_scan_summary* __restrict__ hsum /* host memory: what the host reads */,
                                                       uint32_t* __restrict__ seg_pos, uint32_t* __restrict__ seg_len, uint32_t* __restrict__ seg_index,
-                                                      const uint32_t max_segments, const GjScanBatch B)
+                                                      const uint32_t max_segments_launch, const GjScanBatch B)
 {
+    const gj_geom& g = gj_frame_geom<MIXED>(g_launch);
+    const uint32_t max_segments = MIXED ? min(max_segments_launch, (uint32_t)g.segment_count + GJ_MAX_COMP) : max_segments_launch;
     if (B.sizes != nullptr) {
         const size_t z = blockIdx.z;
         jpeg += z * B.jpeg;
@@ -458,12 +464,15 @@ extern "C" int gj_hip_find_segments_deferred(const gj_geom* g, const uint8_t* d_
 // the second launch of the scan: from gj_find_segments_impl, or later from gj_hip_decode (gj_scan_deferred)
 void gj_launch_marker_table(const gj_geom* g, const uint8_t* d_jpeg, const gj_scan_deferred* sc, const GjScanBatch& B, unsigned frames, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_marker_table, dim3(sc->wgs, 1, frames), dim3(256), 0, st, *g, d_jpeg, sc->begin, sc->size, sc->part_bytes, sc->recs, sc->lists, sc->h_maxlen_parts,
+    auto kern = B.geoms != nullptr ? k_marker_table<true> : k_marker_table<false>;
+    gj_geom gl = *g; // (the host's geometry carries no strides: the frames' records travel in it as they do for the other kernels, gj_frame_geom)
+    gl.fb.geoms = B.geoms;
+    hipLaunchKernelGGL(kern, dim3(sc->wgs, 1, frames), dim3(256), 0, st, gl, d_jpeg, sc->begin, sc->size, sc->part_bytes, sc->recs, sc->lists, sc->h_maxlen_parts,
                        sc->d_summary, sc->h_summary, sc->d_seg_pos, sc->d_seg_len, sc->d_seg_index, sc->max_segments + GJ_MAX_COMP, B);
 }
 void gj_launch_marker_table_deferred(const gj_dec_job* job, hipStream_t st)
 {
-    const GjScanBatch B = {nullptr, 0, 0, 0, 0};
+    const GjScanBatch B = {nullptr, 0, 0, 0, 0, nullptr};
     gj_launch_marker_table(&job->g, job->d_jpeg, &job->scan, B, 1, st);
     gj_debug_stage(job->tune.debug_sync != 0, st, "k_marker_table (deferred)");
 }
@@ -475,7 +484,7 @@ static int gj_find_segments_impl(const gj_geom* g, const uint8_t* d_jpeg, uint64
                                  const gj_tuning* tune, const gj_batch* batch, gj_scan_deferred* defer)
 {
     hipStream_t st = (hipStream_t)stream;
-    GjScanBatch B = {nullptr, 0, 0, 0, 0};
+    GjScanBatch B = {nullptr, 0, 0, 0, 0, nullptr};
     unsigned frames = 1;
     if (batch && batch->d_sizes != nullptr) { // (also a batch of one frame: its size comes from d_sizes like the others')
         if ((batch->jpeg & 15u) != 0 || batch->count > 65535u || batch->count < 1u) return -1;
@@ -484,6 +493,7 @@ static int gj_find_segments_impl(const gj_geom* g, const uint8_t* d_jpeg, uint64
         B.seg = batch->seg;
         B.scratch = batch->scratch;
         B.maxlen = batch->maxlen;
+        B.geoms = batch->d_geoms;
         frames = batch->count;
     }
     if (size <= begin || size > 0xFFFFFFF0ull) return -1;
@@ -525,6 +535,29 @@ static int gj_find_segments_impl(const gj_geom* g, const uint8_t* d_jpeg, uint64
     }
     gj_launch_marker_table(g, d_jpeg, &sc, B, frames, st);
     gj_debug_stage(tune->debug_sync != 0, st, "k_marker_table");
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The first n bytes of every stream of a batch, n bytes apart, straight into pinned host memory (what lies behind a stream's end: zero): one launch
+// and one wait bring the host the headers of a batch whose frames may differ in size (dec_opt_batch_sizes = mixed), where a copy per frame would
+// cost the call ~4 us each. Reads stay inside [0, sizes[z]) of stream z, writes inside [z n, (z + 1) n).
+__global__ __launch_bounds__(256) void k_gather_headers(const uint8_t* __restrict__ jpeg, const uint64_t stride, const uint32_t* __restrict__ sizes, const uint32_t n,
+                                                        uint8_t* __restrict__ out /* host memory */)
+{
+    const size_t z = blockIdx.z;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    out[z * n + i] = i < sizes[z] ? jpeg[z * stride + i] : (uint8_t)0;
+}
+
+extern "C" int gj_hip_gather_headers(const uint8_t* d_jpeg, uint64_t stride, const uint32_t* d_sizes, uint32_t frames, uint32_t n, uint8_t* h_out, gj_stream_t stream)
+{
+    if (frames < 1u || n < 1u) return -1;
+    for (uint32_t f = 0; f < frames; f += 32768u) { // (the grid's z dimension holds 65535)
+        const uint32_t m = frames - f < 32768u ? frames - f : 32768u;
+        hipLaunchKernelGGL(k_gather_headers, dim3((n + 255u) / 256u, 1, m), dim3(256), 0, (hipStream_t)stream, d_jpeg + (size_t)f * stride, stride, d_sizes + f, n,
+                           h_out + (size_t)f * n);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -152,19 +152,22 @@ void gj_launch_segment_select(const gj_dec_job* job, hipStream_t st)
 // selection leaves of the range is filled with null entries -- index 0xFFFFFFFF, length 0: a segment without blocks for both batchable entropy
 // decoders. One workgroup per frame walks the table in trips of its 1024 lanes and keeps the running count per scan (a ballot per scan and wave,
 // the waves' counts through LDS); what it found per scan goes to pinned host memory, where the host compares it with the frame's plan.
-__global__ __launch_bounds__(GJ_SEL_CHUNK) void k_segment_select_batch(const gj_geom g, const gj_region rb, const uint32_t* __restrict__ seg_pos,
+// (MIXED: frames of different image sizes, gj_frame_geom -- the predicate, the scans and the bound of the table are the frame's own)
+template <bool MIXED>
+__global__ __launch_bounds__(GJ_SEL_CHUNK) void k_segment_select_batch(const gj_geom g_launch, const gj_region rb, const uint32_t* __restrict__ seg_pos,
                                                                        const uint32_t* __restrict__ seg_len, const uint32_t* __restrict__ seg_index,
                                                                        const int seg_count_max, const uint32_t* __restrict__ seg_count_ptr,
                                                                        uint32_t* __restrict__ out, const uint32_t out_stride, uint32_t* __restrict__ h_found)
 {
     __shared__ uint32_t s_wave[GJ_MAX_COMP][GJ_SEL_CHUNK / GJ_WAVE];
     const size_t z = blockIdx.z;
-    seg_pos += z * g.fb.seg; seg_len += z * g.fb.seg; seg_index += z * g.fb.seg;
-    out += z * g.fb.seg;
+    const gj_geom& g = gj_frame_geom<MIXED>(g_launch);
+    seg_pos += z * g_launch.fb.seg; seg_len += z * g_launch.fb.seg; seg_index += z * g_launch.fb.seg;
+    out += z * g_launch.fb.seg;
     h_found += z * GJ_MAX_COMP;
     const gj_region_frame& r = rb.d_frames[z]; // (read where it lies: a copy indexed by component would live in scratch memory)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = min((int)seg_count_ptr[z * (sizeof(gj_scan_summary) / 4)], seg_count_max);
+    const int n = min((int)seg_count_ptr[z * (sizeof(gj_scan_summary) / 4)], MIXED ? min(seg_count_max, g.segment_count) : seg_count_max);
     uint32_t first[GJ_MAX_COMP], run[GJ_MAX_COMP];
     {
         uint32_t at = 0;
@@ -220,7 +223,8 @@ void gj_launch_segment_select_batch(const gj_dec_job* job, hipStream_t st)
     const gj_geom& g = job->g;
     const gj_region& r = job->region;
     const uint32_t stride = (uint32_t)g.segment_count + GJ_MAX_COMP;
-    hipLaunchKernelGGL(k_segment_select_batch, dim3(1, 1, job->batch.count), dim3(GJ_SEL_CHUNK), 0, st, g, r, job->d_seg_pos, job->d_seg_len, job->d_seg_index,
+    auto kern = g.fb.geoms != nullptr ? k_segment_select_batch<true> : k_segment_select_batch<false>;
+    hipLaunchKernelGGL(kern, dim3(1, 1, job->batch.count), dim3(GJ_SEL_CHUNK), 0, st, g, r, job->d_seg_pos, job->d_seg_len, job->d_seg_index,
                        job->seg_count, job->d_seg_count, r.d_sel, stride, r.h_sel_count);
 }
 
@@ -275,11 +279,13 @@ __global__ __launch_bounds__(256) void k_idct_region(const gj_geom g, const gj_g
 }
 
 // frame blockIdx.z of a batch of regions (the planes of a frame take as many bytes as its coefficients take elements at most)
+// (MIXED: frames of different image sizes -- the coefficient planes of frame z are laid out by ITS geometry, gj_frame_geom; the cover planes by gr)
+template <bool MIXED>
 __global__ __launch_bounds__(256) void k_idct_region_batch(const gj_geom g, const gj_geom gr, const gj_region rb, const int16_t* __restrict__ coefs,
                                                            const float* __restrict__ qtab, uint8_t* __restrict__ planes)
 {
     const size_t z = blockIdx.z;
-    gj_idct_region_body<true>(g, gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, planes + z * g.fb.coefs);
+    gj_idct_region_body<true>(gj_frame_geom<MIXED>(g), gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, planes + z * g.fb.coefs);
 }
 
 // The same for a frame dec_opt_resize_prescale reduces by s = 8 / N: block (bx, by) of the cover leaves the N x N samples of k_idct_scaled -- the
@@ -346,11 +352,12 @@ __global__ __launch_bounds__(256) void k_idct_region_scaled(const gj_geom g, con
     gj_idct_region_scaled_switch<false>(g, gr, r.frame, coefs, qtab, planes);
 }
 
+template <bool MIXED>
 __global__ __launch_bounds__(256) void k_idct_region_scaled_batch(const gj_geom g, const gj_geom gr, const gj_region rb, const int16_t* __restrict__ coefs,
                                                                   const uint16_t* __restrict__ qtab, uint8_t* __restrict__ planes)
 {
     const size_t z = blockIdx.z;
-    gj_idct_region_scaled_switch<true>(g, gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, planes + z * g.fb.coefs);
+    gj_idct_region_scaled_switch<true>(gj_frame_geom<MIXED>(g), gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, planes + z * g.fb.coefs);
 }
 
 // The same for a frame that is reduced PER COMPONENT (gj_region_frame::per_comp, dec_opt_resize_prescale_subsampled: a 4:2:0-like stream, sub_h == sub_v
@@ -392,11 +399,12 @@ __global__ __launch_bounds__(256) void k_idct_region_scaled_comp(const gj_geom g
     gj_idct_region_scaled_comp_body<false>(g, gr, r.frame, coefs, qtab, qtabf, planes);
 }
 
+template <bool MIXED>
 __global__ __launch_bounds__(256) void k_idct_region_scaled_comp_batch(const gj_geom g, const gj_geom gr, const gj_region rb, const int16_t* __restrict__ coefs,
                                                                        const uint16_t* __restrict__ qtab, const float* __restrict__ qtabf, uint8_t* __restrict__ planes)
 {
     const size_t z = blockIdx.z;
-    gj_idct_region_scaled_comp_body<true>(g, gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, qtabf, planes + z * g.fb.coefs);
+    gj_idct_region_scaled_comp_body<true>(gj_frame_geom<MIXED>(g), gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, qtabf, planes + z * g.fb.coefs);
 }
 
 // sample of component c that pixel (x, y) of the REGION needs, in the cover-sized plane: pixel (r.x + x, r.y + y) of the stream's image
@@ -721,11 +729,15 @@ void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tok
     const dim3 grid(((unsigned)gr.block_count + 255) / 256, 1, frames);
     const unsigned comp = r.resize ? r.comp_mask : 0u;
     const unsigned scales = r.resize && (r.scale_mask || comp) ? r.scale_mask : 1u;
-    if (scales & 1u) hipLaunchKernelGGL(batch ? k_idct_region_batch : k_idct_region, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtabf, job->d_planes);
+    const bool mixed = batch && job->g.fb.geoms != nullptr; // (frames of different image sizes: the instantiations that read every frame's own geometry)
+    auto idct_batch = mixed ? k_idct_region_batch<true> : k_idct_region_batch<false>;
+    auto scaled_batch = mixed ? k_idct_region_scaled_batch<true> : k_idct_region_scaled_batch<false>;
+    auto comp_batch = mixed ? k_idct_region_scaled_comp_batch<true> : k_idct_region_scaled_comp_batch<false>;
+    if (scales & 1u) hipLaunchKernelGGL(batch ? idct_batch : k_idct_region, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtabf, job->d_planes);
     if (scales & ~1u)
-        hipLaunchKernelGGL(batch ? k_idct_region_scaled_batch : k_idct_region_scaled, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtab, job->d_planes);
+        hipLaunchKernelGGL(batch ? scaled_batch : k_idct_region_scaled, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtab, job->d_planes);
     if (comp)
-        hipLaunchKernelGGL(batch ? k_idct_region_scaled_comp_batch : k_idct_region_scaled_comp, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtab,
+        hipLaunchKernelGGL(batch ? comp_batch : k_idct_region_scaled_comp, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtab,
                            job->d_qtabf, job->d_planes);
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[2], st));
     if (r.resize) { // crop-and-resize: gr is the output image's geometry

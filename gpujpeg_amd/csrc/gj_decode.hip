@@ -80,6 +80,11 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     if (rg.on && (job->scale > 1 || job->flipped || (rg.select && (!rg.d_sel || !rg.h_sel_count || g.restart_interval <= 0)) ||
                   (rg_batch ? (g.fb.sizes == nullptr || !rg.select || job->channel_remap) : (g.fb.sizes != nullptr || job->batch.count > 1 || (rg.select && !rg.d_sel_count)))))
         return -1;
+    // (frames of different image sizes, gj_frame_strides::geoms: a batch of crop-and-resize frames alone -- the selection, the sub-sequence decoder in
+    // plane mode and the region IDCT kernels are the stages that read a frame's own geometry --, the same records for g and gs, one per frame of the launch)
+    if ((g.fb.geoms != nullptr || job->batch.d_geoms != nullptr) &&
+        (!rg_batch || !rg.resize || job->tokens || g.fb.geoms != job->batch.d_geoms || job->gs.fb.geoms != g.fb.geoms || job->tune.dec_sub))
+        return -1;
     gj_hip_note_reset();
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[0], st));
     bool par = job->d_huff_tab2 != nullptr && job->seg_count > 0;

@@ -120,6 +120,13 @@ struct gpujpeg_decoder {
     /* dec_opt_resize_prescale_subsampled: 1 = the prescale reduces 4:2:0-like streams too, each component at its own N (gj_region_prescale). Read by that
      * call alone, into its rectangles' description like the two above; no effect without a prescale */
     int resize_prescale_subsampled;
+    /* dec_opt_batch_sizes: 1 = the streams of a crop-and-resize call may differ in image size ("mixed"). Read by that call alone, into its rectangles'
+     * description. The headers of the call's frames (pinned: gathered by one launch from device-resident streams) and every frame's geometry
+     * (pinned staging and device copy, uploaded once per call next to b_rgn) */
+    int batch_sizes_mixed;
+    uint8_t* bh_hdrs; size_t bh_hdrs_cap;
+    gj_geom* bh_geoms; size_t bh_geoms_cap;
+    gj_geom* b_geoms; size_t b_geoms_cap;
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
@@ -273,6 +280,7 @@ int gpujpeg_decoder_destroy(struct gpujpeg_decoder* d)
     gj_hip_free(d->b_rec); gj_hip_free(d->b_jpeg); gj_hip_free(d->b_raw); gj_hip_free(d->b_gather); gj_hip_free(d->b_scatter);
     gj_hip_host_free(d->bh_sum); gj_hip_host_free(d->bh_maxlen); gj_hip_host_free(d->bh_sizes);
     gj_hip_free(d->b_sel); gj_hip_free(d->b_rgn); gj_hip_host_free(d->bh_rgn); gj_hip_host_free(d->bh_found);
+    gj_hip_host_free(d->bh_hdrs); gj_hip_host_free(d->bh_geoms); gj_hip_free(d->b_geoms);
     free(d);
     return 0;
 }
@@ -986,6 +994,7 @@ struct dec_rects {
     const int* origins; int rw, rh;          /* a batch of regions, frame f: the rw x rh pixels at (origins[2f], origins[2f + 1]) */
     const int* rects; const uint8_t* mirror; /* crop-and-resize, frame f: the rectangle rects[4f .. 4f + 3] = x, y, w, h, each with its own size ... */
     struct gj_resize resize;                 /* ... resampled to ONE out_w x out_h image per frame (mirror: per frame, when mirror && mirror[f]) */
+    bool mixed;                              /* ... of streams that may differ in image size (dec_opt_batch_sizes = mixed) */
 };
 
 /* what the parts of a batch call share */
@@ -1008,6 +1017,11 @@ struct dec_batch {
     int img_w, img_h;                    /* the streams' image, as the rectangles were checked against it */
     long stats[4];                       /* gpujpeg_amd_decoder_get_region_stats of the call: sums over the frames */
     bool unselected;                     /* a frame was entropy-decoded in full */
+    /* streams of different image sizes (what.mixed): valid once `prepared` */
+    bool prepared;                       /* every frame's header has been looked at: */
+    uint8_t* fam;                        /* [count] 1: frame f is of the FAMILY -- its header is the cached one except for SOF0's dimensions -- and d->bh_geoms[f] is its geometry */
+    int n_fam;                           /* such frames from `first` on */
+    gj_geom g_max;                       /* the launch's geometry: the family's, with the segment, block and sample counts of its largest frames */
 };
 
 /* one rectangle per frame: a batch of regions, or crop-and-resize */
@@ -1029,20 +1043,143 @@ static struct dec_request batch_request(const struct gpujpeg_decoder* d, const s
     return q;
 }
 
+/* the image parameters of a family frame: the cached header's with the frame's own dimensions (and the line padding that follows from the width) */
+static struct gpujpeg_image_parameters mixed_param_image(const struct gpujpeg_decoder* d, int w, int h)
+{
+    struct gpujpeg_image_parameters pi = d->hdr_cache_r.param_image;
+    pi.width = w;
+    pi.height = h;
+    if (d->req_alignment != 0) { /* (the reader's rule, resolve_output) */
+        const unsigned linesize = (unsigned)gj_pixfmt_unit_size(pi.pixel_format) * (unsigned)w;
+        pi.width_padding = (int)((linesize + d->req_alignment - 1) / d->req_alignment * d->req_alignment - linesize);
+    }
+    return pi;
+}
+
+/* Streams of different image sizes (dec_opt_batch_sizes = mixed): the host looks at every frame's header before anything is planned. The FAMILY of
+ * the call are the frames whose first hdr_cache_len bytes are the cached header's except for the four dimension bytes of SOF0 (where the reader found
+ * them: gj_reader_result::sof_dims): same tables, sampling, restart interval and scan header, so they go through one set of launches, each with the
+ * geometry of its own dimensions (d->bh_geoms[f]; gj_geom_init, one per distinct size). Device-resident streams: ONE gather launch and one wait for
+ * all headers. Every other frame goes the single-frame route later; its rectangle is checked here, against its own header, so that a refusal comes
+ * before anything of the output is written (a header the reader does not take is left to that route's own error). 0 or -1. */
+/* (from: the first frame that has not been decoded yet -- 1 when frame 0 goes ahead of everything) */
+static int batch_mixed_prepare(struct gpujpeg_decoder* d, struct dec_batch* b, int from)
+{
+    struct gj_coder* c = &d->coder;
+    if (b->prepared) return 0;
+    const int count = b->count;
+    const struct gj_reader_result* r = &d->hdr_cache_r;
+    const size_t n = d->hdr_cache_len, dims = r->sof_dims;
+    if (gj_ensure_pinned_buffer((void**)&d->bh_geoms, &d->bh_geoms_cap, (size_t)count * sizeof(gj_geom), (size_t)count * sizeof(gj_geom) * 2) != 0) return -1;
+    memset(b->fam, 0, (size_t)count);
+    b->n_fam = 0;
+    bool family = d->hdr_cache_valid && d->hdr_cache != NULL && dims >= 2 && dims + 4 <= n && b->what.rects != NULL;
+    const uint8_t* hdrs = b->streams;
+    size_t hdr_stride = b->stream_stride;
+    if (family && b->streams_on_device) {
+        const size_t sizes_bytes = (size_t)count * sizeof(uint32_t);
+        if (gj_ensure_device_buffer((void**)&d->b_sizes, &d->b_sizes_cap, sizes_bytes) != 0) return -1;
+        if (gj_ensure_pinned_buffer((void**)&d->bh_sizes, &d->bh_sizes_cap, sizes_bytes, sizes_bytes + sizes_bytes / 2) != 0) return -1;
+        if (gj_ensure_pinned_buffer((void**)&d->bh_hdrs, &d->bh_hdrs_cap, (size_t)count * n, (size_t)count * n * 2) != 0) return -1;
+        for (int f = 0; f < count; f++) d->bh_sizes[f] = b->sizes[f] > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)b->sizes[f];
+        if (gj_hip_memcpy_h2d(d->b_sizes, d->bh_sizes, sizes_bytes, c->stream) != 0 ||
+            gj_hip_gather_headers(b->streams, b->stream_stride, d->b_sizes, (uint32_t)count, (uint32_t)n, d->bh_hdrs, c->stream) != 0 ||
+            gj_hip_stream_sync(c->stream) != 0) {
+            GJ_ERROR("Reading the headers of the batch failed: %s\n", gj_hip_last_error());
+            return -1;
+        }
+        hdrs = d->bh_hdrs;
+        hdr_stride = n;
+    }
+    int slot[64]; /* (one geometry per distinct size: the frame that last had a size of this hash) */
+    for (int i = 0; i < 64; i++) slot[i] = -1;
+    for (int f = 0; f < count; f++) {
+        const uint8_t* hb = hdrs + (size_t)f * hdr_stride;
+        bool fam = family && b->sizes[f] > n + 2 && memcmp(hb, d->hdr_cache, dims) == 0 && memcmp(hb + dims + 4, d->hdr_cache + dims + 4, n - dims - 4) == 0;
+        const int h = fam ? (int)(((unsigned)hb[dims] << 8) | hb[dims + 1]) : 0, w = fam ? (int)(((unsigned)hb[dims + 2] << 8) | hb[dims + 3]) : 0;
+        if (fam && (w < 1 || h < 1)) fam = false;
+        if (fam) {
+            gj_geom* gf = d->bh_geoms + f;
+            const int at = (int)(((unsigned)w * 31u + (unsigned)h) & 63u), same = slot[at];
+            if (same >= 0 && d->bh_geoms[same].width == w && d->bh_geoms[same].height == h) {
+                *gf = d->bh_geoms[same];
+            } else {
+                const struct gpujpeg_image_parameters pi = mixed_param_image(d, w, h);
+                if (gj_geom_init(gf, &r->param, &pi, false) != 0) fam = false;
+                else geom_take_tables(gf, r);
+            }
+            if (fam) slot[at] = f;
+        }
+        if (fam) {
+            b->fam[f] = 1;
+            if (f >= from) b->n_fam++;
+        }
+    }
+    /* (no frame is of the cached header's family and frame 0 has not gone ahead yet: it will, its header becomes the cached one, and this runs again) */
+    for (int f = from; f < count && (b->n_fam > 0 || from > 0); f++) {
+        /* not of the family: its rectangle against its own header */
+        if (b->fam[f]) continue;
+        struct gj_reader_result* rr = malloc(sizeof *rr);
+        if (!rr) return -1;
+        const uint8_t* himage = b->streams + (size_t)f * b->stream_stride;
+        size_t hsize = b->sizes[f];
+        int ok = 1;
+        if (b->streams_on_device) {
+            hsize = hsize < GJ_HDR_WINDOW ? hsize : GJ_HDR_WINDOW;
+            if (gj_hip_memcpy_d2h(d->h_hdr, himage, hsize, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) { free(rr); return -1; }
+            himage = d->h_hdr;
+        }
+        ok = hsize > 4 && gj_reader_parse(himage, hsize, GPUJPEG_LL_QUIET - 1, d->ff_cs_itu601_is_709, d->req_pixel_format, d->req_color_space, d->req_alignment, rr, true) == 0;
+        gj_geom gf, gs;
+        gj_region rg;
+        struct gpujpeg_image_parameters pr;
+        if (ok && gj_geom_init(&gf, &rr->param, &rr->param_image, false) == 0) {
+            const struct dec_request q = batch_request(d, b, f);
+            const int refused = gj_region_plan(&gs, &rg, &gf, &rr->param, &rr->param_image, q.rect, q.resize ? &q.rs : NULL, d->req_alignment, &pr);
+            if (refused != 0) {
+                GJ_ERROR("Frame %d of the batch: the rectangle %d,%d,%d,%d was refused%s!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3], refused == -3 ? " by the resize filter" : "");
+                free(rr);
+                return -1;
+            }
+        }
+        free(rr);
+    }
+    b->prepared = true;
+    return 0;
+}
+
 /* A batch of regions, once the coder is configured for the streams' geometry: every frame's rectangle checked against it (gj_region_plan; a
  * refusal names the frame), its origin and covers into the pinned records, its selection per scan; the largest cover and the largest selection
  * per scan of the call. 0 or -1. Nothing has been launched and nothing of the caller's output has been written when this runs. */
-static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b)
+/* Streams of different image sizes (dec_rects::mixed; from: see batch_mixed_prepare): every frame of the family against ITS geometry; the others keep
+ * the record, plan and geometry of a family frame -- the launches run over their slots too, with whatever their streams hold, and the single-frame
+ * route decodes them afterwards --; g_max, the launch's geometry: the family's with the largest segment, block and sample counts among its frames. */
+static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b, int from)
 {
     struct gj_coder* c = &d->coder;
     const gj_geom* g = &c->geom;
+    const bool mixed = b->what.mixed;
     b->planned = false;
+    if (mixed && batch_mixed_prepare(d, b, from) != 0) return -1;
+    int ref = -1; /* mixed: a frame of the family */
     if (gj_ensure_pinned_buffer((void**)&d->bh_rgn, &d->bh_rgn_cap, (size_t)b->count * sizeof(gj_region_frame), (size_t)b->count * sizeof(gj_region_frame) * 2) != 0) return -1;
     memset(b->plan_max, 0, sizeof b->plan_max);
     int wmax[GJ_MAX_COMP] = {0, 0, 0, 0}, hmax[GJ_MAX_COMP] = {0, 0, 0, 0};
     for (int f = 0; f < b->count; f++) {
         const struct dec_request q = batch_request(d, b, f);
-        const int refused = gj_region_plan(&b->gs_one, &b->rg_one, g, &c->param, &c->param_image, q.rect, q.resize ? &q.rs : NULL, d->req_alignment, &b->pi_r);
+        struct gpujpeg_image_parameters pi_f = c->param_image;
+        if (mixed) {
+            if (!b->fam[f]) continue;
+            g = d->bh_geoms + f;
+            pi_f = mixed_param_image(d, g->width, g->height);
+            if (ref < 0) { ref = f; b->g_max = *g; }
+            if (g->segment_count > b->g_max.segment_count) b->g_max.segment_count = g->segment_count;
+            if (g->block_count > b->g_max.block_count) b->g_max.block_count = g->block_count;
+            if (g->data_size > b->g_max.data_size) b->g_max.data_size = g->data_size;
+            for (int i = 0; i < g->comp_count && i < GJ_MAX_COMP; i++)
+                if (g->comp[i].segment_count > b->g_max.comp[i].segment_count) b->g_max.comp[i].segment_count = g->comp[i].segment_count;
+        }
+        const int refused = gj_region_plan(&b->gs_one, &b->rg_one, g, &c->param, &pi_f, q.rect, q.resize ? &q.rs : NULL, d->req_alignment, &b->pi_r);
         if (refused == -1) GJ_ERROR("Frame %d of the batch: the region %d,%d,%d,%d was refused!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3]);
         if (refused == -3) GJ_ERROR("Frame %d of the batch: the rectangle %d,%d,%d,%d was refused by the resize filter!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3]);
         if (refused != 0) return -1;
@@ -1058,6 +1195,18 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b)
             b->plan[f * GJ_MAX_COMP + sc] = n;
             if (n > b->plan_max[sc]) b->plan_max[sc] = n;
         }
+    }
+    if (mixed) {
+        if (ref < 0) { /* (no family: nothing will be launched) */
+            b->planned = true;
+            return 0;
+        }
+        for (int f = 0; f < b->count; f++)
+            if (!b->fam[f]) {
+                d->bh_rgn[f] = d->bh_rgn[ref];
+                d->bh_geoms[f] = d->bh_geoms[ref];
+                memcpy(b->plan + (size_t)f * GJ_MAX_COMP, b->plan + (size_t)ref * GJ_MAX_COMP, GJ_MAX_COMP * sizeof(int));
+            }
     }
     /* the planes of the largest cover: every frame's cover planes are laid out like this */
     b->gs_max = b->gs_one;
@@ -1099,8 +1248,8 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
         if (d->region_stats[0] != 1) b->unselected = true;
         for (int i = 1; i < 4; i++) b->stats[i] += d->region_stats[i];
         /* (frame 0 ahead of everything: the streams' geometry is known now -- every rectangle is checked before a pixel goes to the caller's slots) */
-        if (ahead && batch_regions_plan(d, b) != 0) return -1;
-        if (!ahead && b->planned && (c->param_image.width != b->img_w || c->param_image.height != b->img_h)) {
+        if (ahead && batch_regions_plan(d, b, 1) != 0) return -1;
+        if (!ahead && b->planned && !b->what.mixed && (c->param_image.width != b->img_w || c->param_image.height != b->img_h)) {
             GJ_ERROR("Frame %d of the batch is a %dx%d image, the others %dx%d!\n", f, c->param_image.width, c->param_image.height, b->img_w, b->img_h);
             return -1;
         }
@@ -1130,14 +1279,17 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
 
 /* The work buffers of one chunk of frames: what a frame takes of each (into B), how many frames fit a chunk (the return value, 0 on error),
  * the buffers and the job's pointers to them. */
-static int batch_chunk_buffers(struct gpujpeg_decoder* d, gj_dec_job* job, gj_batch* B, int n_all, size_t begin, size_t max_size, bool regions)
+/* (g: the launch's geometry -- the coder's, or for streams of different image sizes the one with the family's largest counts, dec_batch::g_max;
+ * min_samples: samples a frame's planes must hold at least -- the planes of the largest cover of such a batch, whose width and height come from
+ * different frames, may be larger than any frame's own) */
+static int batch_chunk_buffers(struct gpujpeg_decoder* d, const gj_geom* g, gj_dec_job* job, gj_batch* B, int n_all, size_t begin, size_t max_size, bool regions,
+                               size_t min_samples)
 {
     struct gj_coder* c = &d->coder;
-    const gj_geom* g = &c->geom;
     const size_t S = (size_t)g->segment_count + GJ_MAX_COMP;
     const size_t seg_frame = (3 * S + 8 + 3) & ~(size_t)3;                                                                   /* words */
     const size_t scratch_frame = (gj_hip_find_segments_scratch_words(begin, max_size, (uint32_t)g->segment_count) + 3) & ~(size_t)3; /* words */
-    const size_t coefs_frame = ((size_t)g->data_size + 63) & ~(size_t)63;                                                   /* int16 */
+    const size_t coefs_frame = ((size_t)(g->data_size > min_samples ? g->data_size : min_samples) + 63) & ~(size_t)63;   /* int16 */
     const int chunk_cap = d->b_chunk > 0 && d->b_chunk < GJ_DEC_BATCH_CHUNK_MAX ? d->b_chunk : GJ_DEC_BATCH_CHUNK_MAX;
     job->g.fb.frames = (uint32_t)(n_all < chunk_cap ? n_all : chunk_cap); /* (what the token / plane choice looks at) */
     const bool tokens = !d->img.resize && gj_hip_decode_wants_tokens(&job->g, max_size, &d->tune) != 0; /* (crop-and-resize: the cover planes) */
@@ -1192,6 +1344,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     /* (the region of the decoder's own option goes frame by frame: the single-frame region kernels do not know the frame dimension; a batch of
      * regions or crop-and-resize -- batch_has_regions -- has kernels that do, and so has a reduced-size decode, dec_opt_scale) */
     const bool regions = batch_has_regions(b);
+    if (regions && b->what.mixed && d->tune.dec_sub) return 0; /* (the tuning aid's sub-sequence sizes: no instantiation for frames of different sizes) */
     bool batched = (regions || !d->region_on) && d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
                    (b->streams_on_device ? (b->stream_stride & 15u) == 0 : true) && d->tab2_ok;
     size_t max_size = 0;
@@ -1212,7 +1365,13 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     }
     /* a batch of regions: the rectangles against the cached header's geometry, unless frame 0 went ahead and they have been checked against its own.
      * A rectangle the CACHED header refuses may be one the streams' own header takes (an older sequence's cache): frame 0 goes ahead and decides. */
-    if (regions && !b->planned && batch_regions_plan(d, b) != 0) return first == 0 && !force_first ? 1 : -1;
+    if (regions && !b->planned && batch_regions_plan(d, b, first) != 0) return first == 0 && !force_first && !b->what.mixed ? 1 : -1;
+    const bool mixed = regions && b->what.mixed;
+    /* (different image sizes: no frame from here on is of the cached header's family -- an older sequence's cache: frame 0 goes ahead and decides --,
+     * or nothing to launch) */
+    if (mixed && b->n_fam < 1) return first == 0 && !force_first ? 1 : 0;
+    /* (... or of a minority: the cached header is that of a stray frame an earlier call decoded last -- frame 0's is the better reference) */
+    if (mixed && 2 * b->n_fam < n_all && first == 0 && !force_first) return 1;
     const size_t frame_raw = regions ? (size_t)b->gs_one.raw_size : dec_raw_size(d);
     if (b->output_stride < frame_raw || (b->frame_raw != 0 && b->frame_raw != frame_raw)) {
         /* the cached header is an OLDER sequence's (a larger image than the caller's slots, ADVICE r4: this used to fail the call): these
@@ -1224,6 +1383,10 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     if (regions) dec_image_set(d, 1, &b->gs_one, &b->pi_r, &b->rg_one); /* (what a region call leaves: the image of one of the frames) */
     gj_dec_job job;
     dec_job_base(d, true, &job);
+    if (mixed) { /* (from here on the launch's geometry: the strides of the tables and the sizes of the work buffers follow the family's largest frames) */
+        g = &b->g_max;
+        job.g = *g;
+    }
     job.seg_count = g->segment_count;
     job.tune.dec_careful = 0;
     job.max_seg_len = d->last_max_seg_len;
@@ -1265,7 +1428,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     if (gj_hip_memcpy_h2d(d->b_sizes, d->bh_sizes, sizes_bytes, c->stream) != 0) return -1;
     gj_batch B;
     memset(&B, 0, sizeof B);
-    const int chunk = batch_chunk_buffers(d, &job, &B, n_all, begin, max_size, regions);
+    const int chunk = batch_chunk_buffers(d, g, &job, &B, n_all, begin, max_size, regions, mixed ? (size_t)b->gs_max.data_size : 0);
     if (chunk < 1) return -1;
     const size_t S = (size_t)g->segment_count + GJ_MAX_COMP;
     if (regions) {
@@ -1274,6 +1437,10 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         if (gj_ensure_device_buffer((void**)&d->b_rgn, &d->b_rgn_cap, rgn_bytes) != 0) return -1;
         if (gj_ensure_pinned_buffer((void**)&d->bh_found, &d->bh_found_cap, found_bytes, found_bytes * 2) != 0) return -1;
         if (gj_hip_memcpy_h2d(d->b_rgn, d->bh_rgn, rgn_bytes, c->stream) != 0) return -1;
+        if (mixed) { /* (every frame's geometry, once per call like the records) */
+            if (gj_ensure_device_buffer((void**)&d->b_geoms, &d->b_geoms_cap, (size_t)count * sizeof(gj_geom)) != 0) return -1;
+            if (gj_hip_memcpy_h2d(d->b_geoms, d->bh_geoms, (size_t)count * sizeof(gj_geom), c->stream) != 0) return -1;
+        }
         memset(d->bh_found, 0xFF, found_bytes);
         job.gs = b->gs_max;
         job.region.select = 1;
@@ -1297,9 +1464,11 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     for (int a = 0; a < n_all; a += chunk) {
         B.count = (uint32_t)(n_all - a < chunk ? n_all - a : chunk);
         B.d_sizes = d->b_sizes + a;
+        B.d_geoms = mixed ? d->b_geoms + first + a : NULL;
         job.batch = B;
         job.g.fb.sizes = B.d_sizes;
-        if (regions || job.scale > 1) job.gs.fb.sizes = B.d_sizes;
+        job.g.fb.geoms = B.d_geoms;
+        if (regions || job.scale > 1) { job.gs.fb.sizes = B.d_sizes; job.gs.fb.geoms = B.d_geoms; }
         if (regions) {
             job.region.d_frames = d->b_rgn + first + a;
             job.region.scale_mask = job.region.comp_mask = 0; /* (which of the three IDCT kernels this chunk's frames need) */
@@ -1316,7 +1485,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         job.d_overflow = &d->bh_sum[a].seq_overflow;
         uint32_t parts = 0;
         if (gj_hip_find_segments_batch(g, job.d_jpeg, begin, max_size, d->b_seg, d->b_seg + S, d->b_seg + 2 * S, (uint32_t)g->segment_count, d->b_scratch,
-                                       d->b_dsum + a, d->d_hdr_cache, (uint32_t)d->hdr_cache_len, d->bh_sum + a, d->bh_maxlen + (size_t)a * max_chunks,
+                                       d->b_dsum + a, mixed ? NULL : d->d_hdr_cache, mixed ? 0u : (uint32_t)d->hdr_cache_len, d->bh_sum + a, d->bh_maxlen + (size_t)a * max_chunks,
                                        (uint32_t)max_chunks, &parts, c->stream, &d->tune, &B) != 0 ||
             gj_hip_decode(&job, c->stream, NULL) != 0) {
             GJ_ERROR("Decoder kernels failed: %s\n", gj_hip_last_error());
@@ -1334,7 +1503,10 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     for (int i = 0; i < n_all; i++) {
         gj_scan_summary* su = d->bh_sum + i;
         summary_take_maxlen(su, d->bh_maxlen + (size_t)i * max_chunks, d->maxlen_parts);
-        if (!spec_summary_ok(d, su, g)) continue;
+        /* (different image sizes: the family's frames alone -- the host compared their headers --, each against its OWN segment count and scans) */
+        if (mixed && !b->fam[first + i]) continue;
+        const gj_geom* gf = mixed ? d->bh_geoms + first + i : g;
+        if (!spec_summary_ok(d, su, gf)) continue;
         if (regions) { /* did the selection find in this stream's table what the plan took from the geometry? (cannot fail for a stream the rule accepts) */
             const int f = first + i;
             if (memcmp(d->bh_found + (size_t)f * GJ_MAX_COMP, b->plan + (size_t)f * GJ_MAX_COMP, GJ_MAX_COMP * sizeof(uint32_t)) != 0) continue;
@@ -1345,7 +1517,8 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         }
         b->frame_done[first + i] = 1;
         accepted++;
-        remember_summary(d, su);
+        /* (what the next launch on this header plans with: a frame of the cached header's own dimensions) */
+        if (!mixed || (gf->width == c->geom.width && gf->height == c->geom.height)) remember_summary(d, su);
     }
     /* not one frame passed: the cached header (an older sequence's, of dimensions the slots happen to hold) is not these streams' */
     return accepted == 0 && first == 0 && !force_first ? 1 : 0;
@@ -1365,7 +1538,8 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
     int rc = -1;
     b.frame_done = calloc((size_t)count, 1);
     if (regions) b.plan = calloc((size_t)count * GJ_MAX_COMP, sizeof(int));
-    if (!b.frame_done || (regions && !b.plan)) goto out;
+    if (regions && b.what.mixed) b.fam = calloc((size_t)count, 1);
+    if (!b.frame_done || (regions && !b.plan) || (regions && b.what.mixed && !b.fam)) goto out;
     /* The header cache is what a batch launches on: frame 0 goes the ordinary way when there is none (or when it has to). A second pass, with
      * force_first, when the cached header turned out to be another sequence's: frame 0 replaces the cache, then the batch. */
     for (int pass = 0; pass < 2; pass++) {
@@ -1380,6 +1554,7 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
         if (again == 0) break;
         b.frame_raw = 0;
         b.planned = false;
+        b.prepared = false;
     }
     /* a batch of regions none of whose rectangles has been looked at (nothing has been launched: no header to launch on that these streams share,
      * or a decoder state without batched launches): frame 0 the ordinary way tells the streams' geometry, and every rectangle is checked against it
@@ -1416,6 +1591,7 @@ out:
     if (rc != 0 && b.host_io) gj_hip_stream_sync(c->stream); /* (what is queued on the stream must not read the caller's streams or write its frames after the error has left) */
     free(b.frame_done);
     free(b.plan);
+    free(b.fam);
     return rc;
 }
 
@@ -1502,7 +1678,8 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
     memset(d->prescales, 1, (size_t)count);
     d->prescales_n = count;
     struct dec_rects what = {.rects = rects, .mirror = mirror, .resize = {.out_w = out_width, .out_h = out_height, .prescale = d->resize_prescale, .filter = d->resize_filter,
-                                                                                   .subsampled = d->resize_prescale_subsampled}};
+                                                                                   .subsampled = d->resize_prescale_subsampled},
+                             .mixed = d->batch_sizes_mixed != 0};
     if (tensor) what.resize.tensor = *tensor;
     int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
     if (rc == 0) { /* (slot [4] of the kernel times, gpujpeg_amd_ext.h: 6 when any frame of the call was prescaled -- 8 when per component: the call's
@@ -1707,6 +1884,12 @@ int gpujpeg_decoder_set_option(struct gpujpeg_decoder* d, const char* opt, const
         GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE_SUBSAMPLED " (" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_OFF " or " GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_ON ")\n", val);
         return GPUJPEG_ERROR;
     }
+    if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_BATCH_SIZES) == 0) { /* read by gpujpeg_amd_decoder_decode_batch_crop_resize (and _tensor) alone */
+        if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME) == 0) { d->batch_sizes_mixed = 0; return GPUJPEG_NOERR; }
+        if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED) == 0) { d->batch_sizes_mixed = 1; return GPUJPEG_NOERR; }
+        GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_BATCH_SIZES " (" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME " or " GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED ")\n", val);
+        return GPUJPEG_ERROR;
+    }
     if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_REGION) == 0) { /* syntax only: the decode call checks the region against its stream */
         if (strcmp(val, "full") == 0) { d->region_on = false; return GPUJPEG_NOERR; }
         long v[4];
@@ -1740,6 +1923,7 @@ void gpujpeg_decoder_print_options(void)
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE "=[1|1/2|1/4|1/8] - largest reduced-size IDCT crop-and-resize may put ahead of its resample (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_FILTER "=[" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_BILINEAR "|" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_ANTIALIAS "] - filter of crop-and-resize's resample: four taps, or a footprint that grows with the reduction (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE_SUBSAMPLED "=[" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_OFF "|" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_ON "] - let that prescale reduce 4:2:0 streams too, each component at its own N (MI355X extension)\n");
+    printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_SIZES "=[" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME "|" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED "] - whether the streams of one crop-and-resize call may differ in image size (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_REGION "=[X,Y,W,H|full] - decode the W x H pixels at (X, Y) only (MI355X extension)\n");
 }
 

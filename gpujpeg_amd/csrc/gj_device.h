@@ -31,6 +31,18 @@ __device__ static constexpr uint8_t GJ_ZZ[64] = {
 // (src/gpujpeg_common.c:813-870); block addressing follows the reference's block list
 // (src/gpujpeg_common.c:1040-1085) but is computed arithmetically instead of being stored.
 // ------------------------------------------------------------------------------------------------
+// The geometry of frame blockIdx.z of a batch: the launch's own (MIXED = false: every frame shares it, the reference is the kernel's argument and
+// costs nothing), or -- a batch of frames of different image sizes, gj_frame_strides::geoms -- the frame's record where it lies in device memory
+// (an address that is the same in every lane: scalar loads, components indexed at run time without a copy in scratch memory). The ONE statement of
+// it: the kernels that know such batches (k_marker_table, k_segment_select_batch, k_huffman_decode_par, k_idct_region*_batch) ask here, once, at
+// entry; the strides (g.fb) are always the launch's.
+template <bool MIXED>
+__device__ __forceinline__ const gj_geom& gj_frame_geom(const gj_geom& g)
+{
+    if constexpr (MIXED) return g.fb.geoms[blockIdx.z];
+    else return g;
+}
+
 struct GjSeg {
     int comp;          // component of the scan (non-interleaved), 0 otherwise
     int index_in_scan; // restart marker index = index_in_scan % 8

@@ -186,6 +186,7 @@ struct gj_reader_result {
     int seg_info_size[GJ_MAX_COMP][GPUJPEG_MAX_SEGMENT_INFO_HEADER_COUNT];
     int seg_info_count[GJ_MAX_COMP];
     size_t header_end; /* offset of the first SOS marker */
+    size_t sof_dims;   /* offset of SOF0's height field: the four bytes height, width (big-endian u16 each) that streams of one family may differ in */
     bool eoi_seen;
 };
 /* parse every marker; when segments != NULL also split scans at RSTn on the host (reference behaviour) */

@@ -385,6 +385,7 @@ int gj_reader_parse(const uint8_t* image, size_t size, int verbose, bool ff_cs_i
             const int precision = d[0];
             r->param_image.height = (int)RD2(d + 1);
             r->param_image.width = (int)RD2(d + 3);
+            r->sof_dims = (size_t)(d + 1 - image);
             r->param.comp_count = d[5];
             if (r->param.comp_count == 0) { GJ_ERROR("SOF0 has 0 components!\n"); return -1; }
             if (r->param.comp_count > GJ_MAX_COMP) { GJ_ERROR("SOF0 has %d components but JPEG can contain at most %d components\n", r->param.comp_count, GJ_MAX_COMP); return -1; }

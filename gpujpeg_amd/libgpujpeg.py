@@ -25,6 +25,11 @@ ENCODER_INPUT_IMAGE, ENCODER_INPUT_OPENGL_TEXTURE, ENCODER_INPUT_GPU_IMAGE = 0, 
 (DECODER_OUTPUT_INTERNAL_BUFFER, DECODER_OUTPUT_CUSTOM_BUFFER, DECODER_OUTPUT_OPENGL_TEXTURE,
  DECODER_OUTPUT_CUDA_BUFFER, DECODER_OUTPUT_CUSTOM_CUDA_BUFFER) = range(5)
 RESTART_AUTO, RESTART_NONE = -1, 0
+# Decoder.set_option(DEC_OPT_BATCH_SIZES, BATCH_SIZES_MIXED): the streams of one decode_batch_crop_resize / _tensor call may differ in image size
+# (include/gpujpeg_amd_ext.h, GPUJPEG_AMD_DEC_OPT_BATCH_SIZES). RESTART_AUTO picks the interval from the image size: encode such a dataset with an
+# explicit restart interval, so that its streams share one header but for the dimensions.
+DEC_OPT_BATCH_SIZES = "dec_opt_batch_sizes"
+BATCH_SIZES_SAME, BATCH_SIZES_MIXED = "same", "mixed"
 # encoder option of the MI355X build (gpujpeg_amd_ext.h: GPUJPEG_AMD_ENC_OPT_HUFFMAN): Annex K.3 tables, or tables built per frame
 ENC_OPT_HUFFMAN = "enc_opt_huffman"
 ENC_HUFFMAN_STANDARD, ENC_HUFFMAN_OPTIMAL = "standard", "optimal"

@@ -96,12 +96,18 @@ typedef struct gj_comp_geom {
 
 /* Decoder kernels of a frame batch (gj_dec_job::batch, blockIdx.z = frame): what lies between the buffers of two frames. It travels with
  * the geometry because every decoder kernel takes the geometry by value; sizes == NULL (everything zero) for a single frame. */
+struct gj_geom;
 typedef struct gj_frame_strides {
     const uint32_t* sizes;    /* [frames] bytes of every frame's stream, device memory */
     uint64_t jpeg, raw;       /* bytes */
     uint64_t coefs, tok, rec; /* int16 coefficients, tokens, block records */
     uint32_t seg;             /* words between the frames' seg_pos (and seg_len, seg_index) */
     uint32_t frames;          /* frames of the launch (what fills the device is the batch, not the frame: gj_hip_decode_wants_tokens) */
+    /* frames of DIFFERENT image sizes (dec_opt_batch_sizes = mixed, crop-and-resize alone): [frames] the geometry of every frame, device memory; NULL:
+     * all frames share the geometry this record travels in. The record of a frame is a whole gj_geom that the kernels read where it lies
+     * (gj_device.h: gj_frame_geom) -- they index its components at run time, and a copy patched in registers would live in scratch memory. Its
+     * own fb is not read. */
+    const struct gj_geom* geoms;
 } gj_frame_strides;
 
 typedef struct gj_geom {
@@ -184,6 +190,7 @@ typedef struct gj_batch {
     uint32_t scratch;        /* decoder: words between the frames' marker-scan scratch */
     uint32_t maxlen;         /* decoder: words between the frames' longest-segment words in pinned host memory */
     const uint32_t* d_sizes; /* decoder: [count] bytes of every frame's stream, in device memory */
+    const struct gj_geom* d_geoms; /* decoder: NULL, or [count] the geometry of every frame (gj_frame_strides::geoms), in device memory */
 } gj_batch;
 
 typedef struct gj_enc_job {
@@ -475,6 +482,10 @@ GJ_HIP_API int gj_hip_find_segments_deferred(const gj_geom* g, const uint8_t* d_
                                              gj_scan_summary* d_summary, const uint8_t* d_hdr_ref, uint32_t hdr_n, gj_scan_summary* h_summary,
                                              uint32_t* h_maxlen_parts, uint32_t maxlen_capacity, uint32_t* maxlen_part_count, gj_stream_t stream,
                                              const gj_tuning* tune, gj_scan_deferred* defer);
+/* The first n bytes of each of `frames` device-resident streams (`stride` bytes apart, d_sizes: their sizes in device memory) into PINNED HOST memory,
+ * stream z's at h_out + z n, zero behind a stream's end; valid once the stream has been waited for. One launch for all of them. */
+GJ_HIP_API int gj_hip_gather_headers(const uint8_t* d_jpeg, uint64_t stride, const uint32_t* d_sizes, uint32_t frames, uint32_t n, uint8_t* h_out,
+                                     gj_stream_t stream);
 /* workgroups the marker scan cuts [begin, size) into at most (capacity of h_maxlen_parts) */
 GJ_HIP_API size_t gj_hip_find_segments_max_chunks(uint64_t begin, uint64_t size);
 

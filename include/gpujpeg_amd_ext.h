@@ -172,6 +172,32 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
 #define GPUJPEG_AMD_DEC_OPT_RESIZE_FILTER "dec_opt_resize_filter"
 #define GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_BILINEAR "bilinear"
 #define GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_ANTIALIAS "antialias"
+/* Decoder option "dec_opt_batch_sizes" = "same" (default) or "mixed": whether the streams of ONE call of gpujpeg_amd_decoder_decode_batch_crop_resize or
+ * gpujpeg_amd_decoder_decode_batch_crop_resize_tensor may differ in image size. Read by those two calls alone (gpujpeg_amd_decoder_decode_batch and
+ * _decode_batch_regions do not read it and keep refusing streams of other dimensions); it holds from the next call on and may be changed between two
+ * calls of a decoder. Another value is refused by gpujpeg_decoder_set_option (GPUJPEG_ERROR) and leaves the setting as it was. With "same" every byte,
+ * counter, launch, refusal and kernel-times slot of every call is what it is without the option.
+ * WITH "mixed" frame f is, byte for byte (tensor call: bit for bit), what the same call returns for a batch of the one stream f with rects[4f .. 4f + 3],
+ * mirror[f] and every other argument and option the same -- the definition over the single-frame region call, as ever. The streams may differ in image
+ * width and height (and in anything else); every rectangle is checked against ITS stream's image, a refusal names the frame and is made before anything of
+ * `output` is written (a stream whose header the reader does not take fails in its own decode instead). param_image and the layout of the output do not
+ * depend on the source sizes. All other refusals stand; dec_opt_resize_prescale, dec_opt_resize_prescale_subsampled, dec_opt_resize_filter, the mirror,
+ * the output formats and the tensor formats compose with it as they do without; gpujpeg_amd_decoder_get_prescales reports every frame's s_f from its own
+ * rectangle and image.
+ *   Routing.   The FAMILY of a call are the frames whose header -- SOI up to and including the first SOS header -- is byte for byte the call's reference
+ *              header except for the four bytes of SOF0 that hold height and width. The reference header is the one the decoder last decoded a frame
+ *              with (a fresh decoder, or one that last saw another sequence: frame 0's, which goes the single-frame route first). Family frames have
+ *              the same DQT, DHT, DRI, sampling, scan header and APPn / COM segments; they go through the batched launches, each with the geometry
+ *              of its own dimensions. Every other frame -- another quality, restart interval 0, another comment, damaged markers, a segment too long
+ *              for the fast entropy decoders, frame 0 of a call whose pixels go to host memory -- goes the single-frame route inside the call.
+ *              gpujpeg_amd_decoder_last_batch counts both kinds, gpujpeg_amd_decoder_get_region_stats gives the sums over the frames (equal to the sums
+ *              of the single calls); slot [4] of the kernel times is as without the option.
+ *   Encoding.  GPUJPEG_ENCODER_RESTART_AUTO-style automatic restart intervals are chosen from the image size, so two images of different size get
+ *              different DRI segments and are NOT of one family: encode a dataset meant for this call with one explicit restart interval (and one
+ *              quality, sampling and interleaving). */
+#define GPUJPEG_AMD_DEC_OPT_BATCH_SIZES "dec_opt_batch_sizes"
+#define GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME "same"
+#define GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED "mixed"
 /* Host-only: the table enc_opt_huffman=optimal builds for one class from symbol counts freq[256] (ITU T.81 Annex K.2: Figures K.1, K.3, K.4;
  * reserved code point, ties to the larger symbol value), code lengths limited to the largest L of 16 .. 10 whose table the library's
  * two-level decode tables take. Writes BITS (bits[1..16]) and HUFFVAL; returns L, or -1 when no count is non-zero. */
