@@ -767,7 +767,8 @@ static int region_scan_segments(const gj_geom* g, const gj_region_frame* r, int 
     const int gridx = g->interleaved ? g->mcu_count_x : g->comp[sc].blocks_x, ri = g->restart_interval;
     const int x0 = g->interleaved ? r->mx0 : r->bx0[sc], x1 = g->interleaved ? r->mx1 : r->bx1[sc];
     const int y0 = g->interleaved ? r->my0 : r->by0[sc], y1 = g->interleaved ? r->my1 : r->by1[sc];
-    if (ri <= 0 || gridx <= 0 || x0 >= x1) return 0;
+    if (ri <= 0) return 1; /* (no restart markers: the scan is one segment, and the predicate takes it whatever the cover -- a scan can be left early, not entered late) */
+    if (gridx <= 0 || x0 >= x1) return 0;
     /* row y's run is the segments lo .. hi of its first and last cell, y gridx + x0 and y gridx + x1 - 1; both move on by gridx cells per row, so
      * quotient and remainder are carried from row to row (this runs in every region call: four divisions per scan, none per row) */
     const long first = (long)y0 * gridx + x0, last = (long)y0 * gridx + x1 - 1, step_q = gridx / ri, step_r = gridx % ri;

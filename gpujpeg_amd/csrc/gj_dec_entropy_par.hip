@@ -118,6 +118,14 @@ __device__ __forceinline__ uint32_t gj_decode_sub(const uint32_t* __restrict__ U
     return (bitpos - end_bit) | ((uint32_t)z << 5) | ((uint32_t)p << 11);
 }
 
+// Leaving a scan WITHOUT restart markers early (a batch of regions on such streams, gj_dec_job::batch_restartless): such a scan cannot be entered in
+// the middle, but nothing behind the last block of the frame's cover is needed. frames: the frames' records (gj_region::d_frames), nullptr = every
+// segment is decoded to its end; left: pinned host words, [frame][GJ_MAX_COMP], where the workgroup that leaves scan c says how many bytes it did not read.
+struct GjLeave {
+    const gj_region_frame* frames;
+    uint32_t* left;
+};
+
 // (MIXED: a batch of frames of different image sizes -- segments, blocks and planes are frame blockIdx.z's own, gj_frame_geom; the strides between the
 // frames' buffers are the launch's)
 template <bool INTERLEAVED, int SUB_BYTES, bool MIXED = false>
@@ -126,7 +134,7 @@ __global__ __launch_bounds__(256) void k_huffman_decode_par(const gj_geom g_laun
                                                             const uint32_t* __restrict__ seg_index, const int seg_count_max,
                                                             const uint32_t* __restrict__ seg_count_ptr, const GjBatchPlan plan,
                                                             const uint16_t* __restrict__ tabs, int16_t* __restrict__ coefs,
-                                                            const int zero_fill /* 1: the planes are not known to be zero */, const GjFold F)
+                                                            const int zero_fill /* 1: the planes are not known to be zero */, const GjFold F, const GjLeave E)
 {
     // every segment of a group ends with a partial sub-sequence: at most CAP_U / SUB + n sub-sequences for n segments (tighter bounds
     // hold only for short sub-sequences; nsub is clamped below all the same, so that a fault in this arithmetic cannot become a write
@@ -539,16 +547,32 @@ __global__ __launch_bounds__(256) void k_huffman_decode_par(const gj_geom g_laun
         const uint8_t* base = jpeg + seg_pos[si0 + jl];
         const uint32_t len = seg_len[si0 + jl];
         const uint32_t first = s_first[jl];
-        if (zero_fill) {
-            for (uint32_t c = (uint32_t)tid; c < (uint32_t)sg.nblocks * 8u; c += 256) {
+        // `need`: blocks of the segment, in coding order, up to and including the last one of the frame's cover -- the whole segment unless the launch
+        // leaves restart-less scans early (GjLeave). Interleaved: through the last block of MCU (my1 - 1) mcu_count_x + mx1 - 1; a component's own
+        // scan: through block (by1 - 1) blocks_x + bx1 - 1. The segment starts the scan (no restart markers).
+        uint32_t need = (uint32_t)sg.nblocks;
+        if (E.frames != nullptr && g.restart_interval <= 0) {
+            const gj_region_frame& rf = E.frames[blockIdx.z];
+            const long long n = INTERLEAVED ? ((long long)(rf.my1 - 1) * g.mcu_count_x + rf.mx1) * P
+                                            : (long long)(rf.by1[sg.comp] - 1) * g.comp[sg.comp].blocks_x + rf.bx1[sg.comp];
+            need = (uint32_t)min(max(n, 1ll), (long long)sg.nblocks);
+        }
+        const bool leave = need < (uint32_t)sg.nblocks;
+        // zero fill: the blocks that will be decoded -- all of them up front, or, where the scan may be left early, through `need` up front and
+        // piece by piece beyond it (a piece ends where its bytes end, not where the cover does)
+        uint32_t filled = 0;
+        auto fill_to = [&](const uint32_t to) {
+            for (uint32_t c = filled * 8u + (uint32_t)tid; c < to * 8u; c += 256) {
                 int c_, m_;
                 const uint64_t off = INTERLEAVED ? gj_segment_block(g, sg, (int)(c >> 3), &c_, &m_) : (uint64_t)(first + (c >> 3)) * 64;
                 reinterpret_cast<uint4*>(coefs + off)[c & 7u] = make_uint4(0, 0, 0, 0);
             }
-        }
+            filled = to;
+        };
+        if (zero_fill) fill_to(need);
         uint32_t src_off = 0, entry = 0, blocks_done = 0;
         int dc_carry[GJ_MAX_COMP] = {0, 0, 0, 0};
-        while (src_off < len) {
+        while (src_off < len && !(leave && blocks_done >= need)) {
             __syncthreads();
             // -- unstuff [src_off, src_off + chunk) plus up to 16 bytes of look-ahead for the symbol that straddles the piece end
             const uint32_t chunk = min(GJ_PAR_PIECE, len - src_off);
@@ -599,6 +623,13 @@ __global__ __launch_bounds__(256) void k_huffman_decode_par(const gj_geom g_laun
             __syncthreads();
             run_rounds(nsub, 0u);
             block_positions(nsub);
+            if (zero_fill && leave) { // (the blocks this piece completes, and the one it ends in)
+                const uint32_t to = min(blocks_done + (nsub > 0 ? s_rec[nsub - 1].y : 0u) + 1u, (uint32_t)sg.nblocks);
+                if (to > filled) {
+                    fill_to(to);
+                    __syncthreads(); // (orders the zeros before the coefficient stores of the other lanes)
+                }
+            }
             // -- coefficients of this piece (DC still as differences)
             const uint32_t tb = s_tabs[jl];
             for (int k = tid; k < nsub; k += 256) {
@@ -634,6 +665,8 @@ __global__ __launch_bounds__(256) void k_huffman_decode_par(const gj_geom g_laun
             blocks_done += piece_blocks;
             src_off += chunk;
         }
+        // (one store per scan that was left early, from one lane: nobody else writes this word)
+        if (leave && src_off < len && tid == 0) E.left[(size_t)blockIdx.z * GJ_MAX_COMP + (INTERLEAVED ? 0 : sg.comp)] = len - src_off;
     }
 }
 
@@ -751,8 +784,13 @@ void gj_launch_huffman_par(const gj_dec_job* job, hipStream_t st)
         F = GjFold{sc.recs, sc.lists, sc.wgs, sc.part_bytes, sc.begin, sc.h_summary, sc.h_maxlen_parts};
         *sc.maxlen_part_count = batches; // (the host takes the maximum over the batches' words)
     }
+    // (a batch of regions on restart-less streams: the scans are left behind their frame's cover -- unless the A/B setting says to decode them to the end)
+    const gj_region& rg = job->region;
+    GjLeave E = {nullptr, nullptr};
+    if (job->batch_restartless && rg.on && rg.d_frames != nullptr && rg.h_left_early != nullptr && g.fb.sizes != nullptr && !job->tune.dec_no_early_stop)
+        E = GjLeave{rg.d_frames, rg.h_left_early};
     hipLaunchKernelGGL(kernel, dim3(batches, 1, job->batch.count > 1 ? job->batch.count : 1u), dim3(256), 0, st, g, job->d_jpeg, job->jpeg_size, job->d_seg_pos, job->d_seg_len,
-                       job->d_seg_index, job->seg_count, fold ? nullptr : job->d_seg_count, plan, job->d_huff_tab2, job->d_coefs, job->clear_coefs ? 0 : 1, F);
+                       job->d_seg_index, job->seg_count, fold ? nullptr : job->d_seg_count, plan, job->d_huff_tab2, job->d_coefs, job->clear_coefs ? 0 : 1, F, E);
 }
 
 // the table launch folded into this kernel (GjFold, gj_dec_internal.h): one frame whose batches are cut per scan (one scan per component, or one interleaved scan)

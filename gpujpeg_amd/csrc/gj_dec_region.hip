@@ -157,7 +157,8 @@ template <bool MIXED>
 __global__ __launch_bounds__(GJ_SEL_CHUNK) void k_segment_select_batch(const gj_geom g_launch, const gj_region rb, const uint32_t* __restrict__ seg_pos,
                                                                        const uint32_t* __restrict__ seg_len, const uint32_t* __restrict__ seg_index,
                                                                        const int seg_count_max, const uint32_t* __restrict__ seg_count_ptr,
-                                                                       uint32_t* __restrict__ out, const uint32_t out_stride, uint32_t* __restrict__ h_found)
+                                                                       uint32_t* __restrict__ out, const uint32_t out_stride, uint32_t* __restrict__ h_found,
+                                                                       uint32_t* __restrict__ h_bytes /* may be null: gj_region::h_sel_bytes */)
 {
     __shared__ uint32_t s_wave[GJ_MAX_COMP][GJ_SEL_CHUNK / GJ_WAVE];
     const size_t z = blockIdx.z;
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(GJ_SEL_CHUNK) void k_segment_select_batch(const gj_
     const gj_region_frame& r = rb.d_frames[z]; // (read where it lies: a copy indexed by component would live in scratch memory)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = min((int)seg_count_ptr[z * (sizeof(gj_scan_summary) / 4)], MIXED ? min(seg_count_max, g.segment_count) : seg_count_max);
-    uint32_t first[GJ_MAX_COMP], run[GJ_MAX_COMP];
+    uint32_t first[GJ_MAX_COMP], run[GJ_MAX_COMP], bytes = 0; // (bytes: the lengths of the entries this lane selected)
     {
         uint32_t at = 0;
 #pragma unroll
@@ -179,6 +180,7 @@ __global__ __launch_bounds__(GJ_SEL_CHUNK) void k_segment_select_batch(const gj_
         const uint32_t s = i < n ? seg_index[i] : 0xFFFFFFFFu;
         const bool in = i < n && gj_segment_in_cover(g, r, (int)s);
         const int sc = in ? gj_segment_scan(g, s) : -1;
+        if (in) bytes += seg_len[i];
         uint32_t below = 0; // selected entries of this lane's scan in front of it inside its wave
 #pragma unroll
         for (int c = 0; c < GJ_MAX_COMP; c++) {
@@ -216,6 +218,16 @@ __global__ __launch_bounds__(GJ_SEL_CHUNK) void k_segment_select_batch(const gj_
 #pragma unroll
     for (int c = 0; c < GJ_MAX_COMP; c++)
         if (tid == c) h_found[c] = run[c];
+    if (h_bytes != nullptr) { // (what the entropy decoder is handed of this frame: the waves' sums through LDS, one store)
+        const uint32_t inc = gj_wave_incl_scan(bytes);
+        if (lane == 63) s_wave[0][wave] = inc;
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t all = 0;
+            for (int w = 0; w < GJ_SEL_CHUNK / GJ_WAVE; w++) all += s_wave[0][w];
+            h_bytes[z] = all;
+        }
+    }
 }
 
 void gj_launch_segment_select_batch(const gj_dec_job* job, hipStream_t st)
@@ -225,7 +237,7 @@ void gj_launch_segment_select_batch(const gj_dec_job* job, hipStream_t st)
     const uint32_t stride = (uint32_t)g.segment_count + GJ_MAX_COMP;
     auto kern = g.fb.geoms != nullptr ? k_segment_select_batch<true> : k_segment_select_batch<false>;
     hipLaunchKernelGGL(kern, dim3(1, 1, job->batch.count), dim3(GJ_SEL_CHUNK), 0, st, g, r, job->d_seg_pos, job->d_seg_len, job->d_seg_index,
-                       job->seg_count, job->d_seg_count, r.d_sel, stride, r.h_sel_count);
+                       job->seg_count, job->d_seg_count, r.d_sel, stride, r.h_sel_count, r.h_sel_bytes);
 }
 
 // ================================================================================================

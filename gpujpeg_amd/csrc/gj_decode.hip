@@ -28,13 +28,14 @@ extern "C" int gj_hip_decode_wants_tokens(const gj_geom* g, uint64_t jpeg_size, 
 
 // A batch of frames (gj_dec_job::batch) is a speculative launch on one header through the sub-sequence entropy decoders -- tokens for non-interleaved
 // 4:4:4, coefficient planes for everything else (the lane-per-segment kernels and the token-fed 4:2:2 IDCT do not know the frame dimension) -- and any
-// of the IDCT-side kernels; no option that touches other buffers.
+// of the IDCT-side kernels; no option that touches other buffers. Streams without restart markers -- one segment per scan, which k_huffman_decode_par
+// decodes piece by piece, plane mode (gj_hip_decode_wants_tokens says no) -- where the job asks for them (gj_dec_job::batch_restartless).
 extern "C" int gj_hip_decode_batchable(const gj_dec_job* job)
 {
     const gj_geom& g = job->g;
     return job->d_huff_tab2 != nullptr && job->d_overflow != nullptr && job->d_seg_count != nullptr && job->seg_count > 0 &&
            !job->flipped && !job->channel_remap && !job->clear_coefs && !job->tune.dec_serial && !job->tune.dec_careful && job->tune.dec_seq != 1 &&
-           g.restart_interval > 0;
+           (g.restart_interval > 0 || job->batch_restartless);
 }
 
 extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event_t ev[4])
@@ -77,7 +78,8 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
         (rg.filter != GJ_RESIZE_FILTER_ANTIALIAS || !rg.resize || (rg.scale_mask & ~1u) != 0 || rg.comp_mask != 0 ||
          (!rg_batch && (rg.frame.scale > 1 || rg.frame.w > GJ_RESIZE_AA_MAX_RATIO * job->gs.width || rg.frame.h > GJ_RESIZE_AA_MAX_RATIO * job->gs.height))))
         return -1;
-    if (rg.on && (job->scale > 1 || job->flipped || (rg.select && (!rg.d_sel || !rg.h_sel_count || g.restart_interval <= 0)) ||
+    // (without restart markers a selection is every segment of every scan: a batch of regions on such streams alone, gj_dec_job::batch_restartless)
+    if (rg.on && (job->scale > 1 || job->flipped || (rg.select && (!rg.d_sel || !rg.h_sel_count || (g.restart_interval <= 0 && !(rg_batch && job->batch_restartless)))) ||
                   (rg_batch ? (g.fb.sizes == nullptr || !rg.select || job->channel_remap) : (g.fb.sizes != nullptr || job->batch.count > 1 || (rg.select && !rg.d_sel_count)))))
         return -1;
     // (frames of different image sizes, gj_frame_strides::geoms: a batch of crop-and-resize frames alone -- the selection, the sub-sequence decoder in

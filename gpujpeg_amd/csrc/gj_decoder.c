@@ -127,6 +127,14 @@ struct gpujpeg_decoder {
     uint8_t* bh_hdrs; size_t bh_hdrs_cap;
     gj_geom* bh_geoms; size_t bh_geoms_cap;
     gj_geom* b_geoms; size_t b_geoms_cap;
+    /* dec_opt_batch_restartless: 1 = the batch calls take streams without restart markers through their batched launches (gj_dec_job::batch_restartless).
+     * Read by every batch call, once, when it starts. What the batched launches of the last such call handed to the entropy decoders and what those
+     * read of it (gpujpeg_amd_decoder_get_entropy_bytes); pinned, per frame of a call with rectangles: the bytes its selection found and, per scan,
+     * the bytes of a restart-less scan that were not read (gj_region::h_sel_bytes, h_left_early) */
+    int batch_restartless;
+    uint64_t entropy_bytes[2]; bool entropy_valid;
+    uint32_t* bh_sel_bytes; size_t bh_sel_bytes_cap;
+    uint32_t* bh_left; size_t bh_left_cap;
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
@@ -281,6 +289,7 @@ int gpujpeg_decoder_destroy(struct gpujpeg_decoder* d)
     gj_hip_host_free(d->bh_sum); gj_hip_host_free(d->bh_maxlen); gj_hip_host_free(d->bh_sizes);
     gj_hip_free(d->b_sel); gj_hip_free(d->b_rgn); gj_hip_host_free(d->bh_rgn); gj_hip_host_free(d->bh_found);
     gj_hip_host_free(d->bh_hdrs); gj_hip_host_free(d->bh_geoms); gj_hip_free(d->b_geoms);
+    gj_hip_host_free(d->bh_sel_bytes); gj_hip_host_free(d->bh_left);
     free(d);
     return 0;
 }
@@ -969,6 +978,7 @@ static int decoder_decode(struct gpujpeg_decoder* d, const struct dec_request* r
 int gpujpeg_decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t image_size, struct gpujpeg_decoder_output* output)
 {
     const struct dec_request q = dec_request_options(d);
+    if (d) d->entropy_valid = false;
     return decoder_decode(d, &q, image, image_size, output);
 }
 
@@ -1022,6 +1032,7 @@ struct dec_batch {
     uint8_t* fam;                        /* [count] 1: frame f is of the FAMILY -- its header is the cached one except for SOF0's dimensions -- and d->bh_geoms[f] is its geometry */
     int n_fam;                           /* such frames from `first` on */
     gj_geom g_max;                       /* the launch's geometry: the family's, with the segment, block and sample counts of its largest frames */
+    bool restartless;                    /* dec_opt_batch_restartless = on: streams without restart markers go through the batched launches too */
 };
 
 /* one rectangle per frame: a batch of regions, or crop-and-resize */
@@ -1392,6 +1403,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     job.max_seg_len = d->last_max_seg_len;
     memcpy(job.scan_bytes, d->last_scan_bytes, sizeof job.scan_bytes);
     job.jpeg_size = max_size;
+    job.batch_restartless = b->restartless ? 1 : 0;
     /* (the two pointers only have to be non-null for the question; they are set per chunk below) */
     job.d_seg_count = &d->d_summary->segment_count;
     job.d_overflow = &d->h_summary->seq_overflow;
@@ -1442,6 +1454,13 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
             if (gj_hip_memcpy_h2d(d->b_geoms, d->bh_geoms, (size_t)count * sizeof(gj_geom), c->stream) != 0) return -1;
         }
         memset(d->bh_found, 0xFF, found_bytes);
+        if (b->restartless) { /* (what every frame's selection hands to the entropy decoder, and what that leaves unread of a restart-less scan) */
+            const size_t sel_bytes = (size_t)count * sizeof(uint32_t), left_bytes = (size_t)count * GJ_MAX_COMP * sizeof(uint32_t);
+            if (gj_ensure_pinned_buffer((void**)&d->bh_sel_bytes, &d->bh_sel_bytes_cap, sel_bytes, sel_bytes * 2) != 0) return -1;
+            if (gj_ensure_pinned_buffer((void**)&d->bh_left, &d->bh_left_cap, left_bytes, left_bytes * 2) != 0) return -1;
+            memset(d->bh_sel_bytes, 0, sel_bytes);
+            memset(d->bh_left, 0, left_bytes);
+        }
         job.gs = b->gs_max;
         job.region.select = 1;
         memset(&job.region.frame, 0, sizeof job.region.frame); /* (not used: d_frames) */
@@ -1478,6 +1497,8 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
                 else job.region.scale_mask |= (unsigned)rf->scale;
             }
             job.region.h_sel_count = d->bh_found + (size_t)(first + a) * GJ_MAX_COMP;
+            job.region.h_sel_bytes = b->restartless ? d->bh_sel_bytes + first + a : NULL;
+            job.region.h_left_early = b->restartless ? d->bh_left + (size_t)(first + a) * GJ_MAX_COMP : NULL;
         }
         job.d_jpeg = d_streams + (size_t)a * d_stride;
         job.d_raw = b->d_out + (size_t)(first + a) * b->d_out_stride;
@@ -1517,6 +1538,18 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         }
         b->frame_done[first + i] = 1;
         accepted++;
+        if (b->restartless) { /* (gpujpeg_amd_decoder_get_entropy_bytes: the table lengths of the frame's segments -- its scans without their restart markers --, or of its selection) */
+            uint64_t handed = 0, left = 0;
+            if (regions) {
+                handed = d->bh_sel_bytes[first + i];
+                for (int sc = 0; sc < GJ_MAX_COMP; sc++) left += d->bh_left[(size_t)(first + i) * GJ_MAX_COMP + sc];
+            } else {
+                for (int sc = 0; sc < (int)su->scan_count && sc < GJ_MAX_COMP; sc++) handed += su->scan_end[sc] - su->scan_start[sc];
+                handed -= 2u * (uint64_t)su->rst_count;
+            }
+            d->entropy_bytes[0] += handed;
+            d->entropy_bytes[1] += handed - (left < handed ? left : handed);
+        }
         /* (what the next launch on this header plans with: a frame of the cached header's own dimensions) */
         if (!mixed || (gf->width == c->geom.width && gf->height == c->geom.height)) remember_summary(d, su);
     }
@@ -1532,6 +1565,9 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
     struct dec_batch b = {.streams = streams, .stream_stride = stream_stride, .sizes = sizes, .count = count, .output_stride = output_stride,
                           .d_out = output, .d_out_stride = output_stride};
     if (what) b.what = *what;
+    b.restartless = d->batch_restartless != 0; /* (the option as it is when the call starts) */
+    d->entropy_valid = false;
+    d->entropy_bytes[0] = d->entropy_bytes[1] = 0;
     const bool regions = batch_has_regions(&b);
     b.streams_on_device = gj_hip_is_device_ptr(streams) != 0;
     b.out_on_device = gj_hip_is_device_ptr(output) != 0;
@@ -1586,6 +1622,7 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
         b.stats[0] = b.unselected ? 2 : 1;
         memcpy(d->region_stats, b.stats, sizeof d->region_stats);
     }
+    d->entropy_valid = b.restartless;
     rc = 0; /* (c->frames counts the frames TIMED with perf_stats, src/gpujpeg_common.c:2238-2254: a batch adds none) */
 out:
     if (rc != 0 && b.host_io) gj_hip_stream_sync(c->stream); /* (what is queued on the stream must not read the caller's streams or write its frames after the error has left) */
@@ -1609,6 +1646,7 @@ int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder* d, const ui
                                              struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !origins) return -1;
+    d->entropy_valid = false;
     if (width < 1 || height < 1) {
         GJ_ERROR("A batch of regions needs a width and a height of at least 1 (given: %d x %d)!\n", width, height);
         return -1;
@@ -1634,6 +1672,7 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
                                     struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !rects) return -1;
+    d->entropy_valid = false;
     d->prescales_n = 0;
     if (out_width < 1 || out_height < 1 || out_width > 16384 || out_height > 16384) {
         GJ_ERROR("Crop-and-resize needs an output width and height of 1 to 16384 (given: %d x %d)!\n", out_width, out_height);
@@ -1708,6 +1747,7 @@ int gpujpeg_amd_decoder_decode_batch_crop_resize_tensor(struct gpujpeg_decoder* 
                                                         struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !rects) return -1;
+    d->entropy_valid = false;
     d->prescales_n = 0;
     if (!format) {
         GJ_ERROR("Tensor output needs a format!\n");
@@ -1884,6 +1924,12 @@ int gpujpeg_decoder_set_option(struct gpujpeg_decoder* d, const char* opt, const
         GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE_SUBSAMPLED " (" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_OFF " or " GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_ON ")\n", val);
         return GPUJPEG_ERROR;
     }
+    if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS) == 0) { /* read by every batch call when it starts */
+        if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_OFF) == 0) { d->batch_restartless = 0; return GPUJPEG_NOERR; }
+        if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_ON) == 0) { d->batch_restartless = 1; return GPUJPEG_NOERR; }
+        GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS " (" GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_OFF " or " GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_ON ")\n", val);
+        return GPUJPEG_ERROR;
+    }
     if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_BATCH_SIZES) == 0) { /* read by gpujpeg_amd_decoder_decode_batch_crop_resize (and _tensor) alone */
         if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME) == 0) { d->batch_sizes_mixed = 0; return GPUJPEG_NOERR; }
         if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED) == 0) { d->batch_sizes_mixed = 1; return GPUJPEG_NOERR; }
@@ -1923,6 +1969,7 @@ void gpujpeg_decoder_print_options(void)
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE "=[1|1/2|1/4|1/8] - largest reduced-size IDCT crop-and-resize may put ahead of its resample (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_FILTER "=[" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_BILINEAR "|" GPUJPEG_AMD_DEC_RESIZE_FILTER_VAL_ANTIALIAS "] - filter of crop-and-resize's resample: four taps, or a footprint that grows with the reduction (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE_SUBSAMPLED "=[" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_OFF "|" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_ON "] - let that prescale reduce 4:2:0 streams too, each component at its own N (MI355X extension)\n");
+    printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS "=[" GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_OFF "|" GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_ON "] - whether the batch calls take streams without restart markers through their batched launches (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_SIZES "=[" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME "|" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED "] - whether the streams of one crop-and-resize call may differ in image size (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_REGION "=[X,Y,W,H|full] - decode the W x H pixels at (X, Y) only (MI355X extension)\n");
 }
@@ -1980,6 +2027,14 @@ int gpujpeg_amd_decoder_get_prescales(struct gpujpeg_decoder* d, uint8_t* dst, i
     if (!d || !dst || d->prescales_n < 1 || capacity < d->prescales_n) return 0;
     memcpy(dst, d->prescales, (size_t)d->prescales_n);
     return d->prescales_n;
+}
+
+int gpujpeg_amd_decoder_get_entropy_bytes(struct gpujpeg_decoder* d, uint64_t out[2])
+{
+    if (!d || !out) return -1;
+    out[0] = d->entropy_valid ? d->entropy_bytes[0] : 0;
+    out[1] = d->entropy_valid ? d->entropy_bytes[1] : 0;
+    return d->entropy_valid ? 0 : -1;
 }
 
 int gpujpeg_amd_decoder_get_region_stats(struct gpujpeg_decoder* d, long out[4])

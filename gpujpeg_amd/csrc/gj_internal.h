@@ -64,8 +64,8 @@ int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const str
  * component less subsampled than the one ahead of it (the reduced planes lie at data_offset N_c^2 / 64: they would overlap otherwise) */
 int gj_geom_prescale_per_component(const gj_geom* full);
 /* the ONE plan of a region call, single frame or frame f of a batch: the three steps above in that order (resize == NULL: a plain region, the first
- * step alone), r->resize / frame.mirror / tensor set, and r->sel_count[sc] = restart segments of scan sc that touch the cover (0 without a restart
- * interval). -1: the rectangle was refused, -2: the resize was; either with the step's own message */
+ * step alone), r->resize / frame.mirror / tensor set, and r->sel_count[sc] = restart segments of scan sc that touch the cover (1 without a restart
+ * interval: the scan's one segment, which gj_segment_in_cover always takes). -1: the rectangle was refused, -2: the resize was; either with the step's own message */
 struct gj_resize { int out_w, out_h, mirror, prescale; gj_tensor tensor; int filter; int subsampled; }; /* prescale: dec_opt_resize_prescale; tensor.on = 0: the bytes of the pixel format;
                                                                                            filter: dec_opt_resize_filter (GJ_RESIZE_FILTER_*; antialias: -3 with a message
                                                                                            for a rectangle more than 256 times the output along an axis, or with a prescale);

@@ -220,10 +220,10 @@ float gj_hip_event_elapsed_ms(gj_event_t a, gj_event_t b)
 // the environment: builds with -DGJ_TUNING_ENV -- the `trace` / `variant` targets of the Makefile and the CPU execution model of
 // tests/hipemu, i.e. what the measurement tools load -- additionally take every setting whose name is in the environment when a coder is created.
 static std::mutex g_tune_mutex;
-static gj_tuning g_tune = {/*no_fused*/ 0, /*enc_split*/ -1, /*enc_tail*/ -1, 0, 0, 0, 0, /*dec_tokens*/ -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static gj_tuning g_tune = {/*no_fused*/ 0, /*enc_split*/ -1, /*enc_tail*/ -1, 0, 0, 0, 0, /*dec_tokens*/ -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 static const char* const g_tune_names[] = {"GPUJPEG_NO_FUSED", "GPUJPEG_HOST_SCAN", "GJ_ENC_NO_WHOLE422", "GJ_DEC_TOKENS", "GJ_DEC_NO_TOKENS", "GJ_DEC_ENTROPY", "GJ_DEC_G",
                                            "GJ_DEC_SUB", "GJ_DEC_NO_SPEC", "GJ_DEC_SEQ", "GJ_DEC_DEBUG_SYNC", "GJ_DEC_TOK_NOCOOP", "GJ_SCAN_SHAPE", "GJ_ENC_BLOCKS",
-                                           "GJ_HOST_TIMING", "GJ_DEC_BALANCE", "GJ_ENC_SPLIT", "GJ_ENC_TAIL", "GJ_DEC_FILL", "GJ_ENC_OUT_CAP", "GJ_IDCT_DENSE", "GJ_COPY_LANES", nullptr};
+                                           "GJ_HOST_TIMING", "GJ_DEC_BALANCE", "GJ_ENC_SPLIT", "GJ_ENC_TAIL", "GJ_DEC_FILL", "GJ_ENC_OUT_CAP", "GJ_IDCT_DENSE", "GJ_DEC_NO_EARLY_STOP", "GJ_COPY_LANES", nullptr};
 // one setting: `name` as in INTEGRATION.md's table, `v` its value (may be empty: "the name is present"); false for an unknown name
 static bool gj_tune_apply(gj_tuning* t, const char* name, const char* v)
 {
@@ -250,6 +250,7 @@ static bool gj_tune_apply(gj_tuning* t, const char* name, const char* v)
     else if (is("GJ_DEC_FILL")) t->dec_fill = num;
     else if (is("GJ_ENC_OUT_CAP")) t->enc_out_cap = num;
     else if (is("GJ_IDCT_DENSE")) t->idct_dense = v[0] == '1';
+    else if (is("GJ_DEC_NO_EARLY_STOP")) t->dec_no_early_stop = v[0] == '1';
     else if (is("GJ_COPY_LANES")) { // (process-wide, not per coder: 0 turns the copy lanes off, <MiB> moves the size from which a copy takes them)
         std::lock_guard<std::mutex> lk(g_lane_mutex);
         g_lanes_enabled = !(v[0] == '0' && v[1] == 0);
@@ -261,7 +262,7 @@ extern "C" int gj_hip_tuning_setting(const char* setting)
 {
     std::lock_guard<std::mutex> lk(g_tune_mutex);
     if (setting == nullptr) { // back to the defaults
-        g_tune = gj_tuning{0, -1, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        g_tune = gj_tuning{0, -1, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         std::lock_guard<std::mutex> lk2(g_lane_mutex);
         g_lanes_enabled = 1;
         g_lane_min_bytes = (size_t)1 << 20;

@@ -30,6 +30,10 @@ RESTART_AUTO, RESTART_NONE = -1, 0
 # explicit restart interval, so that its streams share one header but for the dimensions.
 DEC_OPT_BATCH_SIZES = "dec_opt_batch_sizes"
 BATCH_SIZES_SAME, BATCH_SIZES_MIXED = "same", "mixed"
+# Decoder.set_option(DEC_OPT_BATCH_RESTARTLESS, BATCH_RESTARTLESS_ON): the batch calls take streams without restart markers (what libjpeg, PIL and
+# OpenCV write) through their batched launches (GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS); with it a dataset needs no explicit restart interval
+DEC_OPT_BATCH_RESTARTLESS = "dec_opt_batch_restartless"
+BATCH_RESTARTLESS_OFF, BATCH_RESTARTLESS_ON = "off", "on"
 # encoder option of the MI355X build (gpujpeg_amd_ext.h: GPUJPEG_AMD_ENC_OPT_HUFFMAN): Annex K.3 tables, or tables built per frame
 ENC_OPT_HUFFMAN = "enc_opt_huffman"
 ENC_HUFFMAN_STANDARD, ENC_HUFFMAN_OPTIMAL = "standard", "optimal"
@@ -649,6 +653,14 @@ class Decoder:
         self.lib.L.gpujpeg_amd_decoder_get_region_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
         assert self.lib.L.gpujpeg_amd_decoder_get_region_stats(self.h, a) == 0
         return tuple(int(x) for x in a)
+
+    def entropy_bytes(self):
+        """gpujpeg_amd_decoder_get_entropy_bytes: (rc, bytes handed to the entropy decoders by the batched launches, bytes of them that were read) of the
+        last batch call made with set_option(DEC_OPT_BATCH_RESTARTLESS, BATCH_RESTARTLESS_ON); (-1, 0, 0) after any other call"""
+        a = (C.c_uint64 * 2)()
+        self.lib.L.gpujpeg_amd_decoder_get_entropy_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        rc = self.lib.L.gpujpeg_amd_decoder_get_entropy_bytes(self.h, a)
+        return int(rc), int(a[0]), int(a[1])
 
     def path_counters(self):
         """(speculative launches, of those without the k_marker_table launch, decoded again the careful way) of this decoder so far"""

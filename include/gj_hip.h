@@ -167,6 +167,8 @@ typedef struct gj_tuning {
                             capacity (0: the buffer's size); tests of the overflow guard, which no image reaches through the public API */
     int idct_dense;      /* GJ_IDCT_DENSE=1: every wave of k_idct_tok_rgb444 takes the dense body (full 8x8 transform of the chrominance blocks too); A/B
                             runs on one build, tests of the corner path */
+    int dec_no_early_stop; /* GJ_DEC_NO_EARLY_STOP=1: a batch of regions on restart-less streams (dec_opt_batch_restartless) entropy-decodes every scan to its
+                            end instead of leaving it behind the cover's last block (A/B runs; the bytes are the same) */
     int dec_careful;     /* set by the host for ONE call, never from the environment: a kernel that takes whole segments into LDS met one that
                             does not fit (overflow flag) -- this call uses the kernels without that limit */
 } gj_tuning;
@@ -335,6 +337,12 @@ typedef struct gj_region {
      * the triangle filter of k_resize_region_aa (gj_device.h: gj_resize_aa_taps) over frames of scale 1 -- with a prescaled frame, or outside a
      * resize job, anything but BILINEAR is refused */
     int filter;
+    /* ... and, a batch of regions (d_frames) launched with gj_dec_job::batch_restartless: pinned host words, or NULL. h_sel_bytes[frame]: the sum of the
+     * table lengths of the entries the frame's selection found (k_segment_select_batch) -- what the entropy decoder is handed. h_left_early[frame x
+     * GJ_MAX_COMP + scan]: the bytes of a restart-less scan k_huffman_decode_par did NOT read because the cover's last block had been decoded (the
+     * host zeroes the words before the launch; NULL: every scan is decoded to its end) */
+    uint32_t* h_sel_bytes;
+    uint32_t* h_left_early;
 } gj_region;
 enum { GJ_RESIZE_FILTER_BILINEAR = 0, GJ_RESIZE_FILTER_ANTIALIAS = 1 };
 /* the predicate of the selection (gj_device.h: gj_segment_in_cover) for host code: does restart segment s have a block / an MCU inside the cover?
@@ -402,6 +410,9 @@ typedef struct gj_dec_job {
      * rectangle each: gs then holds the planes of the LARGEST cover of the batch -- per component the widest and the highest one --, every frame's
      * cover planes are laid out like that (gj_frame_strides::coefs bytes apart in d_planes) and gs.fb = g.fb. */
     gj_region region;
+    /* dec_opt_batch_restartless: 1 = a batch (gj_dec_job::batch) of streams WITHOUT restart markers is taken -- one segment per scan, decoded piece
+     * by piece by k_huffman_decode_par, plane mode -- and a batch of regions on them selects every segment. 0: gj_hip_decode_batchable says no */
+    int batch_restartless;
 } gj_dec_job;
 /* 1 when gj_hip_decode takes a batch (gj_dec_job::batch.count > 1) of this job's configuration */
 GJ_HIP_API int gj_hip_decode_batchable(const gj_dec_job* job);

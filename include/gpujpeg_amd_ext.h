@@ -198,6 +198,33 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
 #define GPUJPEG_AMD_DEC_OPT_BATCH_SIZES "dec_opt_batch_sizes"
 #define GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME "same"
 #define GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED "mixed"
+/* Decoder option "dec_opt_batch_restartless" = "off" (default) or "on": whether the batch calls -- gpujpeg_amd_decoder_decode_batch, _decode_batch_ptrs
+ * (with and without dec_opt_scale), _decode_batch_regions, _decode_batch_crop_resize and _decode_batch_crop_resize_tensor (dec_opt_batch_sizes "same" and
+ * "mixed", with the prescale, subsampled-prescale and antialias options) -- take streams WITHOUT restart markers (no DRI segment, restart interval 0:
+ * what libjpeg, PIL, OpenCV and cameras write) through their batched launches. Read by every batch call when it starts; it holds from the next call on
+ * and may be changed between two calls of a decoder. Another value is refused by gpujpeg_decoder_set_option (GPUJPEG_ERROR) and leaves the setting as it
+ * was. With "off" every byte, counter, launch, refusal and kernel-times slot of every call is what it is without the option.
+ * WITH "on" it overrides, in the comments of this header, every "restart interval 0" in a list of what goes frame by frame inside a batch call
+ * (dec_opt_scale, dec_opt_batch_sizes "Routing", the frame-batch introduction, gpujpeg_amd_decoder_decode_batch_regions and
+ * gpujpeg_amd_decoder_decode_batch_crop_resize) and the advice under "Encoding" to give a dataset an explicit restart interval: a folder of files written
+ * by one tool at one quality is one family under dec_opt_batch_sizes = mixed as it is. Nothing else of those lists changes: another header, damaged
+ * markers, frame 0 of a fresh decoder or of a call with host output, and a small stream of several scans whose SOS / SOS / EOI markers share one 4 KB
+ * part of the marker scan still go the single-frame route. Frame f stays, byte for byte (tensor call: bit for bit), what the single-frame call
+ * returns for stream f; gpujpeg_amd_decoder_last_batch counts such frames as batched. Entropy decoding is k_huffman_decode_par through the coefficient
+ * planes (no token mode for these streams): a scan that does not fit the kernel's 8 KB stage is one workgroup that walks it piece by piece, so it
+ * is the BATCH that fills the device, not the frame.
+ *   Regions.   A scan without restart markers cannot be entered in the middle: a selection on such a stream is still every segment of every scan, and
+ *              gpujpeg_amd_decoder_get_region_stats counts them so (out[0] is 1 where the batched launches took the frames; the single-frame region
+ *              call, which is not changed, says 2 and decodes every scan to its end). But it can be LEFT: in a batch of regions or of crop-and-resize
+ *              the workgroup stops reading a scan after the piece that completes the last block of the frame's cover (a prescaled frame: the expanded
+ *              covering rectangle's). Scans that fit the stage whole are decoded whole. What lies in the batch's coefficient planes behind the
+ *              cover is never read: every later call fills the blocks it decodes first.
+ *   gpujpeg_amd_decoder_get_entropy_bytes: after a batch call made with "on", out[0] = the entropy-coded bytes (segment-table lengths) of the segments
+ *              the batched launches handed to the entropy decoders, summed over the frames they took; out[1] = the bytes of them that were read --
+ *              equal unless a scan was left early. Returns 0. After any other call: both 0, returns -1. */
+#define GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS "dec_opt_batch_restartless"
+#define GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_OFF "off"
+#define GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_ON "on"
 /* Host-only: the table enc_opt_huffman=optimal builds for one class from symbol counts freq[256] (ITU T.81 Annex K.2: Figures K.1, K.3, K.4;
  * reserved code point, ties to the larger symbol value), code lengths limited to the largest L of 16 .. 10 whose table the library's
  * two-level decode tables take. Writes BITS (bits[1..16]) and HUFFVAL; returns L, or -1 when no count is non-zero. */
@@ -262,6 +289,9 @@ GPUJPEG_API int gpujpeg_amd_decoder_decode_batch(struct gpujpeg_decoder* decoder
  * region, 1 = region, entropy-decoded the selected restart segments only, 2 = region, every segment entropy-decoded (fallback); out[1] restart
  * segments handed to the entropy decoder; out[2] 8x8 blocks the IDCT side transformed; out[3] segments in the stream */
 GPUJPEG_API int gpujpeg_amd_decoder_get_region_stats(struct gpujpeg_decoder* decoder, long out[4]);
+/* entropy-coded bytes handed to / read by the entropy decoders of the batched launches of the last batch call made with dec_opt_batch_restartless = on
+ * (see there); 0, or -1 with both words 0 after any other call */
+GPUJPEG_API int gpujpeg_amd_decoder_get_entropy_bytes(struct gpujpeg_decoder* decoder, uint64_t out[2]);
 /* A batch of regions: gpujpeg_amd_decoder_decode_batch with one crop per frame -- frame f is the `width` x `height` pixels at
  * (origins[2f], origins[2f + 1]) of stream f's image. The bytes at output + f * output_stride are exactly what gpujpeg_decoder_decode of this decoder
  * returns for stream f with dec_opt_region = "X_f,Y_f,width,height" (every output format and colour space, dec_opt_alignment_bytes, the planar crop
