@@ -2,6 +2,7 @@
 // Restates src/gpujpeg_huffman_gpu_decoder.cu:135-495 (identical results to src/gpujpeg_huffman_cpu_decoder.c:245-372).
 // (part of the decoder's device code, see gj_dec_internal.h for the map of the files)
 #include "gj_dec_internal.h"
+#include "gj_bitreader.h"
 
 // ================================================================================================
 // Entropy decoder: one lane per restart segment (the code is serial inside a segment).
@@ -53,24 +54,6 @@ __device__ __forceinline__ void gj_fill_windows(unsigned long long mask, const u
             if (js[u] >= 0) s_win[js[u] * GJ_WIN_STRIDE + lane] = v[u];
     }
     gj_wave_sync();
-}
-
-// canonical search for codes longer than the fast table (ITU T.81 F.2.2.3); rare
-__device__ __forceinline__ uint32_t gj_decode_slow(uint32_t hi, const uint16_t* t)
-{
-    const uint16_t* maxcode = t + 1024;           // [18] as (lo, hi)
-    const uint16_t* valptr = t + 1024 + 36;       // [17]
-    const uint16_t* mincode = t + 1024 + 36 + 17; // [17] as (lo, hi)
-    const uint16_t* vals = t + 1024 + 36 + 17 + 34;
-    for (int l = GJ_DEC_FAST_BITS + 1; l <= 16; l++) {
-        const int code = (int)(hi >> (32 - l));
-        const int mx = (int)((uint32_t)maxcode[2 * l] | ((uint32_t)maxcode[2 * l + 1] << 16));
-        if (mx >= 0 && code <= mx) {
-            const int mn = (int)((uint32_t)mincode[2 * l] | ((uint32_t)mincode[2 * l + 1] << 16));
-            return ((uint32_t)l << 8) | vals[(valptr[l] + code - mn) & 0xFF];
-        }
-    }
-    return (16u << 8); // corrupt stream: consume 16 bits, symbol 0 (output is undefined but in bounds)
 }
 
 // The loop body is written to compile to (almost) straight-line predicated code: a lone wave per SIMD pays for every

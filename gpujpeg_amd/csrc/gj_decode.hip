@@ -87,8 +87,20 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     if ((g.fb.geoms != nullptr || job->batch.d_geoms != nullptr) &&
         (!rg_batch || !rg.resize || job->tokens || g.fb.geoms != job->batch.d_geoms || job->gs.fb.geoms != g.fb.geoms || job->tune.dec_sub))
         return -1;
+    // (a progressive frame, gj_dec_job::prog: a single frame through the coefficient planes -- its own entropy stage, then the plane route's IDCT side)
+    if (job->prog != nullptr && (g.fb.sizes != nullptr || job->batch.count > 1 || job->tokens || job->scan.valid || rg.select || job->prog->levels < 0 ||
+                                 job->prog->levels > GJ_PROG_MAX_SCANS))
+        return -1;
     gj_hip_note_reset();
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[0], st));
+    if (job->prog != nullptr) {
+        gj_launch_huffman_prog(job, st);
+        gj_debug_stage(job->tune.debug_sync != 0, st, "entropy decoder (progressive)");
+        if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[1], st));
+        gj_launch_idct(job, st, nullptr, ev);
+        if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[3], st));
+        return (hipGetLastError() == hipSuccess && !gj_hip_noted()) ? 0 : -1;
+    }
     bool par = job->d_huff_tab2 != nullptr && job->seg_count > 0;
     if (job->tune.dec_serial) par = false; // the lane-per-segment kernel (A/B measurements, tests)
     const bool fast_ok = par && !job->tune.dec_careful && job->d_overflow != nullptr; // kernels that take whole segments into LDS are allowed

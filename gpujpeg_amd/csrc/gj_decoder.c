@@ -135,6 +135,15 @@ struct gpujpeg_decoder {
     uint64_t entropy_bytes[2]; bool entropy_valid;
     uint32_t* bh_sel_bytes; size_t bh_sel_bytes_cap;
     uint32_t* bh_left; size_t bh_left_cap;
+    /* dec_opt_progressive: 1 = the reader takes SOF2 (the option alone sets the reader's flag). A progressive frame has its own route (dec_progressive):
+     * its scan list, the pinned staging and the device copy of its work list -- decode tables of every table snapshot, then the records --, and its
+     * OWN quantisation tables (u16, then float): d_huff_tab holds the cached header's, which such a frame must leave alone */
+    int progressive;
+    struct gj_prog_info prog;
+    uint8_t* d_prog; size_t d_prog_cap;
+    uint8_t* h_prog; size_t h_prog_cap;
+    uint16_t* d_prog_q; uint16_t* h_prog_q;
+    long prog_stats[4]; bool prog_stats_valid;     /* gpujpeg_amd_decoder_get_progressive_stats */
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
@@ -290,6 +299,7 @@ int gpujpeg_decoder_destroy(struct gpujpeg_decoder* d)
     gj_hip_free(d->b_sel); gj_hip_free(d->b_rgn); gj_hip_host_free(d->bh_rgn); gj_hip_host_free(d->bh_found);
     gj_hip_host_free(d->bh_hdrs); gj_hip_host_free(d->bh_geoms); gj_hip_free(d->b_geoms);
     gj_hip_host_free(d->bh_sel_bytes); gj_hip_host_free(d->bh_left);
+    gj_prog_info_free(&d->prog); gj_hip_free(d->d_prog); gj_hip_host_free(d->h_prog); gj_hip_free(d->d_prog_q); gj_hip_host_free(d->h_prog_q);
     free(d);
     return 0;
 }
@@ -491,7 +501,7 @@ static int dec_host_view(struct gpujpeg_decoder* d, struct dec_call* k)
     }
     k->himage = k->jpeg_on_device ? k->host_copy : k->image;
     const int rc = gj_reader_parse(k->himage, k->image_size, c->param.verbose, d->ff_cs_itu601_is_709, d->req_pixel_format, d->req_color_space,
-                                   d->req_alignment, &k->r, false);
+                                   d->req_alignment, &k->r, false, d->progressive != 0);
     if (rc != 0) GJ_ERROR("Decoder failed when decoding image data!\n");
     return rc > 0 ? -1 : rc; /* (the reader's own error code is what the call returns; a positive one would read as DEC_AGAIN) */
 }
@@ -505,6 +515,12 @@ static int dec_headers(struct gpujpeg_decoder* d, struct dec_call* k)
     /* speculative path: same header as last time (compared on the device for a device-resident stream) */
     k->spec = may_scan && d->hdr_cache_valid && k->image_size > d->hdr_cache_len && !d->tune.dec_no_spec && !k->careful;
     if (k->spec && !k->jpeg_on_device) k->spec = memcmp(k->image, d->hdr_cache, d->hdr_cache_len) == 0;
+    /* (dec_opt_progressive = on: a device-resident stream may be a progressive one, which never launches on the cached header and leaves the cache
+     * alone -- its header is looked at on the host first, where without the option the device compares it behind the launch) */
+    if (k->spec && k->jpeg_on_device && d->progressive) {
+        if (gj_hip_memcpy_d2h(d->h_hdr, k->image, d->hdr_cache_len, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) return -1;
+        k->spec = memcmp(d->h_hdr, d->hdr_cache, d->hdr_cache_len) == 0;
+    }
     if (k->spec) {
         k->r = d->hdr_cache_r;
         k->device_scan = true;
@@ -519,8 +535,9 @@ static int dec_headers(struct gpujpeg_decoder* d, struct dec_call* k)
     /* an odd header, or an APP13 index that makes scanning unnecessary: the host walk */
     k->device_scan = may_scan &&
                      gj_reader_parse(k->himage, hsize, hsize < k->image_size ? GPUJPEG_LL_QUIET - 1 : c->param.verbose, d->ff_cs_itu601_is_709,
-                                     d->req_pixel_format, d->req_color_space, d->req_alignment, &k->r, true) == 0 &&
+                                     d->req_pixel_format, d->req_color_space, d->req_alignment, &k->r, true, d->progressive != 0) == 0 &&
                      k->r.seg_info_count[0] == 0;
+    if (k->device_scan && k->r.progressive) k->device_scan = false; /* (a progressive frame: the host walks every scan) */
     return k->device_scan ? 0 : dec_host_view(d, k);
 }
 
@@ -908,6 +925,150 @@ static void dec_stats(struct gpujpeg_decoder* d, const struct dec_call* k)
                 gpujpeg_pixel_format_get_name(output->param_image.pixel_format), gpujpeg_color_space_get_name(output->param_image.color_space));
 }
 
+/* ---- progressive frames (dec_opt_progressive) ---- */
+/* The plan of a progressive frame, from its scan list (d->prog) and the coder's geometry: the decode tables of every table snapshot and one record
+ * per restart segment of every scan (gj_hip.h: gj_prog_rec), the records of a level back to back, staged in pinned memory and uploaded. 0 or -1. */
+static int prog_plan(struct gpujpeg_decoder* d, gj_prog_plan* plan)
+{
+    struct gj_coder* c = &d->coder;
+    const gj_geom* g = &c->geom;
+    const struct gj_prog_info* info = &d->prog;
+    const size_t tab_bytes = ((size_t)info->pool_count * GJ_DEC_TAB_WORDS * sizeof(uint16_t) + 15) & ~(size_t)15;
+    const size_t nrec = (size_t)info->segs.count;
+    const size_t bytes = tab_bytes + (nrec + 1) * sizeof(gj_prog_rec);
+    if (gj_ensure_pinned_buffer((void**)&d->h_prog, &d->h_prog_cap, bytes, bytes * 2) != 0) return -1;
+    if (gj_ensure_device_buffer((void**)&d->d_prog, &d->d_prog_cap, bytes) != 0) return -1;
+    memset(d->h_prog, 0, bytes);
+    for (int t = 0; t < info->pool_count; t++)
+        if (gj_huffman_decoder_table(info->pool[t].bits, info->pool[t].vals, (uint16_t*)(void*)d->h_prog + (size_t)t * GJ_DEC_TAB_WORDS) != 0) {
+            GJ_ERROR("Invalid Huffman table in a progressive scan!\n");
+            return -1;
+        }
+    gj_prog_rec* recs = (gj_prog_rec*)(void*)(d->h_prog + tab_bytes);
+    memset(plan, 0, sizeof *plan);
+    uint32_t at = 0;
+    for (int level = 0; level < info->levels; level++) {
+        plan->level_first[level] = at;
+        for (int si = 0; si < info->scan_count; si++) {
+            const struct gj_prog_scan* s = &info->scan[si];
+            if (s->level != level) continue;
+            const int ri = s->restart_interval;
+            for (int j = 0; j < s->seg_count; j++) {
+                const int e = s->seg_first + j;
+                const uint32_t number = info->segs.index[e]; /* the segment's number inside its scan */
+                const uint64_t first = ri > 0 ? (uint64_t)number * (uint64_t)ri : 0;
+                if (first >= (uint64_t)s->units) continue;
+                gj_prog_rec* q = &recs[at++];
+                q->pos = info->segs.pos[e];
+                q->len = info->segs.len[e];
+                q->first = (uint32_t)first;
+                q->count = ri > 0 && first + (uint64_t)ri < (uint64_t)s->units ? (uint32_t)ri : (uint32_t)((uint64_t)s->units - first);
+                q->across = (uint32_t)s->across;
+                q->kind = (uint8_t)(s->ss == 0 ? (s->ah == 0 ? GJ_PROG_DC_FIRST : GJ_PROG_DC_REFINE) : (s->ah == 0 ? GJ_PROG_AC_FIRST : GJ_PROG_AC_REFINE));
+                q->ncomp = (uint8_t)s->ncomp;
+                q->ss = (uint8_t)s->ss; q->se = (uint8_t)s->se; q->ah = (uint8_t)s->ah; q->al = (uint8_t)s->al;
+                for (int i = 0; i < s->ncomp; i++) {
+                    const gj_comp_geom* k = &g->comp[s->comp[i]];
+                    q->c[i].base = (uint32_t)(k->data_offset / 64);
+                    q->c[i].pitch = (uint32_t)k->blocks_x;
+                    q->c[i].table = (uint16_t)(s->table[i] >= 0 ? s->table[i] : 0);
+                    q->c[i].h = (uint8_t)(s->ncomp > 1 ? k->samp_h : 1);
+                    q->c[i].v = (uint8_t)(s->ncomp > 1 ? k->samp_v : 1);
+                }
+            }
+        }
+        plan->level_count[level] = at - plan->level_first[level];
+    }
+    plan->levels = info->levels;
+    plan->d_tabs = (const uint16_t*)(const void*)d->d_prog;
+    plan->tab_count = (uint32_t)info->pool_count;
+    plan->d_recs = (const gj_prog_rec*)(const void*)(d->d_prog + tab_bytes);
+    if (gj_hip_memcpy_h2d(d->d_prog, d->h_prog, tab_bytes + (size_t)at * sizeof(gj_prog_rec), c->stream) != 0) return -1;
+    d->prog_stats[0] = 1;
+    d->prog_stats[1] = info->scan_count;
+    d->prog_stats[2] = info->levels;
+    d->prog_stats[3] = (long)at;
+    return 0;
+}
+
+/* A progressive frame, once its first headers are parsed (k->r, k->himage the whole stream): the careful route only -- the host walks every scan, no
+ * launch on the header cache (which is neither read nor written), no device marker scan, no tokens, no selection. The scans fill the coefficient
+ * planes (gj_dec_job::prog), the IDCT side is the plane route of a baseline frame of this geometry, whatever the call asked for. */
+static int dec_progressive(struct gpujpeg_decoder* d, struct dec_call* k)
+{
+    struct gj_coder* c = &d->coder;
+    const struct gj_reader_result* r = &k->r;
+    d->prog_stats_valid = true;
+    memset(d->prog_stats, 0, sizeof d->prog_stats);
+    k->spec = k->device_scan = k->select = false;
+    if (gj_reader_parse_progressive(k->himage, k->image_size, r, &d->prog, false) != 0 || d->prog.bad_scan != 0) {
+        GJ_ERROR("Decoder failed when decoding image data!\n");
+        return DEC_FAILED;
+    }
+    for (int i = 0; i < r->param.comp_count; i++)
+        if (!r->q_present[r->quant_map[i]]) {
+            GJ_ERROR("Component %d refers to a table that was not defined!\n", i);
+            return DEC_FAILED;
+        }
+    for (int i = 0; i < GPUJPEG_METADATA_COUNT; i++) d->metadata.vals[i] = r->metadata.vals[i];
+    if (decoder_configure(d, &r->param, &r->param_image) != 0 || dec_call_geometry(d, k->req) != 0) return DEC_FAILED;
+    c->init_end_time = k->stats ? gpujpeg_get_time() : 0;
+    if (dec_upload(d, k) != 0) return DEC_FAILED;
+    gj_prog_plan plan;
+    if (prog_plan(d, &plan) != 0) return DEC_FAILED;
+    /* quantisation tables: natural order, u16 and float, in the frame's own buffer */
+    const size_t q_bytes = 4 * 64 * (sizeof(uint16_t) + sizeof(float));
+    if (!d->d_prog_q) d->d_prog_q = gj_hip_malloc(q_bytes);
+    if (!d->h_prog_q) d->h_prog_q = gj_hip_host_alloc(q_bytes);
+    if (!d->d_prog_q || !d->h_prog_q) return DEC_FAILED;
+    memset(d->h_prog_q, 0, q_bytes);
+    for (int t = 0; t < 4; t++)
+        if (r->q_present[t]) {
+            uint16_t* qi = d->h_prog_q + t * 64;
+            float* qf = (float*)(void*)(d->h_prog_q + 4 * 64) + t * 64;
+            gj_quant_table_inverse(r->qraw[t], qi);
+            for (int i = 0; i < 64; i++) qf[i] = (float)qi[i];
+        }
+    if (gj_hip_memcpy_h2d(d->d_prog_q, d->h_prog_q, q_bytes, c->stream) != 0) return DEC_FAILED;
+    c->stats.duration_stream = k->stats ? (gpujpeg_get_time() - k->t_read0) * 1000.0 : 0;
+    if (k->stats) gj_hip_event_record(c->timers.copy_in[1], c->stream);
+    if (dec_destination(d, k) != 0) return DEC_FAILED;
+    for (int i = 0; i < c->geom.comp_count; i++) {
+        c->geom.comp[i].q_table = r->quant_map[i];
+        c->geom.comp[i].dc_table = c->geom.comp[i].ac_table = 0;
+    }
+    gj_dec_job job;
+    dec_job_base(d, false, &job);
+    job.d_qtab = d->d_prog_q;
+    job.d_qtabf = (const float*)(const void*)(d->d_prog_q + 4 * 64);
+    job.d_jpeg = k->d_jpeg;
+    job.jpeg_size = k->image_size;
+    job.d_raw = k->d_raw;
+    job.prog = &plan;
+    d->last_folded = 0;
+    d->scan_timed = false;
+    if (gj_channel_remap_check(d->channel_remap, c->param_image.pixel_format) != 0) return DEC_FAILED;
+    if (gj_hip_decode(&job, c->stream, k->stats ? c->timers.ev : NULL) != 0) {
+        GJ_ERROR("Decoder kernels failed: %s\n", gj_hip_last_error());
+        return DEC_FAILED;
+    }
+    if (dec_download(d, k) != 0) return DEC_FAILED;
+    GJ_HT(c, 1);
+    if (gj_hip_stream_sync(c->stream) != 0) {
+        GJ_ERROR("Decoder failed: %s\n", gj_hip_last_error());
+        return DEC_FAILED;
+    }
+    GJ_HT(c, 2);
+    d->region_stats[0] = d->img.region ? 2 : 0;
+    d->region_stats[1] = d->region_stats[3] = d->prog_stats[3];
+    d->region_stats[2] = d->img.region ? (long)d->img.geom.block_count : (long)c->geom.block_count;
+    dec_stats(d, k);
+    k->output->metadata = &d->metadata;
+    GJ_HT(c, 3);
+    c->ht_calls++;
+    return DEC_DONE;
+}
+
 /* one attempt: the stages in the order their work goes onto the stream */
 static int dec_attempt(struct gpujpeg_decoder* d, struct dec_call* k)
 {
@@ -920,6 +1081,9 @@ static int dec_attempt(struct gpujpeg_decoder* d, struct dec_call* k)
 
     int rc = dec_headers(d, k);
     if (rc != 0) return rc;
+    if (k->r.progressive) return dec_progressive(d, k);
+    memset(d->prog_stats, 0, sizeof d->prog_stats);
+    d->prog_stats_valid = true;
     for (int i = 0; i < GPUJPEG_METADATA_COUNT; i++) d->metadata.vals[i] = k->r.metadata.vals[i];
     if (decoder_configure(d, &k->r.param, &k->r.param_image) != 0 || dec_call_geometry(d, k->req) != 0) return DEC_FAILED;
     c->init_end_time = k->stats ? gpujpeg_get_time() : 0;
@@ -1033,6 +1197,8 @@ struct dec_batch {
     int n_fam;                           /* such frames from `first` on */
     gj_geom g_max;                       /* the launch's geometry: the family's, with the segment, block and sample counts of its largest frames */
     bool restartless;                    /* dec_opt_batch_restartless = on: streams without restart markers go through the batched launches too */
+    bool ahead_progressive;              /* frame 0 went ahead and was a progressive frame: it planned no rectangles (batch_decode_one); ahead_w x ahead_h: its image */
+    int ahead_w, ahead_h;
 };
 
 /* one rectangle per frame: a batch of regions, or crop-and-resize */
@@ -1140,7 +1306,7 @@ static int batch_mixed_prepare(struct gpujpeg_decoder* d, struct dec_batch* b, i
             if (gj_hip_memcpy_d2h(d->h_hdr, himage, hsize, c->stream) != 0 || gj_hip_stream_sync(c->stream) != 0) { free(rr); return -1; }
             himage = d->h_hdr;
         }
-        ok = hsize > 4 && gj_reader_parse(himage, hsize, GPUJPEG_LL_QUIET - 1, d->ff_cs_itu601_is_709, d->req_pixel_format, d->req_color_space, d->req_alignment, rr, true) == 0;
+        ok = hsize > 4 && gj_reader_parse(himage, hsize, GPUJPEG_LL_QUIET - 1, d->ff_cs_itu601_is_709, d->req_pixel_format, d->req_color_space, d->req_alignment, rr, true, d->progressive != 0) == 0;
         gj_geom gf, gs;
         gj_region rg;
         struct gpujpeg_image_parameters pr;
@@ -1259,7 +1425,13 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
         if (d->region_stats[0] != 1) b->unselected = true;
         for (int i = 1; i < 4; i++) b->stats[i] += d->region_stats[i];
         /* (frame 0 ahead of everything: the streams' geometry is known now -- every rectangle is checked before a pixel goes to the caller's slots) */
-        if (ahead && batch_regions_plan(d, b, 1) != 0) return -1;
+        /* (a PROGRESSIVE frame 0 tells nothing of the kind about the baseline streams behind it -- its restart interval is its own, and the plan counts restart
+         * segments --: the rectangles are then planned against the header the batched launches run on, batch_launches) */
+        if (ahead && !b->what.mixed && d->prog_stats[0] != 0) {
+            b->ahead_progressive = true;
+            b->ahead_w = c->param_image.width;
+            b->ahead_h = c->param_image.height;
+        } else if (ahead && batch_regions_plan(d, b, 1) != 0) return -1;
         if (!ahead && b->planned && !b->what.mixed && (c->param_image.width != b->img_w || c->param_image.height != b->img_h)) {
             GJ_ERROR("Frame %d of the batch is a %dx%d image, the others %dx%d!\n", f, c->param_image.width, c->param_image.height, b->img_w, b->img_h);
             return -1;
@@ -1376,7 +1548,10 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     }
     /* a batch of regions: the rectangles against the cached header's geometry, unless frame 0 went ahead and they have been checked against its own.
      * A rectangle the CACHED header refuses may be one the streams' own header takes (an older sequence's cache): frame 0 goes ahead and decides. */
-    if (regions && !b->planned && batch_regions_plan(d, b, first) != 0) return first == 0 && !force_first && !b->what.mixed ? 1 : -1;
+    /* (behind a progressive frame 0 that went ahead nothing has vouched for the cached header: an older sequence's, of another size than frame 0's image
+     * or with a geometry that refuses a rectangle, is no reason to fail the call -- nothing is launched, and every frame's own call decides) */
+    if (regions && !b->planned && b->ahead_progressive && (r->param_image.width != b->ahead_w || r->param_image.height != b->ahead_h)) return 0;
+    if (regions && !b->planned && batch_regions_plan(d, b, first) != 0) return b->ahead_progressive ? 0 : first == 0 && !force_first && !b->what.mixed ? 1 : -1;
     const bool mixed = regions && b->what.mixed;
     /* (different image sizes: no frame from here on is of the cached header's family -- an older sequence's cache: frame 0 goes ahead and decides --,
      * or nothing to launch) */
@@ -1849,7 +2024,7 @@ int gpujpeg_decoder_get_image_info2(uint8_t* image, size_t image_size, struct gp
 {
     struct gj_reader_result r;
     const bool count_segments = (flags & GPUJPEG_COUNT_SEG_COUNT_REQ) != 0;
-    const int rc = gj_reader_parse(image, image_size, verbose, false, GPUJPEG_PIXFMT_NATIVE, GPUJPEG_NONE, 0, &r, !count_segments);
+    const int rc = gj_reader_parse(image, image_size, verbose, false, GPUJPEG_PIXFMT_NATIVE, GPUJPEG_NONE, 0, &r, !count_segments, false);
     if (rc != 0) return rc;
     memset(info, 0, sizeof *info);
     info->param_image = r.param_image;
@@ -1956,6 +2131,12 @@ int gpujpeg_decoder_set_option(struct gpujpeg_decoder* d, const char* opt, const
         d->region_on = true;
         return GPUJPEG_NOERR;
     }
+    if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_PROGRESSIVE) == 0) { /* holds from the next decode call on */
+        if (strcmp(val, GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_OFF) == 0) { d->progressive = 0; return GPUJPEG_NOERR; }
+        if (strcmp(val, GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_ON) == 0) { d->progressive = 1; return GPUJPEG_NOERR; }
+        GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_PROGRESSIVE " (" GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_OFF " or " GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_ON ")\n", val);
+        return GPUJPEG_ERROR;
+    }
     GJ_ERROR("Invalid decoder option: %s!\n", opt);
     return GPUJPEG_ERROR;
 }
@@ -1971,6 +2152,7 @@ void gpujpeg_decoder_print_options(void)
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE_SUBSAMPLED "=[" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_OFF "|" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_ON "] - let that prescale reduce 4:2:0 streams too, each component at its own N (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS "=[" GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_OFF "|" GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_ON "] - whether the batch calls take streams without restart markers through their batched launches (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_SIZES "=[" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME "|" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED "] - whether the streams of one crop-and-resize call may differ in image size (MI355X extension)\n");
+    printf("\t" GPUJPEG_AMD_DEC_OPT_PROGRESSIVE "=[" GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_OFF "|" GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_ON "] - whether progressive (SOF2) streams are decoded (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_REGION "=[X,Y,W,H|full] - decode the W x H pixels at (X, Y) only (MI355X extension)\n");
 }
 
@@ -2042,6 +2224,42 @@ int gpujpeg_amd_decoder_get_region_stats(struct gpujpeg_decoder* d, long out[4])
     if (!d || !out) return -1;
     memcpy(out, d->region_stats, sizeof d->region_stats);
     return 0;
+}
+
+int gpujpeg_amd_decoder_get_progressive_stats(struct gpujpeg_decoder* d, long out[4])
+{
+    if (!d || !out) return -1;
+    for (int i = 0; i < 4; i++) out[i] = d->prog_stats_valid ? d->prog_stats[i] : 0;
+    return d->prog_stats_valid ? 0 : -1;
+}
+
+int gpujpeg_amd_host_stream_info(const uint8_t* image, size_t size, int out[8])
+{
+    if (!image || !out) return -1;
+    memset(out, 0, 8 * sizeof(int));
+    struct gj_reader_result* r = malloc(sizeof *r);
+    struct gj_prog_info* info = calloc(1, sizeof *info);
+    int rc = -1;
+    if (r && info && gj_reader_parse(image, size, GPUJPEG_LL_QUIET - 1, false, GPUJPEG_PIXFMT_NATIVE, GPUJPEG_NONE, 0, r, false, true) == 0) {
+        out[0] = r->param_image.width;
+        out[1] = r->param_image.height;
+        out[2] = r->param.comp_count;
+        out[3] = r->progressive ? 1 : 0;
+        out[4] = r->scan_count;
+        out[5] = 1;
+        out[6] = r->param.restart_interval;
+        rc = 0;
+        if (r->progressive && (rc = gj_reader_parse_progressive(image, size, r, info, true)) == 0) {
+            out[4] = info->scan_count;
+            out[5] = info->levels;
+            out[7] = info->bad_scan;
+            if (info->scan_count > 0) out[6] = info->scan[0].restart_interval;
+        }
+    }
+    if (info) gj_prog_info_free(info);
+    free(info);
+    free(r);
+    return rc;
 }
 
 void gpujpeg_amd_decoder_set_fused(struct gpujpeg_decoder* d, int enabled) { d->use_fused = enabled != 0; }

@@ -188,6 +188,8 @@ struct gj_reader_result {
     size_t header_end; /* offset of the first SOS marker */
     size_t sof_dims;   /* offset of SOF0's height field: the four bytes height, width (big-endian u16 each) that streams of one family may differ in */
     bool eoi_seen;
+    bool progressive;  /* the frame header is SOF2 (only with allow_progressive): the parse ended at the first SOS -- header_end, scan_begin[0], the tables
+                          defined up to there; param.interleaved says "whole-MCU planes"; the scans are gj_reader_parse_progressive's */
 };
 /* parse every marker; when segments != NULL also split scans at RSTn on the host (reference behaviour) */
 struct gj_host_segments {
@@ -196,8 +198,32 @@ struct gj_host_segments {
 };
 int gj_reader_parse(const uint8_t* image, size_t size, int verbose, bool ff_cs_itu601_is_709,
                     enum gpujpeg_pixel_format req_pixfmt, enum gpujpeg_color_space req_cs, unsigned req_alignment,
-                    struct gj_reader_result* r, bool headers_only);
+                    struct gj_reader_result* r, bool headers_only, bool allow_progressive /* SOF2 is taken (dec_opt_progressive); false: refused as ever */);
 int gj_reader_split_scans(const uint8_t* image, const struct gj_reader_result* r, const gj_geom* g, struct gj_host_segments* segs, int verbose);
+
+/* the scans of a progressive frame (gj_reader.c: gj_reader_parse_progressive) */
+struct gj_prog_scan {
+    int ncomp, comp[GJ_MAX_COMP];   /* components of the scan: indices into the frame's, ascending */
+    int ss, se, ah, al;
+    int restart_interval;           /* as DRI stood at the SOS: MCUs of a scan of several components, BLOCKS of a scan of one */
+    int table[GJ_MAX_COMP];         /* per scan component, the entry of gj_prog_info::pool it decodes with: the DC table in a first DC scan, the AC table
+                                       in an AC scan; -1 in a DC refinement (bits only) */
+    int across, units;              /* what it codes: one component -- the ceil(w_c / 8) x ceil(h_c / 8) blocks of the component in raster order, `across`
+                                       per row (NOT the padded plane's pitch); several -- the MCUs of the frame's grid */
+    size_t begin, end;              /* its entropy-coded data: first byte, the marker behind */
+    int seg_first, seg_count;       /* its restart segments in gj_prog_info::segs (index: the segment's number inside the scan) */
+    int level;                      /* 0, or 1 + the highest level of an earlier scan that shares a component and a coefficient with it */
+};
+struct gj_prog_table { uint8_t bits[17]; uint8_t vals[256]; }; /* BITS / HUFFVAL in force at a scan's SOS */
+struct gj_prog_info {
+    int scan_count, levels;
+    int bad_scan;                   /* 0: a valid script (ITU T.81 Annex G); else 1 + the first scan that breaks a rule */
+    struct gj_prog_scan scan[GJ_PROG_MAX_SCANS];
+    struct gj_prog_table* pool; int pool_count, pool_cap;
+    struct gj_host_segments segs;
+};
+int gj_reader_parse_progressive(const uint8_t* image, size_t size, const struct gj_reader_result* r, struct gj_prog_info* info, bool quiet);
+void gj_prog_info_free(struct gj_prog_info* info);
 
 /* ---- image file I/O (src/utils/image_delegate.c, pam.c, y4m.c) ---- */
 int gj_image_load(const char* filename, enum gpujpeg_image_file_format fmt, uint8_t** image, size_t* size);

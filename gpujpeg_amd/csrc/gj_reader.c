@@ -116,9 +116,11 @@ static int push_segment(struct gj_host_segments* s, uint32_t pos, uint32_t len, 
  *  - an RSTn that is not the expected one ends the segment right there, everything up to the expected marker is skipped (:1074-1100);
  *    if that one never comes before EOI / SOS, the walk goes on and the marker's two bytes stay inside the segment (:1103-1107);
  *  - EOI, SOS and APPn end the scan; an empty last segment is dropped (FFmpeg bug #8412, :1132-1135);
- *  - any other marker is an error (:1145-1148) -- except 0xFF fill bytes, which the reference rejects and we skip (T.81 B.1.1.2). */
+ *  - any other marker is an error (:1145-1148) -- except 0xFF fill bytes, which the reference rejects and we skip (T.81 B.1.1.2).
+ * prog (a scan of a progressive frame, dec_opt_progressive; false: nothing changes): the table and restart definitions that may stand between two
+ * scans (DHT, DQT, DRI) and COM end the scan too, and so does the end of the data -- a progressive stream may stop after any whole scan. */
 static long walk_scan(const uint8_t* image, size_t begin, size_t size, uint32_t first_index, int max_segments,
-                      struct gj_host_segments* segs, int* segment_count)
+                      struct gj_host_segments* segs, int* segment_count, bool prog)
 {
     const uint8_t* p = image + begin;
     const uint8_t* end = image + size;
@@ -129,6 +131,14 @@ static long walk_scan(const uint8_t* image, size_t begin, size_t size, uint32_t 
     int previous = 0xD0 - 1;
     for (;;) {
         const uint8_t* f = memchr(p, 0xFF, (size_t)(end - p));
+        if ((f == NULL || f + 1 >= end) && prog) {
+            if (end > seg_start) {
+                if (segs && idx < max_segments && push_segment(segs, (uint32_t)(seg_start - image), (uint32_t)((size_t)(end - seg_start) - dropped), first_index + (uint32_t)idx) != 0) return -1;
+                idx++;
+            }
+            *segment_count = idx;
+            return (long)size;
+        }
         if (f == NULL || f + 1 >= end) {
             GJ_ERROR("JPEG data unexpected ended while reading SOS marker!\n");
             return -1;
@@ -177,7 +187,7 @@ static long walk_scan(const uint8_t* image, size_t begin, size_t size, uint32_t 
             dropped = 0;
             continue;
         }
-        if (m == 0xD9 || m == 0xDA || (m >= 0xE0 && m <= 0xEF)) {
+        if (m == 0xD9 || m == 0xDA || (m >= 0xE0 && m <= 0xEF) || (prog && (m == 0xC4 || m == 0xDB || m == 0xDD || m == 0xFE))) {
             /* end of the scan; an empty trailing segment is dropped */
             if (f > seg_start) {
                 if (segs && idx < max_segments && push_segment(segs, (uint32_t)(seg_start - image), (uint32_t)((size_t)(f - seg_start) - dropped), first_index + (uint32_t)idx) != 0) return -1;
@@ -261,7 +271,7 @@ static bool seg_info_valid(const struct gj_reader_result* r, int scan, size_t be
 }
 
 int gj_reader_parse(const uint8_t* image, size_t size, int verbose, bool ff_cs_itu601_is_709, enum gpujpeg_pixel_format req_pixfmt,
-                    enum gpujpeg_color_space req_cs, unsigned req_alignment, struct gj_reader_result* r, bool headers_only)
+                    enum gpujpeg_color_space req_cs, unsigned req_alignment, struct gj_reader_result* r, bool headers_only, bool allow_progressive)
 {
     memset(r, 0, sizeof *r);
     gpujpeg_set_default_parameters(&r->param);
@@ -378,8 +388,12 @@ int gj_reader_parse(const uint8_t* image, size_t size, int verbose, bool ff_cs_i
                 r->q_present[tq] = true;
             }
             break; }
+        case 0xC2: /* SOF2: only for a caller that allows it (dec_opt_progressive); the frame header itself is SOF0's */
+            if (!allow_progressive) { GJ_ERROR("Marker SOF2 (Progressive with Huffman coding) is not supported!\n"); return -1; }
+            r->progressive = true;
+            goto sof;
         case 0xC1: GJ_WARN("Reading SOF1 as it was SOF0 marker (should work but verify it)!\n"); /* fall through */
-        case 0xC0: { /* SOF0 (reader.c:806-893) */
+        case 0xC0: sof: { /* SOF0 (reader.c:806-893) */
             if (len < 8) { GJ_ERROR("SOF0 marker length should be at least 8 but %d was presented!\n", len); return -1; }
             if (r->header_color_space != GPUJPEG_NONE) r->param.color_space_internal = r->header_color_space;
             const int precision = d[0];
@@ -442,9 +456,16 @@ int gj_reader_parse(const uint8_t* image, size_t size, int verbose, bool ff_cs_i
             break; }
         case 0xDA: { /* SOS (reader.c:1257-1372) */
             if (!have_sof) { GJ_ERROR("SOS marker before SOF0!\n"); return -1; }
-            const int n = d[0];
+            const int n = dl >= 1 ? d[0] : 0; /* (a segment of length 2 has no payload to read) */
             if (len != n * 2 + 6) { GJ_ERROR("Wrong SOS length (expected %d, got %d)\n", n * 2 + 6, len); return -1; }
             if (r->scan_count >= GJ_MAX_COMP) { GJ_ERROR("SOS marker reached maximum number of scans (%d)!\n", GJ_MAX_COMP); return -1; }
+            if (r->progressive) { /* the scans of a progressive frame are gj_reader_parse_progressive's: this parse ends at the first one */
+                r->param.interleaved = r->param.comp_count > 1; /* (the planes' layout: whole MCUs) */
+                r->header_end = (size_t)(p - 2 - image);
+                r->scan_begin[0] = (size_t)(p + len - image);
+                r->scan_count = 1;
+                return 0;
+            }
             if (n == 1) {
                 if (r->scan_count == 0) r->param.interleaved = 0;
             } else {
@@ -478,14 +499,13 @@ int gj_reader_parse(const uint8_t* image, size_t size, int verbose, bool ff_cs_i
                 stop = (long)(begin + seg_info_entry(r, scan, total / 4 - 1));
             } else {
                 int count = 0;
-                stop = walk_scan(image, begin, size, 0, 0, NULL, &count);
+                stop = walk_scan(image, begin, size, 0, 0, NULL, &count, false);
                 if (stop < 0) return -1;
             }
             r->scan_end[scan] = (size_t)stop;
             r->scan_count++;
             p = image + stop;
             continue; }
-        case 0xC2: GJ_ERROR("Marker SOF2 (Progressive with Huffman coding) is not supported!\n"); return -1;
         case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC8: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
             GJ_ERROR("Marker %s (not baseline sequential Huffman) is not supported!\n", marker_name(m));
             return -1;
@@ -532,9 +552,188 @@ int gj_reader_split_scans(const uint8_t* image, const struct gj_reader_result* r
             }
         } else {
             int count = 0;
-            if (walk_scan(image, r->scan_begin[scan], r->scan_end[scan] + 2, first, max_segs, segs, &count) < 0) return -1;
+            if (walk_scan(image, r->scan_begin[scan], r->scan_end[scan] + 2, first, max_segs, segs, &count, false) < 0) return -1;
             if (count > max_segs && verbose >= 0) GJ_WARN("%d segments read, expected %d. Broken JPEG?\n", count, max_segs);
         }
     }
     return 0;
 }
+
+/* ---- progressive frames (SOF2, ITU T.81 Annex G): the scan list ---- */
+void gj_prog_info_free(struct gj_prog_info* info)
+{
+    free(info->pool);
+    free(info->segs.pos); free(info->segs.len); free(info->segs.index);
+    memset(info, 0, sizeof *info);
+}
+
+/* the pool entry that holds the definition of (slot, class) as it stands: a new one unless a scan has taken this definition before */
+static int prog_table(struct gj_prog_info* info, int cur[4][2], const uint8_t hbits[4][2][17], const uint8_t hvals[4][2][256], int slot, int tc)
+{
+    if (cur[slot][tc] >= 0) return cur[slot][tc];
+    if (info->pool_count == info->pool_cap) {
+        const int cap = info->pool_cap ? info->pool_cap * 2 : 16;
+        struct gj_prog_table* t = realloc(info->pool, (size_t)cap * sizeof *t);
+        if (!t) return -1;
+        info->pool = t;
+        info->pool_cap = cap;
+    }
+    memcpy(info->pool[info->pool_count].bits, hbits[slot][tc], 17);
+    memcpy(info->pool[info->pool_count].vals, hvals[slot][tc], 256);
+    return cur[slot][tc] = info->pool_count++;
+}
+
+#define PROG_BAD(...) do { if (!quiet) GJ_ERROR(__VA_ARGS__); info->bad_scan = 1 + index; return 0; } while (0)
+
+/* From the first SOS of a frame gj_reader_parse found progressive (r) to the end of the stream: every scan with its components, band, bit positions,
+ * restart interval, the byte range and restart segments of its data (the host walk) and snapshots of the Huffman tables it uses -- DHT may
+ * redefine a slot in front of any scan, a scan decodes with the definitions that stand at its SOS. The script is checked against Annex G by
+ * tracking, per component and coefficient, the last Al: info->bad_scan = 1 + the first scan that breaks a rule (the message names it and the
+ * rule; quiet: no message), GJ_PROG_MAX_SCANS + 1 for a stream with more scans than that. Returns -1 when the markers cannot be read. */
+int gj_reader_parse_progressive(const uint8_t* image, size_t size, const struct gj_reader_result* r, struct gj_prog_info* info, bool quiet)
+{
+    info->scan_count = info->levels = info->bad_scan = info->pool_count = 0;
+    info->segs.count = 0;
+    uint8_t hbits[4][2][17], hvals[4][2][256];
+    bool present[4][2];
+    int cur[4][2];
+    memcpy(hbits, r->hbits, sizeof hbits);
+    memcpy(hvals, r->hvals, sizeof hvals);
+    memcpy(present, r->h_present, sizeof present);
+    for (int i = 0; i < 8; i++) cur[i / 2][i % 2] = -1;
+    int8_t last_al[GJ_MAX_COMP][64];
+    memset(last_al, -1, sizeof last_al);
+    int ri = r->param.restart_interval;
+    const int nc = r->param.comp_count, W = r->param_image.width, H = r->param_image.height;
+    int max_h = 1, max_v = 1, per_mcu = 0;
+    for (int c = 0; c < nc; c++) {
+        if (r->param.sampling_factor[c].horizontal > max_h) max_h = r->param.sampling_factor[c].horizontal;
+        if (r->param.sampling_factor[c].vertical > max_v) max_v = r->param.sampling_factor[c].vertical;
+        per_mcu += r->param.sampling_factor[c].horizontal * r->param.sampling_factor[c].vertical;
+    }
+    if (nc > 1 && per_mcu > 10) {
+        if (!quiet) GJ_ERROR("SOF2 sampling factors need %d blocks per MCU, JPEG allows 10!\n", per_mcu);
+        return -1;
+    }
+    const uint8_t* end = image + size;
+    const uint8_t* p = image + r->header_end;
+    for (;;) {
+        if (end - p < 2) break; /* (a progressive stream may end after any whole scan) */
+        if (p[0] != 0xFF) {
+            if (!quiet) GJ_ERROR("Failed to read marker from JPEG data (0xFF was expected but 0x%X was presented)\n", p[0]);
+            return -1;
+        }
+        while (p + 1 < end && p[1] == 0xFF) p++;
+        const int m = p[1];
+        p += 2;
+        if (m == 0xD9) break;
+        if (end - p < 2) { if (!quiet) GJ_ERROR("Marker %s goes beyond end of data\n", marker_name(m)); return -1; }
+        const int len = (int)RD2(p);
+        if (len < 2 || len > end - p) { if (!quiet) GJ_ERROR("Marker %s goes beyond end of data\n", marker_name(m)); return -1; }
+        const uint8_t* d = p + 2;
+        const int dl = len - 2;
+        if (m == 0xC4) { /* DHT: as in gj_reader_parse */
+            int o = 0;
+            while (o < dl) {
+                const int tc = d[o] >> 4, th = d[o] & 15;
+                if (tc > 1 || th > 3 || o + 17 > dl) { if (!quiet) GJ_ERROR("DHT marker between the scans of a progressive frame is malformed!\n"); return -1; }
+                int count = 0;
+                hbits[th][tc][0] = 0;
+                for (int i = 1; i <= 16; i++) { hbits[th][tc][i] = d[o + i]; count += d[o + i]; }
+                if (count > 256 || o + 17 + count > dl) { if (!quiet) GJ_ERROR("DHT marker unexpected end when reading huffman values!\n"); return -1; }
+                memcpy(hvals[th][tc], d + o + 17, (size_t)count);
+                present[th][tc] = true;
+                cur[th][tc] = -1;
+                o += 17 + count;
+            }
+        } else if (m == 0xDD) {
+            if (len != 4) { if (!quiet) GJ_ERROR("DRI marker length should be 4 but %d was presented!\n", len); return -1; }
+            ri = (int)RD2(d);
+        } else if (m == 0xDA) {
+            const int index = info->scan_count;
+            if (index >= GJ_PROG_MAX_SCANS) PROG_BAD("The progressive frame has more than %d scans!\n", GJ_PROG_MAX_SCANS);
+            const int n = dl >= 1 ? d[0] : 0; /* (a segment of length 2 has no payload to read) */
+            if (n < 1 || n > GJ_MAX_COMP || len != n * 2 + 6) { if (!quiet) GJ_ERROR("Wrong SOS length (expected %d, got %d)\n", n * 2 + 6, len); return -1; }
+            struct gj_prog_scan* s = &info->scan[index];
+            memset(s, 0, sizeof *s);
+            s->ncomp = n;
+            s->ss = d[1 + 2 * n]; s->se = d[2 + 2 * n]; s->ah = d[3 + 2 * n] >> 4; s->al = d[3 + 2 * n] & 15;
+            s->restart_interval = ri;
+            int slots[GJ_MAX_COMP][2];
+            for (int i = 0; i < n; i++) {
+                const int id = d[1 + 2 * i], tab = d[2 + 2 * i];
+                int ci = -1;
+                for (int c = 0; c < nc; c++) if (r->comp_id[c] == id) { ci = c; break; }
+                if (ci < 0) PROG_BAD("Progressive scan %d: component id %d is not defined by SOF2!\n", index, id);
+                for (int j = 0; j < i; j++)
+                    if (s->comp[j] >= ci) PROG_BAD("Progressive scan %d: its components are not in the frame's order!\n", index);
+                s->comp[i] = ci;
+                slots[i][0] = (tab >> 4) & 15;
+                slots[i][1] = tab & 15;
+                s->table[i] = -1;
+            }
+            /* Annex G.1.1.1: the band and the bit positions */
+            if (s->ss > s->se || s->se > 63) PROG_BAD("Progressive scan %d: Ss = %d, Se = %d is no band!\n", index, s->ss, s->se);
+            if (s->ss == 0 && s->se != 0) PROG_BAD("Progressive scan %d: a scan with the DC coefficient must have Se = 0, not %d!\n", index, s->se);
+            if (s->ss > 0 && n != 1) PROG_BAD("Progressive scan %d: an AC scan has one component, not %d!\n", index, n);
+            if (s->al > 13) PROG_BAD("Progressive scan %d: Al = %d is larger than 13!\n", index, s->al);
+            if (s->ah != 0 && s->al != s->ah - 1) PROG_BAD("Progressive scan %d: a refinement has Al = Ah - 1, not Ah = %d, Al = %d!\n", index, s->ah, s->al);
+            for (int i = 0; i < n; i++) {
+                int8_t* la = last_al[s->comp[i]];
+                if (s->ss > 0 && la[0] < 0) PROG_BAD("Progressive scan %d: an AC scan of component %d comes before its DC scan!\n", index, s->comp[i]);
+                for (int k = s->ss; k <= s->se; k++) {
+                    if (s->ah == 0 && la[k] >= 0) PROG_BAD("Progressive scan %d: coefficient %d of component %d has had its first scan!\n", index, k, s->comp[i]);
+                    if (s->ah != 0 && la[k] != s->ah) PROG_BAD("Progressive scan %d: refinement with Ah = %d, but coefficient %d of component %d was last coded with Al = %d!\n", index, s->ah, k, s->comp[i], la[k]);
+                }
+                for (int k = s->ss; k <= s->se; k++) la[k] = (int8_t)s->al;
+            }
+            /* the tables the scan decodes with, as they stand now */
+            const int tc = s->ss == 0 ? 0 : 1;
+            for (int i = 0; i < n && !(s->ss == 0 && s->ah != 0); i++) { /* (a DC refinement reads bits only) */
+                const int slot = slots[i][tc];
+                if (slot > 3 || !present[slot][tc]) PROG_BAD("Progressive scan %d: %s table slot %d was never defined!\n", index, tc ? "AC" : "DC", slot);
+                if ((s->table[i] = prog_table(info, cur, hbits, hvals, slot, tc)) < 0) return -1;
+            }
+            /* what it codes: the blocks of its one component, or whole MCUs of the frame's grid */
+            if (n == 1) {
+                const struct gpujpeg_component_sampling_factor* f = &r->param.sampling_factor[s->comp[0]];
+                const int wc = (W * f->horizontal + max_h - 1) / max_h, hc = (H * f->vertical + max_v - 1) / max_v;
+                s->across = (wc + 7) / 8;
+                s->units = s->across * ((hc + 7) / 8);
+            } else {
+                s->across = (W + 8 * max_h - 1) / (8 * max_h);
+                s->units = s->across * ((H + 8 * max_v - 1) / (8 * max_v));
+            }
+            s->begin = (size_t)(p + len - image);
+            const int max_segs = ri > 0 ? (s->units + ri - 1) / ri : 1;
+            int count = 0;
+            s->seg_first = info->segs.count;
+            const long stop = walk_scan(image, s->begin, size, 0, max_segs, &info->segs, &count, true);
+            if (stop < 0) return -1;
+            s->seg_count = info->segs.count - s->seg_first;
+            s->end = (size_t)stop;
+            /* dependency level: behind every earlier scan that shares a component and a coefficient with it */
+            for (int e = 0; e < index; e++) {
+                const struct gj_prog_scan* b = &info->scan[e];
+                bool shares = false;
+                for (int i = 0; i < n; i++)
+                    for (int j = 0; j < b->ncomp; j++) shares |= s->comp[i] == b->comp[j];
+                if (shares && b->ss <= s->se && s->ss <= b->se && b->level + 1 > s->level) s->level = b->level + 1;
+            }
+            if (s->level + 1 > info->levels) info->levels = s->level + 1;
+            info->scan_count++;
+            p = image + stop;
+            continue;
+        } else if (!(m == 0xDB || m == 0xFE || (m >= 0xE0 && m <= 0xEF))) { /* (DQT behind the first scan: the tables of the frame header hold) */
+            if (!quiet) GJ_ERROR("JPEG data contains not supported %s marker!\n", marker_name(m));
+            return -1;
+        }
+        p += len;
+    }
+    if (info->scan_count == 0) {
+        if (!quiet) GJ_ERROR("JPEG data contain no image!\n");
+        return -1;
+    }
+    return 0;
+}
+#undef PROG_BAD

@@ -34,6 +34,11 @@ BATCH_SIZES_SAME, BATCH_SIZES_MIXED = "same", "mixed"
 # OpenCV write) through their batched launches (GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS); with it a dataset needs no explicit restart interval
 DEC_OPT_BATCH_RESTARTLESS = "dec_opt_batch_restartless"
 BATCH_RESTARTLESS_OFF, BATCH_RESTARTLESS_ON = "off", "on"
+# Decoder.set_option(DEC_OPT_PROGRESSIVE, PROGRESSIVE_ON): progressive streams (SOF2) are decoded, to the image of their baseline twin
+# (GPUJPEG_AMD_DEC_OPT_PROGRESSIVE); at most PROGRESSIVE_MAX_SCANS scans. Decoder.progressive_stats() and stream_info() tell what a stream is
+DEC_OPT_PROGRESSIVE = "dec_opt_progressive"
+PROGRESSIVE_OFF, PROGRESSIVE_ON = "off", "on"
+PROGRESSIVE_MAX_SCANS = 64
 # encoder option of the MI355X build (gpujpeg_amd_ext.h: GPUJPEG_AMD_ENC_OPT_HUFFMAN): Annex K.3 tables, or tables built per frame
 ENC_OPT_HUFFMAN = "enc_opt_huffman"
 ENC_HUFFMAN_STANDARD, ENC_HUFFMAN_OPTIMAL = "standard", "optimal"
@@ -254,6 +259,16 @@ def crop_resize_plan(lib, image_w, image_h, all_components_1x1, rect, out_w, out
     r4 = (C.c_int * 4)(*[int(v) for v in rect])
     rc = lib.L.gpujpeg_amd_host_crop_resize_plan(int(image_w), int(image_h), int(bool(all_components_1x1)), r4, int(out_w), int(out_h), int(max_scale), out)
     return tuple(out) if rc == 0 else None
+
+
+def stream_info(lib, jpeg):
+    """gpujpeg_amd_host_stream_info (host only, lib: a Library): (width, height, components, progressive 0 / 1, scans, dependency levels, restart
+    interval, 0 for a valid scan script or 1 + the first offending scan) of a baseline or progressive stream; None when its headers cannot be parsed"""
+    a = np.ascontiguousarray(jpeg, np.uint8)
+    out = (C.c_int * 8)()
+    f = lib.L.gpujpeg_amd_host_stream_info
+    f.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+    return tuple(out) if f(a.ctypes.data, a.size, out) == 0 else None
 
 
 def resize_weights(lib, n_src, n_out, i, capacity=None):
@@ -490,11 +505,19 @@ class Decoder:
                                  "before a stream has been parsed, and the streams are in device memory")
             bound = int(frame_bytes)
         else:
-            pi0, p0 = ImageParameters(), Parameters()
+            # (gpujpeg_amd_host_stream_info takes progressive streams too, which gpujpeg_decoder_get_image_info refuses)
             first = np.ascontiguousarray(streams[0])
-            if self.lib.L.gpujpeg_decoder_get_image_info(first.ctypes.data_as(C.c_void_p), first.size, C.byref(pi0), C.byref(p0), None) != 0:
-                raise RuntimeError("gpujpeg_decoder_get_image_info failed")
-            bound = max(int(pi0.width) * int(pi0.height) * 4 + 4096, 1)  # (the library checks the real frame size against the stride)
+            if hasattr(self.lib.L, "gpujpeg_amd_host_stream_info"):
+                info = stream_info(self.lib, first)
+                if info is None:
+                    raise RuntimeError("gpujpeg_amd_host_stream_info failed")
+                w0, h0 = info[0], info[1]
+            else:
+                pi0, p0 = ImageParameters(), Parameters()
+                if self.lib.L.gpujpeg_decoder_get_image_info(first.ctypes.data_as(C.c_void_p), first.size, C.byref(pi0), C.byref(p0), None) != 0:
+                    raise RuntimeError("gpujpeg_decoder_get_image_info failed")
+                w0, h0 = pi0.width, pi0.height
+            bound = max(int(w0) * int(h0) * 4 + 4096, 1)  # (the library checks the real frame size against the stride)
         out = np.empty(bound * n, np.uint8)
         rc = self.lib.L.gpujpeg_amd_decoder_decode_batch(self.h, base, in_stride, csz, n, out.ctypes.data, bound, C.byref(pi))
         if rc != 0:
@@ -653,6 +676,14 @@ class Decoder:
         self.lib.L.gpujpeg_amd_decoder_get_region_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
         assert self.lib.L.gpujpeg_amd_decoder_get_region_stats(self.h, a) == 0
         return tuple(int(x) for x in a)
+
+    def progressive_stats(self):
+        """gpujpeg_amd_decoder_get_progressive_stats: (rc, 1 if the last decode call's frame was progressive, scans decoded, dependency levels = entropy
+        launches, scan segments = waves launched); rc -1 and zeros before the first call"""
+        a = (C.c_long * 4)()
+        self.lib.L.gpujpeg_amd_decoder_get_progressive_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        rc = self.lib.L.gpujpeg_amd_decoder_get_progressive_stats(self.h, a)
+        return (int(rc),) + tuple(int(x) for x in a)
 
     def entropy_bytes(self):
         """gpujpeg_amd_decoder_get_entropy_bytes: (rc, bytes handed to the entropy decoders by the batched launches, bytes of them that were read) of the

@@ -354,6 +354,38 @@ GJ_HIP_API uint32_t gj_hip_tensor_element(const gj_tensor* t, int c, int v);
  * code: first tap, tap count, the weights (NULL: not wanted) and their sum. -1: arguments the call refuses (sizes, i, n_src > 256 n_out), -2: capacity < count */
 GJ_HIP_API int gj_hip_resize_aa_weights(int n_src, int n_out, int i, int* first, int* count, uint32_t* weights, int capacity, uint64_t* sum);
 
+/* Progressive streams (SOF2, dec_opt_progressive): the work list of k_huffman_decode_prog, ONE WAVE PER RECORD. A record is one restart segment of
+ * one scan and says everything the wave needs -- no record refers to a frame: where its blocks lie is given per component as the block index of the
+ * plane's first block in d_coefs and the plane's pitch in blocks, so that a later batch over frames only has to add a plane base per record.
+ * A scan of one component (every AC scan, a DC scan of one component) codes the ceil(w_c / 8) x ceil(h_c / 8) blocks of the component in raster
+ * order (`across` of them per row) inside the plane's pitch; a DC scan of several components codes whole MCUs of the FRAME's grid (`across` MCUs
+ * per row), component c's h x v blocks of every MCU. first / count: blocks of the first kind of scan, MCUs of the second. */
+enum { GJ_PROG_DC_FIRST = 0, GJ_PROG_DC_REFINE = 1, GJ_PROG_AC_FIRST = 2, GJ_PROG_AC_REFINE = 3 };
+typedef struct gj_prog_comp {
+    uint32_t base;                 /* block index (64 coefficients each) of the component plane's first block */
+    uint32_t pitch;                /* blocks per row of the plane */
+    uint16_t table;                /* entry of the table pool: the DC table of a first DC scan, the AC table of an AC scan */
+    uint8_t h, v;                  /* blocks per MCU (scans of several components) */
+} gj_prog_comp;
+typedef struct gj_prog_rec {
+    uint32_t pos, len;             /* the segment's entropy-coded bytes in the stream */
+    uint32_t first, count;         /* first block / MCU of the segment and how many it codes */
+    uint32_t across;               /* coded blocks / MCUs per row */
+    uint8_t kind, ncomp, ss, se, ah, al, reserved[2];
+    gj_prog_comp c[GJ_MAX_COMP];
+} gj_prog_rec;
+/* the plan of a progressive frame: scans whose coefficients do not depend on each other form a LEVEL and are launched together, the levels one
+ * after the other on the stream (gj_decoder.c: the level of a scan is 1 + the highest level among the earlier scans that share a component and
+ * a coefficient with it). Records of a level lie back to back. */
+#define GJ_PROG_MAX_SCANS 64
+typedef struct gj_prog_plan {
+    const gj_prog_rec* d_recs;     /* device memory */
+    const uint16_t* d_tabs;        /* device memory: the table pool, GJ_DEC_TAB_WORDS words per entry */
+    uint32_t tab_count;
+    int levels;
+    uint32_t level_first[GJ_PROG_MAX_SCANS], level_count[GJ_PROG_MAX_SCANS];
+} gj_prog_plan;
+
 typedef struct gj_dec_job {
     gj_geom g;                     /* pixel_format / color_space describe the requested output */
     const uint8_t* d_jpeg;         /* whole file in HBM */
@@ -413,6 +445,9 @@ typedef struct gj_dec_job {
     /* dec_opt_batch_restartless: 1 = a batch (gj_dec_job::batch) of streams WITHOUT restart markers is taken -- one segment per scan, decoded piece
      * by piece by k_huffman_decode_par, plane mode -- and a batch of regions on them selects every segment. 0: gj_hip_decode_batchable says no */
     int batch_restartless;
+    /* a progressive frame (host memory, NULL: a baseline frame): the coefficient planes are cleared and filled by k_huffman_decode_prog, one launch
+     * per level, in place of the entropy decoders above -- no segment table, no tokens, no selection, no batch --; the IDCT side is the plane route's */
+    const gj_prog_plan* prog;
 } gj_dec_job;
 /* 1 when gj_hip_decode takes a batch (gj_dec_job::batch.count > 1) of this job's configuration */
 GJ_HIP_API int gj_hip_decode_batchable(const gj_dec_job* job);

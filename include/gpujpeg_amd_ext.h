@@ -225,6 +225,55 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
 #define GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS "dec_opt_batch_restartless"
 #define GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_OFF "off"
 #define GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_ON "on"
+/* Decoder option dec_opt_progressive = "off" (default) | "on" (gpujpeg_decoder_set_option): whether gpujpeg_decoder_decode takes PROGRESSIVE streams --
+ * frame header SOF2: 8-bit samples, Huffman coding, 1 to 4 components, sampling factors 1 to 4, at most 10 blocks per MCU, 8-bit DQT (what "save for
+ * the web", mozjpeg and a few percent of any scraped dataset are). It holds from the next decode call on and may be changed between two calls; another
+ * value is refused (GPUJPEG_ERROR) and leaves the setting as it was. With "off" every byte, return code, message, counter, launch and kernel-times slot
+ * of every call is what it is without the option, and a SOF2 stream is refused by the reader. gpujpeg_decoder_get_image_info takes no decoder and
+ * refuses SOF2 always: gpujpeg_amd_host_stream_info below tells a caller the sizes.
+ * WITH "on" the call returns the image the same decoder returns for the stream's BASELINE TWIN -- the SOF0 stream with the same quantisation tables,
+ * component ids, sampling, APPn segments and quantised coefficients --, byte for byte, in every output pixel format, colour space and
+ * dec_opt_alignment_bytes: the scans fill the quantised coefficient planes (k_huffman_decode_prog, one wave per restart segment of a scan), and
+ * everything behind those planes is the plane route of any other frame. So dec_opt_scale works through the coefficient-plane kernels, dec_opt_region
+ * too (every segment is decoded: gpujpeg_amd_decoder_get_region_stats reports mode 2), gpujpeg_amd_decoder_read_coefficients after
+ * gpujpeg_amd_decoder_keep_coefficients returns the full planes, dec_opt_flipped and dec_opt_channel_remap behave as on any plane-route frame (what
+ * that route refuses stays refused). Inside a batch call (decode_batch, _ptrs, _regions, _crop_resize, _crop_resize_tensor, every option of those) a
+ * progressive frame goes the single-frame route -- "another header" --, gpujpeg_amd_decoder_last_batch counts it as single, frame f is byte for byte
+ * the single call on stream f, and a call may mix baseline and progressive streams freely; with dec_opt_batch_sizes = mixed a progressive stream is
+ * never of the family. A progressive frame never launches on a cached header, never takes the device marker scan or token mode (the host walks
+ * the stream), and leaves the header cache as it found it -- in host memory and in device memory: while the option is "on", the header of a
+ * device-resident stream is brought to the host and compared there before a single-frame call launches on the cached header (one small copy and wait
+ * per such call; with "off" the device compares it behind the launch, as ever). The batched launches of a batch call do run over a progressive
+ * stream's slot like over any stream with another header, and its frame is decoded again the single-frame way.
+ *   Scans.     Any script that is valid under ITU T.81 Annex G: DC scans (Ss = Se = 0) over any non-empty subset of the components, two or more
+ *              interleaved; AC scans of one component, 1 <= Ss <= Se <= 63; the first scan of a coefficient has Ah = 0, a refinement Ah = the
+ *              Al the coefficient was last coded with and Al = Ah - 1; no AC scan of a component ahead of a DC scan that covers it; Al <= 13; at most
+ *              GPUJPEG_AMD_PROGRESSIVE_MAX_SCANS scans (the library's own cap). DHT may redefine a slot in front of any scan: a scan decodes
+ *              with the tables as they stand at its SOS. DRI applies to every scan: MCUs in a scan of several components, BLOCKS in a scan of one;
+ *              RSTn resets the DC prediction and the EOB run. The stream may end after any whole scan: the scans that are there give the image.
+ *              Inside a scan, a segment that ends early reads zero bits, as in the other decoders.
+ *   Refused    by the decode call, with a message and a negative return, the decoder usable as before: a script that breaks a rule (the message
+ *              names the scan and the rule), more scans than the cap, arithmetic coding (SOF10), 12-bit samples, a scan that names a table
+ *              slot that was never defined.
+ *   Geometry.  Every component's plane has the padded, whole-MCU layout of the interleaved geometry: pitch blocks_x. A scan of ONE component
+ *              codes only ceil(w_c / 8) x ceil(h_c / 8) blocks, w_c = ceil(W H_c / Hmax) and h_c likewise, in raster order INSIDE that pitch; a DC
+ *              scan of several components codes whole MCUs of the grid the FRAME's largest factors give, also when it holds a subset of the
+ *              components. The padded blocks that scans of one component skip keep the DC their DC scan gave them, and zero AC.
+ *   Launches.  Scans whose coefficients do not depend on each other form a LEVEL -- level 0, or 1 + the highest level among the earlier scans that
+ *              share a component and a coefficient with the scan -- and are decoded by one launch, the levels one after the other (libjpeg's
+ *              ten-scan colour script: 3 levels of 5 + 4 + 1 scans). Kernel-times slot [0] is the sum over those launches (with the clear of the
+ *              planes in front of them), slot [4] what the IDCT side sets.
+ * gpujpeg_amd_decoder_get_progressive_stats: about the last decode call -- out[0] 1 if the frame was progressive, else 0 (and the rest 0); out[1] scans
+ * decoded; out[2] levels = entropy launches; out[3] restart segments of scans = waves launched. Returns 0; -1 with zeros before the first call.
+ * gpujpeg_amd_host_stream_info (host only, no device): out[0..2] width, height, components; out[3] 1 for SOF2, else 0; out[4] scans; out[5] levels
+ * (a baseline stream: 1); out[6] the restart interval; out[7] 0 for a valid script, else 1 + the first offending scan (more scans than the cap:
+ * the cap + 1). Returns 0; -1 when the headers cannot be parsed. */
+#define GPUJPEG_AMD_DEC_OPT_PROGRESSIVE "dec_opt_progressive"
+#define GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_OFF "off"
+#define GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_ON "on"
+#define GPUJPEG_AMD_PROGRESSIVE_MAX_SCANS 64
+GPUJPEG_API int gpujpeg_amd_decoder_get_progressive_stats(struct gpujpeg_decoder* decoder, long out[4]);
+GPUJPEG_API int gpujpeg_amd_host_stream_info(const uint8_t* image, size_t size, int out[8]);
 /* Host-only: the table enc_opt_huffman=optimal builds for one class from symbol counts freq[256] (ITU T.81 Annex K.2: Figures K.1, K.3, K.4;
  * reserved code point, ties to the larger symbol value), code lengths limited to the largest L of 16 .. 10 whose table the library's
  * two-level decode tables take. Writes BITS (bits[1..16]) and HUFFVAL; returns L, or -1 when no count is non-zero. */
