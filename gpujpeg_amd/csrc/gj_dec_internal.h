@@ -9,7 +9,8 @@
 //   gj_dec_entropy_seq.hip      one lane per restart segment (interleaved scans with many short segments): k_huffman_decode_win over a ring the
 //                               lane refills itself (token mode), k_huffman_decode_seq over an LDS stage (plane mode)
 //   gj_dec_entropy_serial.hip   k_huffman_decode: one lane per restart segment, stream windows (Huffman tables that do not fit the two-level layout)
-//   gj_dec_entropy_prog.hip     k_huffman_decode_prog: progressive streams (SOF2), one wave per restart segment of a scan, lane k = zig-zag position k
+//   gj_dec_entropy_prog.hip     k_huffman_decode_prog: progressive streams (SOF2), one wave per restart segment of a scan, lane k = zig-zag position k;
+//                               k_huffman_decode_prog_batch: the same over a chunk of frames (both are gj_dec_entropy_prog_body.h, included once each)
 //   gj_dec_idct.hip             k_idct_fused_* (from the planes), k_idct_tok_* (from tokens; the full-size and the region kernel around one core:
 //                               gj_tok_tables, gj_tok_idct3), k_idct / k_postprocess / k_copy_planes_out (generic); gj_launch_idct: the IDCT side of
 //                               every kind of call and its one tail (debug stage, channel remap, gj_dec_job::idct_path)

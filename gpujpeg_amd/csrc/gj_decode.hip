@@ -33,6 +33,11 @@ extern "C" int gj_hip_decode_wants_tokens(const gj_geom* g, uint64_t jpeg_size, 
 extern "C" int gj_hip_decode_batchable(const gj_dec_job* job)
 {
     const gj_geom& g = job->g;
+    // (a chunk of progressive frames, gj_dec_job::prog with gj_prog_plan::d_frames: its own entropy stage -- no segment table, no two-level tables, no
+    // overflow word, and restart intervals are the records' business --, the same IDCT-side kernels)
+    if (job->prog != nullptr)
+        return job->prog->d_frames != nullptr && !job->flipped && !job->channel_remap && !job->tokens && !job->scan.valid && !job->region.select && g.fb.geoms == nullptr &&
+               job->batch.d_geoms == nullptr;
     return job->d_huff_tab2 != nullptr && job->d_overflow != nullptr && job->d_seg_count != nullptr && job->seg_count > 0 &&
            !job->flipped && !job->channel_remap && !job->clear_coefs && !job->tune.dec_serial && !job->tune.dec_careful && job->tune.dec_seq != 1 &&
            (g.restart_interval > 0 || job->batch_restartless);
@@ -78,17 +83,19 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
         (rg.filter != GJ_RESIZE_FILTER_ANTIALIAS || !rg.resize || (rg.scale_mask & ~1u) != 0 || rg.comp_mask != 0 ||
          (!rg_batch && (rg.frame.scale > 1 || rg.frame.w > GJ_RESIZE_AA_MAX_RATIO * job->gs.width || rg.frame.h > GJ_RESIZE_AA_MAX_RATIO * job->gs.height))))
         return -1;
+    // (a chunk of progressive frames has no selection: every segment of every scan is decoded)
     // (without restart markers a selection is every segment of every scan: a batch of regions on such streams alone, gj_dec_job::batch_restartless)
     if (rg.on && (job->scale > 1 || job->flipped || (rg.select && (!rg.d_sel || !rg.h_sel_count || (g.restart_interval <= 0 && !(rg_batch && job->batch_restartless)))) ||
-                  (rg_batch ? (g.fb.sizes == nullptr || !rg.select || job->channel_remap) : (g.fb.sizes != nullptr || job->batch.count > 1 || (rg.select && !rg.d_sel_count)))))
+                  (rg_batch ? (g.fb.sizes == nullptr || (job->prog != nullptr ? rg.select != 0 : !rg.select) || job->channel_remap) : (g.fb.sizes != nullptr || job->batch.count > 1 || (rg.select && !rg.d_sel_count)))))
         return -1;
     // (frames of different image sizes, gj_frame_strides::geoms: a batch of crop-and-resize frames alone -- the selection, the sub-sequence decoder in
     // plane mode and the region IDCT kernels are the stages that read a frame's own geometry --, the same records for g and gs, one per frame of the launch)
     if ((g.fb.geoms != nullptr || job->batch.d_geoms != nullptr) &&
         (!rg_batch || !rg.resize || job->tokens || g.fb.geoms != job->batch.d_geoms || job->gs.fb.geoms != g.fb.geoms || job->tune.dec_sub))
         return -1;
-    // (a progressive frame, gj_dec_job::prog: a single frame through the coefficient planes -- its own entropy stage, then the plane route's IDCT side)
-    if (job->prog != nullptr && (g.fb.sizes != nullptr || job->batch.count > 1 || job->tokens || job->scan.valid || rg.select || job->prog->levels < 0 ||
+    // (a progressive frame, gj_dec_job::prog: through the coefficient planes -- its own entropy stage, then the plane route's IDCT side --, a single
+    // frame, or a chunk of frames with its per-frame records, which the check of every batch above has passed)
+    if (job->prog != nullptr && ((job->prog->d_frames != nullptr) != (g.fb.sizes != nullptr) || job->tokens || job->scan.valid || rg.select || job->prog->levels < 0 ||
                                  job->prog->levels > GJ_PROG_MAX_SCANS))
         return -1;
     gj_hip_note_reset();

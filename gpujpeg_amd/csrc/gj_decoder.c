@@ -144,6 +144,14 @@ struct gpujpeg_decoder {
     uint8_t* h_prog; size_t h_prog_cap;
     uint16_t* d_prog_q; uint16_t* h_prog_q;
     long prog_stats[4]; bool prog_stats_valid;     /* gpujpeg_amd_decoder_get_progressive_stats */
+    /* dec_opt_batch_progressive: 1 = the batch calls take the progressive frames that form a group through batched launches of their own
+     * (batch_progressive). Read by every batch call, once, when it starts. What those launches of the last such call took
+     * (gpujpeg_amd_decoder_get_progressive_batch_stats); pinned: the device-resident streams of the call's candidates for the host's walk; device:
+     * the frames of a chunk whose slots in the caller's output are not a constant distance apart, before they are copied there */
+    int batch_progressive;
+    long pb_stats[4]; bool pb_stats_valid;
+    uint8_t* bh_pstreams; size_t bh_pstreams_cap;
+    uint8_t* b_praw; size_t b_praw_cap;
 };
 
 /* what a call decodes to: the stream's image, or the reduced one */
@@ -299,6 +307,7 @@ int gpujpeg_decoder_destroy(struct gpujpeg_decoder* d)
     gj_hip_free(d->b_sel); gj_hip_free(d->b_rgn); gj_hip_host_free(d->bh_rgn); gj_hip_host_free(d->bh_found);
     gj_hip_host_free(d->bh_hdrs); gj_hip_host_free(d->bh_geoms); gj_hip_free(d->b_geoms);
     gj_hip_host_free(d->bh_sel_bytes); gj_hip_host_free(d->bh_left);
+    gj_hip_host_free(d->bh_pstreams); gj_hip_free(d->b_praw);
     gj_prog_info_free(&d->prog); gj_hip_free(d->d_prog); gj_hip_host_free(d->h_prog); gj_hip_free(d->d_prog_q); gj_hip_host_free(d->h_prog_q);
     free(d);
     return 0;
@@ -928,6 +937,43 @@ static void dec_stats(struct gpujpeg_decoder* d, const struct dec_call* k)
 /* ---- progressive frames (dec_opt_progressive) ---- */
 /* The plan of a progressive frame, from its scan list (d->prog) and the coder's geometry: the decode tables of every table snapshot and one record
  * per restart segment of every scan (gj_hip.h: gj_prog_rec), the records of a level back to back, staged in pinned memory and uploaded. 0 or -1. */
+/* the records of one level of one frame's scan list, back to back at `recs` (room: the frame's segment count) -> how many; frame: what the records of a
+ * chunk of frames name (gj_prog_rec::frame), 0 for a single frame */
+static uint32_t prog_level_records(const struct gj_prog_info* info, const gj_geom* g, int level, unsigned frame, gj_prog_rec* recs)
+{
+    uint32_t at = 0;
+    for (int si = 0; si < info->scan_count; si++) {
+        const struct gj_prog_scan* s = &info->scan[si];
+        if (s->level != level) continue;
+        const int ri = s->restart_interval;
+        for (int j = 0; j < s->seg_count; j++) {
+            const int e = s->seg_first + j;
+            const uint32_t number = info->segs.index[e]; /* the segment's number inside its scan */
+            const uint64_t first = ri > 0 ? (uint64_t)number * (uint64_t)ri : 0;
+            if (first >= (uint64_t)s->units) continue;
+            gj_prog_rec* q = &recs[at++];
+            q->pos = info->segs.pos[e];
+            q->len = info->segs.len[e];
+            q->first = (uint32_t)first;
+            q->count = ri > 0 && first + (uint64_t)ri < (uint64_t)s->units ? (uint32_t)ri : (uint32_t)((uint64_t)s->units - first);
+            q->across = (uint32_t)s->across;
+            q->kind = (uint8_t)(s->ss == 0 ? (s->ah == 0 ? GJ_PROG_DC_FIRST : GJ_PROG_DC_REFINE) : (s->ah == 0 ? GJ_PROG_AC_FIRST : GJ_PROG_AC_REFINE));
+            q->ncomp = (uint8_t)s->ncomp;
+            q->ss = (uint8_t)s->ss; q->se = (uint8_t)s->se; q->ah = (uint8_t)s->ah; q->al = (uint8_t)s->al;
+            q->frame = (uint16_t)frame;
+            for (int i = 0; i < s->ncomp; i++) {
+                const gj_comp_geom* k = &g->comp[s->comp[i]];
+                q->c[i].base = (uint32_t)(k->data_offset / 64);
+                q->c[i].pitch = (uint32_t)k->blocks_x;
+                q->c[i].table = (uint16_t)(s->table[i] >= 0 ? s->table[i] : 0);
+                q->c[i].h = (uint8_t)(s->ncomp > 1 ? k->samp_h : 1);
+                q->c[i].v = (uint8_t)(s->ncomp > 1 ? k->samp_v : 1);
+            }
+        }
+    }
+    return at;
+}
+
 static int prog_plan(struct gpujpeg_decoder* d, gj_prog_plan* plan)
 {
     struct gj_coder* c = &d->coder;
@@ -949,34 +995,7 @@ static int prog_plan(struct gpujpeg_decoder* d, gj_prog_plan* plan)
     uint32_t at = 0;
     for (int level = 0; level < info->levels; level++) {
         plan->level_first[level] = at;
-        for (int si = 0; si < info->scan_count; si++) {
-            const struct gj_prog_scan* s = &info->scan[si];
-            if (s->level != level) continue;
-            const int ri = s->restart_interval;
-            for (int j = 0; j < s->seg_count; j++) {
-                const int e = s->seg_first + j;
-                const uint32_t number = info->segs.index[e]; /* the segment's number inside its scan */
-                const uint64_t first = ri > 0 ? (uint64_t)number * (uint64_t)ri : 0;
-                if (first >= (uint64_t)s->units) continue;
-                gj_prog_rec* q = &recs[at++];
-                q->pos = info->segs.pos[e];
-                q->len = info->segs.len[e];
-                q->first = (uint32_t)first;
-                q->count = ri > 0 && first + (uint64_t)ri < (uint64_t)s->units ? (uint32_t)ri : (uint32_t)((uint64_t)s->units - first);
-                q->across = (uint32_t)s->across;
-                q->kind = (uint8_t)(s->ss == 0 ? (s->ah == 0 ? GJ_PROG_DC_FIRST : GJ_PROG_DC_REFINE) : (s->ah == 0 ? GJ_PROG_AC_FIRST : GJ_PROG_AC_REFINE));
-                q->ncomp = (uint8_t)s->ncomp;
-                q->ss = (uint8_t)s->ss; q->se = (uint8_t)s->se; q->ah = (uint8_t)s->ah; q->al = (uint8_t)s->al;
-                for (int i = 0; i < s->ncomp; i++) {
-                    const gj_comp_geom* k = &g->comp[s->comp[i]];
-                    q->c[i].base = (uint32_t)(k->data_offset / 64);
-                    q->c[i].pitch = (uint32_t)k->blocks_x;
-                    q->c[i].table = (uint16_t)(s->table[i] >= 0 ? s->table[i] : 0);
-                    q->c[i].h = (uint8_t)(s->ncomp > 1 ? k->samp_h : 1);
-                    q->c[i].v = (uint8_t)(s->ncomp > 1 ? k->samp_v : 1);
-                }
-            }
-        }
+        at += prog_level_records(info, g, level, 0, recs + at);
         plan->level_count[level] = at - plan->level_first[level];
     }
     plan->levels = info->levels;
@@ -989,6 +1008,24 @@ static int prog_plan(struct gpujpeg_decoder* d, gj_prog_plan* plan)
     d->prog_stats[2] = info->levels;
     d->prog_stats[3] = (long)at;
     return 0;
+}
+
+/* the quantisation tables of a progressive frame (a group of them: any of its frames'): natural order, u16 and float, in the buffer of their own */
+static int prog_quant_tables(struct gpujpeg_decoder* d, const struct gj_reader_result* r)
+{
+    const size_t q_bytes = 4 * 64 * (sizeof(uint16_t) + sizeof(float));
+    if (!d->d_prog_q) d->d_prog_q = gj_hip_malloc(q_bytes);
+    if (!d->h_prog_q) d->h_prog_q = gj_hip_host_alloc(q_bytes);
+    if (!d->d_prog_q || !d->h_prog_q) return -1;
+    memset(d->h_prog_q, 0, q_bytes);
+    for (int t = 0; t < 4; t++)
+        if (r->q_present[t]) {
+            uint16_t* qi = d->h_prog_q + t * 64;
+            float* qf = (float*)(void*)(d->h_prog_q + 4 * 64) + t * 64;
+            gj_quant_table_inverse(r->qraw[t], qi);
+            for (int i = 0; i < 64; i++) qf[i] = (float)qi[i];
+        }
+    return gj_hip_memcpy_h2d(d->d_prog_q, d->h_prog_q, q_bytes, d->coder.stream);
 }
 
 /* A progressive frame, once its first headers are parsed (k->r, k->himage the whole stream): the careful route only -- the host walks every scan, no
@@ -1016,20 +1053,7 @@ static int dec_progressive(struct gpujpeg_decoder* d, struct dec_call* k)
     if (dec_upload(d, k) != 0) return DEC_FAILED;
     gj_prog_plan plan;
     if (prog_plan(d, &plan) != 0) return DEC_FAILED;
-    /* quantisation tables: natural order, u16 and float, in the frame's own buffer */
-    const size_t q_bytes = 4 * 64 * (sizeof(uint16_t) + sizeof(float));
-    if (!d->d_prog_q) d->d_prog_q = gj_hip_malloc(q_bytes);
-    if (!d->h_prog_q) d->h_prog_q = gj_hip_host_alloc(q_bytes);
-    if (!d->d_prog_q || !d->h_prog_q) return DEC_FAILED;
-    memset(d->h_prog_q, 0, q_bytes);
-    for (int t = 0; t < 4; t++)
-        if (r->q_present[t]) {
-            uint16_t* qi = d->h_prog_q + t * 64;
-            float* qf = (float*)(void*)(d->h_prog_q + 4 * 64) + t * 64;
-            gj_quant_table_inverse(r->qraw[t], qi);
-            for (int i = 0; i < 64; i++) qf[i] = (float)qi[i];
-        }
-    if (gj_hip_memcpy_h2d(d->d_prog_q, d->h_prog_q, q_bytes, c->stream) != 0) return DEC_FAILED;
+    if (prog_quant_tables(d, r) != 0) return DEC_FAILED;
     c->stats.duration_stream = k->stats ? (gpujpeg_get_time() - k->t_read0) * 1000.0 : 0;
     if (k->stats) gj_hip_event_record(c->timers.copy_in[1], c->stream);
     if (dec_destination(d, k) != 0) return DEC_FAILED;
@@ -1142,7 +1166,7 @@ static int decoder_decode(struct gpujpeg_decoder* d, const struct dec_request* r
 int gpujpeg_decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t image_size, struct gpujpeg_decoder_output* output)
 {
     const struct dec_request q = dec_request_options(d);
-    if (d) d->entropy_valid = false;
+    if (d) d->entropy_valid = d->pb_stats_valid = false;
     return decoder_decode(d, &q, image, image_size, output);
 }
 
@@ -1199,6 +1223,7 @@ struct dec_batch {
     bool restartless;                    /* dec_opt_batch_restartless = on: streams without restart markers go through the batched launches too */
     bool ahead_progressive;              /* frame 0 went ahead and was a progressive frame: it planned no rectangles (batch_decode_one); ahead_w x ahead_h: its image */
     int ahead_w, ahead_h;
+    bool prog_batch;                     /* dec_opt_batch_progressive = on and dec_opt_progressive = on: groups of progressive frames go through batched launches (batch_progressive) */
 };
 
 /* one rectangle per frame: a batch of regions, or crop-and-resize */
@@ -1325,6 +1350,52 @@ static int batch_mixed_prepare(struct gpujpeg_decoder* d, struct dec_batch* b, i
     return 0;
 }
 
+/* The rectangles of a set of frames that share one geometry -- the frames of the baseline batched launches (batch_regions_plan), or a group of
+ * progressive frames (batch_progressive) --: the image, region and parameters of the frame planned last, and per component the widest and the highest
+ * cover so far */
+struct cover_plan {
+    gj_geom gs_one; gj_region rg_one; struct gpujpeg_image_parameters pi_r;
+    int wmax[GJ_MAX_COMP], hmax[GJ_MAX_COMP];
+};
+
+/* frame f's rectangle against geometry g (gj_region_plan; a refusal names the frame): its origin and covers into *out, the scale it takes into the
+ * call's prescales, its cover into the largest one. 0 or -1. */
+static int batch_cover_frame(struct gpujpeg_decoder* d, const struct dec_batch* b, int f, const gj_geom* g, const struct gpujpeg_parameters* param,
+                             const struct gpujpeg_image_parameters* pi_f, struct cover_plan* cp, gj_region_frame* out)
+{
+    const struct dec_request q = batch_request(d, b, f);
+    const int refused = gj_region_plan(&cp->gs_one, &cp->rg_one, g, param, pi_f, q.rect, q.resize ? &q.rs : NULL, d->req_alignment, &cp->pi_r);
+    if (refused == -1) GJ_ERROR("Frame %d of the batch: the region %d,%d,%d,%d was refused!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3]);
+    if (refused == -3) GJ_ERROR("Frame %d of the batch: the rectangle %d,%d,%d,%d was refused by the resize filter!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3]);
+    if (refused != 0) return -1;
+    if (q.resize && f < d->prescales_n) d->prescales[f] = (uint8_t)cp->rg_one.frame.scale;
+    const gj_region_frame* rf = &cp->rg_one.frame;
+    *out = *rf;
+    for (int i = 0; i < g->comp_count && i < GJ_MAX_COMP; i++) {
+        if (rf->bx1[i] - rf->bx0[i] > cp->wmax[i]) cp->wmax[i] = rf->bx1[i] - rf->bx0[i];
+        if (rf->by1[i] - rf->by0[i] > cp->hmax[i]) cp->hmax[i] = rf->by1[i] - rf->by0[i];
+    }
+    return 0;
+}
+
+/* the planes of the largest cover: every frame's cover planes are laid out like this (*gs_max: the image of the frame planned last over them) */
+static void batch_cover_planes(const struct cover_plan* cp, const gj_geom* g, gj_geom* gs_max)
+{
+    *gs_max = cp->gs_one;
+    uint64_t offset = 0;
+    for (int i = 0; i < g->comp_count && i < GJ_MAX_COMP; i++) {
+        gj_comp_geom* k = &gs_max->comp[i];
+        k->blocks_x = cp->wmax[i];
+        k->blocks_y = cp->hmax[i];
+        k->data_width = cp->wmax[i] * 8;
+        k->data_height = cp->hmax[i] * 8;
+        k->data_offset = offset;
+        offset += (uint64_t)k->data_width * k->data_height;
+    }
+    gs_max->data_size = offset;
+    gs_max->block_count = (int)(offset / 64);
+}
+
 /* A batch of regions, once the coder is configured for the streams' geometry: every frame's rectangle checked against it (gj_region_plan; a
  * refusal names the frame), its origin and covers into the pinned records, its selection per scan; the largest cover and the largest selection
  * per scan of the call. 0 or -1. Nothing has been launched and nothing of the caller's output has been written when this runs. */
@@ -1341,9 +1412,9 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b, in
     int ref = -1; /* mixed: a frame of the family */
     if (gj_ensure_pinned_buffer((void**)&d->bh_rgn, &d->bh_rgn_cap, (size_t)b->count * sizeof(gj_region_frame), (size_t)b->count * sizeof(gj_region_frame) * 2) != 0) return -1;
     memset(b->plan_max, 0, sizeof b->plan_max);
-    int wmax[GJ_MAX_COMP] = {0, 0, 0, 0}, hmax[GJ_MAX_COMP] = {0, 0, 0, 0};
+    struct cover_plan cp;
+    memset(&cp, 0, sizeof cp);
     for (int f = 0; f < b->count; f++) {
-        const struct dec_request q = batch_request(d, b, f);
         struct gpujpeg_image_parameters pi_f = c->param_image;
         if (mixed) {
             if (!b->fam[f]) continue;
@@ -1356,17 +1427,8 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b, in
             for (int i = 0; i < g->comp_count && i < GJ_MAX_COMP; i++)
                 if (g->comp[i].segment_count > b->g_max.comp[i].segment_count) b->g_max.comp[i].segment_count = g->comp[i].segment_count;
         }
-        const int refused = gj_region_plan(&b->gs_one, &b->rg_one, g, &c->param, &pi_f, q.rect, q.resize ? &q.rs : NULL, d->req_alignment, &b->pi_r);
-        if (refused == -1) GJ_ERROR("Frame %d of the batch: the region %d,%d,%d,%d was refused!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3]);
-        if (refused == -3) GJ_ERROR("Frame %d of the batch: the rectangle %d,%d,%d,%d was refused by the resize filter!\n", f, q.rect[0], q.rect[1], q.rect[2], q.rect[3]);
-        if (refused != 0) return -1;
-        if (q.resize && f < d->prescales_n) d->prescales[f] = (uint8_t)b->rg_one.frame.scale;
-        const gj_region_frame* rf = &b->rg_one.frame;
-        d->bh_rgn[f] = *rf;
-        for (int i = 0; i < g->comp_count && i < GJ_MAX_COMP; i++) {
-            if (rf->bx1[i] - rf->bx0[i] > wmax[i]) wmax[i] = rf->bx1[i] - rf->bx0[i];
-            if (rf->by1[i] - rf->by0[i] > hmax[i]) hmax[i] = rf->by1[i] - rf->by0[i];
-        }
+        if (batch_cover_frame(d, b, f, g, &c->param, &pi_f, &cp, d->bh_rgn + f) != 0) return -1;
+        b->gs_one = cp.gs_one; b->rg_one = cp.rg_one; b->pi_r = cp.pi_r;
         for (int sc = 0; sc < GJ_MAX_COMP; sc++) {
             const int n = b->rg_one.sel_count[sc];
             b->plan[f * GJ_MAX_COMP + sc] = n;
@@ -1385,20 +1447,7 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b, in
                 memcpy(b->plan + (size_t)f * GJ_MAX_COMP, b->plan + (size_t)ref * GJ_MAX_COMP, GJ_MAX_COMP * sizeof(int));
             }
     }
-    /* the planes of the largest cover: every frame's cover planes are laid out like this */
-    b->gs_max = b->gs_one;
-    uint64_t offset = 0;
-    for (int i = 0; i < g->comp_count && i < GJ_MAX_COMP; i++) {
-        gj_comp_geom* k = &b->gs_max.comp[i];
-        k->blocks_x = wmax[i];
-        k->blocks_y = hmax[i];
-        k->data_width = wmax[i] * 8;
-        k->data_height = hmax[i] * 8;
-        k->data_offset = offset;
-        offset += (uint64_t)k->data_width * k->data_height;
-    }
-    b->gs_max.data_size = offset;
-    b->gs_max.block_count = (int)(offset / 64);
+    batch_cover_planes(&cp, g, &b->gs_max);
     b->img_w = c->param_image.width;
     b->img_h = c->param_image.height;
     b->planned = true;
@@ -1464,18 +1513,19 @@ static int batch_decode_one(struct gpujpeg_decoder* d, struct dec_batch* b, int 
  * the buffers and the job's pointers to them. */
 /* (g: the launch's geometry -- the coder's, or for streams of different image sizes the one with the family's largest counts, dec_batch::g_max;
  * min_samples: samples a frame's planes must hold at least -- the planes of the largest cover of such a batch, whose width and height come from
- * different frames, may be larger than any frame's own) */
+ * different frames, may be larger than any frame's own; planes_only: a chunk of progressive frames -- coefficient planes and, where the IDCT side wants
+ * them, component planes: no segment table, no marker-scan scratch, no compacted table, no tokens, so that the memory goes to frames) */
 static int batch_chunk_buffers(struct gpujpeg_decoder* d, const gj_geom* g, gj_dec_job* job, gj_batch* B, int n_all, size_t begin, size_t max_size, bool regions,
-                               size_t min_samples)
+                               size_t min_samples, bool planes_only)
 {
     struct gj_coder* c = &d->coder;
     const size_t S = (size_t)g->segment_count + GJ_MAX_COMP;
-    const size_t seg_frame = (3 * S + 8 + 3) & ~(size_t)3;                                                                   /* words */
-    const size_t scratch_frame = (gj_hip_find_segments_scratch_words(begin, max_size, (uint32_t)g->segment_count) + 3) & ~(size_t)3; /* words */
+    const size_t seg_frame = planes_only ? 0 : (3 * S + 8 + 3) & ~(size_t)3;                                                 /* words */
+    const size_t scratch_frame = planes_only ? 0 : (gj_hip_find_segments_scratch_words(begin, max_size, (uint32_t)g->segment_count) + 3) & ~(size_t)3; /* words */
     const size_t coefs_frame = ((size_t)(g->data_size > min_samples ? g->data_size : min_samples) + 63) & ~(size_t)63;   /* int16 */
     const int chunk_cap = d->b_chunk > 0 && d->b_chunk < GJ_DEC_BATCH_CHUNK_MAX ? d->b_chunk : GJ_DEC_BATCH_CHUNK_MAX;
     job->g.fb.frames = (uint32_t)(n_all < chunk_cap ? n_all : chunk_cap); /* (what the token / plane choice looks at) */
-    const bool tokens = !d->img.resize && gj_hip_decode_wants_tokens(&job->g, max_size, &d->tune) != 0; /* (crop-and-resize: the cover planes) */
+    const bool tokens = !planes_only && !d->img.resize && gj_hip_decode_wants_tokens(&job->g, max_size, &d->tune) != 0; /* (crop-and-resize: the cover planes) */
     const size_t tok_frame = tokens ? (max_size * 4 + 64 + 63) & ~(size_t)63 : 0;                                            /* tokens */
     const size_t rec_frame = tokens ? ((size_t)g->block_count + 8 + 7) & ~(size_t)7 : 0;                                    /* records */
     /* (a batch of regions: the cover planes of every configuration that does not take the token-fed region kernel, and a compacted table per frame;
@@ -1487,9 +1537,9 @@ static int batch_chunk_buffers(struct gpujpeg_decoder* d, const gj_geom* g, gj_d
     if (chunk > chunk_cap) chunk = chunk_cap;
     if (chunk > n_all) chunk = n_all;
     if (chunk < 1) chunk = 1;
-    if (gj_ensure_device_buffer((void**)&d->b_seg, &d->b_seg_cap, seg_frame * 4 * (size_t)chunk) != 0) return 0;
-    if (regions && gj_ensure_device_buffer((void**)&d->b_sel, &d->b_sel_cap, seg_frame * 4 * (size_t)chunk) != 0) return 0;
-    if (gj_ensure_device_buffer((void**)&d->b_scratch, &d->b_scratch_cap, scratch_frame * 4 * (size_t)chunk + 64) != 0) return 0;
+    if (!planes_only && gj_ensure_device_buffer((void**)&d->b_seg, &d->b_seg_cap, seg_frame * 4 * (size_t)chunk) != 0) return 0;
+    if (!planes_only && regions && gj_ensure_device_buffer((void**)&d->b_sel, &d->b_sel_cap, seg_frame * 4 * (size_t)chunk) != 0) return 0;
+    if (!planes_only && gj_ensure_device_buffer((void**)&d->b_scratch, &d->b_scratch_cap, scratch_frame * 4 * (size_t)chunk + 64) != 0) return 0;
     if (gj_ensure_device_buffer((void**)&d->b_coefs, &d->b_coefs_cap, coefs_frame * 2 * (size_t)chunk) != 0) return 0;
     if (planes && gj_ensure_device_buffer((void**)&d->b_planes, &d->b_planes_cap, coefs_frame * (size_t)chunk) != 0) return 0;
     if (planes) job->d_planes = d->b_planes;
@@ -1499,9 +1549,9 @@ static int batch_chunk_buffers(struct gpujpeg_decoder* d, const gj_geom* g, gj_d
         if (gj_ensure_device_buffer((void**)&d->b_rec, &d->b_rec_cap, rec_frame * 8 * (size_t)chunk) != 0) return 0;
         if (d->b_rec_cap != had && gj_hip_memset(d->b_rec, 0, d->b_rec_cap, c->stream) != 0) return 0;
     }
-    job->d_seg_pos = d->b_seg;
-    job->d_seg_len = d->b_seg + S;
-    job->d_seg_index = d->b_seg + 2 * S;
+    job->d_seg_pos = planes_only ? NULL : d->b_seg;
+    job->d_seg_len = planes_only ? NULL : d->b_seg + S;
+    job->d_seg_index = planes_only ? NULL : d->b_seg + 2 * S;
     job->d_coefs = d->b_coefs;
     job->tokens = tokens ? 1 : 0;
     job->d_tok = tokens ? d->b_tok : NULL;
@@ -1615,7 +1665,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     if (gj_hip_memcpy_h2d(d->b_sizes, d->bh_sizes, sizes_bytes, c->stream) != 0) return -1;
     gj_batch B;
     memset(&B, 0, sizeof B);
-    const int chunk = batch_chunk_buffers(d, g, &job, &B, n_all, begin, max_size, regions, mixed ? (size_t)b->gs_max.data_size : 0);
+    const int chunk = batch_chunk_buffers(d, g, &job, &B, n_all, begin, max_size, regions, mixed ? (size_t)b->gs_max.data_size : 0, false);
     if (chunk < 1) return -1;
     const size_t S = (size_t)g->segment_count + GJ_MAX_COMP;
     if (regions) {
@@ -1732,6 +1782,363 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     return accepted == 0 && first == 0 && !force_first ? 1 : 0;
 }
 
+/* ---- groups of progressive frames through batched launches (dec_opt_batch_progressive, gpujpeg_amd_ext.h) ---- */
+/* a frame of the call that is still undecoded when the pass runs */
+struct prog_cand {
+    int f;                         /* frame of the call */
+    const uint8_t* himage;        /* its whole stream in host memory: the host walks every scan, as dec_progressive does */
+    struct gj_reader_result r;
+    struct gj_prog_info info;
+};
+/* the progressive candidates that agree in everything the stages behind the coefficient planes read (prog_same_group) */
+struct prog_group {
+    int n; int* member;            /* indices into the candidates, ascending frames */
+    struct gpujpeg_parameters param; /* the first member's, restart interval 0: the restart intervals are the records' */
+    gj_geom g;
+    size_t max_size;               /* the longest stream */
+    struct cover_plan cp; gj_geom gs_max; gj_region_frame* rf; /* a call with rectangles: every member's against g, the planes of the largest cover */
+};
+
+static size_t prog_align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+/* width and height, component count, ids and sampling, what the reader made of APPn / Adobe / JFIF (its colour-space and pixel-format decisions), and
+ * per component the CONTENTS of its quantisation table. Huffman tables, scan scripts and restart intervals may differ. */
+static bool prog_same_group(const struct gj_reader_result* a, const struct gj_reader_result* b)
+{
+    struct gpujpeg_parameters pa = a->param, pb = b->param;
+    pa.restart_interval = pb.restart_interval = 0;
+    if (!gj_parameters_equal(&pa, &pb) || !gj_image_parameters_equal(&a->param_image, &b->param_image) || a->header_color_space != b->header_color_space) return false;
+    for (int i = 0; i < a->param.comp_count && i < GJ_MAX_COMP; i++)
+        if (a->comp_id[i] != b->comp_id[i] || memcmp(a->qraw[a->quant_map[i]], b->qraw[b->quant_map[i]], 64) != 0) return false;
+    return true;
+}
+
+/* the frame header of a stream, from its first n bytes alone: 1 = SOF2, 0 = another one (or a scan, or the end, ahead of any), -1 = not within these
+ * bytes or not a marker sequence -- what spares the pass the parse, and a device-resident stream the copy, of a frame that is not progressive */
+#define GJ_PROG_SNIFF_BYTES 1024
+static int prog_sniff(const uint8_t* p, size_t n)
+{
+    if (n < 4 || p[0] != 0xFF || p[1] != 0xD8) return -1;
+    size_t at = 2;
+    while (at + 4 <= n) {
+        if (p[at] != 0xFF) return -1;
+        const unsigned m = p[at + 1];
+        if (m == 0xFF) { at++; continue; } /* (fill bytes) */
+        if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) return m == 0xC2 ? 1 : 0;
+        if (m == 0xDA || m == 0xD9) return 0;
+        if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) { at += 2; continue; } /* (markers without a length) */
+        at += 2 + (((size_t)p[at + 2] << 8) | p[at + 3]);
+    }
+    return -1;
+}
+
+/* inside a level the longest serial walks start first (ties: by frame and position, so that the order is one) */
+static int prog_longest_first(const void* pa, const void* pb)
+{
+    const gj_prog_rec* a = pa;
+    const gj_prog_rec* b = pb;
+    if (a->len != b->len) return a->len > b->len ? -1 : 1;
+    if (a->frame != b->frame) return a->frame < b->frame ? -1 : 1;
+    return a->pos < b->pos ? -1 : a->pos > b->pos ? 1 : 0;
+}
+
+/* One group: the coder configured for its geometry, its quantisation tables, the table pools, per-frame records and work lists of all its frames in one
+ * pinned buffer with one upload, its host streams staged once, then per chunk of frames one gj_hip_decode -- the chunk's planes cleared, one entropy
+ * launch per level, the IDCT side of a baseline batch --, and one wait. 0 (frame_done set for the members; or nothing done: a group whose frames do not
+ * fit the caller's slots goes the single-frame route, which says so) or -1. */
+static int batch_progressive_group(struct gpujpeg_decoder* d, struct dec_batch* b, struct prog_cand* cand, const struct prog_group* G)
+{
+    struct gj_coder* c = &d->coder;
+    const bool regions = batch_has_regions(b);
+    const int n = G->n;
+    const struct gj_reader_result* r0 = &cand[G->member[0]].r;
+    if (decoder_configure(d, &G->param, &r0->param_image) != 0) return -1;
+    if (regions) {
+        dec_image_set(d, 1, &G->cp.gs_one, &G->cp.pi_r, &G->cp.rg_one); /* (what a region call leaves: the image of one of the frames) */
+    } else {
+        const struct dec_request q = dec_request_options(d);
+        if (dec_call_geometry(d, &q) != 0) return -1;
+    }
+    const size_t frame_raw = regions ? (size_t)G->cp.gs_one.raw_size : dec_raw_size(d);
+    if (b->output_stride < frame_raw || (b->frame_raw != 0 && b->frame_raw != frame_raw)) return 0;
+    b->frame_raw = frame_raw;
+    for (int i = 0; i < c->geom.comp_count; i++) {
+        c->geom.comp[i].q_table = r0->quant_map[i];
+        c->geom.comp[i].dc_table = c->geom.comp[i].ac_table = 0;
+    }
+    if (prog_quant_tables(d, r0) != 0) return -1;
+    gj_dec_job job;
+    dec_job_base(d, false, &job);
+    job.d_qtab = d->d_prog_q;
+    job.d_qtabf = (const float*)(const void*)(d->d_prog_q + 4 * 64);
+    job.jpeg_size = G->max_size;
+    gj_batch B;
+    memset(&B, 0, sizeof B);
+    const int chunk = batch_chunk_buffers(d, &c->geom, &job, &B, n, 0, G->max_size, regions, 0, true); /* (planes, no tokens, no segment table) */
+    if (chunk < 1) return -1;
+    const int chunks = (n + chunk - 1) / chunk;
+
+    /* the one upload: table pools | per-frame records | rectangles | stream sizes | work lists */
+    size_t pool_total = 0, rec_total = 0;
+    for (int i = 0; i < n; i++) {
+        pool_total += (size_t)cand[G->member[i]].info.pool_count;
+        rec_total += (size_t)cand[G->member[i]].info.segs.count;
+    }
+    const size_t tab_bytes = prog_align16(pool_total * GJ_DEC_TAB_WORDS * sizeof(uint16_t)), pf_bytes = prog_align16((size_t)n * sizeof(gj_prog_frame));
+    const size_t rf_bytes = regions ? prog_align16((size_t)n * sizeof(gj_region_frame)) : 0, sz_bytes = prog_align16((size_t)n * sizeof(uint32_t));
+    const size_t rec_at = tab_bytes + pf_bytes + rf_bytes + sz_bytes, bytes = rec_at + (rec_total + 1) * sizeof(gj_prog_rec);
+    if (gj_ensure_pinned_buffer((void**)&d->h_prog, &d->h_prog_cap, bytes, bytes + bytes / 2) != 0) return -1;
+    if (gj_ensure_device_buffer((void**)&d->d_prog, &d->d_prog_cap, bytes) != 0) return -1;
+    memset(d->h_prog, 0, bytes);
+    gj_prog_frame* pf = (gj_prog_frame*)(void*)(d->h_prog + tab_bytes);
+    uint32_t* sz = (uint32_t*)(void*)(d->h_prog + tab_bytes + pf_bytes + rf_bytes);
+    gj_prog_rec* recs = (gj_prog_rec*)(void*)(d->h_prog + rec_at);
+    if (regions) memcpy(d->h_prog + tab_bytes + pf_bytes, G->rf, (size_t)n * sizeof(gj_region_frame));
+    /* streams in host memory: one staging area, slots on 16-byte addresses; device-resident ones are read where they lie */
+    const size_t slot = prog_align16(G->max_size + 64);
+    if (!b->streams_on_device) {
+        if (gj_ensure_device_buffer((void**)&d->b_jpeg, &d->b_jpeg_cap, slot * (size_t)n) != 0) return -1;
+        b->host_io = true;
+    }
+    size_t tab = 0;
+    for (int i = 0; i < n; i++) {
+        const struct prog_cand* k = &cand[G->member[i]];
+        for (int t = 0; t < k->info.pool_count; t++)
+            if (gj_huffman_decoder_table(k->info.pool[t].bits, k->info.pool[t].vals, (uint16_t*)(void*)d->h_prog + (tab + (size_t)t) * GJ_DEC_TAB_WORDS) != 0) {
+                GJ_ERROR("Invalid Huffman table in a progressive scan!\n");
+                return -1;
+            }
+        pf[i].stream = b->streams_on_device ? (uint64_t)k->f * b->stream_stride : (uint64_t)i * slot;
+        pf[i].size = (uint32_t)b->sizes[k->f];
+        pf[i].tab_first = (uint32_t)tab;
+        pf[i].coef_block = (uint64_t)(i % chunk) * (B.coefs / 64);
+        sz[i] = pf[i].size;
+        tab += (size_t)k->info.pool_count;
+        if (!b->streams_on_device && gj_hip_memcpy_h2d(d->b_jpeg + (size_t)i * slot, k->himage, b->sizes[k->f], c->stream) != 0) return -1;
+    }
+    /* the work list of every chunk: level l of ALL its frames back to back, the longest segments first */
+    gj_prog_plan* plans = calloc((size_t)chunks, sizeof *plans);
+    if (!plans) return -1;
+    uint32_t at = 0;
+    long launches = 0;
+    for (int ch = 0; ch < chunks; ch++) {
+        gj_prog_plan* P = &plans[ch];
+        const int a = ch * chunk, m = n - a < chunk ? n - a : chunk;
+        for (int i = 0; i < m; i++)
+            if (cand[G->member[a + i]].info.levels > P->levels) P->levels = cand[G->member[a + i]].info.levels;
+        for (int level = 0; level < P->levels && level < GJ_PROG_MAX_SCANS; level++) {
+            P->level_first[level] = at;
+            for (int i = 0; i < m; i++) at += prog_level_records(&cand[G->member[a + i]].info, &c->geom, level, (unsigned)i, recs + at);
+            P->level_count[level] = at - P->level_first[level];
+            qsort(recs + P->level_first[level], P->level_count[level], sizeof *recs, prog_longest_first);
+            if (P->level_count[level] > 0) launches++;
+        }
+        P->d_recs = (const gj_prog_rec*)(const void*)(d->d_prog + rec_at);
+        P->d_tabs = (const uint16_t*)(const void*)d->d_prog;
+        P->tab_count = (uint32_t)pool_total;
+        P->d_frames = (const gj_prog_frame*)(const void*)(d->d_prog + tab_bytes) + a;
+    }
+    int rc = gj_hip_memcpy_h2d(d->d_prog, d->h_prog, rec_at + (size_t)at * sizeof(gj_prog_rec), c->stream);
+    const uint32_t* d_sizes = (const uint32_t*)(const void*)(d->d_prog + tab_bytes + pf_bytes + rf_bytes);
+    const gj_region_frame* d_rf = (const gj_region_frame*)(const void*)(d->d_prog + tab_bytes + pf_bytes);
+    const size_t praw = prog_align16(frame_raw);
+    job.d_jpeg = b->streams_on_device ? b->streams : d->b_jpeg;
+    job.g.fb.jpeg = B.jpeg = b->streams_on_device ? b->stream_stride : slot; /* (not read: every frame's record says where its stream lies) */
+    job.g.fb.coefs = B.coefs;
+    if (regions) {
+        job.gs = G->gs_max;
+        job.region.select = 0; /* (every segment of every scan is decoded) */
+        job.region.d_sel = NULL;
+        job.region.d_sel_count = job.region.h_sel_count = NULL;
+        memset(&job.region.frame, 0, sizeof job.region.frame); /* (not used: d_frames) */
+    }
+    for (int ch = 0; ch < chunks && rc == 0; ch++) {
+        const int a = ch * chunk, m = n - a < chunk ? n - a : chunk;
+        /* where the pixels go: the caller's slots where the chunk's frames lie a constant distance apart, else back to back and copied there */
+        const int f0 = cand[G->member[a]].f, step = m > 1 ? cand[G->member[a + 1]].f - f0 : 1;
+        bool strided = true;
+        for (int i = 1; i < m; i++) strided = strided && cand[G->member[a + i]].f - cand[G->member[a + i - 1]].f == step;
+        if (!strided && gj_ensure_device_buffer((void**)&d->b_praw, &d->b_praw_cap, praw * (size_t)chunk) != 0) { rc = -1; break; }
+        B.count = (uint32_t)m;
+        B.raw = strided ? (uint64_t)step * b->d_out_stride : praw;
+        B.d_sizes = d_sizes + a;
+        job.batch = B;
+        job.g.fb.sizes = B.d_sizes;
+        job.g.fb.raw = B.raw;
+        job.g.fb.frames = (uint32_t)m;
+        if (regions || job.scale > 1) job.gs.fb = job.g.fb; /* (the pixel kernels of a batch of regions and of a reduced-size batch take gs only) */
+        if (regions) {
+            job.region.d_frames = d_rf + a;
+            job.region.scale_mask = job.region.comp_mask = 0; /* (which of the three IDCT kernels this chunk's frames need) */
+            for (int i = 0; i < m; i++) {
+                if (G->rf[a + i].per_comp) job.region.comp_mask |= (unsigned)G->rf[a + i].scale;
+                else job.region.scale_mask |= (unsigned)G->rf[a + i].scale;
+            }
+        }
+        job.d_raw = strided ? b->d_out + (size_t)f0 * b->d_out_stride : d->b_praw;
+        job.prog = &plans[ch];
+        if (!gj_hip_decode_batchable(&job) || gj_hip_decode(&job, c->stream, NULL) != 0) {
+            GJ_ERROR("Decoder kernels failed: %s\n", gj_hip_last_error());
+            rc = -1;
+        }
+        for (int i = 0; i < m && rc == 0 && !strided; i++)
+            rc = gj_hip_memcpy_d2d(b->d_out + (size_t)cand[G->member[a + i]].f * b->d_out_stride, d->b_praw + (size_t)i * praw, frame_raw, c->stream);
+    }
+    if (gj_hip_stream_sync(c->stream) != 0 && rc == 0) {
+        GJ_ERROR("Decoder failed: %s\n", gj_hip_last_error());
+        rc = -1;
+    }
+    free(plans);
+    if (rc != 0) return -1;
+    if (regions || job.scale > 1) c->kernel_ms[4] = (float)d->last_idct_path; /* (which IDCT side the batched launches took, gpujpeg_amd_ext.h) */
+    for (int i = 0; i < n; i++) {
+        const struct prog_cand* k = &cand[G->member[i]];
+        b->frame_done[k->f] = 1;
+        if (regions) { /* (gpujpeg_amd_decoder_get_region_stats: what the frame's own region call reports -- every segment decoded, its cover's blocks) */
+            const gj_region_frame* rf = &G->rf[i];
+            b->unselected = true;
+            b->stats[1] += (long)k->info.segs.count;
+            b->stats[3] += (long)k->info.segs.count;
+            for (int q = 0; q < c->geom.comp_count && q < GJ_MAX_COMP; q++) b->stats[2] += (long)(rf->bx1[q] - rf->bx0[q]) * (rf->by1[q] - rf->by0[q]);
+        }
+    }
+    d->pb_stats[0] += n;
+    d->pb_stats[1] += 1;
+    d->pb_stats[2] += launches;
+    d->pb_stats[3] += (long)at;
+    return 0;
+}
+
+/* The pass of a batch call between the baseline batched launches and the single-frame route: the candidates -- the frames still undecoded -- are brought
+ * to the host whole (device-resident streams: every copy queued, ONE wait) and parsed (gj_reader_parse + gj_reader_parse_progressive); the progressive
+ * ones the parser takes form groups (prog_same_group; with rectangles: every member's rectangle planned against the group's geometry, a refusal names
+ * the frame and fails the call before a group has written anything), and every group of two or more runs through batch_progressive_group, one after the
+ * other. Everything else stays undecoded for the single-frame route, which gives it the message and return code it always had. The header cache and
+ * what the speculative launches remember (remember_summary) are neither read nor written. Frames of different image sizes are different groups:
+ * per-frame geometry inside one set of progressive launches is not built. 0 or -1. */
+static int batch_progressive(struct gpujpeg_decoder* d, struct dec_batch* b)
+{
+    struct gj_coder* c = &d->coder;
+    const bool regions = batch_has_regions(b);
+    /* (a decoder state in which the baseline batched launches decline too: every frame goes the single-frame route) */
+    if ((!regions && d->region_on) || d->keep_coefs || !d->use_fused || d->flipped || d->channel_remap || d->host_scan || d->tune.dec_no_spec) return 0;
+    int left = 0;
+    for (int f = 0; f < b->count; f++)
+        if (!b->frame_done[f]) {
+            if (b->sizes[f] < 4 || b->sizes[f] > 0x7FFFFFF0u) return 0;
+            left++;
+        }
+    if (left < 2) return 0;
+    /* a look at the frame header first: a baseline frame that is left (a call whose progressive frame 0 left no header to launch on has many) is neither
+     * copied to the host nor parsed. Device-resident streams: the first bytes of all of them by ONE gather launch */
+    const uint8_t* heads = b->streams;
+    size_t head_stride = b->stream_stride;
+    if (b->streams_on_device) {
+        const size_t sizes_bytes = (size_t)b->count * sizeof(uint32_t), hdr_bytes = (size_t)b->count * GJ_PROG_SNIFF_BYTES;
+        if (gj_ensure_device_buffer((void**)&d->b_sizes, &d->b_sizes_cap, sizes_bytes) != 0) return -1;
+        if (gj_ensure_pinned_buffer((void**)&d->bh_sizes, &d->bh_sizes_cap, sizes_bytes, sizes_bytes + sizes_bytes / 2) != 0) return -1;
+        if (gj_ensure_pinned_buffer((void**)&d->bh_hdrs, &d->bh_hdrs_cap, hdr_bytes, hdr_bytes * 2) != 0) return -1;
+        for (int f = 0; f < b->count; f++) d->bh_sizes[f] = (uint32_t)b->sizes[f];
+        if (gj_hip_memcpy_h2d(d->b_sizes, d->bh_sizes, sizes_bytes, c->stream) != 0 ||
+            gj_hip_gather_headers(b->streams, b->stream_stride, d->b_sizes, (uint32_t)b->count, GJ_PROG_SNIFF_BYTES, d->bh_hdrs, c->stream) != 0 ||
+            gj_hip_stream_sync(c->stream) != 0) {
+            GJ_ERROR("Reading the headers of the batch failed: %s\n", gj_hip_last_error());
+            return -1;
+        }
+        heads = d->bh_hdrs;
+        head_stride = GJ_PROG_SNIFF_BYTES;
+    }
+    struct prog_cand* cand = calloc((size_t)left, sizeof *cand);
+    struct prog_group* groups = calloc((size_t)left, sizeof *groups);
+    int ncand = 0, ngroups = 0, rc = -1;
+    if (!cand || !groups) goto out;
+    for (int f = 0; f < b->count; f++) {
+        const size_t seen = b->streams_on_device && b->sizes[f] > GJ_PROG_SNIFF_BYTES ? GJ_PROG_SNIFF_BYTES : b->sizes[f];
+        if (b->frame_done[f] || prog_sniff(heads + (size_t)f * head_stride, seen) == 0) continue; /* (1, or not told by these bytes: the parse decides) */
+        cand[ncand].f = f;
+        cand[ncand++].himage = b->streams + (size_t)f * b->stream_stride;
+    }
+    if (ncand < 2) { rc = 0; goto out; }
+    if (b->streams_on_device) {
+        /* a RUN of neighbouring candidates comes with one copy of everything from its first stream to the end of its last -- 255 frames of a dataset
+         * are one submission, not 255 --, unless the gaps between the streams would more than double what is copied */
+        size_t bytes = 0;
+        for (int pass = 0; pass < 2; pass++) { /* (0: the size of the pinned buffer, 1: the copies) */
+            size_t at = 0;
+            for (int k = 0; k < ncand;) {
+                int e = k + 1;
+                size_t sum = b->sizes[cand[k].f];
+                while (e < ncand && cand[e].f == cand[e - 1].f + 1) sum += b->sizes[cand[e++].f];
+                const size_t span = (size_t)(e - 1 - k) * b->stream_stride + b->sizes[cand[e - 1].f];
+                if (e - k > 1 && span > 2 * sum + 4096) e = k + 1; /* (streams far apart: one by one) */
+                const size_t n = e - k > 1 ? span : b->sizes[cand[k].f];
+                if (pass == 1) {
+                    if (gj_hip_memcpy_d2h(d->bh_pstreams + at, b->streams + (size_t)cand[k].f * b->stream_stride, n, c->stream) != 0) goto out;
+                    for (int i = k; i < e; i++) cand[i].himage = d->bh_pstreams + at + (size_t)(i - k) * b->stream_stride;
+                }
+                at += prog_align16(n);
+                k = e;
+            }
+            bytes = at;
+            if (pass == 0 && gj_ensure_pinned_buffer((void**)&d->bh_pstreams, &d->bh_pstreams_cap, bytes, bytes + bytes / 2) != 0) goto out;
+        }
+        if (gj_hip_stream_sync(c->stream) != 0) goto out;
+    }
+    /* the groups: a candidate joins the first group it agrees with */
+    for (int k = 0; k < ncand; k++) {
+        struct prog_cand* q = &cand[k];
+        const size_t size = b->sizes[q->f];
+        if (gj_reader_parse(q->himage, size, GPUJPEG_LL_QUIET - 1, d->ff_cs_itu601_is_709, d->req_pixel_format, d->req_color_space, d->req_alignment, &q->r, true, true) != 0 ||
+            !q->r.progressive || q->r.scan_begin[0] >= size)
+            continue;
+        if (gj_reader_parse_progressive(q->himage, size, &q->r, &q->info, true) != 0 || q->info.bad_scan != 0 || q->info.levels > GJ_PROG_MAX_SCANS) continue;
+        bool tables = true;
+        for (int i = 0; i < q->r.param.comp_count; i++)
+            if (q->r.quant_map[i] < 0 || q->r.quant_map[i] > 3 || !q->r.q_present[q->r.quant_map[i]]) tables = false;
+        if (!tables) continue;
+        int gi = 0;
+        while (gi < ngroups && !prog_same_group(&cand[groups[gi].member[0]].r, &q->r)) gi++;
+        struct prog_group* G = &groups[gi];
+        if (gi == ngroups) {
+            G->member = calloc((size_t)ncand, sizeof *G->member);
+            if (!G->member) goto out;
+            ngroups++;
+        }
+        G->member[G->n++] = k;
+        if (size > G->max_size) G->max_size = size;
+    }
+    /* every group's geometry; a call with rectangles: every member's rectangle against it, before any group is launched */
+    for (int gi = 0; gi < ngroups; gi++) {
+        struct prog_group* G = &groups[gi];
+        if (G->n < 2) continue;
+        const struct gj_reader_result* r0 = &cand[G->member[0]].r;
+        G->param = r0->param;
+        G->param.restart_interval = 0;
+        /* (what the single call refuses for this image: nothing is launched, the frames go the ordinary way and that call says why) */
+        const int w = r0->param_image.width, s = d->scale > 1 ? d->scale : 1;
+        bool refused = gj_geom_init(&G->g, &G->param, &r0->param_image, false) != 0;
+        if (!refused && !regions) refused = r0->param_image.pixel_format == GPUJPEG_422_U8_P1020 && ((s > 1 ? GPUJPEG_AMD_SCALED_DIM(w, s) : w) & 1);
+        /* (a call whose rectangles have been checked against the baseline frames' image: a frame of another size fails that call, as ever) */
+        if (!refused && regions && b->planned && !b->what.mixed) refused = w != b->img_w || r0->param_image.height != b->img_h;
+        if (refused) { G->n = 0; continue; }
+        if (!regions) continue;
+        G->rf = calloc((size_t)G->n, sizeof *G->rf);
+        if (!G->rf) goto out;
+        for (int i = 0; i < G->n; i++)
+            if (batch_cover_frame(d, b, cand[G->member[i]].f, &G->g, &G->param, &r0->param_image, &G->cp, G->rf + i) != 0) goto out;
+        batch_cover_planes(&G->cp, &G->g, &G->gs_max);
+    }
+    for (int gi = 0; gi < ngroups; gi++)
+        if (groups[gi].n >= 2 && batch_progressive_group(d, b, cand, &groups[gi]) != 0) goto out;
+    rc = 0;
+out:
+    for (int gi = 0; groups && gi < ngroups; gi++) { free(groups[gi].member); free(groups[gi].rf); }
+    for (int k = 0; cand && k < ncand; k++) gj_prog_info_free(&cand[k].info);
+    free(groups);
+    free(cand);
+    return rc;
+}
+
 /* the batch call proper; what: the rectangles of a batch of regions or of crop-and-resize, or NULL */
 static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_t stream_stride, const size_t* sizes, int count, const struct dec_rects* what,
                         uint8_t* output, size_t output_stride, struct gpujpeg_image_parameters* param_image)
@@ -1741,8 +2148,10 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
                           .d_out = output, .d_out_stride = output_stride};
     if (what) b.what = *what;
     b.restartless = d->batch_restartless != 0; /* (the option as it is when the call starts) */
-    d->entropy_valid = false;
+    d->entropy_valid = d->pb_stats_valid = false;
     d->entropy_bytes[0] = d->entropy_bytes[1] = 0;
+    b.prog_batch = d->batch_progressive != 0 && d->progressive != 0; /* (both options as they are when the call starts) */
+    memset(d->pb_stats, 0, sizeof d->pb_stats);
     const bool regions = batch_has_regions(&b);
     b.streams_on_device = gj_hip_is_device_ptr(streams) != 0;
     b.out_on_device = gj_hip_is_device_ptr(output) != 0;
@@ -1775,6 +2184,8 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
         b.frame_done[0] = 1;
         b.first = 1;
     }
+    /* the progressive frames among what is left, where they form groups (dec_opt_batch_progressive) */
+    if (b.prog_batch && batch_progressive(d, &b) != 0) goto out;
     /* whatever is left: the ordinary call, frame by frame */
     d->b_last_batched = 0;
     for (int f = b.first; f < count; f++) d->b_last_batched += b.frame_done[f] ? 1 : 0;
@@ -1798,6 +2209,7 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
         memcpy(d->region_stats, b.stats, sizeof d->region_stats);
     }
     d->entropy_valid = b.restartless;
+    d->pb_stats_valid = b.prog_batch;
     rc = 0; /* (c->frames counts the frames TIMED with perf_stats, src/gpujpeg_common.c:2238-2254: a batch adds none) */
 out:
     if (rc != 0 && b.host_io) gj_hip_stream_sync(c->stream); /* (what is queued on the stream must not read the caller's streams or write its frames after the error has left) */
@@ -1821,7 +2233,7 @@ int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder* d, const ui
                                              struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !origins) return -1;
-    d->entropy_valid = false;
+    d->entropy_valid = d->pb_stats_valid = false;
     if (width < 1 || height < 1) {
         GJ_ERROR("A batch of regions needs a width and a height of at least 1 (given: %d x %d)!\n", width, height);
         return -1;
@@ -1847,7 +2259,7 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
                                     struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !rects) return -1;
-    d->entropy_valid = false;
+    d->entropy_valid = d->pb_stats_valid = false;
     d->prescales_n = 0;
     if (out_width < 1 || out_height < 1 || out_width > 16384 || out_height > 16384) {
         GJ_ERROR("Crop-and-resize needs an output width and height of 1 to 16384 (given: %d x %d)!\n", out_width, out_height);
@@ -1922,7 +2334,7 @@ int gpujpeg_amd_decoder_decode_batch_crop_resize_tensor(struct gpujpeg_decoder* 
                                                         struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !rects) return -1;
-    d->entropy_valid = false;
+    d->entropy_valid = d->pb_stats_valid = false;
     d->prescales_n = 0;
     if (!format) {
         GJ_ERROR("Tensor output needs a format!\n");
@@ -2105,6 +2517,12 @@ int gpujpeg_decoder_set_option(struct gpujpeg_decoder* d, const char* opt, const
         GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS " (" GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_OFF " or " GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_ON ")\n", val);
         return GPUJPEG_ERROR;
     }
+    if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_BATCH_PROGRESSIVE) == 0) { /* read by every batch call when it starts */
+        if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_OFF) == 0) { d->batch_progressive = 0; return GPUJPEG_NOERR; }
+        if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_ON) == 0) { d->batch_progressive = 1; return GPUJPEG_NOERR; }
+        GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_BATCH_PROGRESSIVE " (" GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_OFF " or " GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_ON ")\n", val);
+        return GPUJPEG_ERROR;
+    }
     if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_BATCH_SIZES) == 0) { /* read by gpujpeg_amd_decoder_decode_batch_crop_resize (and _tensor) alone */
         if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME) == 0) { d->batch_sizes_mixed = 0; return GPUJPEG_NOERR; }
         if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED) == 0) { d->batch_sizes_mixed = 1; return GPUJPEG_NOERR; }
@@ -2153,6 +2571,7 @@ void gpujpeg_decoder_print_options(void)
     printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS "=[" GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_OFF "|" GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_ON "] - whether the batch calls take streams without restart markers through their batched launches (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_SIZES "=[" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME "|" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED "] - whether the streams of one crop-and-resize call may differ in image size (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_PROGRESSIVE "=[" GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_OFF "|" GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_ON "] - whether progressive (SOF2) streams are decoded (MI355X extension)\n");
+    printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_PROGRESSIVE "=[" GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_OFF "|" GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_ON "] - whether the batch calls take groups of progressive streams through batched launches (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_REGION "=[X,Y,W,H|full] - decode the W x H pixels at (X, Y) only (MI355X extension)\n");
 }
 
@@ -2231,6 +2650,13 @@ int gpujpeg_amd_decoder_get_progressive_stats(struct gpujpeg_decoder* d, long ou
     if (!d || !out) return -1;
     for (int i = 0; i < 4; i++) out[i] = d->prog_stats_valid ? d->prog_stats[i] : 0;
     return d->prog_stats_valid ? 0 : -1;
+}
+
+int gpujpeg_amd_decoder_get_progressive_batch_stats(struct gpujpeg_decoder* d, long out[4])
+{
+    if (!d || !out) return -1;
+    for (int i = 0; i < 4; i++) out[i] = d->pb_stats_valid ? d->pb_stats[i] : 0;
+    return d->pb_stats_valid ? 0 : -1;
 }
 
 int gpujpeg_amd_host_stream_info(const uint8_t* image, size_t size, int out[8])

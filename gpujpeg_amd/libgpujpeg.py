@@ -39,6 +39,11 @@ BATCH_RESTARTLESS_OFF, BATCH_RESTARTLESS_ON = "off", "on"
 DEC_OPT_PROGRESSIVE = "dec_opt_progressive"
 PROGRESSIVE_OFF, PROGRESSIVE_ON = "off", "on"
 PROGRESSIVE_MAX_SCANS = 64
+# Decoder.set_option(DEC_OPT_BATCH_PROGRESSIVE, BATCH_PROGRESSIVE_ON): with DEC_OPT_PROGRESSIVE on, the batch calls take the progressive frames that
+# form a group (same size, sampling and quantisation tables) through batched launches (GPUJPEG_AMD_DEC_OPT_BATCH_PROGRESSIVE);
+# Decoder.progressive_batch_stats() tells what they took
+DEC_OPT_BATCH_PROGRESSIVE = "dec_opt_batch_progressive"
+BATCH_PROGRESSIVE_OFF, BATCH_PROGRESSIVE_ON = "off", "on"
 # encoder option of the MI355X build (gpujpeg_amd_ext.h: GPUJPEG_AMD_ENC_OPT_HUFFMAN): Annex K.3 tables, or tables built per frame
 ENC_OPT_HUFFMAN = "enc_opt_huffman"
 ENC_HUFFMAN_STANDARD, ENC_HUFFMAN_OPTIMAL = "standard", "optimal"
@@ -683,6 +688,14 @@ class Decoder:
         a = (C.c_long * 4)()
         self.lib.L.gpujpeg_amd_decoder_get_progressive_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
         rc = self.lib.L.gpujpeg_amd_decoder_get_progressive_stats(self.h, a)
+        return (int(rc),) + tuple(int(x) for x in a)
+
+    def progressive_batch_stats(self):
+        """gpujpeg_amd_decoder_get_progressive_batch_stats: (rc, frames the batched progressive launches took, groups, entropy launches, records = waves)
+        of the last batch call made with DEC_OPT_PROGRESSIVE and DEC_OPT_BATCH_PROGRESSIVE both on; (-1, 0, 0, 0, 0) after any other call"""
+        a = (C.c_long * 4)()
+        self.lib.L.gpujpeg_amd_decoder_get_progressive_batch_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        rc = self.lib.L.gpujpeg_amd_decoder_get_progressive_batch_stats(self.h, a)
         return (int(rc),) + tuple(int(x) for x in a)
 
     def entropy_bytes(self):

@@ -356,7 +356,7 @@ GJ_HIP_API int gj_hip_resize_aa_weights(int n_src, int n_out, int i, int* first,
 
 /* Progressive streams (SOF2, dec_opt_progressive): the work list of k_huffman_decode_prog, ONE WAVE PER RECORD. A record is one restart segment of
  * one scan and says everything the wave needs -- no record refers to a frame: where its blocks lie is given per component as the block index of the
- * plane's first block in d_coefs and the plane's pitch in blocks, so that a later batch over frames only has to add a plane base per record.
+ * plane's first block in d_coefs and the plane's pitch in blocks, so that a chunk of frames (gj_prog_frame, below) only adds a plane base per record's frame.
  * A scan of one component (every AC scan, a DC scan of one component) codes the ceil(w_c / 8) x ceil(h_c / 8) blocks of the component in raster
  * order (`across` of them per row) inside the plane's pitch; a DC scan of several components codes whole MCUs of the FRAME's grid (`across` MCUs
  * per row), component c's h x v blocks of every MCU. first / count: blocks of the first kind of scan, MCUs of the second. */
@@ -371,9 +371,21 @@ typedef struct gj_prog_rec {
     uint32_t pos, len;             /* the segment's entropy-coded bytes in the stream */
     uint32_t first, count;         /* first block / MCU of the segment and how many it codes */
     uint32_t across;               /* coded blocks / MCUs per row */
-    uint8_t kind, ncomp, ss, se, ah, al, reserved[2];
+    uint8_t kind, ncomp, ss, se, ah, al;
+    uint16_t frame;                /* a chunk of frames (gj_prog_plan::d_frames): the record's frame in the chunk; a single frame: 0, not read */
     gj_prog_comp c[GJ_MAX_COMP];
 } gj_prog_rec;
+/* A chunk of progressive frames behind ONE set of launches (dec_opt_batch_progressive, k_huffman_decode_prog_batch): what a record's frame number
+ * stands for. pos / len of the frame's records stay relative to the frame's OWN stream -- a 32-bit offset into a staging area of 256 streams is not
+ * safe --, the table numbers of its records count from tab_first, their block numbers from coef_block; the kernel clamps positions to `size`, table
+ * numbers to the whole pool and block numbers to the frame's own planes. The frames of one chunk share the geometry: frames of different image sizes
+ * are different launches (per-frame geometry for progressive frames is not built). */
+typedef struct gj_prog_frame {
+    uint64_t stream;               /* bytes from gj_dec_job::d_jpeg to the frame's stream */
+    uint32_t size;                 /* bytes of the stream */
+    uint32_t tab_first;            /* first entry of the frame's tables in the pool */
+    uint64_t coef_block;           /* block index of the frame's planes in gj_dec_job::d_coefs: frame number in the chunk x gj_frame_strides::coefs / 64 */
+} gj_prog_frame;
 /* the plan of a progressive frame: scans whose coefficients do not depend on each other form a LEVEL and are launched together, the levels one
  * after the other on the stream (gj_decoder.c: the level of a scan is 1 + the highest level among the earlier scans that share a component and
  * a coefficient with it). Records of a level lie back to back. */
@@ -384,6 +396,9 @@ typedef struct gj_prog_plan {
     uint32_t tab_count;
     int levels;
     uint32_t level_first[GJ_PROG_MAX_SCANS], level_count[GJ_PROG_MAX_SCANS];
+    /* a chunk of frames: device memory, [gj_batch::count] (NULL: a single frame). Level l is then level l of ALL the chunk's frames, its records in
+     * descending order of len -- the longest serial walks start first --, and `levels` the deepest frame's */
+    const gj_prog_frame* d_frames;
 } gj_prog_plan;
 
 typedef struct gj_dec_job {
@@ -446,7 +461,11 @@ typedef struct gj_dec_job {
      * by piece by k_huffman_decode_par, plane mode -- and a batch of regions on them selects every segment. 0: gj_hip_decode_batchable says no */
     int batch_restartless;
     /* a progressive frame (host memory, NULL: a baseline frame): the coefficient planes are cleared and filled by k_huffman_decode_prog, one launch
-     * per level, in place of the entropy decoders above -- no segment table, no tokens, no selection, no batch --; the IDCT side is the plane route's */
+     * per level, in place of the entropy decoders above -- no segment table, no tokens, no selection --; the IDCT side is the plane route's.
+     * With gj_dec_job::batch (and gj_prog_plan::d_frames): a chunk of progressive frames of one geometry and one set of quantisation tables -- the
+     * chunk's planes cleared once, one k_huffman_decode_prog_batch launch per level, then the IDCT side exactly as a baseline batch has it (full size,
+     * scale, a batch of regions -- WITHOUT a selection: every segment is decoded --, crop-and-resize). Nothing but d_jpeg, d_coefs, d_planes, d_raw,
+     * d_qtab / d_qtabf, g / gs with their fb, batch.count, scale and region is read. */
     const gj_prog_plan* prog;
 } gj_dec_job;
 /* 1 when gj_hip_decode takes a batch (gj_dec_job::batch.count > 1) of this job's configuration */

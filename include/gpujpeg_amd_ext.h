@@ -274,6 +274,47 @@ GPUJPEG_API int gpujpeg_amd_host_huffman_table_check(const uint8_t bits[17], con
 #define GPUJPEG_AMD_PROGRESSIVE_MAX_SCANS 64
 GPUJPEG_API int gpujpeg_amd_decoder_get_progressive_stats(struct gpujpeg_decoder* decoder, long out[4]);
 GPUJPEG_API int gpujpeg_amd_host_stream_info(const uint8_t* image, size_t size, int out[8]);
+/* Decoder option "dec_opt_batch_progressive" = "off" (default) or "on": whether the batch calls -- gpujpeg_amd_decoder_decode_batch, _decode_batch_ptrs
+ * (with and without dec_opt_scale), _decode_batch_regions, _decode_batch_crop_resize and _decode_batch_crop_resize_tensor (with the prescale,
+ * subsampled-prescale and antialias options, the mirror, every output and tensor format those calls take) -- take the PROGRESSIVE frames of a call
+ * through batched launches of their own. Read by every batch call when it starts; it holds from the next call on and may be changed between two calls
+ * of a decoder. Another value is refused by gpujpeg_decoder_set_option (GPUJPEG_ERROR) and leaves the setting as it was. With "off", or with
+ * dec_opt_progressive = "off" (a SOF2 stream then fails the call as ever), every byte, counter, launch, refusal, message and kernel-times slot of every
+ * call is what it is without the option: a progressive frame goes the single-frame route and gpujpeg_amd_decoder_last_batch counts it as single.
+ * WITH "on" (and dec_opt_progressive = "on") it overrides, in the comment of dec_opt_progressive above, "inside a batch call a progressive frame goes
+ * the single-frame route" for the progressive frames that form a GROUP. Frame f stays, byte for byte (tensor call: bit for bit), what the single-frame
+ * call returns for stream f -- its baseline twin's image --, and gpujpeg_amd_decoder_last_batch counts the frames of a group as batched.
+ *   Group.     The candidates are the frames of the call that are still undecoded after frame 0 has gone ahead (fresh decoder, host output, stale
+ *              header cache) and the baseline batched launches have run, both exactly as without the option. Among them a group is the progressive
+ *              frames that agree in everything the stages behind the coefficient planes read: image width and height; component count, ids and
+ *              sampling factors; per component the CONTENTS of its quantisation table (64 values, not the slot number); and what the reader makes of
+ *              APPn / Adobe / JFIF (its colour-space decisions, not the segments' bytes). Huffman tables, DHT redefinitions between scans, scan
+ *              scripts, restart intervals and a stream that ends after a whole scan may differ freely inside a group: libjpeg writes optimised
+ *              tables into every progressive file, so a folder of files saved by one tool at one quality and size is one group although no two of
+ *              their headers are byte-equal. A group needs at least 2 frames; a call may hold several groups, which run one after the other. With
+ *              dec_opt_batch_sizes = mixed every distinct image size is its own group: per-frame geometry for progressive frames of different sizes
+ *              inside one set of launches is NOT built.
+ *   Routing.   The single-frame route, with the same message and return code as without the option: a progressive frame in a group of one; a frame
+ *              whose headers or scan script the parser refuses; every frame while the decoder is in a state in which the baseline batched launches
+ *              decline too (gpujpeg_amd_decoder_keep_coefficients, gpujpeg_amd_decoder_set_fused(0), dec_opt_flipped, dec_opt_channel_remap, the
+ *              decoder's own dec_opt_region, a scale the single call refuses). A rectangle the single call would refuse is refused before anything
+ *              of the output is written, with the frame named.
+ *   Launches.  Per chunk of a group's frames (gpujpeg_amd_decoder_set_batch_chunk) one clear of the chunk's coefficient planes, then level l of ALL
+ *              the chunk's frames in ONE k_huffman_decode_prog_batch launch -- as many launches as the chunk's deepest frame has levels, one wave per
+ *              restart segment of a scan as in the single-frame kernel, the longest segments of a level first --, then the IDCT side as a baseline
+ *              batch has it. The host walks every scan of every candidate whose frame header is SOF2 first (device-resident streams: one
+ *              launch gathers the first KB of every stream, then one copy per run of neighbouring progressive streams, one wait). The header
+ *              cache is neither read nor written: a baseline batch call afterwards launches on the header it had cached.
+ *   Counters.  gpujpeg_amd_decoder_get_region_stats after a batch of regions or of crop-and-resize: the four numbers of the same call with the option
+ *              off (a progressive frame contributes mode 2, its scan segments, its cover's blocks). gpujpeg_amd_decoder_get_prescales and
+ *              _get_entropy_bytes are unchanged (progressive frames add nothing to the latter). Kernel-times slot [4] is what the last set of batched
+ *              launches took. gpujpeg_amd_decoder_get_progressive_stats keeps its meaning: the last single-frame decode inside the call.
+ * gpujpeg_amd_decoder_get_progressive_batch_stats: after a batch call made with both options "on", out[0] = frames the batched progressive launches
+ * took, out[1] = groups, out[2] = k_huffman_decode_prog_batch launches, out[3] = records (waves). Returns 0. After any other call: zeros, returns -1. */
+#define GPUJPEG_AMD_DEC_OPT_BATCH_PROGRESSIVE "dec_opt_batch_progressive"
+#define GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_OFF "off"
+#define GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_ON "on"
+GPUJPEG_API int gpujpeg_amd_decoder_get_progressive_batch_stats(struct gpujpeg_decoder* decoder, long out[4]);
 /* Host-only: the table enc_opt_huffman=optimal builds for one class from symbol counts freq[256] (ITU T.81 Annex K.2: Figures K.1, K.3, K.4;
  * reserved code point, ties to the larger symbol value), code lengths limited to the largest L of 16 .. 10 whose table the library's
  * two-level decode tables take. Writes BITS (bits[1..16]) and HUFFVAL; returns L, or -1 when no count is non-zero. */
