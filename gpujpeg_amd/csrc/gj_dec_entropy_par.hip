@@ -128,7 +128,10 @@ struct GjLeave {
 
 // (MIXED: a batch of frames of different image sizes -- segments, blocks and planes are frame blockIdx.z's own, gj_frame_geom; the strides between the
 // frames' buffers are the launch's)
-template <bool INTERLEAVED, int SUB_BYTES, bool MIXED = false>
+// (HDRS: frames with headers of their own, gj_batch::own_headers -- the two-level tables loaded into LDS are the frame's table set's,
+// gj_frame_tabset_words; the selectors in s_ptab come from the frame's geometry as for MIXED. An instantiation of its own: no LDS, and the
+// instantiations of the batches without such records keep their code)
+template <bool INTERLEAVED, int SUB_BYTES, bool MIXED = false, bool HDRS = false>
 __global__ __launch_bounds__(256) void k_huffman_decode_par(const gj_geom g_launch, const uint8_t* __restrict__ jpeg, uint64_t jpeg_size,
                                                             const uint32_t* __restrict__ seg_pos, const uint32_t* __restrict__ seg_len,
                                                             const uint32_t* __restrict__ seg_index, const int seg_count_max,
@@ -179,7 +182,7 @@ __global__ __launch_bounds__(256) void k_huffman_decode_par(const gj_geom g_laun
     if (tid == 0) s_nlong = 0;
     __syncthreads();
     {
-        const uint4* src = reinterpret_cast<const uint4*>(tabs);
+        const uint4* src = reinterpret_cast<const uint4*>(tabs + gj_frame_tabset_words<HDRS>(g_launch));
         uint4* dst = reinterpret_cast<uint4*>(s_tab);
         for (int t = tid; t < 4 * GJ_DEC2_WORDS / 8; t += 256) dst[t] = src[t];
     }
@@ -776,6 +779,8 @@ void gj_launch_huffman_par(const gj_dec_job* job, hipStream_t st)
     if (g.fb.geoms != nullptr) {
         if (es) { gj_hip_note((int)hipErrorInvalidValue); return; }
         kernel = g.interleaved ? k_huffman_decode_par<true, 32, true> : k_huffman_decode_par<false, GJ_PAR_SUB, true>;
+        if (job->batch.own_headers) // (... with headers of their own: every frame's own table set)
+            kernel = g.interleaved ? k_huffman_decode_par<true, 32, true, true> : k_huffman_decode_par<false, GJ_PAR_SUB, true, true>;
     }
     GjFold F = {nullptr, nullptr, 0, 0, 0, nullptr, nullptr};
     const bool fold = gj_par_folds_table(job);

@@ -49,8 +49,12 @@ struct GjScanBatch {
 };
 
 // ITERS pieces of 4 KB per round (16 bytes per lane and piece), `rounds` rounds per workgroup
-template <int ITERS>
-__global__ __launch_bounds__(256) void k_marker_scan(const uint8_t* __restrict__ jpeg, const uint64_t begin, uint64_t size, const uint32_t rounds,
+// (HDRS: a batch of frames with headers of their own. The parts are cut from the launch's `begin` -- the smallest of the frames' -- for all frames
+// alike, so that one record / list layout serves the launch; what lies in front of frame blockIdx.z's OWN first scan byte is to this frame what the
+// bytes in front of `begin` are to every launch: no 0xFF, and it follows none. The header bytes in between -- an Exif thumbnail is a complete JPEG with
+// SOS, RSTn and EOI -- reach no list, no count and no record. An instantiation of its own: the others keep their code.)
+template <int ITERS, bool HDRS = false>
+__global__ __launch_bounds__(256) void k_marker_scan(const uint8_t* __restrict__ jpeg, const uint64_t begin_launch, uint64_t size, const uint32_t rounds,
                                                      uint32_t* __restrict__ recs, uint32_t* __restrict__ lists, gj_scan_summary* __restrict__ hsum /* host memory */,
                                                      const uint8_t* __restrict__ hdr_ref, const uint32_t hdr_n, const GjScanBatch B)
 {
@@ -61,13 +65,15 @@ __global__ __launch_bounds__(256) void k_marker_scan(const uint8_t* __restrict__
         recs += z * B.scratch; lists += z * B.scratch;
         hsum += z;
     }
+    // (the frame's own first scan byte: never in front of the launch's, whatever the record says)
+    const uint64_t begin = HDRS ? max((uint64_t)GJ_REC_BEGIN(B.geoms[blockIdx.z]), begin_launch) : begin_launch;
     __shared__ uint32_t s_tmp[4];
     __shared__ uint32_t s_blk[ITERS * 4 < 4 ? 4 : ITERS * 4]; // restart markers of (piece, wave), then their exclusive prefix sums
     __shared__ uint32_t s_own_other, s_own_q[2], s_own_after[2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t me = blockIdx.x;
     // the parts are cut on 16-byte addresses: the first lane's begins in front of `begin`
-    const uintptr_t a0 = (reinterpret_cast<uintptr_t>(jpeg) + begin) & ~(uintptr_t)15;
+    const uintptr_t a0 = (reinterpret_cast<uintptr_t>(jpeg) + begin_launch) & ~(uintptr_t)15;
     const uint64_t part0 = (uint64_t)(a0 - reinterpret_cast<uintptr_t>(jpeg)) + (uint64_t)me * 4096u * ITERS * rounds;
     uint32_t* const list = lists + (size_t)me * GJ_SCAN_LIST;
     uint32_t* const rec = recs + (size_t)me * GJ_SCAN_REC_WORDS;
@@ -206,8 +212,10 @@ __global__ __launch_bounds__(256) void k_marker_scan(const uint8_t* __restrict__
 
 // (MIXED: a batch of frames of different image sizes -- the scans' first segments and segment counts, and the bound of the table, are frame
 // blockIdx.z's own, gj_frame_geom)
-template <bool MIXED>
-__global__ __launch_bounds__(256) void k_marker_table(const gj_geom g_launch, const uint8_t* __restrict__ jpeg, const uint64_t begin, uint64_t size, const uint32_t part_bytes,
+// (HDRS: ... with headers of their own -- the parts lie where k_marker_scan<.., true> cut them, from the launch's begin; the first scan starts at the
+// frame's own)
+template <bool MIXED, bool HDRS = false>
+__global__ __launch_bounds__(256) void k_marker_table(const gj_geom g_launch, const uint8_t* __restrict__ jpeg, const uint64_t begin_launch, uint64_t size, const uint32_t part_bytes,
                                                       const uint32_t* __restrict__ recs, const uint32_t* __restrict__ lists, uint32_t* __restrict__ wg_maxlen /* host memory */,
                                                       gj_scan_summary* __restrict__ sum, gj_scan_summary* __restrict__ hsum /* host memory: what the host reads */,
                                                       uint32_t* __restrict__ seg_pos, uint32_t* __restrict__ seg_len, uint32_t* __restrict__ seg_index,
@@ -224,7 +232,8 @@ __global__ __launch_bounds__(256) void k_marker_table(const gj_geom g_launch, co
         sum += z; hsum += z;
         seg_pos += z * B.seg; seg_len += z * B.seg; seg_index += z * B.seg;
     }
-    __shared__ uint32_t s_mpos[GJ_SCAN_LIST];              // the workgroup's restart markers in order: offset in its part | code & 7 << 24
+    const uint64_t begin = HDRS ? max((uint64_t)GJ_REC_BEGIN(B.geoms[blockIdx.z]), begin_launch) : begin_launch;
+    __shared__ uint32_t s_mpos[GJ_SCAN_LIST];             // the workgroup's restart markers in order: offset in its part | code & 7 << 24
     __shared__ uint32_t s_tmp[4];
     __shared__ uint32_t s_opos[GJ_SCAN_MAX_OTHER], s_ocode[GJ_SCAN_MAX_OTHER], s_olen[GJ_SCAN_MAX_OTHER], s_orank[GJ_SCAN_MAX_OTHER]; // other markers so far
     __shared__ uint32_t s_ob[GJ_SCAN_MAX_OTHER][2];                                                                                  // ... the 8 bytes behind their codes
@@ -236,7 +245,7 @@ __global__ __launch_bounds__(256) void k_marker_table(const gj_geom g_launch, co
     __shared__ uint32_t s_geo_first[GJ_MAX_COMP + 1], s_geo_limit[GJ_MAX_COMP + 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t me = blockIdx.x, nwg = gridDim.x;
-    const uintptr_t a0 = (reinterpret_cast<uintptr_t>(jpeg) + begin) & ~(uintptr_t)15;
+    const uintptr_t a0 = (reinterpret_cast<uintptr_t>(jpeg) + begin_launch) & ~(uintptr_t)15;
     const uint64_t part0 = (uint64_t)(a0 - reinterpret_cast<uintptr_t>(jpeg)) + (uint64_t)me * part_bytes;
     GJ_TRACE_M(3);
     if (tid == 0) { s_nother = 0; s_prev_wg = -1; s_prev_last = 0; s_maxlen = 0; s_bad = 0; s_own_n = 0; s_tot = 0; }
@@ -462,9 +471,9 @@ extern "C" int gj_hip_find_segments_deferred(const gj_geom* g, const uint8_t* d_
 }
 
 // the second launch of the scan: from gj_find_segments_impl, or later from gj_hip_decode (gj_scan_deferred)
-void gj_launch_marker_table(const gj_geom* g, const uint8_t* d_jpeg, const gj_scan_deferred* sc, const GjScanBatch& B, unsigned frames, hipStream_t st)
+void gj_launch_marker_table(const gj_geom* g, const uint8_t* d_jpeg, const gj_scan_deferred* sc, const GjScanBatch& B, unsigned frames, hipStream_t st, bool own_headers)
 {
-    auto kern = B.geoms != nullptr ? k_marker_table<true> : k_marker_table<false>;
+    auto kern = B.geoms != nullptr ? (own_headers ? k_marker_table<true, true> : k_marker_table<true>) : k_marker_table<false>;
     gj_geom gl = *g; // (the host's geometry carries no strides: the frames' records travel in it as they do for the other kernels, gj_frame_geom)
     gl.fb.geoms = B.geoms;
     hipLaunchKernelGGL(kern, dim3(sc->wgs, 1, frames), dim3(256), 0, st, gl, d_jpeg, sc->begin, sc->size, sc->part_bytes, sc->recs, sc->lists, sc->h_maxlen_parts,
@@ -473,7 +482,7 @@ void gj_launch_marker_table(const gj_geom* g, const uint8_t* d_jpeg, const gj_sc
 void gj_launch_marker_table_deferred(const gj_dec_job* job, hipStream_t st)
 {
     const GjScanBatch B = {nullptr, 0, 0, 0, 0, nullptr};
-    gj_launch_marker_table(&job->g, job->d_jpeg, &job->scan, B, 1, st);
+    gj_launch_marker_table(&job->g, job->d_jpeg, &job->scan, B, 1, st, false);
     gj_debug_stage(job->tune.debug_sync != 0, st, "k_marker_table (deferred)");
 }
 
@@ -485,9 +494,12 @@ static int gj_find_segments_impl(const gj_geom* g, const uint8_t* d_jpeg, uint64
 {
     hipStream_t st = (hipStream_t)stream;
     GjScanBatch B = {nullptr, 0, 0, 0, 0, nullptr};
+    bool own_headers = false;
     unsigned frames = 1;
     if (batch && batch->d_sizes != nullptr) { // (also a batch of one frame: its size comes from d_sizes like the others')
         if ((batch->jpeg & 15u) != 0 || batch->count > 65535u || batch->count < 1u) return -1;
+        if (batch->own_headers && (batch->d_geoms == nullptr || d_hdr_ref != nullptr)) return -1; // (headers of their own: frames of their own sizes, no header to compare)
+        own_headers = batch->own_headers != 0;
         B.sizes = batch->d_sizes;
         B.jpeg = batch->jpeg;
         B.seg = batch->seg;
@@ -517,6 +529,8 @@ static int gj_find_segments_impl(const gj_geom* g, const uint8_t* d_jpeg, uint64
     uint32_t* recs = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(d_scratch) + 15) & ~(uintptr_t)15); // [wgs] records, then [wgs] lists
     uint32_t* lists = recs + (size_t)gj_hip_find_segments_max_chunks(begin, size) * GJ_SCAN_REC_WORDS;
     auto kern = iters == 1 ? k_marker_scan<1> : iters == 2 ? k_marker_scan<2> : iters == 4 ? k_marker_scan<4> : iters == 8 ? k_marker_scan<8> : k_marker_scan<16>;
+    if (own_headers)
+        kern = iters == 1 ? k_marker_scan<1, true> : iters == 2 ? k_marker_scan<2, true> : iters == 4 ? k_marker_scan<4, true> : iters == 8 ? k_marker_scan<8, true> : k_marker_scan<16, true>;
     hipLaunchKernelGGL(kern, dim3(wgs, 1, frames), dim3(256), 0, st, d_jpeg, begin, size, rounds, recs, lists, h_summary, d_hdr_ref, hdr_n, B);
     gj_debug_stage(tune->debug_sync != 0, st, "k_marker_scan");
     gj_scan_deferred sc;
@@ -533,7 +547,7 @@ static int gj_find_segments_impl(const gj_geom* g, const uint8_t* d_jpeg, uint64
         *defer = sc;
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
-    gj_launch_marker_table(g, d_jpeg, &sc, B, frames, st);
+    gj_launch_marker_table(g, d_jpeg, &sc, B, frames, st, own_headers);
     gj_debug_stage(tune->debug_sync != 0, st, "k_marker_table");
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

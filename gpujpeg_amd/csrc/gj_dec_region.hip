@@ -292,12 +292,14 @@ __global__ __launch_bounds__(256) void k_idct_region(const gj_geom g, const gj_g
 
 // frame blockIdx.z of a batch of regions (the planes of a frame take as many bytes as its coefficients take elements at most)
 // (MIXED: frames of different image sizes -- the coefficient planes of frame z are laid out by ITS geometry, gj_frame_geom; the cover planes by gr)
-template <bool MIXED>
+// (HDRS: frames with headers of their own, gj_batch::own_headers -- frame z's quantisation tables are its table set's, gj_frame_tabset_words; an
+// instantiation of its own, so that the batches without such records keep their code)
+template <bool MIXED, bool HDRS = false>
 __global__ __launch_bounds__(256) void k_idct_region_batch(const gj_geom g, const gj_geom gr, const gj_region rb, const int16_t* __restrict__ coefs,
                                                            const float* __restrict__ qtab, uint8_t* __restrict__ planes)
 {
     const size_t z = blockIdx.z;
-    gj_idct_region_body<true>(gj_frame_geom<MIXED>(g), gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, planes + z * g.fb.coefs);
+    gj_idct_region_body<true>(gj_frame_geom<MIXED>(g), gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab + gj_frame_tabset_words<HDRS>(g) / 2, planes + z * g.fb.coefs);
 }
 
 // The same for a frame dec_opt_resize_prescale reduces by s = 8 / N: block (bx, by) of the cover leaves the N x N samples of k_idct_scaled -- the
@@ -364,12 +366,12 @@ __global__ __launch_bounds__(256) void k_idct_region_scaled(const gj_geom g, con
     gj_idct_region_scaled_switch<false>(g, gr, r.frame, coefs, qtab, planes);
 }
 
-template <bool MIXED>
+template <bool MIXED, bool HDRS = false>
 __global__ __launch_bounds__(256) void k_idct_region_scaled_batch(const gj_geom g, const gj_geom gr, const gj_region rb, const int16_t* __restrict__ coefs,
                                                                   const uint16_t* __restrict__ qtab, uint8_t* __restrict__ planes)
 {
     const size_t z = blockIdx.z;
-    gj_idct_region_scaled_switch<true>(gj_frame_geom<MIXED>(g), gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, planes + z * g.fb.coefs);
+    gj_idct_region_scaled_switch<true>(gj_frame_geom<MIXED>(g), gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab + gj_frame_tabset_words<HDRS>(g), planes + z * g.fb.coefs);
 }
 
 // The same for a frame that is reduced PER COMPONENT (gj_region_frame::per_comp, dec_opt_resize_prescale_subsampled: a 4:2:0-like stream, sub_h == sub_v
@@ -411,12 +413,13 @@ __global__ __launch_bounds__(256) void k_idct_region_scaled_comp(const gj_geom g
     gj_idct_region_scaled_comp_body<false>(g, gr, r.frame, coefs, qtab, qtabf, planes);
 }
 
-template <bool MIXED>
+template <bool MIXED, bool HDRS = false>
 __global__ __launch_bounds__(256) void k_idct_region_scaled_comp_batch(const gj_geom g, const gj_geom gr, const gj_region rb, const int16_t* __restrict__ coefs,
                                                                        const uint16_t* __restrict__ qtab, const float* __restrict__ qtabf, uint8_t* __restrict__ planes)
 {
     const size_t z = blockIdx.z;
-    gj_idct_region_scaled_comp_body<true>(gj_frame_geom<MIXED>(g), gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab, qtabf, planes + z * g.fb.coefs);
+    const size_t set = gj_frame_tabset_words<HDRS>(g);
+    gj_idct_region_scaled_comp_body<true>(gj_frame_geom<MIXED>(g), gr, rb.d_frames[z], coefs + z * g.fb.coefs, qtab + set, qtabf + set / 2, planes + z * g.fb.coefs);
 }
 
 // sample of component c that pixel (x, y) of the REGION needs, in the cover-sized plane: pixel (r.x + x, r.y + y) of the stream's image
@@ -742,9 +745,10 @@ void gj_launch_idct_region(const gj_dec_job* job, hipStream_t st, const bool tok
     const unsigned comp = r.resize ? r.comp_mask : 0u;
     const unsigned scales = r.resize && (r.scale_mask || comp) ? r.scale_mask : 1u;
     const bool mixed = batch && job->g.fb.geoms != nullptr; // (frames of different image sizes: the instantiations that read every frame's own geometry)
-    auto idct_batch = mixed ? k_idct_region_batch<true> : k_idct_region_batch<false>;
-    auto scaled_batch = mixed ? k_idct_region_scaled_batch<true> : k_idct_region_scaled_batch<false>;
-    auto comp_batch = mixed ? k_idct_region_scaled_comp_batch<true> : k_idct_region_scaled_comp_batch<false>;
+    const bool hdrs = mixed && job->batch.own_headers != 0;    // (... with headers of their own: and every frame's own table set)
+    auto idct_batch = hdrs ? k_idct_region_batch<true, true> : mixed ? k_idct_region_batch<true> : k_idct_region_batch<false>;
+    auto scaled_batch = hdrs ? k_idct_region_scaled_batch<true, true> : mixed ? k_idct_region_scaled_batch<true> : k_idct_region_scaled_batch<false>;
+    auto comp_batch = hdrs ? k_idct_region_scaled_comp_batch<true, true> : mixed ? k_idct_region_scaled_comp_batch<true> : k_idct_region_scaled_comp_batch<false>;
     if (scales & 1u) hipLaunchKernelGGL(batch ? idct_batch : k_idct_region, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtabf, job->d_planes);
     if (scales & ~1u)
         hipLaunchKernelGGL(batch ? scaled_batch : k_idct_region_scaled, grid, dim3(256), 0, st, job->g, gr, r, job->d_coefs, job->d_qtab, job->d_planes);

@@ -93,6 +93,8 @@ extern "C" int gj_hip_decode(const gj_dec_job* job, gj_stream_t stream, gj_event
     if ((g.fb.geoms != nullptr || job->batch.d_geoms != nullptr) &&
         (!rg_batch || !rg.resize || job->tokens || g.fb.geoms != job->batch.d_geoms || job->gs.fb.geoms != g.fb.geoms || job->tune.dec_sub))
         return -1;
+    // (... with headers of their own, gj_batch::own_headers: inside such a batch alone -- the header records lie in the frames' geometry records)
+    if (job->batch.own_headers && g.fb.geoms == nullptr) return -1;
     // (a progressive frame, gj_dec_job::prog: through the coefficient planes -- its own entropy stage, then the plane route's IDCT side --, a single
     // frame, or a chunk of frames with its per-frame records, which the check of every batch above has passed)
     if (job->prog != nullptr && ((job->prog->d_frames != nullptr) != (g.fb.sizes != nullptr) || job->tokens || job->scan.valid || rg.select || job->prog->levels < 0 ||

@@ -127,6 +127,16 @@ struct gpujpeg_decoder {
     uint8_t* bh_hdrs; size_t bh_hdrs_cap;
     gj_geom* bh_geoms; size_t bh_geoms_cap;
     gj_geom* b_geoms; size_t b_geoms_cap;
+    /* dec_opt_batch_headers: 1 = the family of such a call holds every stream of the reference's shape, whatever its tables and marker segments ("any").
+     * Read by that call alone, and only next to "mixed". Every frame's header record and the pool of table sets (pinned staging and device copy,
+     * uploaded once per call next to b_geoms), the headers that did not end inside the gather window (pinned), and what the last such call took
+     * (gpujpeg_amd_decoder_get_batch_header_stats) */
+    int batch_headers_any;
+    uint16_t* bh_tabsets; size_t bh_tabsets_cap;
+    uint16_t* b_tabsets; size_t b_tabsets_cap;
+    uint8_t* bh_long_hdrs; size_t bh_long_hdrs_cap;
+    long hdr_stats[4]; bool hdr_stats_valid;
+    double hdr_ms[3];                              /* ... and where the host's look at the headers spent its time (gpujpeg_amd_decoder_get_batch_header_times) */
     /* dec_opt_batch_restartless: 1 = the batch calls take streams without restart markers through their batched launches (gj_dec_job::batch_restartless).
      * Read by every batch call, once, when it starts. What the batched launches of the last such call handed to the entropy decoders and what those
      * read of it (gpujpeg_amd_decoder_get_entropy_bytes); pinned, per frame of a call with rectangles: the bytes its selection found and, per scan,
@@ -306,6 +316,7 @@ int gpujpeg_decoder_destroy(struct gpujpeg_decoder* d)
     gj_hip_host_free(d->bh_sum); gj_hip_host_free(d->bh_maxlen); gj_hip_host_free(d->bh_sizes);
     gj_hip_free(d->b_sel); gj_hip_free(d->b_rgn); gj_hip_host_free(d->bh_rgn); gj_hip_host_free(d->bh_found);
     gj_hip_host_free(d->bh_hdrs); gj_hip_host_free(d->bh_geoms); gj_hip_free(d->b_geoms);
+    gj_hip_host_free(d->bh_tabsets); gj_hip_free(d->b_tabsets); gj_hip_host_free(d->bh_long_hdrs);
     gj_hip_host_free(d->bh_sel_bytes); gj_hip_host_free(d->bh_left);
     gj_hip_host_free(d->bh_pstreams); gj_hip_free(d->b_praw);
     gj_prog_info_free(&d->prog); gj_hip_free(d->d_prog); gj_hip_host_free(d->h_prog); gj_hip_free(d->d_prog_q); gj_hip_host_free(d->h_prog_q);
@@ -415,6 +426,27 @@ static bool spec_summary_ok(const struct gpujpeg_decoder* d, const gj_scan_summa
     if (su->header_differs != 0 || su->seq_overflow != 0 || accept_device_scan(su, &chk, g) != 0 || (int)su->segment_count != g->segment_count) return false;
     for (int i = 0; i < g->comp_count; i++)
         if (chk.huff_map[i][0] != r->huff_map[i][0] || chk.huff_map[i][1] != r->huff_map[i][1]) return false;
+    return true;
+}
+
+/* what the acceptance rule reads of a header: the component ids and the Huffman selectors of every component's SOS header, as the launch assumed them */
+struct hdr_sel {
+    uint8_t comp_id[GJ_MAX_COMP]; uint8_t huff[GJ_MAX_COMP][2];
+    uint8_t refused; /* 1: the reader did not take this frame's header -- its errors are on stderr already (the reader prints them whatever the
+                        verbosity): the frame is not parsed, and so not reported, a second time */
+};
+/* The same rule for a frame that was launched on its OWN header (dec_opt_batch_headers = any): against that header's ids and selectors. */
+static bool spec_summary_ok_own(const struct hdr_sel* s, const gj_scan_summary* su, const gj_geom* g)
+{
+    struct gj_reader_result chk; /* (accept_device_scan reads comp_id and writes huff_map, nothing else) */
+    for (int i = 0; i < GJ_MAX_COMP; i++) {
+        chk.comp_id[i] = s->comp_id[i];
+        chk.huff_map[i][0] = s->huff[i][0];
+        chk.huff_map[i][1] = s->huff[i][1];
+    }
+    if (su->header_differs != 0 || su->seq_overflow != 0 || accept_device_scan(su, &chk, g) != 0 || (int)su->segment_count != g->segment_count) return false;
+    for (int i = 0; i < g->comp_count; i++)
+        if (chk.huff_map[i][0] != s->huff[i][0] || chk.huff_map[i][1] != s->huff[i][1]) return false;
     return true;
 }
 
@@ -1166,7 +1198,7 @@ static int decoder_decode(struct gpujpeg_decoder* d, const struct dec_request* r
 int gpujpeg_decoder_decode(struct gpujpeg_decoder* d, uint8_t* image, size_t image_size, struct gpujpeg_decoder_output* output)
 {
     const struct dec_request q = dec_request_options(d);
-    if (d) d->entropy_valid = d->pb_stats_valid = false;
+    if (d) d->entropy_valid = d->pb_stats_valid = d->hdr_stats_valid = false;
     return decoder_decode(d, &q, image, image_size, output);
 }
 
@@ -1193,6 +1225,7 @@ struct dec_rects {
     const int* rects; const uint8_t* mirror; /* crop-and-resize, frame f: the rectangle rects[4f .. 4f + 3] = x, y, w, h, each with its own size ... */
     struct gj_resize resize;                 /* ... resampled to ONE out_w x out_h image per frame (mirror: per frame, when mirror && mirror[f]) */
     bool mixed;                              /* ... of streams that may differ in image size (dec_opt_batch_sizes = mixed) */
+    bool any;                                /* ... and in tables and marker segments (dec_opt_batch_headers = any; with mixed alone) */
 };
 
 /* what the parts of a batch call share */
@@ -1220,6 +1253,10 @@ struct dec_batch {
     uint8_t* fam;                        /* [count] 1: frame f is of the FAMILY -- its header is the cached one except for SOF0's dimensions -- and d->bh_geoms[f] is its geometry */
     int n_fam;                           /* such frames from `first` on */
     gj_geom g_max;                       /* the launch's geometry: the family's, with the segment, block and sample counts of its largest frames */
+    /* ... with headers of their own (what.any): d->bh_geoms[f] carries family frame f's header record (GJ_REC_BEGIN ...), d->bh_tabsets the pool of n_sets table sets */
+    struct hdr_sel* sel;                 /* [count] what the acceptance rule reads of family frame f's own header */
+    int n_sets;
+    size_t begin_min;                    /* the smallest first scan byte among the family's frames from `first` on */
     bool restartless;                    /* dec_opt_batch_restartless = on: streams without restart markers go through the batched launches too */
     bool ahead_progressive;              /* frame 0 went ahead and was a progressive frame: it planned no rectangles (batch_decode_one); ahead_w x ahead_h: its image */
     int ahead_w, ahead_h;
@@ -1258,6 +1295,319 @@ static struct gpujpeg_image_parameters mixed_param_image(const struct gpujpeg_de
     return pi;
 }
 
+/* the geometry of a family frame of w x h pixels into d->bh_geoms[f]: one gj_geom_init per distinct size of a call (slot[64], all -1 at first: the
+ * frame that last had a size of this hash); the table selectors are the caller's to set. false: the geometry refuses the size */
+static bool mixed_frame_geom(struct gpujpeg_decoder* d, int slot[64], int f, int w, int h, const struct gpujpeg_parameters* param)
+{
+    gj_geom* gf = d->bh_geoms + f;
+    const int at = (int)(((unsigned)w * 31u + (unsigned)h) & 63u), same = slot[at];
+    if (same >= 0 && d->bh_geoms[same].width == w && d->bh_geoms[same].height == h) {
+        *gf = d->bh_geoms[same];
+    } else {
+        const struct gpujpeg_image_parameters pi = mixed_param_image(d, w, h);
+        if (gj_geom_init(gf, param, &pi, false) != 0) return false;
+    }
+    slot[at] = f;
+    return true;
+}
+
+/* ---- frames with headers of their own (dec_opt_batch_headers = any, gpujpeg_amd_ext.h) ---- */
+/* The first window of every device-resident stream that the gather launch brings to the host: JFIF + DQT + SOF0 + DHT + SOS are ~620 bytes with the
+ * Annex K tables and ~350 with optimised ones, a comment or a small Exif block (orientation, camera, date: under 1 KB) fits next to them; an Exif
+ * thumbnail or an ICC profile (3 KB to 64 KB) does not, whatever window below GJ_HDR_WINDOW is chosen -- such a header is fetched on its own. 256
+ * frames are 1 MB of pinned memory. */
+#define GJ_HDR_GATHER 4096
+
+/* Where the first scan's data begin, from the first n bytes of a stream alone: the offset behind the first SOS header; 0: the header does not end
+ * within these bytes; -1: not a marker sequence. (The walk of gj_reader_parse without its reading: what tells a header that is cut by the window
+ * from one the reader refuses.) */
+static long hdr_scan_begin(const uint8_t* p, size_t n)
+{
+    if (n < 4) return 0;
+    if (p[0] != 0xFF || p[1] != 0xD8) return -1;
+    size_t o = 2;
+    for (;;) {
+        if (o + 4 > n) return 0;
+        if (p[o] != 0xFF) return -1;
+        while (o + 1 < n && p[o + 1] == 0xFF) o++; /* fill bytes */
+        if (o + 4 > n) return 0;
+        const int m = p[o + 1];
+        if (m == 0xD8) { o += 2; continue; }
+        if (m == 0xD9 || (m >= 0xD0 && m <= 0xD7) || m == 0x01 || m == 0x00) return -1;
+        const size_t len = ((size_t)p[o + 2] << 8) | p[o + 3];
+        if (len < 2) return -1;
+        if (m == 0xDA) return o + 2 + len <= n ? (long)(o + 2 + len) : 0;
+        o += 2 + len;
+    }
+}
+
+/* The family rule: does the parse of a frame's header agree with the reference's in everything the batched launches take from the LAUNCH -- baseline,
+ * component count, ids and sampling, interleaving, restart interval, and what the reader made of APPn / JFIF / Adobe and the ids (colour space,
+ * pixel format)? Width, height (and the line padding that follows from the width), tables and table slots are the frame's own. */
+static bool hdr_same_shape(const struct gj_reader_result* ref, const struct gj_reader_result* r)
+{
+    if (ref->progressive || r->progressive) return false;
+    struct gpujpeg_image_parameters ia = ref->param_image, ib = r->param_image;
+    ib.width = ia.width; ib.height = ia.height; ib.width_padding = ia.width_padding;
+    if (!gj_parameters_equal(&ref->param, &r->param) || !gj_image_parameters_equal(&ia, &ib) || ref->header_color_space != r->header_color_space) return false;
+    for (int i = 0; i < ref->param.comp_count && i < GJ_MAX_COMP; i++)
+        if (ref->comp_id[i] != r->comp_id[i]) return false;
+    return true;
+}
+
+/* The tables a header's components reference, numbered in the order of their first use (component 0's first): q[i], dc[i], ac[i] = component i's
+ * place in a table set, *_src[k] = the header's slot that place k is filled from. Two headers that reference the same contents through different
+ * slots have the same set. false: a Huffman table outside slots 0 and 1 (referenced, or merely defined), or a table that is referenced but not defined. */
+struct hdr_tabs { int nq, ndc, nac; int q[GJ_MAX_COMP], dc[GJ_MAX_COMP], ac[GJ_MAX_COMP]; int q_src[4], dc_src[2], ac_src[2]; };
+static bool hdr_take_tables(const struct gj_reader_result* r, struct hdr_tabs* t)
+{
+    memset(t, 0, sizeof *t);
+    for (int tc = 0; tc < 2; tc++)
+        if (r->h_present[2][tc] || r->h_present[3][tc]) return false;
+    for (int i = 0; i < r->param.comp_count && i < GJ_MAX_COMP; i++) {
+        const int qs = r->quant_map[i], ds = r->huff_map[i][0], as = r->huff_map[i][1];
+        if (qs < 0 || qs > 3 || ds < 0 || ds > 1 || as < 0 || as > 1 || !r->q_present[qs] || !r->h_present[ds][0] || !r->h_present[as][1]) return false;
+        int k;
+        for (k = 0; k < t->nq && t->q_src[k] != qs; k++) {}
+        if (k == t->nq) t->q_src[t->nq++] = qs;
+        t->q[i] = k;
+        for (k = 0; k < t->ndc && t->dc_src[k] != ds; k++) {}
+        if (k == t->ndc) t->dc_src[t->ndc++] = ds;
+        t->dc[i] = k;
+        for (k = 0; k < t->nac && t->ac_src[k] != as; k++) {}
+        if (k == t->nac) t->ac_src[t->nac++] = as;
+        t->ac[i] = k;
+    }
+    return true;
+}
+
+/* what a table set is made from, byte for byte: the counts, the 64 values of every quantisation table, BITS and HUFFVAL of every Huffman table, in
+ * the order of hdr_tabs; what sets are deduplicated by */
+#define GJ_HDR_KEY_BYTES (4 + 4 * 64 + 4 * (17 + 256))
+static void hdr_tabs_key(const struct gj_reader_result* r, const struct hdr_tabs* t, uint8_t key[GJ_HDR_KEY_BYTES])
+{
+    memset(key, 0, GJ_HDR_KEY_BYTES);
+    key[0] = (uint8_t)t->nq; key[1] = (uint8_t)t->ndc; key[2] = (uint8_t)t->nac;
+    uint8_t* p = key + 4;
+    for (int k = 0; k < t->nq; k++, p += 64) memcpy(p, r->qraw[t->q_src[k]], 64);
+    for (int k = 0; k < t->ndc; k++, p += 17 + 256) { memcpy(p, r->hbits[t->dc_src[k]][0], 17); memcpy(p + 17, r->hvals[t->dc_src[k]][0], 256); }
+    for (int k = 0; k < t->nac; k++, p += 17 + 256) { memcpy(p, r->hbits[t->ac_src[k]][1], 17); memcpy(p + 17, r->hvals[t->ac_src[k]][1], 256); }
+}
+
+/* a table set (GJ_TABSET_WORDS, gj_hip.h) from its key; false: a Huffman table does not fit the two-level layout */
+static bool tabset_build(const uint8_t key[GJ_HDR_KEY_BYTES], uint16_t* set)
+{
+    memset(set, 0, GJ_TABSET_WORDS * sizeof(uint16_t));
+    const int nq = key[0], ndc = key[1], nac = key[2];
+    const uint8_t* p = key + 4;
+    for (int k = 0; k < nq; k++, p += 64) {
+        uint16_t* qi = set + k * 64;
+        float* qf = (float*)(void*)(set + GJ_TABSET_QF_OFFSET) + k * 64;
+        gj_quant_table_inverse(p, qi);
+        for (int i = 0; i < 64; i++) qf[i] = (float)qi[i];
+    }
+    for (int k = 0; k < ndc; k++, p += 17 + 256)
+        if (gj_huffman_decoder_table2(p, p + 17, 0, set + GJ_TABSET_TAB2_OFFSET + (k * 2 + 0) * GJ_DEC2_WORDS) != 0) return false;
+    for (int k = 0; k < nac; k++, p += 17 + 256)
+        if (gj_huffman_decoder_table2(p, p + 17, 1, set + GJ_TABSET_TAB2_OFFSET + (k * 2 + 1) * GJ_DEC2_WORDS) != 0) return false;
+    return true;
+}
+
+/* the distinct table sets of a call while its headers are looked at: keys and sets in ordinary memory (the sets move to the pinned pool once their
+ * number is known), found through an open-addressing table of key numbers; setno[k] = the set of key k, or -1: its tables do not fit the layout --
+ * its frames are no family frames, and it takes no place among the sets */
+struct tabset_pool { int n, nkeys, cap, kcap; uint8_t* keys; int* setno; uint16_t* sets; int* slots; unsigned mask; };
+static void tabset_pool_free(struct tabset_pool* P) { free(P->keys); free(P->sets); free(P->setno); free(P->slots); memset(P, 0, sizeof *P); }
+static int tabset_pool_init(struct tabset_pool* P, int frames)
+{
+    memset(P, 0, sizeof *P);
+    unsigned m = 16;
+    while (m < 2u * (unsigned)frames) m *= 2;
+    P->slots = malloc((size_t)m * sizeof(int));
+    if (!P->slots) return -1;
+    for (unsigned i = 0; i < m; i++) P->slots[i] = -1;
+    P->mask = m - 1;
+    return 0;
+}
+/* the number of the key's set (built when the key is new), -1: its tables do not fit, -2: out of memory */
+static int tabset_pool_find(struct tabset_pool* P, const uint8_t key[GJ_HDR_KEY_BYTES])
+{
+    uint32_t h = 2166136261u;
+    for (int i = 0; i < GJ_HDR_KEY_BYTES; i++) h = (h ^ key[i]) * 16777619u;
+    unsigned at = h & P->mask;
+    for (; P->slots[at] >= 0; at = (at + 1) & P->mask)
+        if (memcmp(P->keys + (size_t)P->slots[at] * GJ_HDR_KEY_BYTES, key, GJ_HDR_KEY_BYTES) == 0) return P->setno[P->slots[at]];
+    if (P->nkeys == P->kcap) {
+        const int cap = P->kcap ? P->kcap * 2 : 4;
+        uint8_t* keys = realloc(P->keys, (size_t)cap * GJ_HDR_KEY_BYTES);
+        if (keys) P->keys = keys;
+        int* setno = realloc(P->setno, (size_t)cap * sizeof(int));
+        if (setno) P->setno = setno;
+        if (!keys || !setno) return -2;
+        P->kcap = cap;
+    }
+    if (P->n == P->cap) {
+        const int cap = P->cap ? P->cap * 2 : 4;
+        uint16_t* sets = realloc(P->sets, (size_t)cap * GJ_TABSET_WORDS * sizeof(uint16_t));
+        if (!sets) return -2;
+        P->sets = sets;
+        P->cap = cap;
+    }
+    memcpy(P->keys + (size_t)P->nkeys * GJ_HDR_KEY_BYTES, key, GJ_HDR_KEY_BYTES);
+    const int set = tabset_build(key, P->sets + (size_t)P->n * GJ_TABSET_WORDS) ? P->n++ : -1;
+    P->setno[P->nkeys] = set;
+    P->slots[at] = P->nkeys++;
+    return set;
+}
+
+/* The family of a call whose frames may have headers of their own (dec_rects::any): every frame's header is parsed (header only, quiet) and compared
+ * with the reference's parse (hdr_same_shape); a family frame gets the geometry of its own dimensions with the places of ITS tables in its table
+ * set (d->bh_geoms[f]), with its header record in that record's fb (GJ_REC_BEGIN, GJ_REC_TABSET: first scan byte, set), and what the acceptance rule reads of its header (b->sel[f]); the
+ * distinct sets go to the pinned pool (d->bh_tabsets, b->n_sets). b->fam[f]: 1, or 3 when the header is also byte for byte the cached one except for
+ * the dimensions -- the frames a "mixed" call would have taken, whose summaries the next launch on the cached header may plan with. Device-resident
+ * streams: one launch gathers the first GJ_HDR_GATHER bytes of every stream; the headers that do not end inside them are copied on their own, up to
+ * GJ_HDR_WINDOW bytes each, with one wait for all of them. 0 or -1. */
+static int batch_any_family(struct gpujpeg_decoder* d, struct dec_batch* b, int from, bool family)
+{
+    struct gj_coder* c = &d->coder;
+    const int count = b->count;
+    const struct gj_reader_result* ref = &d->hdr_cache_r;
+    const size_t n = d->hdr_cache_len, dims = ref->sof_dims;
+    const bool bytes_rule = d->hdr_cache != NULL && dims >= 2 && dims + 4 <= n;
+    memset(d->hdr_stats, 0, sizeof d->hdr_stats);
+    memset(d->hdr_ms, 0, sizeof d->hdr_ms);
+    const double t_begin = gpujpeg_get_time();
+    b->n_sets = 0;
+    b->begin_min = 0;
+    memset(b->sel, 0, (size_t)count * sizeof *b->sel);
+    if (!family) return 0;
+    int rc = -1;
+    struct tabset_pool P;
+    struct gj_reader_result* rr = malloc(sizeof *rr);
+    int* long_at = NULL; /* device-resident streams: where frame f's header lies in d->bh_long_hdrs (slot number), -1: inside its gather window */
+    if (!rr || tabset_pool_init(&P, count) != 0) { free(rr); return -1; }
+    if (b->streams_on_device) {
+        const size_t sizes_bytes = (size_t)count * sizeof(uint32_t);
+        long_at = malloc((size_t)count * sizeof(int));
+        if (!long_at) goto out;
+        if (gj_ensure_device_buffer((void**)&d->b_sizes, &d->b_sizes_cap, sizes_bytes) != 0) goto out;
+        if (gj_ensure_pinned_buffer((void**)&d->bh_sizes, &d->bh_sizes_cap, sizes_bytes, sizes_bytes + sizes_bytes / 2) != 0) goto out;
+        if (gj_ensure_pinned_buffer((void**)&d->bh_hdrs, &d->bh_hdrs_cap, (size_t)count * GJ_HDR_GATHER, (size_t)count * GJ_HDR_GATHER * 2) != 0) goto out;
+        for (int f = 0; f < count; f++) d->bh_sizes[f] = b->sizes[f] > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)b->sizes[f];
+        if (gj_hip_memcpy_h2d(d->b_sizes, d->bh_sizes, sizes_bytes, c->stream) != 0 ||
+            gj_hip_gather_headers(b->streams, b->stream_stride, d->b_sizes, (uint32_t)count, GJ_HDR_GATHER, d->bh_hdrs, c->stream) != 0 ||
+            gj_hip_stream_sync(c->stream) != 0) {
+            GJ_ERROR("Reading the headers of the batch failed: %s\n", gj_hip_last_error());
+            goto out;
+        }
+        d->hdr_stats[2] = (long)count * GJ_HDR_GATHER;
+        int n_long = 0;
+        for (int f = 0; f < count; f++) {
+            const size_t have = b->sizes[f] < GJ_HDR_GATHER ? b->sizes[f] : GJ_HDR_GATHER;
+            long_at[f] = b->sizes[f] > GJ_HDR_GATHER && hdr_scan_begin(d->bh_hdrs + (size_t)f * GJ_HDR_GATHER, have) == 0 ? n_long++ : -1;
+        }
+        if (n_long > 0) {
+            if (gj_ensure_pinned_buffer((void**)&d->bh_long_hdrs, &d->bh_long_hdrs_cap, (size_t)n_long * GJ_HDR_WINDOW, (size_t)n_long * GJ_HDR_WINDOW * 2) != 0) goto out;
+            for (int f = 0; f < count; f++) {
+                if (long_at[f] < 0) continue;
+                const size_t take = b->sizes[f] < GJ_HDR_WINDOW ? b->sizes[f] : GJ_HDR_WINDOW;
+                if (gj_hip_memcpy_d2h(d->bh_long_hdrs + (size_t)long_at[f] * GJ_HDR_WINDOW, b->streams + (size_t)f * b->stream_stride, take, c->stream) != 0) goto out;
+                d->hdr_stats[2] += (long)take;
+            }
+            if (gj_hip_stream_sync(c->stream) != 0) {
+                GJ_ERROR("Reading the headers of the batch failed: %s\n", gj_hip_last_error());
+                goto out;
+            }
+            d->hdr_stats[3] = n_long;
+        }
+    }
+    d->hdr_ms[0] = (gpujpeg_get_time() - t_begin) * 1000.0;
+    int slot[64]; /* (one geometry per distinct size: the frame that last had a size of this hash) */
+    for (int i = 0; i < 64; i++) slot[i] = -1;
+    for (int f = 0; f < count; f++) {
+        const double t_frame = gpujpeg_get_time();
+        double t_parsed = t_frame;
+        /* (the clock is read three times per frame, ~0.1 us of a parse of 1 to 3 us: [1] reader, [2] family rule, table key and set, geometry) */
+#define GJ_HDR_FRAME_DONE() do { const double t_ = gpujpeg_get_time(); d->hdr_ms[1] += (t_parsed - t_frame) * 1000.0; d->hdr_ms[2] += (t_ - t_parsed) * 1000.0; } while (0)
+        const uint8_t* hp = b->streams + (size_t)f * b->stream_stride;
+        size_t hn = b->sizes[f];
+        if (b->streams_on_device) {
+            hp = long_at[f] < 0 ? d->bh_hdrs + (size_t)f * GJ_HDR_GATHER : d->bh_long_hdrs + (size_t)long_at[f] * GJ_HDR_WINDOW;
+            const size_t cap = long_at[f] < 0 ? (size_t)GJ_HDR_GATHER : (size_t)GJ_HDR_WINDOW;
+            if (hn > cap) hn = cap;
+        }
+        if (hn <= 4 || b->sizes[f] > 0x1FFFFFF0u) { GJ_HDR_FRAME_DONE(); continue; }
+        if (gj_reader_parse(hp, hn, GPUJPEG_LL_QUIET - 1, d->ff_cs_itu601_is_709, d->req_pixel_format, d->req_color_space, d->req_alignment, rr, true, d->progressive != 0) != 0) {
+            b->sel[f].refused = 1;
+            t_parsed = gpujpeg_get_time();
+            GJ_HDR_FRAME_DONE();
+            continue;
+        }
+        t_parsed = gpujpeg_get_time();
+        if (!hdr_same_shape(ref, rr)) { GJ_HDR_FRAME_DONE(); continue; }
+        const size_t begin = rr->scan_begin[0];
+        if (begin > GJ_HDR_WINDOW || b->sizes[f] <= begin + 2) { GJ_HDR_FRAME_DONE(); continue; }
+        if (!rr->param.interleaved && rr->param.comp_count > 1) {
+            /* the selectors of the second and later scans stand in THEIR SOS headers: a stream in host memory is walked for them; a device-resident
+             * one is launched with the reference's, and the acceptance rule compares them with what the marker scan finds */
+            if (!b->streams_on_device) {
+                if (gj_reader_parse(hp, hn, GPUJPEG_LL_QUIET - 1, d->ff_cs_itu601_is_709, d->req_pixel_format, d->req_color_space, d->req_alignment, rr, false, d->progressive != 0) != 0 ||
+                    !hdr_same_shape(ref, rr) || rr->scan_begin[0] != begin) {
+                    GJ_HDR_FRAME_DONE();
+                    continue;
+                }
+            } else {
+                for (int i = 1; i < rr->param.comp_count && i < GJ_MAX_COMP; i++) { rr->huff_map[i][0] = ref->huff_map[i][0]; rr->huff_map[i][1] = ref->huff_map[i][1]; }
+            }
+        }
+        const int w = rr->param_image.width, h = rr->param_image.height;
+        struct hdr_tabs t;
+        if (w < 1 || h < 1 || !hdr_take_tables(rr, &t)) { GJ_HDR_FRAME_DONE(); continue; }
+        uint8_t key[GJ_HDR_KEY_BYTES];
+        hdr_tabs_key(rr, &t, key);
+        const int set = tabset_pool_find(&P, key);
+        if (set == -2) goto out;
+        if (set < 0) { GJ_HDR_FRAME_DONE(); continue; }
+        gj_geom* gf = d->bh_geoms + f;
+        if (!mixed_frame_geom(d, slot, f, w, h, &ref->param)) { GJ_HDR_FRAME_DONE(); continue; }
+        for (int i = 0; i < gf->comp_count && i < GJ_MAX_COMP; i++) {
+            gf->comp[i].q_table = t.q[i];
+            gf->comp[i].dc_table = t.dc[i];
+            gf->comp[i].ac_table = t.ac[i];
+            b->sel[f].comp_id[i] = rr->comp_id[i];
+            b->sel[f].huff[i][0] = (uint8_t)rr->huff_map[i][0];
+            b->sel[f].huff[i][1] = (uint8_t)rr->huff_map[i][1];
+        }
+        memset(&gf->fb, 0, sizeof gf->fb); /* (the header record: the pool's count follows once it is known) */
+        GJ_REC_BEGIN(*gf) = begin;
+        GJ_REC_TABSET(*gf) = (uint32_t)set;
+        const bool bytes = bytes_rule && begin == n && hn >= n && memcmp(hp, d->hdr_cache, dims) == 0 && memcmp(hp + dims + 4, d->hdr_cache + dims + 4, n - dims - 4) == 0;
+        b->fam[f] = bytes ? 3 : 1;
+        if (f >= from) {
+            if (b->n_fam == 0 || begin < b->begin_min) b->begin_min = begin;
+            b->n_fam++;
+        }
+        GJ_HDR_FRAME_DONE();
+    }
+#undef GJ_HDR_FRAME_DONE
+    if (P.n > 0) {
+        const size_t bytes = (size_t)P.n * GJ_TABSET_WORDS * sizeof(uint16_t);
+        if (gj_ensure_pinned_buffer((void**)&d->bh_tabsets, &d->bh_tabsets_cap, bytes, bytes + bytes / 2) != 0) goto out;
+        memcpy(d->bh_tabsets, P.sets, bytes);
+    }
+    b->n_sets = P.n;
+    for (int f = 0; f < count; f++)
+        if (b->fam[f]) GJ_REC_TABSETS(d->bh_geoms[f]) = (uint32_t)P.n;
+    d->hdr_stats[0] = b->n_fam;
+    d->hdr_stats[1] = P.n;
+    rc = 0;
+out:
+    tabset_pool_free(&P);
+    free(long_at);
+    free(rr);
+    return rc;
+}
+
 /* Streams of different image sizes (dec_opt_batch_sizes = mixed): the host looks at every frame's header before anything is planned. The FAMILY of
  * the call are the frames whose first hdr_cache_len bytes are the cached header's except for the four dimension bytes of SOF0 (where the reader found
  * them: gj_reader_result::sof_dims): same tables, sampling, restart interval and scan header, so they go through one set of launches, each with the
@@ -1276,9 +1626,15 @@ static int batch_mixed_prepare(struct gpujpeg_decoder* d, struct dec_batch* b, i
     memset(b->fam, 0, (size_t)count);
     b->n_fam = 0;
     bool family = d->hdr_cache_valid && d->hdr_cache != NULL && dims >= 2 && dims + 4 <= n && b->what.rects != NULL;
+    /* (headers of their own, dec_rects::any: the rule over the parsed headers instead of the bytes -- the reference is the cached header's parse) */
+    const bool any = b->what.any;
+    if (any) {
+        family = d->hdr_cache_valid && b->what.rects != NULL;
+        if (batch_any_family(d, b, from, family) != 0) return -1;
+    }
     const uint8_t* hdrs = b->streams;
     size_t hdr_stride = b->stream_stride;
-    if (family && b->streams_on_device) {
+    if (!any && family && b->streams_on_device) {
         const size_t sizes_bytes = (size_t)count * sizeof(uint32_t);
         if (gj_ensure_device_buffer((void**)&d->b_sizes, &d->b_sizes_cap, sizes_bytes) != 0) return -1;
         if (gj_ensure_pinned_buffer((void**)&d->bh_sizes, &d->bh_sizes_cap, sizes_bytes, sizes_bytes + sizes_bytes / 2) != 0) return -1;
@@ -1295,22 +1651,14 @@ static int batch_mixed_prepare(struct gpujpeg_decoder* d, struct dec_batch* b, i
     }
     int slot[64]; /* (one geometry per distinct size: the frame that last had a size of this hash) */
     for (int i = 0; i < 64; i++) slot[i] = -1;
-    for (int f = 0; f < count; f++) {
+    for (int f = 0; f < count && !any; f++) {
         const uint8_t* hb = hdrs + (size_t)f * hdr_stride;
         bool fam = family && b->sizes[f] > n + 2 && memcmp(hb, d->hdr_cache, dims) == 0 && memcmp(hb + dims + 4, d->hdr_cache + dims + 4, n - dims - 4) == 0;
         const int h = fam ? (int)(((unsigned)hb[dims] << 8) | hb[dims + 1]) : 0, w = fam ? (int)(((unsigned)hb[dims + 2] << 8) | hb[dims + 3]) : 0;
         if (fam && (w < 1 || h < 1)) fam = false;
         if (fam) {
-            gj_geom* gf = d->bh_geoms + f;
-            const int at = (int)(((unsigned)w * 31u + (unsigned)h) & 63u), same = slot[at];
-            if (same >= 0 && d->bh_geoms[same].width == w && d->bh_geoms[same].height == h) {
-                *gf = d->bh_geoms[same];
-            } else {
-                const struct gpujpeg_image_parameters pi = mixed_param_image(d, w, h);
-                if (gj_geom_init(gf, &r->param, &pi, false) != 0) fam = false;
-                else geom_take_tables(gf, r);
-            }
-            if (fam) slot[at] = f;
+            fam = mixed_frame_geom(d, slot, f, w, h, &r->param);
+            if (fam) geom_take_tables(d->bh_geoms + f, r);
         }
         if (fam) {
             b->fam[f] = 1;
@@ -1321,6 +1669,7 @@ static int batch_mixed_prepare(struct gpujpeg_decoder* d, struct dec_batch* b, i
     for (int f = from; f < count && (b->n_fam > 0 || from > 0); f++) {
         /* not of the family: its rectangle against its own header */
         if (b->fam[f]) continue;
+        if (any && b->sel[f].refused) continue; /* (a header the reader has just refused: left to the single-frame route's own error, as below) */
         struct gj_reader_result* rr = malloc(sizeof *rr);
         if (!rr) return -1;
         const uint8_t* himage = b->streams + (size_t)f * b->stream_stride;
@@ -1420,7 +1769,7 @@ static int batch_regions_plan(struct gpujpeg_decoder* d, struct dec_batch* b, in
             if (!b->fam[f]) continue;
             g = d->bh_geoms + f;
             pi_f = mixed_param_image(d, g->width, g->height);
-            if (ref < 0) { ref = f; b->g_max = *g; }
+            if (ref < 0) { ref = f; b->g_max = *g; memset(&b->g_max.fb, 0, sizeof b->g_max.fb); /* (a frame's record may carry its header record there) */ }
             if (g->segment_count > b->g_max.segment_count) b->g_max.segment_count = g->segment_count;
             if (g->block_count > b->g_max.block_count) b->g_max.block_count = g->block_count;
             if (g->data_size > b->g_max.data_size) b->g_max.data_size = g->data_size;
@@ -1578,12 +1927,14 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
      * regions or crop-and-resize -- batch_has_regions -- has kernels that do, and so has a reduced-size decode, dec_opt_scale) */
     const bool regions = batch_has_regions(b);
     if (regions && b->what.mixed && d->tune.dec_sub) return 0; /* (the tuning aid's sub-sequence sizes: no instantiation for frames of different sizes) */
+    /* (headers of their own: every family frame brings its tables and its header's length, which batch_any_family has checked against its size) */
+    const bool any = regions && b->what.mixed && b->what.any;
     bool batched = (regions || !d->region_on) && d->hdr_cache_valid && !d->need_planes && !d->host_scan && !d->tune.dec_no_spec && !d->keep_coefs && c->configured &&
-                   (b->streams_on_device ? (b->stream_stride & 15u) == 0 : true) && d->tab2_ok;
+                   (b->streams_on_device ? (b->stream_stride & 15u) == 0 : true) && (d->tab2_ok || any);
     size_t max_size = 0;
     for (int f = first; f < count; f++) {
         if (sizes[f] > max_size) max_size = sizes[f];
-        if (sizes[f] <= d->hdr_cache_len + 2 || sizes[f] > 0x1FFFFFF0u) batched = false;
+        if ((!any && sizes[f] <= d->hdr_cache_len + 2) || sizes[f] > 0x1FFFFFF0u) batched = false;
     }
     if (!batched || n_all < 1) return 0;
     dec_image_set(d, 1, NULL, NULL, NULL);
@@ -1622,6 +1973,13 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     if (mixed) { /* (from here on the launch's geometry: the strides of the tables and the sizes of the work buffers follow the family's largest frames) */
         g = &b->g_max;
         job.g = *g;
+        memset(&job.g.fb, 0, sizeof job.g.fb); /* (a frame's record may carry its header record there: the launch's strides are set below) */
+    }
+    if (any) { /* (the tables: the call's pool of table sets, laid out like the decoder's own block behind d_qtab -- uploaded below, once) */
+        if (b->n_sets < 1 || gj_ensure_device_buffer((void**)&d->b_tabsets, &d->b_tabsets_cap, (size_t)b->n_sets * GJ_TABSET_WORDS * sizeof(uint16_t)) != 0) return -1;
+        job.d_qtab = d->b_tabsets;
+        job.d_huff_tab2 = d->b_tabsets + GJ_TABSET_TAB2_OFFSET;
+        job.d_qtabf = (const float*)(const void*)(d->b_tabsets + GJ_TABSET_QF_OFFSET);
     }
     job.seg_count = g->segment_count;
     job.tune.dec_careful = 0;
@@ -1634,7 +1992,9 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
     job.d_overflow = &d->h_summary->seq_overflow;
     if (!gj_hip_decode_batchable(&job)) return 0;
 
-    const size_t begin = r->scan_begin[0];
+    /* (headers of their own: ONE part layout for the marker scan of every chunk, from the smallest first scan byte among the call's family frames -- the
+     * scratch and the longest-segment words are sized for it, and every frame masks what lies in front of its own, GJ_REC_BEGIN) */
+    const size_t begin = any ? b->begin_min : r->scan_begin[0];
     /* streams in host memory: one staging area, slots on 16-byte addresses */
     const uint8_t* d_streams = b->streams + (size_t)first * b->stream_stride;
     size_t d_stride = b->stream_stride;
@@ -1678,6 +2038,9 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
             if (gj_ensure_device_buffer((void**)&d->b_geoms, &d->b_geoms_cap, (size_t)count * sizeof(gj_geom)) != 0) return -1;
             if (gj_hip_memcpy_h2d(d->b_geoms, d->bh_geoms, (size_t)count * sizeof(gj_geom), c->stream) != 0) return -1;
         }
+        if (any) { /* (the pool of table sets: one upload; every frame's header record has gone up inside its geometry record) */
+            if (gj_hip_memcpy_h2d(d->b_tabsets, d->bh_tabsets, (size_t)b->n_sets * GJ_TABSET_WORDS * sizeof(uint16_t), c->stream) != 0) return -1;
+        }
         memset(d->bh_found, 0xFF, found_bytes);
         if (b->restartless) { /* (what every frame's selection hands to the entropy decoder, and what that leaves unread of a restart-less scan) */
             const size_t sel_bytes = (size_t)count * sizeof(uint32_t), left_bytes = (size_t)count * GJ_MAX_COMP * sizeof(uint32_t);
@@ -1709,6 +2072,7 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         B.count = (uint32_t)(n_all - a < chunk ? n_all - a : chunk);
         B.d_sizes = d->b_sizes + a;
         B.d_geoms = mixed ? d->b_geoms + first + a : NULL;
+        B.own_headers = any ? 1u : 0u;
         job.batch = B;
         job.g.fb.sizes = B.d_sizes;
         job.g.fb.geoms = B.d_geoms;
@@ -1752,7 +2116,8 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
         /* (different image sizes: the family's frames alone -- the host compared their headers --, each against its OWN segment count and scans) */
         if (mixed && !b->fam[first + i]) continue;
         const gj_geom* gf = mixed ? d->bh_geoms + first + i : g;
-        if (!spec_summary_ok(d, su, gf)) continue;
+        /* (headers of their own: the rule against the frame's OWN ids and selectors) */
+        if (any ? !spec_summary_ok_own(&b->sel[first + i], su, gf) : !spec_summary_ok(d, su, gf)) continue;
         if (regions) { /* did the selection find in this stream's table what the plan took from the geometry? (cannot fail for a stream the rule accepts) */
             const int f = first + i;
             if (memcmp(d->bh_found + (size_t)f * GJ_MAX_COMP, b->plan + (size_t)f * GJ_MAX_COMP, GJ_MAX_COMP * sizeof(uint32_t)) != 0) continue;
@@ -1776,7 +2141,8 @@ static int batch_launches(struct gpujpeg_decoder* d, struct dec_batch* b, bool f
             d->entropy_bytes[1] += handed - (left < handed ? left : handed);
         }
         /* (what the next launch on this header plans with: a frame of the cached header's own dimensions) */
-        if (!mixed || (gf->width == c->geom.width && gf->height == c->geom.height)) remember_summary(d, su);
+        /* (headers of their own: and of the cached header's own bytes -- what a "mixed" call would have remembered, no more) */
+        if (!mixed || (gf->width == c->geom.width && gf->height == c->geom.height && (!any || (b->fam[first + i] & 2)))) remember_summary(d, su);
     }
     /* not one frame passed: the cached header (an older sequence's, of dimensions the slots happen to hold) is not these streams' */
     return accepted == 0 && first == 0 && !force_first ? 1 : 0;
@@ -2148,7 +2514,7 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
                           .d_out = output, .d_out_stride = output_stride};
     if (what) b.what = *what;
     b.restartless = d->batch_restartless != 0; /* (the option as it is when the call starts) */
-    d->entropy_valid = d->pb_stats_valid = false;
+    d->entropy_valid = d->pb_stats_valid = d->hdr_stats_valid = false;
     d->entropy_bytes[0] = d->entropy_bytes[1] = 0;
     b.prog_batch = d->batch_progressive != 0 && d->progressive != 0; /* (both options as they are when the call starts) */
     memset(d->pb_stats, 0, sizeof d->pb_stats);
@@ -2159,7 +2525,8 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
     b.frame_done = calloc((size_t)count, 1);
     if (regions) b.plan = calloc((size_t)count * GJ_MAX_COMP, sizeof(int));
     if (regions && b.what.mixed) b.fam = calloc((size_t)count, 1);
-    if (!b.frame_done || (regions && !b.plan) || (regions && b.what.mixed && !b.fam)) goto out;
+    if (regions && b.what.mixed && b.what.any) b.sel = calloc((size_t)count, sizeof *b.sel);
+    if (!b.frame_done || (regions && !b.plan) || (regions && b.what.mixed && !b.fam) || (regions && b.what.mixed && b.what.any && !b.sel)) goto out;
     /* The header cache is what a batch launches on: frame 0 goes the ordinary way when there is none (or when it has to). A second pass, with
      * force_first, when the cached header turned out to be another sequence's: frame 0 replaces the cache, then the batch. */
     for (int pass = 0; pass < 2; pass++) {
@@ -2210,12 +2577,16 @@ static int decode_batch(struct gpujpeg_decoder* d, const uint8_t* streams, size_
     }
     d->entropy_valid = b.restartless;
     d->pb_stats_valid = b.prog_batch;
+    /* (gpujpeg_amd_decoder_get_batch_header_stats: what the last look at the call's headers found; none -- a decoder state without batched launches -- zeros) */
+    d->hdr_stats_valid = regions && b.what.mixed && b.what.any;
+    if (d->hdr_stats_valid && !b.prepared) { memset(d->hdr_stats, 0, sizeof d->hdr_stats); memset(d->hdr_ms, 0, sizeof d->hdr_ms); }
     rc = 0; /* (c->frames counts the frames TIMED with perf_stats, src/gpujpeg_common.c:2238-2254: a batch adds none) */
 out:
     if (rc != 0 && b.host_io) gj_hip_stream_sync(c->stream); /* (what is queued on the stream must not read the caller's streams or write its frames after the error has left) */
     free(b.frame_done);
     free(b.plan);
     free(b.fam);
+    free(b.sel);
     return rc;
 }
 
@@ -2233,7 +2604,7 @@ int gpujpeg_amd_decoder_decode_batch_regions(struct gpujpeg_decoder* d, const ui
                                              struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !origins) return -1;
-    d->entropy_valid = d->pb_stats_valid = false;
+    d->entropy_valid = d->pb_stats_valid = d->hdr_stats_valid = false;
     if (width < 1 || height < 1) {
         GJ_ERROR("A batch of regions needs a width and a height of at least 1 (given: %d x %d)!\n", width, height);
         return -1;
@@ -2259,7 +2630,7 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
                                     struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !rects) return -1;
-    d->entropy_valid = d->pb_stats_valid = false;
+    d->entropy_valid = d->pb_stats_valid = d->hdr_stats_valid = false;
     d->prescales_n = 0;
     if (out_width < 1 || out_height < 1 || out_width > 16384 || out_height > 16384) {
         GJ_ERROR("Crop-and-resize needs an output width and height of 1 to 16384 (given: %d x %d)!\n", out_width, out_height);
@@ -2305,7 +2676,7 @@ static int decode_batch_crop_resize(struct gpujpeg_decoder* d, const uint8_t* st
     d->prescales_n = count;
     struct dec_rects what = {.rects = rects, .mirror = mirror, .resize = {.out_w = out_width, .out_h = out_height, .prescale = d->resize_prescale, .filter = d->resize_filter,
                                                                                    .subsampled = d->resize_prescale_subsampled},
-                             .mixed = d->batch_sizes_mixed != 0};
+                             .mixed = d->batch_sizes_mixed != 0, .any = d->batch_sizes_mixed != 0 && d->batch_headers_any != 0};
     if (tensor) what.resize.tensor = *tensor;
     int rc = decode_batch(d, streams, stream_stride, sizes, count, &what, output, output_stride, param_image);
     if (rc == 0) { /* (slot [4] of the kernel times, gpujpeg_amd_ext.h: 6 when any frame of the call was prescaled -- 8 when per component: the call's
@@ -2334,7 +2705,7 @@ int gpujpeg_amd_decoder_decode_batch_crop_resize_tensor(struct gpujpeg_decoder* 
                                                         struct gpujpeg_image_parameters* param_image)
 {
     if (!d || !streams || !sizes || count < 1 || !output || !rects) return -1;
-    d->entropy_valid = d->pb_stats_valid = false;
+    d->entropy_valid = d->pb_stats_valid = d->hdr_stats_valid = false;
     d->prescales_n = 0;
     if (!format) {
         GJ_ERROR("Tensor output needs a format!\n");
@@ -2529,6 +2900,12 @@ int gpujpeg_decoder_set_option(struct gpujpeg_decoder* d, const char* opt, const
         GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_BATCH_SIZES " (" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME " or " GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED ")\n", val);
         return GPUJPEG_ERROR;
     }
+    if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_BATCH_HEADERS) == 0) { /* read by gpujpeg_amd_decoder_decode_batch_crop_resize (and _tensor) alone, next to dec_opt_batch_sizes = mixed */
+        if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_HEADERS_VAL_SAME) == 0) { d->batch_headers_any = 0; return GPUJPEG_NOERR; }
+        if (strcmp(val, GPUJPEG_AMD_DEC_BATCH_HEADERS_VAL_ANY) == 0) { d->batch_headers_any = 1; return GPUJPEG_NOERR; }
+        GJ_ERROR("Unknown value %s for " GPUJPEG_AMD_DEC_OPT_BATCH_HEADERS " (" GPUJPEG_AMD_DEC_BATCH_HEADERS_VAL_SAME " or " GPUJPEG_AMD_DEC_BATCH_HEADERS_VAL_ANY ")\n", val);
+        return GPUJPEG_ERROR;
+    }
     if (strcmp(opt, GPUJPEG_AMD_DEC_OPT_REGION) == 0) { /* syntax only: the decode call checks the region against its stream */
         if (strcmp(val, "full") == 0) { d->region_on = false; return GPUJPEG_NOERR; }
         long v[4];
@@ -2570,6 +2947,7 @@ void gpujpeg_decoder_print_options(void)
     printf("\t" GPUJPEG_AMD_DEC_OPT_RESIZE_PRESCALE_SUBSAMPLED "=[" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_OFF "|" GPUJPEG_AMD_DEC_RESIZE_PRESCALE_SUBSAMPLED_VAL_ON "] - let that prescale reduce 4:2:0 streams too, each component at its own N (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_RESTARTLESS "=[" GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_OFF "|" GPUJPEG_AMD_DEC_BATCH_RESTARTLESS_VAL_ON "] - whether the batch calls take streams without restart markers through their batched launches (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_SIZES "=[" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_SAME "|" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED "] - whether the streams of one crop-and-resize call may differ in image size (MI355X extension)\n");
+    printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_HEADERS "=[" GPUJPEG_AMD_DEC_BATCH_HEADERS_VAL_SAME "|" GPUJPEG_AMD_DEC_BATCH_HEADERS_VAL_ANY "] - whether the streams of one such call (" GPUJPEG_AMD_DEC_OPT_BATCH_SIZES "=" GPUJPEG_AMD_DEC_BATCH_SIZES_VAL_MIXED ") may differ in tables and marker segments and still share its batched launches (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_PROGRESSIVE "=[" GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_OFF "|" GPUJPEG_AMD_DEC_PROGRESSIVE_VAL_ON "] - whether progressive (SOF2) streams are decoded (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_BATCH_PROGRESSIVE "=[" GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_OFF "|" GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_ON "] - whether the batch calls take groups of progressive streams through batched launches (MI355X extension)\n");
     printf("\t" GPUJPEG_AMD_DEC_OPT_REGION "=[X,Y,W,H|full] - decode the W x H pixels at (X, Y) only (MI355X extension)\n");
@@ -2657,6 +3035,20 @@ int gpujpeg_amd_decoder_get_progressive_batch_stats(struct gpujpeg_decoder* d, l
     if (!d || !out) return -1;
     for (int i = 0; i < 4; i++) out[i] = d->pb_stats_valid ? d->pb_stats[i] : 0;
     return d->pb_stats_valid ? 0 : -1;
+}
+
+int gpujpeg_amd_decoder_get_batch_header_stats(struct gpujpeg_decoder* d, long out[4])
+{
+    if (!d || !out) return -1;
+    for (int i = 0; i < 4; i++) out[i] = d->hdr_stats_valid ? d->hdr_stats[i] : 0;
+    return d->hdr_stats_valid ? 0 : -1;
+}
+
+int gpujpeg_amd_decoder_get_batch_header_times(struct gpujpeg_decoder* d, double ms[3])
+{
+    if (!d || !ms) return -1;
+    for (int i = 0; i < 3; i++) ms[i] = d->hdr_stats_valid ? d->hdr_ms[i] : 0.0;
+    return d->hdr_stats_valid ? 0 : -1;
 }
 
 int gpujpeg_amd_host_stream_info(const uint8_t* image, size_t size, int out[8])

@@ -43,6 +43,19 @@ __device__ __forceinline__ const gj_geom& gj_frame_geom(const gj_geom& g)
     else return g;
 }
 
+// The tables of frame blockIdx.z of a batch: how many uint16 words behind the launch's table pointers its set lies. HDRS = false: the launch's one set
+// (0, costs nothing); HDRS: the set of the frame's record (GJ_REC_TABSET of its geometry record, gj_hip.h), its index clamped to the pool's count so that a damaged record
+// cannot become a read behind the pool. The same in every lane: scalar loads. The ONE statement of it, asked once at entry by the kernels that read
+// tables in such batches (k_huffman_decode_par, k_idct_region*_batch).
+template <bool HDRS>
+__device__ __forceinline__ size_t gj_frame_tabset_words(const gj_geom& g)
+{
+    if constexpr (HDRS) {
+        const gj_geom& rec = g.fb.geoms[blockIdx.z];
+        return (size_t)min(GJ_REC_TABSET(rec), max(GJ_REC_TABSETS(rec), 1u) - 1u) * GJ_TABSET_WORDS;
+    } else return 0;
+}
+
 struct GjSeg {
     int comp;          // component of the scan (non-interleaved), 0 otherwise
     int index_in_scan; // restart marker index = index_in_scan % 8

@@ -44,6 +44,11 @@ PROGRESSIVE_MAX_SCANS = 64
 # Decoder.progressive_batch_stats() tells what they took
 DEC_OPT_BATCH_PROGRESSIVE = "dec_opt_batch_progressive"
 BATCH_PROGRESSIVE_OFF, BATCH_PROGRESSIVE_ON = "off", "on"
+# Decoder.set_option(DEC_OPT_BATCH_HEADERS, BATCH_HEADERS_ANY): next to DEC_OPT_BATCH_SIZES = mixed, the streams of one crop-and-resize call may also
+# differ in quantisation tables, Huffman tables and marker segments and still share the batched launches (GPUJPEG_AMD_DEC_OPT_BATCH_HEADERS);
+# Decoder.batch_header_stats() tells what the call's family was
+DEC_OPT_BATCH_HEADERS = "dec_opt_batch_headers"
+BATCH_HEADERS_SAME, BATCH_HEADERS_ANY = "same", "any"
 # encoder option of the MI355X build (gpujpeg_amd_ext.h: GPUJPEG_AMD_ENC_OPT_HUFFMAN): Annex K.3 tables, or tables built per frame
 ENC_OPT_HUFFMAN = "enc_opt_huffman"
 ENC_HUFFMAN_STANDARD, ENC_HUFFMAN_OPTIMAL = "standard", "optimal"
@@ -697,6 +702,23 @@ class Decoder:
         self.lib.L.gpujpeg_amd_decoder_get_progressive_batch_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
         rc = self.lib.L.gpujpeg_amd_decoder_get_progressive_batch_stats(self.h, a)
         return (int(rc),) + tuple(int(x) for x in a)
+
+    def batch_header_stats(self):
+        """gpujpeg_amd_decoder_get_batch_header_stats: (rc, frames the host admitted to the family, distinct table sets uploaded, header bytes brought to
+        the host, frames whose header was fetched on its own) of the last crop-and-resize call made with DEC_OPT_BATCH_SIZES = mixed and
+        DEC_OPT_BATCH_HEADERS = any; (-1, 0, 0, 0, 0) after any other call"""
+        a = (C.c_long * 4)()
+        self.lib.L.gpujpeg_amd_decoder_get_batch_header_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        rc = self.lib.L.gpujpeg_amd_decoder_get_batch_header_stats(self.h, a)
+        return (int(rc),) + tuple(int(x) for x in a)
+
+    def batch_header_times(self):
+        """gpujpeg_amd_decoder_get_batch_header_times: (rc, ms bringing device-resident headers to the host, ms parsing, ms family rule + table sets +
+        geometries) of the last call batch_header_stats() describes; (-1, 0.0, 0.0, 0.0) after any other call"""
+        a = (C.c_double * 3)()
+        self.lib.L.gpujpeg_amd_decoder_get_batch_header_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        rc = self.lib.L.gpujpeg_amd_decoder_get_batch_header_times(self.h, a)
+        return (int(rc),) + tuple(float(x) for x in a)
 
     def entropy_bytes(self):
         """gpujpeg_amd_decoder_get_entropy_bytes: (rc, bytes handed to the entropy decoders by the batched launches, bytes of them that were read) of the

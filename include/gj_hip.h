@@ -106,9 +106,19 @@ typedef struct gj_frame_strides {
     /* frames of DIFFERENT image sizes (dec_opt_batch_sizes = mixed, crop-and-resize alone): [frames] the geometry of every frame, device memory; NULL:
      * all frames share the geometry this record travels in. The record of a frame is a whole gj_geom that the kernels read where it lies
      * (gj_device.h: gj_frame_geom) -- they index its components at run time, and a copy patched in registers would live in scratch memory. Its
-     * own fb is not read. */
+     * own fb is not read as strides: in a batch whose frames have headers of their OWN (dec_opt_batch_headers = any, gj_batch::own_headers) it is where
+     * the frame's header record lies (GJ_REC_BEGIN, GJ_REC_TABSET, GJ_REC_TABSETS below), so that neither the geometry that every decoder kernel
+     * takes by value nor the per-frame record grows by a byte for it. */
     const struct gj_geom* geoms;
 } gj_frame_strides;
+/* The header record of a frame of such a batch, in the fb of ITS geometry record `rec` (geoms[z]):
+ *   GJ_REC_BEGIN    the first byte behind the frame's first SOS header: what lies in front of it is no 0xFF and follows none for the marker scan
+ *   GJ_REC_TABSET   which table set of the launch's pool (GJ_TABSET_WORDS) the frame is decoded with -- set s lies s x GJ_TABSET_WORDS words behind
+ *                   the job's table pointers
+ *   GJ_REC_TABSETS  the sets in the pool; the kernels clamp the index to it */
+#define GJ_REC_BEGIN(rec) ((rec).fb.jpeg)
+#define GJ_REC_TABSET(rec) ((rec).fb.frames)
+#define GJ_REC_TABSETS(rec) ((rec).fb.seg)
 
 typedef struct gj_geom {
     int width, height, width_padding;
@@ -193,6 +203,7 @@ typedef struct gj_batch {
     uint32_t maxlen;         /* decoder: words between the frames' longest-segment words in pinned host memory */
     const uint32_t* d_sizes; /* decoder: [count] bytes of every frame's stream, in device memory */
     const struct gj_geom* d_geoms; /* decoder: NULL, or [count] the geometry of every frame (gj_frame_strides::geoms), in device memory */
+    uint32_t own_headers;          /* decoder: 1 = every frame's geometry record carries its header record (GJ_REC_BEGIN ...; dec_opt_batch_headers = any); with d_geoms alone */
 } gj_batch;
 
 typedef struct gj_enc_job {
@@ -491,6 +502,14 @@ GJ_HIP_API int gj_hip_decode_wants_tokens(const gj_geom* g, uint64_t jpeg_size, 
  * the block is complete at >= 64), bit 15 set for a non-zero AC coefficient (what the token decoder counts and stores). */
 #define GJ_DEC2_SUBTABLES 6
 #define GJ_DEC2_WORDS (1024 + 64 * GJ_DEC2_SUBTABLES)
+
+/* A table set: what the batched kernels read for ONE header, in the order the decoder's own table block holds it behind gj_dec_job::d_qtab -- the
+ * four uint16 inverse quantisation tables (natural order), the four two-level Huffman tables [2 slots][2 classes], the four float quantisation
+ * tables. A pool of them (gj_batch::own_headers, GJ_REC_TABSET) lies GJ_TABSET_WORDS uint16 words apart: d_qtab, d_huff_tab2 and d_qtabf of the job point
+ * into set 0. A multiple of 8 words, so that every set is read with 16-byte loads. */
+#define GJ_TABSET_TAB2_OFFSET (4 * 64)
+#define GJ_TABSET_QF_OFFSET (GJ_TABSET_TAB2_OFFSET + 4 * GJ_DEC2_WORDS)
+#define GJ_TABSET_WORDS (GJ_TABSET_QF_OFFSET + 4 * 64 * 2)
 
 /* events (may be NULL): 0 start, 1 after Huffman, 2 after IDCT, 3 after postprocess */
 #define GJ_DEC_EVENTS 4

@@ -315,6 +315,52 @@ GPUJPEG_API int gpujpeg_amd_host_stream_info(const uint8_t* image, size_t size, 
 #define GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_OFF "off"
 #define GPUJPEG_AMD_DEC_BATCH_PROGRESSIVE_VAL_ON "on"
 GPUJPEG_API int gpujpeg_amd_decoder_get_progressive_batch_stats(struct gpujpeg_decoder* decoder, long out[4]);
+/* Decoder option "dec_opt_batch_headers" = "same" (default) or "any": whether the FAMILY of a dec_opt_batch_sizes = mixed call (see there, "Routing")
+ * holds only streams whose headers are byte-equal, or every baseline stream of the same SHAPE whatever its tables and marker segments. Read by
+ * gpujpeg_amd_decoder_decode_batch_crop_resize and gpujpeg_amd_decoder_decode_batch_crop_resize_tensor alone, and only while dec_opt_batch_sizes = mixed
+ * is set (without it the option has no effect); it holds from the next call on and may be changed between two calls of a decoder. Another value is
+ * refused by gpujpeg_decoder_set_option (GPUJPEG_ERROR) and leaves the setting as it was. With "same" every byte, counter, launch, refusal, message
+ * and kernel-times slot of every call is what it is without the option, and the batched launches run the kernel instantiations they run without it.
+ * WITH "any" the definition does not change: frame f is, byte for byte (tensor call: bit for bit), what the same call returns for the one stream f.
+ * Only the routing does -- two files saved at different qualities (other DQT), files with optimised Huffman tables (a DHT of their own each) and files
+ * that carry Exif, ICC or a comment (other APPn / COM segments, another header length) are of ONE family.
+ *   Family.    The reference is the PARSED result of the reference header, chosen as without the option (a fresh decoder: frame 0's, after frame 0
+ *              went the single-frame route; the minority rule stands). A frame is of the family when the reader's parse of ITS header agrees with the
+ *              reference in: frame type SOF0 with 8-bit samples; component count, component ids and sampling factors; interleaving (the later SOS
+ *              headers of a non-interleaved stream are checked when the marker scan has found them); the restart interval ("absent" equals only
+ *              "absent"); and everything the reader decides about colour space and pixel format from APPn / JFIF / Adobe and the component ids. Its
+ *              DC and AC tables must sit in DHT slots 0 and 1 (no DHT for slot 2 or 3) and fit the two-level decode layout, and it must define every
+ *              table it references. Free to differ: width and height; the 64 values of any quantisation table; the contents of any Huffman table;
+ *              which slots the components use; number and order of DQT / DHT segments; APPn / COM segments; so also the length of the header, up to
+ *              64 KB. A non-interleaved stream in DEVICE memory is taken with the reference's table selectors for its second and later scans (its
+ *              own are not known before the launch); where they turn out to be others the frame goes the single-frame route.
+ *   Routing.   The single-frame route inside the call, with the message and return code it has without the option: another sampling, component count
+ *              or restart interval; a progressive stream (unless dec_opt_batch_progressive takes it); a DHT in slot 2 or 3; a table that does not fit
+ *              the layout; a header longer than 64 KB; damaged markers; a segment too long for the fast entropy decoder. Every rectangle is checked
+ *              against its own stream's image before anything of `output` is written.
+ *   Tables.    One TABLE SET -- the uint16 and float inverse quantisation tables and the four two-level Huffman tables -- per distinct content of the
+ *              DQT values and DHT bits / values the frame's components reference (a folder of files with the Annex K tables at one quality is one
+ *              set whatever its comments say, and whichever slots its files use); all sets go to the device in one upload; every frame carries the
+ *              index of its set and the offset of its first scan byte. The marker scan treats the bytes in front of a frame's own scan as it treats
+ *              the bytes in front of the scan of a byte-equal family: an Exif thumbnail -- a complete JPEG with SOS, RSTn and EOI inside APP1 --
+ *              reaches no table entry and no count. Device-resident streams: one launch gathers the first 4 KB of every stream; a header that does
+ *              not end inside them is fetched on its own, one wait for all of those.
+ *   State.     Family frames neither read nor write the header cache beyond what a "mixed" call does: a "same" call on a byte-equal family afterwards
+ *              behaves as if the "any" call had been a "mixed" call. Everything dec_opt_batch_sizes = mixed composes with composes with "any":
+ *              dec_opt_batch_restartless (files from libjpeg have no DRI), the prescales, the antialias filter, the mirror, the output and tensor
+ *              formats, gpujpeg_amd_decoder_set_batch_chunk and dec_opt_batch_progressive, whose pass runs after the baseline launches.
+ * gpujpeg_amd_decoder_get_batch_header_stats: after a crop-and-resize call made with "any" (and "mixed"), out[0] = frames the host admitted to the
+ * family, out[1] = distinct table sets uploaded, out[2] = header bytes brought to the host, out[3] = frames whose header did not end within the first
+ * gather window and was fetched on its own. Returns 0. After any other call: zeros, returns -1. */
+#define GPUJPEG_AMD_DEC_OPT_BATCH_HEADERS "dec_opt_batch_headers"
+#define GPUJPEG_AMD_DEC_BATCH_HEADERS_VAL_SAME "same"
+#define GPUJPEG_AMD_DEC_BATCH_HEADERS_VAL_ANY "any"
+GPUJPEG_API int gpujpeg_amd_decoder_get_batch_header_stats(struct gpujpeg_decoder* decoder, long out[4]);
+/* Where the host's look at the headers of that call spent its time, in milliseconds of the host's clock: ms[0] = bringing the headers of
+ * device-resident streams to the host (the gather launch, the copies of long headers, their waits; 0 for streams in host memory), ms[1] = the
+ * reader's parse of every header, ms[2] = the family rule, the table keys, building the distinct table sets and the frames' geometries. Returns 0
+ * after a call made with "any" (and "mixed"); after any other call: zeros, returns -1. */
+GPUJPEG_API int gpujpeg_amd_decoder_get_batch_header_times(struct gpujpeg_decoder* decoder, double ms[3]);
 /* Host-only: the table enc_opt_huffman=optimal builds for one class from symbol counts freq[256] (ITU T.81 Annex K.2: Figures K.1, K.3, K.4;
  * reserved code point, ties to the larger symbol value), code lengths limited to the largest L of 16 .. 10 whose table the library's
  * two-level decode tables take. Writes BITS (bits[1..16]) and HUFFVAL; returns L, or -1 when no count is non-zero. */
