@@ -786,6 +786,39 @@ static int region_scan_segments(const gj_geom* g, const gj_region_frame* r, int 
     return (int)n;
 }
 
+/* The orientation a stream carries (Exif APP1 tag 0x0112, SPIFF) against a rectangle: the display image D of an image_w x image_h stored image I is I
+ * turned clockwise by `rot` quarter turns, then mirrored left-right if `flip` (np.rot90(I, -rot), then [:, ::-1]); rect = x, y, w, h lies in D, a
+ * resample of it to out_w x out_h pixels of the display orientation is wanted, mirror: the result mirrored once more. out = x', y', w', h' -- the
+ * pre-image of the rectangle in I --, OW', OH' -- the size of R', the resample of that pre-image in stored orientation: out_w x out_h, swapped for
+ * odd rot --, the bits that turn R' into the result, 0. Output pixel (i, j) is pixel (i', j') of R':
+ *     (a, b) = T ? (j, i) : (i, j);  i' = FX ? OW' - 1 - a : a;  j' = FY ? OH' - 1 - b : b        (GJ_ORIENT_FX / _FY / _T)
+ * The mirror and the stream's flip both reverse the columns of the OUTPUT, which is FX of an upright frame and FY of a transposed one; with
+ * rot = flip = 0 the rectangle and the size come back as given and the bits are the mirror flag. -1: a rectangle that is not inside D, an output
+ * size outside 1 .. 16384. Host arithmetic only; no decode call reads it (gpujpeg_amd_host_orientation_plan). */
+int gj_orientation_plan(int image_w, int image_h, int rot, int flip, const int rect[4], int out_w, int out_h, int mirror, int out[8])
+{
+    rot &= 3;
+    const int W = image_w, H = image_h, dw = (rot & 1) ? H : W, dh = (rot & 1) ? W : H;
+    int x = rect[0];
+    const int y = rect[1], w = rect[2], h = rect[3];
+    if (W < 1 || H < 1 || x < 0 || y < 0 || w < 1 || h < 1 || x >= dw || y >= dh || w > dw - x || h > dh - y) return -1;
+    if (out_w < 1 || out_h < 1 || out_w > 16384 || out_h > 16384) return -1;
+    if (flip) x = dw - x - w; /* (the rectangle in the turned image ahead of its mirroring) */
+    int bits;
+    switch (rot) { /* D[r][c] = I[r][c] | I[H - 1 - c][r] | I[H - 1 - r][W - 1 - c] | I[c][W - 1 - r] */
+    case 1: out[0] = y; out[1] = H - x - w; out[2] = h; out[3] = w; bits = GJ_ORIENT_T | GJ_ORIENT_FY; break;
+    case 2: out[0] = W - x - w; out[1] = H - y - h; out[2] = w; out[3] = h; bits = GJ_ORIENT_FX | GJ_ORIENT_FY; break;
+    case 3: out[0] = W - y - h; out[1] = x; out[2] = h; out[3] = w; bits = GJ_ORIENT_T | GJ_ORIENT_FX; break;
+    default: out[0] = x; out[1] = y; out[2] = w; out[3] = h; bits = 0; break;
+    }
+    if ((flip != 0) != (mirror != 0)) bits ^= (bits & GJ_ORIENT_T) ? GJ_ORIENT_FY : GJ_ORIENT_FX;
+    out[4] = (rot & 1) ? out_h : out_w;
+    out[5] = (rot & 1) ? out_w : out_h;
+    out[6] = bits;
+    out[7] = 0;
+    return 0;
+}
+
 int gj_region_plan(gj_geom* gr, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* pi,
                    const int rect[4], const struct gj_resize* resize, unsigned alignment, struct gpujpeg_image_parameters* pi_out)
 {

@@ -3008,6 +3008,31 @@ int gpujpeg_amd_decoder_get_prescales(struct gpujpeg_decoder* d, uint8_t* dst, i
     return d->prescales_n;
 }
 
+int gpujpeg_amd_host_orientation_plan(int image_w, int image_h, int rotation, int flip, const int rect[4], int out_w, int out_h, int mirror, int out[8])
+{
+    if (!rect || !out || rotation < 0 || rotation > 3) return -1;
+    return gj_orientation_plan(image_w, image_h, rotation, flip != 0, rect, out_w, out_h, mirror != 0, out);
+}
+
+int gpujpeg_amd_host_stream_orientation(const uint8_t* image, size_t size, int out[5])
+{
+    if (!image || !out) return -1;
+    memset(out, 0, 5 * sizeof(int));
+    struct gj_reader_result* r = malloc(sizeof *r);
+    int rc = -1;
+    if (r && gj_reader_parse(image, size, GPUJPEG_LL_QUIET - 1, false, GPUJPEG_PIXFMT_NATIVE, GPUJPEG_NONE, 0, r, true, true) == 0) {
+        const bool set = r->metadata.vals[GPUJPEG_METADATA_ORIENTATION].set;
+        out[0] = set ? 1 : 0;
+        out[1] = set ? (int)r->metadata.vals[GPUJPEG_METADATA_ORIENTATION].orient.rotation : 0;
+        out[2] = set ? (int)r->metadata.vals[GPUJPEG_METADATA_ORIENTATION].orient.flip : 0;
+        out[3] = (out[1] & 1) ? r->param_image.height : r->param_image.width;
+        out[4] = (out[1] & 1) ? r->param_image.width : r->param_image.height;
+        rc = 0;
+    }
+    free(r);
+    return rc;
+}
+
 int gpujpeg_amd_decoder_get_entropy_bytes(struct gpujpeg_decoder* d, uint64_t out[2])
 {
     if (!d || !out) return -1;

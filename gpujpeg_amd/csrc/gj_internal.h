@@ -60,6 +60,13 @@ int gj_crop_resize_plan(int image_w, int image_h, int all_components_1x1, const 
  * frames of s > 1 are reduced per component, gj_region_frame::per_comp) */
 int gj_region_prescale(gj_geom* go, gj_region* r, const gj_geom* full, const struct gpujpeg_parameters* param, const struct gpujpeg_image_parameters* param_image,
                        const int rect[4], int out_w, int out_h, int max_scale, int subsampled, unsigned alignment, struct gpujpeg_image_parameters* pi_out);
+/* a rectangle of a stream's DISPLAY image (the image_w x image_h image turned clockwise by `rot` quarter turns, then mirrored left-right if `flip`)
+ * -> out = x', y', w', h' (its pre-image in the stored image), OW', OH' (out_w x out_h, swapped for odd rot), the bits that turn the resample of the
+ * pre-image into the display-oriented result (mirror folded in), 0; -1 for a rectangle outside the display image or an output size outside 1 .. 16384 */
+#define GJ_ORIENT_FX 1 /* reverse the columns of R' */
+#define GJ_ORIENT_FY 2 /* reverse its rows */
+#define GJ_ORIENT_T 4  /* swap the output axes */
+int gj_orientation_plan(int image_w, int image_h, int rot, int flip, const int rect[4], int out_w, int out_h, int mirror, int out[8]);
 /* 1 for a stream dec_opt_resize_prescale_subsampled reduces per component: every component sub_h == sub_v in {1, 2}, at least one 2, and no
  * component less subsampled than the one ahead of it (the reduced planes lie at data_offset N_c^2 / 64: they would overlap otherwise) */
 int gj_geom_prescale_per_component(const gj_geom* full);

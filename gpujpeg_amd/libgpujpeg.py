@@ -224,6 +224,9 @@ class Library:
         if hasattr(L, "gpujpeg_amd_host_crop_resize_plan"):
             L.gpujpeg_amd_host_crop_resize_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
             L.gpujpeg_amd_decoder_get_prescales.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int]
+        if hasattr(L, "gpujpeg_amd_host_orientation_plan"):
+            L.gpujpeg_amd_host_orientation_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+            L.gpujpeg_amd_host_stream_orientation.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
         if hasattr(L, "gpujpeg_amd_host_resize_weights"):
             L.gpujpeg_amd_host_resize_weights.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.c_int,
                                                           C.POINTER(C.c_uint64)]
@@ -269,6 +272,25 @@ def crop_resize_plan(lib, image_w, image_h, all_components_1x1, rect, out_w, out
     r4 = (C.c_int * 4)(*[int(v) for v in rect])
     rc = lib.L.gpujpeg_amd_host_crop_resize_plan(int(image_w), int(image_h), int(bool(all_components_1x1)), r4, int(out_w), int(out_h), int(max_scale), out)
     return tuple(out) if rc == 0 else None
+
+
+def orientation_plan(lib, image_w, image_h, rotation, flip, rect, out_w, out_h, mirror=False):
+    """gpujpeg_amd_host_orientation_plan (host only, lib: a Library): rect = (x, y, w, h) in the display image of an image_w x image_h stored image turned
+    by `rotation` quarter turns clockwise and then mirrored if `flip`, wanted as out_w x out_h display-oriented pixels -> (x', y', w', h', OW', OH', bits):
+    the rectangle and output size to hand to decode_batch_crop_resize, and bits = 1 reverse the columns of its frame | 2 reverse its rows | 4 swap the
+    axes; None for a rectangle outside the display image or an output size outside 1 .. 16384"""
+    out = (C.c_int * 8)()
+    r4 = (C.c_int * 4)(*[int(v) for v in rect])
+    rc = lib.L.gpujpeg_amd_host_orientation_plan(int(image_w), int(image_h), int(rotation), int(bool(flip)), r4, int(out_w), int(out_h), int(bool(mirror)), out)
+    return tuple(out)[:7] if rc == 0 else None
+
+
+def stream_orientation(lib, jpeg):
+    """gpujpeg_amd_host_stream_orientation (host only, lib: a Library): (set 0 / 1, rotation, flip, display width, display height) as the reader finds them
+    in the stream's headers (Exif APP1 or SPIFF); None when the headers cannot be parsed"""
+    a = np.ascontiguousarray(jpeg, np.uint8)
+    out = (C.c_int * 5)()
+    return tuple(out) if lib.L.gpujpeg_amd_host_stream_orientation(a.ctypes.data, a.size, out) == 0 else None
 
 
 def stream_info(lib, jpeg):

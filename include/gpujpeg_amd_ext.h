@@ -534,6 +534,26 @@ GPUJPEG_API int gpujpeg_amd_host_resize_weights(int n_src, int n_out, int i, int
 /* s_f of every frame of the decoder's last gpujpeg_amd_decoder_decode_batch_crop_resize call, as launched: dst[f], one byte per frame. Returns the
  * frame count, or 0 on error (no such call yet, the last one failed, capacity too small). */
 GPUJPEG_API int gpujpeg_amd_decoder_get_prescales(struct gpujpeg_decoder* decoder, uint8_t* dst, int capacity);
+/* Orientation for callers of the crop-and-resize calls. The batch calls return pixels in STORED orientation and do not look at the orientation a
+ * stream carries (Exif APP1 tag 0x0112 of IFD0 in either byte order, or the SPIFF directory entry: gpujpeg_decoder_output::metadata of the single
+ * call). The two host-only functions below give a caller what it takes to honour it without parsing Exif or restating the geometry:
+ * (rot, flip) is what the reader's metadata holds -- rot quarter turns clockwise, then mirrored left-right if flip; (0, 0) when nothing set it; a flawed
+ * tag or a truncated Exif block counts as not set, exactly as the reader decides. The DISPLAY image D of the stored W x H image I is I turned clockwise by
+ * rot quarter turns, then mirrored left-right if flip (numpy: np.rot90(I, k=-rot), then [:, ::-1]); D is H x W for odd rot.
+ * Out of scope here: applying the orientation inside any decode call; writing or rewriting Exif; any change to the reader's orientation parsing. */
+/* Host-only, no device: the orientation the reader finds in a stream's headers. out = set (0 / 1), rotation, flip, display width, display height
+ * (rotation and flip 0 when not set). Returns 0, or -1 when the headers cannot be parsed. */
+GPUJPEG_API int gpujpeg_amd_host_stream_orientation(const uint8_t* image, size_t size, int out[5]);
+/* Host-only: rect = x, y, w, h in the display image of an image_w x image_h stored image with `rotation` (0 .. 3) and `flip`, to be resampled to
+ * out_w x out_h pixels of the display orientation and, with mirror != 0, mirrored once more. Writes out = x', y', w', h' -- the rectangle's pre-image in the
+ * stored image: what to hand to gpujpeg_amd_decoder_decode_batch_crop_resize --, OW', OH' -- the output size to ask that call for: out_w x out_h, swapped
+ * for odd rotations --, bits, 0, and returns 0. With R' the OW' x OH' frame that call returns (no mirror), pixel (i, j) of the display-oriented result is
+ * pixel (i', j') of R':  (a, b) = bits & 4 ? (j, i) : (i, j);  i' = bits & 1 ? OW' - 1 - a : a;  j' = bits & 2 ? OH' - 1 - b : b  -- in numpy
+ * np.rot90(R', -rotation), then [:, ::-1] if flip, then [:, ::-1] if mirror. With rotation = flip = 0 the rectangle and the size come back as given and
+ * bits is the mirror flag. Returns -1 for a rectangle with w or h < 1 or not inside the display image, an output size outside 1 .. 16384, a rotation
+ * outside 0 .. 3. */
+GPUJPEG_API int gpujpeg_amd_host_orientation_plan(int image_w, int image_h, int rotation, int flip, const int rect[4], int out_w, int out_h, int mirror,
+                                                  int out[8]);
 
 #ifdef __cplusplus
 }
