@@ -35,8 +35,9 @@ extern "C" GJ_HIP_API int gj_hip_trace_stop_encoder(int n) { return hipMemcpyToS
 //      that average more than 16 bits per coefficient position), the last partial dword stays in a register;
 //   4. prefix sums over the block lengths give exact bit positions inside per-segment streams; the rows of the coefficient area
 //      above GJ_ENC_PRIV_ROWS become the shared bit window (nothing else lives in LDS: 36 KB per workgroup, four per CU);
-//   5. every lane shift-merges its private dwords into the window (ds_or_b32), coalesced copy of the unstuffed segment streams to
-//      d_temp with byte and 0xFF counts per segment (k_scan_segments / k_assemble finish the stream).
+//   5. every lane shift-merges its private dwords into the window (ds_or_b32; a wave whose blocks have no completed dword merges the
+//      register tails alone), the workgroup copies the window -- the unstuffed segment streams back to back -- to d_temp as one run of
+//      dwords, with byte and 0xFF counts per segment (k_gather finishes the stream).
 //
 // A block whose stream does not fit in place (noise at q100) continues it in its own slot of d_temp and reads it back for the
 // merge; a tile whose streams exceed the window takes several windows.
@@ -213,13 +214,34 @@ __device__ __forceinline__ void gj_merge_stream(const GjWalk& w, const uint8_t* 
     if (ndw > w.produced + 1) emit(0u);
 }
 
+// gj_merge_stream for a lane without a completed dword (the rule for chrominance on ordinary content: the caller takes this side when no lane of
+// the wave has one): the stream is the 64-bit tail alone, so the three output dwords are three shifts of it -- no source loops, no `stored`, no count
+// of the tail's dwords (the parts of the tail that carry no bits shift to zero, and a zero is never stored).
+template <bool WHOLE>
+__device__ __forceinline__ void gj_merge_tail_only(const uint64_t tail, const uint32_t sh, const uint32_t d0, uint32_t* s_bits, const uint32_t wbase,
+                                                   const uint32_t wend)
+{
+    const uint32_t hi = (uint32_t)(tail >> 32), lo = (uint32_t)tail;
+    const uint32_t o0 = hi >> sh, o1 = __builtin_amdgcn_alignbit(hi, lo, sh), o2 = __builtin_amdgcn_alignbit(lo, 0u, sh);
+    if (o0 && (WHOLE || (d0 >= wbase && d0 < wend))) atomicOr(&s_bits[d0 - wbase], o0);
+    if (o1 && (WHOLE || (d0 + 1u >= wbase && d0 + 1u < wend))) atomicOr(&s_bits[d0 + 1u - wbase], o1);
+    if (o2 && (WHOLE || (d0 + 2u >= wbase && d0 + 2u < wend))) atomicOr(&s_bits[d0 + 2u - wbase], o2);
+}
+
+#ifdef GJ_HIPEMU
+// CPU execution model only (tests/test_encoder_tile_tail.py): waves with a block of gj_code_tile that merged with gj_merge_stream [0] and with
+// gj_merge_tail_only [1], counted once per wave and component
+extern "C" GJ_HIP_API unsigned long long gj_emu_enc_merge_waves[2];
+unsigned long long gj_emu_enc_merge_waves[2] = {0, 0};
+#endif
+
 // Steps 2-5 for one component of a tile. i = thread, j = local segment of the lane's block, k = block inside its segment,
 // nblocks = blocks of that segment, table = 0 luminance / 1 chrominance tables, dc_dist = lanes back to the previous block of the
 // same component; region = the tile's area of d_temp (GJ_TEMP_BYTES_PER_BLOCK per block: the tile's UNSTUFFED stream from its start --
 // every segment on a dword boundary, in the order of the scan --, block i's spill slot at i * GJ_TEMP_BYTES_PER_BLOCK, which the stream
 // reaches only after block i has been merged into it), seg_count_left = segments of the scan from the tile's first one on (the last
 // one of a scan gets no restart marker); seg_bytes / seg_ff = unstuffed size and 0xFF count per segment (k_gather stuffs).
-// Returns the size of the tile's FINISHED stream (stuffed, restart markers included; the same in every thread).
+// Returns the size of the tile's FINISHED stream (stuffed, restart markers included) in the threads of the first wave, 0 in the others.
 __device__ __forceinline__ uint32_t gj_code_tile(const GjCoderLds& L, const int i, const int j, const int k, const bool active, const int spt,
                                                  const int nblocks, const int table, const int dc_dist, const int seg_count_left,
                                                  uint8_t* __restrict__ region,
@@ -332,46 +354,67 @@ __device__ __forceinline__ uint32_t gj_code_tile(const GjCoderLds& L, const int 
     const int ndw = w.produced + (fill + pad_bits > 32 ? 2 : (fill + pad_bits > 0 ? 1 : 0)); // stream dwords incl. the tail
     const int nseg = min(spt, seg_count_left);
     uint32_t* const dst = reinterpret_cast<uint32_t*>(region); // dword d of the tile stream
-    for (uint32_t wbase = 0; wbase < total_dw; wbase += GJ_ENC_WIN_DW) {
-        const uint32_t wend = min(total_dw, wbase + (uint32_t)GJ_ENC_WIN_DW);
-        if (wbase) {
-            __syncthreads(); // previous window drained
-            for (uint32_t d = i; d < wend - wbase; d += 256) s_bits[d] = 0;
-            __syncthreads();
+    // a wave none of whose blocks has completed a dword merges tails only (wave-uniform: one ballot)
+    const bool tails_only = __ballot(w.produced > 0) == 0ull;
+#ifdef GJ_HIPEMU
+    if (__ballot(active) != 0ull && lane == 0) __atomic_fetch_add(&gj_emu_enc_merge_waves[tails_only ? 1 : 0], 1ull, __ATOMIC_RELAXED);
+#endif
+    // the drain of a window: the segments lie back to back in the tile stream (every one on a dword boundary), so the workgroup copies the window as
+    // ONE run of dwords; a dword with 0xFF bytes -- rare -- looks up its segment in segbase[0 .. nseg) and adds its count there
+    auto drain = [&](const uint32_t wbase, const uint32_t wend) {
+        for (uint32_t d = wbase + (uint32_t)i; d < wend; d += 256) {
+            const uint32_t v = s_bits[d - wbase];
+            dst[d] = __builtin_bswap32(v);
+            // 0xFF bytes (the unused low bytes of a segment's last dword are zero)
+            const uint32_t ffm = ((v & 0x7F7F7F7Fu) + 0x01010101u) & v & 0x80808080u;
+            if (ffm) {
+                int lo = 0, hi = nseg;
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (L.segbase[mid] <= d) lo = mid; else hi = mid;
+                }
+                atomicAdd(&L.segff[lo], (uint32_t)__builtin_popcount(ffm));
+            }
         }
-        if (active && d0 + (uint32_t)ndw + 1u > wbase && d0 < wend) {
-            if (total_dw <= (uint32_t)GJ_ENC_WIN_DW) gj_merge_stream<true>(w, col, spill, tail, ndw, sh, d0, s_bits, 0u, total_dw);
-            else gj_merge_stream<false>(w, col, spill, tail, ndw, sh, d0, s_bits, wbase, wend);
+    };
+    if (total_dw <= (uint32_t)GJ_ENC_WIN_DW) { // the tile's stream fits the window (anything but noise at high qualities): straight through
+        if (active) {
+            if (tails_only) gj_merge_tail_only<true>(tail, sh, d0, s_bits, 0u, total_dw);
+            else gj_merge_stream<true>(w, col, spill, tail, ndw, sh, d0, s_bits, 0u, total_dw);
         }
         __syncthreads(); // B4: window complete
-        // every wave drains whole segments: no search for the owner of a dword, the 0xFF count of a segment is one wave reduction
-        for (int sl = wave; sl < nseg; sl += 4) {
-            const uint32_t sb = L.segbase[sl], nfl = (L.segbits[sl] + 31u) >> 5;
-            const uint32_t lo = max(sb, wbase), hi = min(sb + nfl, wend);
-            uint32_t ffc = 0;
-            for (uint32_t d = lo + (uint32_t)lane; d < hi; d += 64) {
-                const uint32_t v = s_bits[d - wbase];
-                // 0xFF bytes (the unused low bytes of a segment's last dword are zero)
-                ffc += (uint32_t)__builtin_popcount(((v & 0x7F7F7F7Fu) + 0x01010101u) & v & 0x80808080u);
-                dst[d] = __builtin_bswap32(v);
+        drain(0u, total_dw);
+    } else {
+        for (uint32_t wbase = 0; wbase < total_dw; wbase += GJ_ENC_WIN_DW) {
+            const uint32_t wend = min(total_dw, wbase + (uint32_t)GJ_ENC_WIN_DW);
+            if (wbase) {
+                __syncthreads(); // previous window drained
+                for (uint32_t d = i; d < wend - wbase; d += 256) s_bits[d] = 0;
+                __syncthreads();
             }
-            ffc = gj_wave_incl_scan(ffc);
-            if (lane == 63 && ffc) L.segff[sl] += ffc;
+            if (active && d0 + (uint32_t)ndw + 1u > wbase && d0 < wend) {
+                if (tails_only) gj_merge_tail_only<false>(tail, sh, d0, s_bits, wbase, wend);
+                else gj_merge_stream<false>(w, col, spill, tail, ndw, sh, d0, s_bits, wbase, wend);
+            }
+            __syncthreads(); // B4: window complete
+            drain(wbase, wend);
         }
     }
     __syncthreads(); // B5: 0xFF counts complete; the coefficient area may be overwritten by the next component
     if (trace0 >= 0) GJ_TRACE_E(trace0 + 3); // merged and drained
-    // the segments' sizes for k_gather, and what the tile's stream will measure once it is stuffed
-    uint32_t out = 0;
-    if (lane < nseg) {
-        const uint32_t nb = (L.segbits[lane] + 7u) >> 3, ff = L.segff[lane];
-        out = nb + ff + (lane != seg_count_left - 1 ? 2u : 0u);
-        if (wave == 0) {
+    // the segments' sizes for k_gather, and what the tile's stream will measure once it is stuffed: the first wave alone
+    uint32_t size = 0;
+    if (wave == 0) {
+        uint32_t out = 0;
+        if (lane < nseg) {
+            const uint32_t nb = (L.segbits[lane] + 7u) >> 3, ff = L.segff[lane];
+            out = nb + ff + (lane != seg_count_left - 1 ? 2u : 0u);
             seg_bytes[first_segment + lane] = nb;
             seg_ff[first_segment + lane] = ff;
         }
+        size = (uint32_t)__builtin_amdgcn_readlane((int)gj_wave_incl_scan(out), 63);
     }
-    return (uint32_t)__builtin_amdgcn_readlane((int)gj_wave_incl_scan(out), 63);
+    return size;
 }
 
 __device__ __forceinline__ void gj_load_coder_lut(uint32_t* s_lut, const uint32_t* __restrict__ lut, const int i)
