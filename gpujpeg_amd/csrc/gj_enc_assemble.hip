@@ -10,170 +10,212 @@
 // k_gather: the tile streams -> the file. Replaces k_scan_segments + k_assemble behind the k_encode_* kernels (the reference:
 // serialisation + compaction kernels and the host's stitching, src/gpujpeg_huffman_gpu_encoder.cu:417-613, src/gpujpeg_encoder.c:567-629).
 //
-// An encoder workgroup leaves the UNSTUFFED stream of its tile in the tile's area of d_temp (segments on dword boundaries), the
-// segments' byte and 0xFF counts, the size the tile's stream will have in the file, and adds that size to the total of its group of
-// 32 tiles (one atomic, nobody waits for it). Here ONE WAVE takes one tile stream, ~6000 waves at once for an 8K frame, and everything
-// it needs is asked for in one trip: the group totals and the sizes of its group's tiles in front of it (its place in the file), its
-// segments' counts, and the first 2 KB of its stream (where those are follows from the launch's geometry, not from loaded values).
-// Then the stream is stuffed in flight: a lane takes a dword, finds its segment (the segment starts are marked in LDS: a wave prefix
-// sum of the marks), counts its 0xFF bytes; a second prefix sum places it; a dword without 0xFF leaves as one unaligned 4-byte store,
-// restart markers follow the last dword of a segment. Round 3 needed a launch for the offsets (5 us), a wave per four
-// segments with two dependent trips and byte stores (16 us), and 19 MB of traffic for the same.
+// An encoder workgroup leaves the UNSTUFFED stream of its tile in the tile's area of d_temp (segments on dword boundaries, back to back),
+// the segments' byte counts, the size the tile's stream will have in the file, and adds that size to the total of its group of
+// 32 tiles (one atomic, nobody waits for it). Here ONE WAVE takes one tile stream, ~6000 waves at once for an 8K frame, on its own: the
+// four waves of a workgroup share nothing and never wait for each other. Which tile a wave has is the same for its 64 lanes, and the
+// compiler is told so (readfirstlane of the wave index): scan, segment range, source address, header sizes live in scalar registers.
+// Everything the wave needs is asked for in one trip: the group totals and the sizes of its group's tiles in front of it (their sum
+// is its place in the file: two wave reductions), its segments' byte counts, and the first 2 KB of its stream (where those are follows
+// from the launch's geometry, not from loaded values).
+// Then the stream is stuffed in flight, 256 dwords a round: a lane takes FOUR consecutive dwords with one 16-byte load (tile areas start
+// on multiples of GJ_TEMP_BYTES_PER_BLOCK = 13 x 16 bytes) and the four bytes LDS holds for them: a segment's lane has noted at the
+// segment's LAST dword how many of its bytes do not count and whether a restart marker follows, and which. The bytes a lane puts
+// into the file are then 16 + its 0xFF bytes - the bytes that do not count + 2 per marker, and ONE wave prefix sum per round places
+// every lane: no dword has to know its segment. A lane whose dwords are whole, unmarked and free of 0xFF leaves them as one unaligned
+// 16-byte store; another lane stores its clean dwords one by one, and the few that are left (0xFF inside, a segment's end) go byte by
+// byte, one such dword per lane and turn, as long as any lane has one.
+// Round 3 needed a launch for the offsets (5 us), a wave per four segments with two dependent trips and byte stores (16 us), and
+// 19 MB of traffic for the same; up to round 6 a lane took one dword a round, found its segment with a second prefix sum and two
+// ds_bpermute, and the workgroup's waves met at four barriers for two workgroup scans of which only the totals were used.
 // ================================================================================================
-#define GJ_GATHER_PRELOAD 8 // rounds of 64 dwords whose loads are issued before anything is known about the tile stream
-#define GJ_GATHER_MARK_DW 2048 // dwords of a tile stream whose segment starts are marked in LDS at a time
+#define GJ_GATHER_PRELOAD 2 // rounds of 256 dwords whose loads are issued before anything is known about the tile stream
+#define GJ_GATHER_MARK_DW 2048 // dwords of a tile stream whose segment ends are noted in LDS at a time
+#ifndef GJ_GATHER_STORE16
+#define GJ_GATHER_STORE16 1 // 1: a clean lane leaves with one unaligned 16-byte store, 0: with four unaligned dword stores (profiles/gather_wide.md)
+#endif
+// -DGJ_TRACE_PHASES (the `trace` target of the Makefile, tools/gather_valu_budget.py): gj_hip_trace_stop_gather(n) ends every wave at stamp n, so
+// that SQ_INSTS_VALU of the launch counts the vector instructions in front of that stamp (as gj_hip_trace_stop_encoder in gj_enc_tiles.hip)
+#ifdef GJ_TRACE_PHASES
+static __device__ int gj_trace_stop_g = 1 << 30;
+extern "C" GJ_HIP_API int gj_hip_trace_stop_gather(int n) { return hipMemcpyToSymbol(HIP_SYMBOL(gj_trace_stop_g), &n, sizeof n) == hipSuccess ? 0 : -1; }
+#define GJ_TRACE_G(slot) do { if ((slot) >= gj_trace_stop_g) __builtin_amdgcn_endpgm(); } while (0)
+#else
+#define GJ_TRACE_G(slot) ((void)0)
+#endif
+// what a segment notes at its last dword: bits 0-2 one bit per byte of the dword that does not count (0 .. 3 of them), bits 3-4 both set when a
+// restart marker follows (popcount = its two bytes), bits 5-7 which
+#define GJ_GATHER_PAD 0x07070707u
+#define GJ_GATHER_RST 0x18181818u
 __global__ __launch_bounds__(256) void k_gather(const GjTail T0)
 {
     GjTail T = T0;
     { // frame blockIdx.z of a batch: its own tile list, group totals, tile streams, segment counts, stream buffer and result words
         const size_t fz = blockIdx.z;
         T.piece += fz * T0.f_tail; T.group += fz * T0.f_tail; T.group_other += fz * T0.f_tail;
-        T.temp += fz * T0.f_temp; T.seg_bytes += fz * T0.f_seg; T.seg_ff += fz * T0.f_seg;
+        T.temp += fz * T0.f_temp; T.seg_bytes += fz * T0.f_seg;
         T.jpeg += fz * T0.f_jpeg; T.d_result += fz * 2;
         if (T.h_result) T.h_result += fz * 2;
     }
-    __shared__ uint32_t s_tmp[4];
     __shared__ __attribute__((aligned(16))) uint8_t s_mark[4][GJ_GATHER_MARK_DW];
-    const int i = threadIdx.x, lane = i & 63, wave = i >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // (the same in all lanes: what follows from it is scalar)
     const uint32_t P = T.npieces, NG = T.ngroups;
-    const uint32_t p0 = blockIdx.x * 4u, p = p0 + (uint32_t)wave;
-    const bool have = p < P;
+    const uint32_t p = blockIdx.x * 4u + wave;
     if (blockIdx.x == 0) // the next call's group totals
-        for (uint32_t g = i; g < NG; g += 256) T.group_other[g] = 0;
+        for (uint32_t g = threadIdx.x; g < NG; g += 256) T.group_other[g] = 0;
+    if (p >= P) return; // (a wave without a tile: nobody waits for it)
     // ---- this wave's tile stream: where its segments and its bytes are (no loaded value needed)
-    const uint32_t scan = gj_tail_scan_of(T, have ? p : 0u);
-    const uint32_t t = (have ? p : 0u) - gj_pick4(T.scan_first, scan), seg0 = t * T.spt, scan_segs = gj_pick4(T.segs, scan);
-    const uint32_t nseg = have ? min(T.spt, scan_segs - seg0) : 0u;
+    const uint32_t scan = gj_tail_scan_of(T, p);
+    const uint32_t t = p - gj_pick4(T.scan_first, scan), seg0 = t * T.spt, scan_segs = gj_pick4(T.segs, scan);
+    const uint32_t nseg = min(T.spt, scan_segs - seg0);
     const uint32_t s0 = gj_pick4(T.seg_first, scan) + seg0;
     const uint64_t src_block = (uint64_t)gj_pick4(T.block_first, scan) + (uint64_t)seg0 * T.seg_blocks;
-    const uint32_t* const src = reinterpret_cast<const uint32_t*>(T.temp + src_block * GJ_TEMP_BYTES_PER_BLOCK);
-    // dwords of the tile's area: nothing is read behind them, nor behind the buffer (the area of a scan's last tile ends with its last,
-    // shorter segment; found by the execution model under AddressSanitizer in round 4: the preload below read up to 35 blocks further)
+    const uint32_t* const src = reinterpret_cast<const uint32_t*>(T.temp + src_block * GJ_TEMP_BYTES_PER_BLOCK); // (a multiple of 16 bytes: gj_hip_encode asserts it)
+    // dwords of the tile's area, a multiple of four: nothing is read behind them, nor behind the buffer (the area of a scan's last tile ends
+    // with its last, shorter segment; found by the execution model under AddressSanitizer in round 4: the preload below read up to 35 blocks further)
     const uint64_t room = T.temp_blocks > src_block ? T.temp_blocks - src_block : 0u;
     const uint32_t src_dw = (uint32_t)min((uint64_t)nseg * T.seg_blocks, room) * (GJ_TEMP_BYTES_PER_BLOCK / 4u);
-    // ---- one trip: group totals, the sizes of the tiles of the group in front of the workgroup's first one and of the workgroup's
-    // own, the segments' counts, the first rounds of the stream
-    const uint32_t ga = p0 >> 5;
+    // ---- one trip: group totals, the sizes of the tiles of the group in front of this one, the segments' byte counts, the first rounds of the stream
+    const uint32_t ga = p >> 5;
     uint32_t before = 0, all = 0;
-    for (uint32_t g0 = 0; g0 < NG; g0 += 1024) {
+    for (uint32_t g0 = 0; g0 < NG; g0 += 256) {
         uint32_t v[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const uint32_t g = g0 + (uint32_t)u * 256u + (uint32_t)i;
+            const uint32_t g = g0 + (uint32_t)u * 64u + lane;
             v[u] = g < NG ? T.group[g] : 0u;
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const uint32_t g = g0 + (uint32_t)u * 256u + (uint32_t)i;
+            const uint32_t g = g0 + (uint32_t)u * 64u + lane;
             all += v[u];
             before += g < ga ? v[u] : 0u;
         }
     }
-    if ((uint32_t)i < (p0 & 31u)) before += T.piece[(ga << 5) + i];
-    uint32_t in_front = 0; // of this wave's tile inside the workgroup
-    if (wave > 0 && have) in_front += T.piece[p0];
-    if (wave > 1 && have) in_front += T.piece[p0 + 1];
-    if (wave > 2 && have) in_front += T.piece[p0 + 2];
-    uint32_t nb = 0, ff = 0;
-    if ((uint32_t)lane < nseg) {
-        nb = T.seg_bytes[s0 + lane];
-        ff = T.seg_ff[s0 + lane];
-    }
-    uint32_t pre[GJ_GATHER_PRELOAD];
+    if (lane < (p & 31u)) before += T.piece[(ga << 5) + lane];
+    const uint32_t nb = lane < nseg ? T.seg_bytes[s0 + lane] : 0u;
+    uint4 pre[GJ_GATHER_PRELOAD];
 #pragma unroll
     for (int m = 0; m < GJ_GATHER_PRELOAD; m++) {
-        const uint32_t d = (uint32_t)m * 64u + (uint32_t)lane;
-        pre[m] = d < src_dw ? src[d] : 0u;
+        const uint32_t d = (uint32_t)m * 256u + 4u * lane;
+        pre[m] = d < src_dw ? *reinterpret_cast<const uint4*>(src + d) : make_uint4(0u, 0u, 0u, 0u);
     }
-    uint32_t done_bytes, all_bytes;
-    gj_wg256_incl_scan(before, s_tmp, &done_bytes);
-    gj_wg256_incl_scan(all, s_tmp, &all_bytes);
+    const uint32_t done_bytes = (uint32_t)__builtin_amdgcn_readlane((int)gj_wave_incl_scan(before), 63);
+    const uint32_t all_bytes = (uint32_t)__builtin_amdgcn_readlane((int)gj_wave_incl_scan(all), 63);
     const uint64_t total = (uint64_t)T.main_hdr + gj_pick4(T.hdr_end, gj_tail_scan_of(T, P - 1)) + all_bytes + 2u;
     const bool overflow = total > T.capacity;
-    if (p0 + 4 >= P && i == 0) { // (the workgroup of the last tile stream)
+    uint8_t* const out = T.jpeg;
+    if (p == P - 1 && lane == 0) { // (the wave of the last tile stream)
         T.d_result[0] = (uint32_t)total;
         T.d_result[1] = overflow ? 1u : 0u;
         if (T.h_result) { // the host's (pinned, device-visible) copy: no copy launch behind the kernel
             T.h_result[0] = (uint32_t)total;
             T.h_result[1] = overflow ? 1u : 0u;
         }
+        if (!overflow) { // EOI: the file's last two bytes
+            out[(uint32_t)total - 2u] = 0xFF;
+            out[(uint32_t)total - 1u] = 0xD9;
+        }
     }
-    if (!have || overflow) return;
-    const uint32_t F = T.main_hdr + gj_pick4(T.hdr_end, scan) + done_bytes + in_front; // the tile stream's first byte in the file
-    uint8_t* const out = T.jpeg;
+    if (overflow) return;
+    const uint32_t F = T.main_hdr + gj_pick4(T.hdr_end, scan) + done_bytes; // the tile stream's first byte in the file
     if (t == 0) { // first tile of a scan: its header (APP13 placeholders + SOS) sits right in front
         const uint32_t h1 = gj_pick4(T.hdr_end, scan), h0 = scan == 0 ? 0u : gj_pick4(T.hdr_end, scan - 1);
         for (uint32_t b = lane; b < h1 - h0; b += 64) out[F - (h1 - h0) + b] = T.scan_hdr[h0 + b];
     }
-    // ---- lane sl keeps segment sl: its dwords, its first dword in the tile stream, its first byte in the file, the 0xFF bytes in front
-    // of it. Everything a dword needs to know about its segment is two words: where its bytes go if none of the tile's dwords held a
-    // 0xFF (minus 4 x its index), and the segment's last dword with the bytes that count in it.
+    GJ_TRACE_G(1); // set up: the file offset is known
+    // ---- lane sl keeps segment sl: its last dword in the tile stream and what it notes there
     const uint32_t last = scan_segs - seg0 - 1u; // (local index of the scan's last segment: no restart marker behind it)
-    const uint32_t ndw = (nb + 3u) >> 2, olen = nb + ff + ((uint32_t)lane < nseg && (uint32_t)lane != last ? 2u : 0u);
-    const uint32_t dwi = gj_wave_incl_scan(ndw), dwb = dwi - ndw;
-    const uint32_t oi = gj_wave_incl_scan(olen), ob = F + oi - olen;
-    const uint32_t ffi = gj_wave_incl_scan(ff);
+    const uint32_t ndw = (nb + 3u) >> 2;
+    const uint32_t dwi = gj_wave_incl_scan(ndw);
     const uint32_t total_dw = (uint32_t)__builtin_amdgcn_readlane((int)dwi, 63);
-    const uint32_t end = F + (uint32_t)__builtin_amdgcn_readlane((int)oi, 63);
-    if (p == P - 1 && lane == 0) { // EOI
-        out[end] = 0xFF;
-        out[end + 1] = 0xD9;
-    }
-    const uint32_t seg_a = ob - 4u * dwb - (ffi - ff);                               // byte q of dword d: seg_a + 4 d + 0xFF bytes in front of d
-    const uint32_t seg_e = (dwi - 1u) | ((nb - 4u * (ndw - 1u)) << 28);              // last dword | its bytes (1 .. 4) << 28
-    // which dwords begin a segment: a byte per dword in LDS (tile streams of more dwords take several passes)
+    const uint32_t note = ((1u << (4u * ndw - nb)) - 1u) | (lane != last ? 0x18u | (((seg0 + lane) & 7u) << 5) : 0u); // (RSTn: src/gpujpeg_huffman_gpu_encoder.cu:497-502)
+    GJ_TRACE_G(2); // segment books
     uint8_t* const mark = s_mark[wave];
-    uint32_t ffrun = 0, segs_before = 0; // 0xFF bytes / segment starts of the dwords of earlier rounds
-    for (uint32_t c0 = 0; c0 < total_dw; c0 += GJ_GATHER_MARK_DW) {
+    uint32_t pos = F; // where the round's first byte goes
+    for (uint32_t c0 = 0; c0 < total_dw; c0 += GJ_GATHER_MARK_DW) { // (tile streams of more dwords take several passes)
         const uint32_t c1 = min(total_dw, c0 + (uint32_t)GJ_GATHER_MARK_DW);
         gj_wave_sync();
-#pragma unroll
-        for (int z = 0; z < GJ_GATHER_MARK_DW / 256; z++) reinterpret_cast<uint32_t*>(mark)[z * 64 + lane] = 0;
+        // (a byte per dword: a lane's 16 bytes are 16 dwords' notes; whole rounds of 256 dwords are cleared)
+        static_assert(GJ_GATHER_MARK_DW == 2048, "two clearing stores of 1024 bytes");
+        reinterpret_cast<uint4*>(mark)[lane] = make_uint4(0u, 0u, 0u, 0u);
+        if (c1 - c0 > 1024u) reinterpret_cast<uint4*>(mark)[64u + lane] = make_uint4(0u, 0u, 0u, 0u);
         gj_wave_sync();
-        if ((uint32_t)lane < nseg && dwb >= c0 && dwb < c1) mark[dwb - c0] = 1;
+        if (lane < nseg && dwi - 1u >= c0 && dwi - 1u < c1) mark[dwi - 1u - c0] = (uint8_t)note;
         gj_wave_sync();
-        for (uint32_t m = c0 >> 6; m * 64u < c1; m++) {
-            const uint32_t d = m * 64u + (uint32_t)lane;
-            const bool live = d < total_dw;
-            uint32_t v = 0;
-            if (m < GJ_GATHER_PRELOAD) {
+        for (uint32_t r0 = c0; r0 < c1; r0 += 256u) {
+            const uint32_t d0 = r0 + 4u * lane;
+            uint4 x = make_uint4(0u, 0u, 0u, 0u);
+            if (r0 < GJ_GATHER_PRELOAD * 256u) {
 #pragma unroll
                 for (int q = 0; q < GJ_GATHER_PRELOAD; q++)
-                    if (m == (uint32_t)q) v = pre[q];
-            } else if (live) {
-                v = src[d];
+                    if (r0 == (uint32_t)q * 256u) x = pre[q];
+            } else if (d0 < total_dw && d0 < src_dw) {
+                x = *reinterpret_cast<const uint4*>(src + d0);
             }
-            const uint32_t seg = gj_wave_incl_scan(live ? mark[d - c0] : 0u) + segs_before - 1u; // the segment of dword d
-            const int sidx = (int)((live ? seg : 0u) << 2);
-            const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute(sidx, (int)seg_a), e = (uint32_t)__builtin_amdgcn_ds_bpermute(sidx, (int)seg_e);
-            const bool ends = live && d == (e & 0x0FFFFFFFu);
-            const int vb = live ? (ends ? (int)(e >> 28) : 4) : 0;
-            const uint32_t ffm = live ? ((v & 0x7F7F7F7Fu) + 0x01010101u) & v & 0x80808080u : 0u; // (the bytes behind a segment's end are zero)
-            const uint32_t ffc = (uint32_t)__builtin_popcount(ffm);
-            const uint32_t fi = gj_wave_incl_scan(ffc) + ffrun; // 0xFF bytes up to and including this dword
-            if (live) {
-                uint32_t q = a + 4u * d + (fi - ffc);
-                if (ffc == 0 && vb == 4) {
-                    *reinterpret_cast<gj_u32_unaligned*>(out + q) = v;
-                    q += 4;
-                } else {
+            uint32_t v[4] = {x.x, x.y, x.z, x.w};
+            const uint32_t M = *reinterpret_cast<const uint32_t*>(mark + (d0 - c0));
+            const uint32_t nlive = (uint32_t)min(4, max(0, (int)(total_dw - d0))); // the lane's dwords that belong to the stream
+            if (r0 + 256u > total_dw) { // (the stream's last round: what lies behind it in the area is not looked at)
+#pragma unroll
+                for (int k = 1; k < 4; k++) v[k] = (uint32_t)k < nlive ? v[k] : 0u;
+                v[0] = nlive ? v[0] : 0u;
+            }
+            uint32_t ffm[4], ffc = 0; // (the bytes behind a segment's end are zero)
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                ffm[k] = ((v[k] & 0x7F7F7F7Fu) + 0x01010101u) & v[k] & 0x80808080u;
+                ffc += (uint32_t)__builtin_popcount(ffm[k]);
+            }
+            const uint32_t bytes = 4u * nlive + ffc + (uint32_t)__builtin_popcount(M & GJ_GATHER_RST) - (uint32_t)__builtin_popcount(M & GJ_GATHER_PAD);
+            const uint32_t bi = gj_wave_incl_scan(bytes);
+            uint32_t q = pos + bi - bytes;
+            pos += (uint32_t)__builtin_amdgcn_readlane((int)bi, 63);
+            uint32_t dirty = 0, qk[4]; // the lane's dwords that go byte by byte, and where each dword's bytes go
+            if ((M | ffm[0] | ffm[1] | ffm[2] | ffm[3]) == 0 && nlive == 4) {
+#if GJ_GATHER_STORE16
+                __builtin_memcpy(out + q, v, 16);
+#else
+#pragma unroll
+                for (int k = 0; k < 4; k++) *reinterpret_cast<gj_u32_unaligned*>(out + q + 4 * k) = v[k];
+#endif
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const uint32_t mk = (M >> (8 * k)) & 0xFFu;
+                    qk[k] = q;
+                    if ((uint32_t)k < nlive) {
+                        if ((mk | ffm[k]) == 0) *reinterpret_cast<gj_u32_unaligned*>(out + q) = v[k];
+                        else dirty |= 1u << k;
+                    }
+                    q += 4u + (uint32_t)__builtin_popcount(ffm[k]) + (uint32_t)__builtin_popcount(mk & 0x18u) - (uint32_t)__builtin_popcount(mk & 0x07u);
+                }
+            }
+            while (__ballot(dirty != 0)) { // a turn: every lane that has one writes one such dword
+                if (dirty) {
+                    const uint32_t k = (uint32_t)__builtin_ctz(dirty);
+                    dirty &= dirty - 1u;
+                    const uint32_t w = k == 0 ? v[0] : k == 1 ? v[1] : k == 2 ? v[2] : v[3];
+                    uint32_t o = k == 0 ? qk[0] : k == 1 ? qk[1] : k == 2 ? qk[2] : qk[3];
+                    const uint32_t mk = (M >> (8u * k)) & 0xFFu;
+                    const int vb = 4 - __builtin_popcount(mk & 0x07u);
 #pragma unroll
                     for (int b = 0; b < 4; b++)
                         if (b < vb) {
-                            const uint32_t byte = (v >> (8 * b)) & 0xFFu;
-                            out[q++] = (uint8_t)byte;
-                            if (byte == 0xFFu) out[q++] = 0;
+                            const uint32_t byte = (w >> (8 * b)) & 0xFFu;
+                            out[o++] = (uint8_t)byte;
+                            if (byte == 0xFFu) out[o++] = 0;
                         }
-                }
-                if (ends && seg != last) { // RSTn (src/gpujpeg_huffman_gpu_encoder.cu:497-502)
-                    out[q] = 0xFF;
-                    out[q + 1] = (uint8_t)(0xD0 + ((seg0 + seg) & 7u));
+                    if (mk & 0x08u) { // RSTn behind the segment's last dword
+                        out[o] = 0xFF;
+                        out[o + 1] = (uint8_t)(0xD0u + (mk >> 5));
+                    }
                 }
             }
-            ffrun = (uint32_t)__builtin_amdgcn_readlane((int)fi, 63);
-            segs_before = (uint32_t)__builtin_amdgcn_readlane((int)seg, 63) + 1u;
         }
     }
+    GJ_TRACE_G(3); // rounds (what follows is the kernel's end)
 }
 
 // the workgroup's Huffman tables in the layout of GjCoderLds::lut: the host has them ready behind its (code << 8 | size) tables

@@ -6,6 +6,7 @@
 //   k_fused_* or k_preprocess + k_dct -> k_huffman -> k_scan_segments + k_assemble   through coefficient planes
 //   optimal tables: the same, cut in two calls behind the planes: ... -> k_huffman_count | host builds the tables | k_huffman -> ...
 #include "gj_enc_internal.h"
+#include <assert.h>
 
 // k_gather's arguments (and the encoder kernels': they use the tile list and the group totals) for a launch that leaves
 // `pieces` tile streams of `spt` segments; scan s begins with stream scan_first[s]
@@ -204,6 +205,13 @@ extern "C" int gj_hip_encode(const gj_enc_job* job, gj_stream_t stream, gj_event
                        job->d_seg_ff);
     }
     if (ev) GJ_HIP_CHECK(hipEventRecord((hipEvent_t)ev[3], st));
+    // (k_gather reads a tile's stream 16 bytes a lane: tile areas start on multiples of GJ_TEMP_BYTES_PER_BLOCK = 13 x 16 bytes behind d_temp,
+    // in every frame of a batch)
+    static_assert(GJ_TEMP_BYTES_PER_BLOCK % 16 == 0, "k_gather's 16-byte loads");
+    if (tiles && ((((uintptr_t)job->d_temp) & 15u) != 0 || (frames > 1 && (job->batch.temp & 15u) != 0))) {
+        assert(!"d_temp and its batch stride are multiples of 16 bytes");
+        return -1;
+    }
     if (tiles) // the tile streams -> the file: one wave each
         hipLaunchKernelGGL(k_gather, dim3((T.npieces + 3) / 4, 1, frames), dim3(256), 0, st, T);
     const bool seg_info = job->segment_info && g.restart_interval > 0;
